@@ -25,6 +25,8 @@ Prints ONE JSON line (rank 0).  Besides the contract keys it carries
   control_exact_products : the same step with --precision exact (three f16 pieces, nine bf16 products: every product exact)
   extra          : short runs of the other BASELINE configs (cfg2, cfg4 = NAF, cfg5), steps/s each
 (N = 1, rank 0 only for the last three; --quick skips them.)
+
+--dump-outputs DIR writes what the timed region's last train-step call computed (rank 0) as DIR/<name>.npy: see dump_outputs.
 """
 import argparse
 import json
@@ -158,6 +160,32 @@ def sub_bench(extra_args, env=None, timeout=420):
         return {"error": repr(e)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, agent, kind, B):
+    """what a caller of the timed path holds after its last train-step call, one float32 DIR/<name>.npy per array: every network's
+    flat parameters (the step's result), the last minibatch's loss / gradient-norm stats and, for DDPG, that minibatch's per-row
+    actions, dQ/da, Q and TD (cpp_ddpg_last_values).  Weights, replay fill and sampler are seeded, so the same flags give the same
+    inputs from run to run and two builds can be compared array by array.  Returns {name: shape}."""
+    arrays = {}
+    for net in agent.networks():
+        arrays["params_" + net.namespace.replace("/", "_")] = net.get_params()
+    if kind == "ddpg":
+        arrays["last_stats"] = agent.trainer.last_stats()           # (TD loss, actor grad norm, critic grad norm)
+        for name, v in zip(("actions", "dq_da", "q", "td"), agent.trainer.last_values(B)):
+            arrays["last_" + name] = v
+    else:
+        arrays["last_stats"] = agent.naf.last_stats()               # (loss, pre-clip gradient norm, non-finite flag)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "dump of %d bytes exceeds %d" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype == np.float32, (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def self_launch(n):
     """re-run this command line as n ranks: python -m torch.distributed.run --nnodes=1 --nproc-per-node n bench.py <same flags>."""
     import socket
@@ -199,7 +227,11 @@ def main():
     ap.add_argument("--force-dp", action="store_true", help="use the data-parallel learner path (RCCL all-reduce) even at world size 1")
     ap.add_argument("--overlap", action="store_true", help="data-parallel: reduce the fully connected layers' gradients beside the conv backward")
     ap.add_argument("--sync-every", type=int, default=1, help="data-parallel: k local minibatches between parameter averagings (1: gradient all-reduce per minibatch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last train step computed (rank 0) as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     BATCHES_PER_STEP = max(1, args.batches_per_step)
 
     # keep real stdout for the ONE JSON line: RCCL / libraries print banners to fd 1
@@ -344,6 +376,8 @@ def main():
         elapsed = max(float(t.item()) for t in every)         # the MAX over the ranks is the job's time
     ms_per_step = 1e3 * elapsed / steps
     value = world * steps / elapsed
+    # (before the profiled pass below, which trains on: the state the timed region left)
+    dumped = dump_outputs(args.dump_outputs, agent, kind, B) if args.dump_outputs and rank == 0 else None
 
     # ---- what a first N > 1 run must tell us without anybody watching it (nobody has had more than one GPU): which form the step took on
     # every rank (one hipGraph with the all-reduce inside, or the same launches on the stream because the capture was refused -- and why),
@@ -561,6 +595,8 @@ def main():
         "conv_kernels_without_a_layers_row": unmapped_conv,
         "kernels": kernels,
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     side = rank == 0 and world == 1 and not args.quick
     if side and not args.no_cpu_baseline and kind == "ddpg":
         out["cpu_baseline"] = cpu_baseline_torch(shape, B)

@@ -77,3 +77,32 @@ def test_bench_force_dp_compares_the_two_graphs_in_one_process():
     assert dp["replicas_bit_identical"] is True and len(dp["per_rank"][0]["params_sha256_16"]) == 16, dp
     assert dp["exposed_allreduce_us_per_minibatch"] is not None and 0.5 < dp["exposed_allreduce_us_per_minibatch"] < 200.0, dp
     assert dp["allreduce_bytes"] == 4 * 236163, dp          # cfg3: actor 87 282 + critic 148 881 floats (0.94 MB)
+
+
+def test_bench_dump_outputs_are_the_same_for_the_same_flags_and_follow_steps(tmp_path):
+    """--dump-outputs DIR: the last timed train step's results as float32 .npy files (every network's parameters, the last minibatch's
+    stats and per-row values), within 64 MB; the same flags give the same arrays bit for bit in a fresh process, and --steps changes
+    them (it sets the number of timed minibatches, and the dump is taken right behind them)."""
+    import numpy as np
+
+    def dump(name, steps):
+        out = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "5", "--quick",
+                            "--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        d = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == steps and d["dump_outputs"]["dir"] == str(out)
+        files = sorted(p.name for p in out.iterdir())
+        assert files == sorted(n + ".npy" for n in d["dump_outputs"]["arrays"]), files
+        return {f[:-4]: np.load(str(out / f)) for f in files}
+
+    a, b, c = dump("a", 7), dump("b", 7), dump("c", 8)
+    for k in ("params_actor", "params_critic", "params_target_actor", "params_target_critic", "last_stats", "last_actions",
+              "last_dq_da", "last_q", "last_td"):
+        assert k in a, sorted(a)
+    assert a["params_actor"].size == 87282 and a["params_critic"].size == 148881 and a["last_q"].shape == (256, 1)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k, v in a.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), k
+        assert np.array_equal(v, b[k]), k
+    assert not np.array_equal(a["params_critic"], c["params_critic"])
