@@ -104,6 +104,13 @@ SIGNATURES = {
     "cpp_replay_sample": (_I, [_P, _I, _P, _U64, _U64, _I, _P]),
     "cpp_replay_last_indexes": (_I, [_P, _I, _P]),
     "cpp_replay_fill_synthetic": (_I, [_P, _I, _U64]),
+    "cpp_replay_enable_priorities": (_I, [_P, C.c_float, C.c_float]),
+    "cpp_replay_set_priority_beta": (_I, [_P, C.c_float]),
+    "cpp_replay_update_priorities": (_I, [_P, _P, _I, _P]),
+    "cpp_replay_read_priorities": (_I, [_P, _P, _I, _P]),
+    "cpp_replay_read_priority_tree": (_I, [_P, _P, _L]),
+    "cpp_replay_last_weights": (_I, [_P, _I, _P]),
+    "cpp_replay_draw_prioritized": (_I, [_P, _I, _U64, _P, _P]),
     "cpp_ddpg_create": (_I, [_P, _P, _P, _P, _P, C.POINTER(DdpgHyper), _PP]),
     "cpp_ddpg_destroy": (_I, [_P]),
     "cpp_ddpg_train_actor": (_I, [_P, _P]),

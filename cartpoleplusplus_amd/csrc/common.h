@@ -58,6 +58,7 @@ enum KernelId {
   K_CONV1_DW_GATHER,      // conv1 dW (f16 pipes) + sample / statistics of the next minibatch in one launch (conv1_dw_gather.hip)
   K_ALLREDUCE,            // the data-parallel step's gradient all-reduce (RCCL), as the stream sees it between the gradient kernels and the update
   K_CONV1_IMAGE,          // conv1's operand images as a launch of their own (conv_rs16.h; in the fused step they ride in the optimiser's launch)
+  K_PER,                  // prioritized replay: sum-tree updates, draws and importance weights (per.hip)
   K_NUM_KERNELS
 };
 
@@ -275,7 +276,7 @@ int launch_state_to_f32(cpp_ctx* ctx, float* dst, long ldd, const void* src, int
                         int rows);
 int launch_actor_head_grad(cpp_ctx* ctx, float* dz, const float* dq_da, const float* act, int n);
 int launch_td(cpp_ctx* ctx, const float* q, const float* tq, const float* r, const float* mask,
-              float discount, int B, float* td, float* dq, float* loss);
+              float discount, int B, float* td, float* dq, float* loss, const float* w = nullptr);   // w: importance weights (per.hip)
 
 // ---------------------------------------------------------------------------------------------
 // replay + whitening statistics (replay.hip)
@@ -419,11 +420,37 @@ struct DdpgHeadsArgs {
   const float *h1a, *h1ta; int ld_h1a, n1a;        // B x (n1a + 1)
   const float *W2, *W2_t;                          // [(n1a + 1)][n2a]
   float *h2a_out, *dz_h1a;                         // B x ld_h2a (first n2a columns), B x n1a
+  // optional: importance weights of the rows (prioritized replay, per.hip): loss = mean(w td^2), dz_q = (td w) 2 / B
+  const float* w;
 };
 #define DDPG_HEADS_MAX_WGS 256
 size_t ddpg_heads_lds_bytes(const DdpgHeadsArgs& h);
 bool ddpg_heads_supported(const DdpgHeadsArgs& h);
 int launch_ddpg_heads(cpp_ctx* ctx, const DdpgHeadsArgs& h);
+
+// ---------------------------------------------------------------------------------------------
+// prioritized replay (per.hip)
+// ---------------------------------------------------------------------------------------------
+#define PER_THREADS 256
+#define PER_MAX_ROWS 1024        // rows per launch of per_update_sample_kernel (leaf writes, draws): one LDS list
+#define PER_TOP_NODES 1024       // tree nodes [1, PER_TOP_NODES) staged in LDS for the draws
+struct PerArgs {
+  double* tree; int L;                             // nodes [1, 2^(L+1)), leaves at 2^L
+  const int32_t* size_ptr;                         // rows in the memory (device word)
+  float* maxp;                                     // running maximum priority (device word)
+  // phases 1-2: leaf writes
+  const int32_t* up_rows; int n_up;                // n_up <= PER_MAX_ROWS; 0: none
+  const float* up_td;                              // priority powf(|td| + eps, alpha); nullptr: *maxp (new rows)
+  float alpha, eps;
+  // phases 3-4: rows + importance weights (B <= PER_MAX_ROWS; 0: none)
+  int B;
+  const int32_t* w_rows;                           // non-null: the weights of these rows, no draw
+  uint64_t seed; uint64_t* counter; int counter_add, bump;   // draw key: (seed, *counter + counter_add); bump: ++*counter after it
+  const float* beta;
+  int32_t* out_rows; float* out_w;
+};
+int launch_per_update_sample(cpp_ctx* ctx, const PerArgs& a);
+int launch_per_rebuild(cpp_ctx* ctx, double* tree, int L, long n, const float* maxp);
 
 struct NafHeadArgs {
   const float* value; const float* mu; const float* lv; const float* action; const float* reward;

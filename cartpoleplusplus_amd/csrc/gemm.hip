@@ -345,10 +345,10 @@ int launch_actor_head_grad(cpp_ctx* ctx, float* dz, const float* dq_da, const fl
 }
 
 // ddpg_cartpole.py:199-209: y = r + (mask*discount)*Q'(s2, mu'(s2)); td = Q - y; loss = mean(td^2);
-// dq = d loss / d Q = 2 td / B.
-__global__ __launch_bounds__(256) void td_kernel(const float* q, const float* tq, const float* r,
-                                                 const float* mask, float discount, int B, float* td,
-                                                 float* dq, float* loss) {
+// dq = d loss / d Q = 2 td / B.  WEIGHTED (prioritized replay): loss = mean(w td^2), dq = (td w) 2 / B.
+template <bool WEIGHTED>
+__device__ __forceinline__ void td_body(const float* q, const float* tq, const float* r, const float* mask, float discount, int B,
+                                        float* td, float* dq, float* loss, const float* w) {
   __shared__ double red[256];
   double s = 0.0;
   const float inv_b = 2.f / (float)B;
@@ -356,8 +356,13 @@ __global__ __launch_bounds__(256) void td_kernel(const float* q, const float* tq
     const float y = r[i] + (mask[i] * discount) * tq[i];
     const float t = q[i] - y;
     td[i] = t;
-    if (dq) dq[i] = t * inv_b;
-    s += (double)t * (double)t;
+    if (WEIGHTED) {
+      if (dq) dq[i] = (t * w[i]) * inv_b;
+      s += (double)w[i] * ((double)t * (double)t);
+    } else {
+      if (dq) dq[i] = t * inv_b;
+      s += (double)t * (double)t;
+    }
   }
   red[threadIdx.x] = s;
   __syncthreads();
@@ -368,11 +373,23 @@ __global__ __launch_bounds__(256) void td_kernel(const float* q, const float* tq
   if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)B);
 }
 
+__global__ __launch_bounds__(256) void td_kernel(const float* q, const float* tq, const float* r,
+                                                 const float* mask, float discount, int B, float* td,
+                                                 float* dq, float* loss) {
+  td_body<false>(q, tq, r, mask, discount, B, td, dq, loss, nullptr);
+}
+
+__global__ __launch_bounds__(256) void td_weighted_kernel(const float* q, const float* tq, const float* r, const float* mask, float discount,
+                                                          int B, float* td, float* dq, float* loss, const float* w) {
+  td_body<true>(q, tq, r, mask, discount, B, td, dq, loss, w);
+}
+
 int launch_td(cpp_ctx* ctx, const float* q, const float* tq, const float* r, const float* mask,
-              float discount, int B, float* td, float* dq, float* loss) {
+              float discount, int B, float* td, float* dq, float* loss, const float* w) {
   prof_begin(ctx);
-  hipLaunchKernelGGL(td_kernel, dim3(1), dim3(256), 0, ctx->stream, q, tq, r, mask, discount, B, td,
-                     dq, loss);
+  if (w) hipLaunchKernelGGL(td_weighted_kernel, dim3(1), dim3(256), 0, ctx->stream, q, tq, r, mask, discount, B, td, dq, loss, w);
+  else hipLaunchKernelGGL(td_kernel, dim3(1), dim3(256), 0, ctx->stream, q, tq, r, mask, discount, B, td,
+                          dq, loss);
   LAUNCH_CHECK();
   prof_end(ctx, K_TD);
   return 0;

@@ -6,7 +6,7 @@
 //   h3  = relu([h2c, a] W3 + b3),  dQ/da at a = mu(s1)     critic, 2nd evaluation -> actor's grad_ys = -dQ/da through tanh
 //   q   = relu([h2c, a_batch] W3 + b3) wq + bq             critic on the fed actions
 //   q'  = relu([h2c', a'] W3' + b3') wq' + bq'              target critic at the target actor's action
-//   td  = q - (r + mask discount q'),  loss = mean(td^2),  dz_q = 2 td / B
+//   td  = q - (r + mask discount q'),  loss = mean(td^2),  dz_q = 2 td / B   (prioritized replay: mean(w td^2), 2 td w / B)
 //   and one layer of both backward passes: dz of the critic's concat layer and of the layers feeding the two heads.
 // A team of 64 lanes (one wave) works on one row, a workgroup of 256 threads on 4 rows (grid = B / 4); the weights it needs sit
 // in LDS (lane t owns unit t of the concat layer and element t of every row vector).  The batch loss is
@@ -46,7 +46,8 @@ __device__ __forceinline__ float team_sum(float v) {
 
 // AT: compile-time bound of the action loops; EXACT: A == AT (the loops then carry no branches that keep the compiler from
 // batching their LDS reads and interleaving the team sums)
-template <int AT, bool EXACT>
+// WEIGHTED: prioritized replay's importance weight of the row scales its loss term and dz_q (the uniform instances never read h.w)
+template <int AT, bool EXACT, bool WEIGHTED>
 __global__ __launch_bounds__(HEADS_THREADS) void ddpg_heads_kernel(const DdpgHeadsArgs h) {
   extern __shared__ __attribute__((aligned(16))) float hl[];
   constexpr int N3P = HEADS_N3P;
@@ -121,6 +122,7 @@ __global__ __launch_bounds__(HEADS_THREADS) void ddpg_heads_kernel(const DdpgHea
 #pragma unroll
   for (int i = 0; i < AT; ++i) abv[i] = (rv && i < A) ? h.act[(long)row * A + i] : 0.f;
   const float rrow = rv ? h.r[row] : 0.f, mrow = rv ? h.mask[row] : 0.f;
+  const float wrow = (WEIGHTED && rv) ? h.w[row] : 1.f;
   static_assert(N3P + 1 <= HEADS_THREADS, "one q-layer weight per thread");
   const float wq_a = tid < n3 ? h.wq[tid] : (tid == N3P ? h.wq[n3] : 0.f), wqt_a = tid < n3 ? h.wq_t[tid] : (tid == N3P ? h.wq_t[n3] : 0.f);
   float wov[2], wotv[2];                               // (n2a + 1) * A <= 2 * 256
@@ -210,7 +212,7 @@ __global__ __launch_bounds__(HEADS_THREADS) void ddpg_heads_kernel(const DdpgHea
   for (int i = 0; i < AT; ++i)
     if (i < A) { dqda[i] = team_sum(dzm * W3[(n2c + i) * WS + t]); adz[i] = -dqda[i] * (1.f - a[i] * a[i]); }
   const float td = rv ? qb - (rrow + (mrow * h.discount) * qt) : 0.f;
-  const float dzq = td * (2.f / (float)h.B);
+  const float dzq = WEIGHTED ? (td * wrow) * (2.f / (float)h.B) : td * (2.f / (float)h.B);
   if (rv && t == 0) { h.td[row] = td; h.dzq[row] = dzq; h.q_out[row] = qb; h.tq_out[row] = qt; }
   if (rv && t < A) {
 #pragma unroll
@@ -266,7 +268,7 @@ __global__ __launch_bounds__(HEADS_THREADS) void ddpg_heads_kernel(const DdpgHea
   HCK();
   // ---- loss = mean(td^2): one partial per workgroup; the reader adds the partials in order (cpp_ddpg_last_stats)
   __shared__ double lred[HEADS_ROWS];
-  if (t == 0) lred[team] = (double)td * (double)td;
+  if (t == 0) lred[team] = WEIGHTED ? (double)wrow * ((double)td * (double)td) : (double)td * (double)td;
   __syncthreads();
   if (tid == 0) {
     double s = 0.0;
@@ -298,10 +300,12 @@ bool ddpg_heads_supported(const DdpgHeadsArgs& h) {
 int launch_ddpg_heads(cpp_ctx* ctx, const DdpgHeadsArgs& h) {
   const size_t lds = ddpg_heads_lds_bytes(h);
   typedef void (*kern_t)(const DdpgHeadsArgs);
-  static const kern_t kerns[6] = {ddpg_heads_kernel<1, true>, ddpg_heads_kernel<2, true>, ddpg_heads_kernel<4, true>,
-                                  ddpg_heads_kernel<8, true>, ddpg_heads_kernel<4, false>, ddpg_heads_kernel<8, false>};
-  const int ki = h.A == 1 ? 0 : h.A == 2 ? 1 : h.A == 4 ? 2 : h.A == 8 ? 3 : h.A == 3 ? 4 : 5;
-  static size_t attr[CPP_MAX_DEVICES][6] = {};      // (kernel attributes are per device)
+  static const kern_t kerns[12] = {ddpg_heads_kernel<1, true, false>, ddpg_heads_kernel<2, true, false>, ddpg_heads_kernel<4, true, false>,
+                                   ddpg_heads_kernel<8, true, false>, ddpg_heads_kernel<4, false, false>, ddpg_heads_kernel<8, false, false>,
+                                   ddpg_heads_kernel<1, true, true>, ddpg_heads_kernel<2, true, true>, ddpg_heads_kernel<4, true, true>,
+                                   ddpg_heads_kernel<8, true, true>, ddpg_heads_kernel<4, false, true>, ddpg_heads_kernel<8, false, true>};
+  const int ki = (h.A == 1 ? 0 : h.A == 2 ? 1 : h.A == 4 ? 2 : h.A == 8 ? 3 : h.A == 3 ? 4 : 5) + (h.w ? 6 : 0);
+  static size_t attr[CPP_MAX_DEVICES][12] = {};      // (kernel attributes are per device)
   size_t& have = attr[cpp_dev_slot(ctx)][ki];
   if (lds > have) {
     HIP_CHECK(hipFuncSetAttribute((const void*)kerns[ki], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -33,6 +33,9 @@ struct cpp_ddpg {
   int sq_cnt[2];           // norm partials the last gradient pass left per list in cpp_ctx::sq_part (<= 0: none, run the sumsq kernel)
   int pre_variant;         // variant of the next cpp_ddpg_sample_and_compute call if its key still matches (0: sample)
   int32_t* slot_set[2][2]; // the two sets of slot arrays of step_batch
+  // prioritized replay (step_body, per.hip): the importance weights the gradient pass reads, and the launch that follows the TD values
+  // of the minibatch (its priorities into the tree, the next minibatch's rows and weights)
+  const float* per_w; std::function<int()> per_hook;
   Arena arena;
 };
 
@@ -58,6 +61,7 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   d->h_replay_uid = 0; d->h_write_gen = 0; d->pre_variant = 0; d->h_B = 0; d->h_seed = 0;
   memset(d->slot_set, 0, sizeof(d->slot_set));
   d->heads_grid = d->heads_B = d->loss_parts = d->loss_B = 0;
+  d->per_w = nullptr;
   const int A = actor->spec.action_dim;
   int rc = dalloc(d->arena, &d->gradbuf, (size_t)(d->nA + d->nC));
   if (!rc) rc = dalloc(d->arena, &d->dq_da, (size_t)d->maxB * A);
@@ -413,6 +417,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     hd.q_out = c->ws[0].out; hd.tq_out = tc->ws[0].out; hd.td = d->td; hd.dzq = c->ws[0].dz[nc - 1];
     hd.dz3 = c->ws[0].dz[cat]; hd.dz2c = c->ws[0].dz[cat - 1];
     hd.loss_part = d->heads_part;
+    hd.w = d->per_w;
     fused = ddpg_heads_supported(hd);
     // the actors are one layer deeper than the critics' prefix (100-100-50 against 200-50): their last hidden layer joins the
     // heads kernel so that both stacks reach it, and leave it, in the same number of GEMM levels.  CPP_HEADS_PRE=0: GEMMs.
@@ -446,6 +451,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
       tcP = G.gemm(fc_fwd_args(tc, tc->ws[0], l, B), {tcP});
     }
     const int hk = G.fn([=] { return launch_ddpg_heads(ctx, hd); }, {aF, taF, cP, tcP});
+    if (d->per_hook) G.fn(d->per_hook, {hk});      // (prioritized replay: as soon as the TD values are known)
     // ---- actor backward below its head (the head's dX is part of the fused kernel)
     G.gemm(sqg(0, fc_dw_args(a, a->ws[0], na - 1, B, a->ws[0].dz[na - 1])), {hk});
     adz = hk;
@@ -530,8 +536,10 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   }
 
   // ---- TD target + critic backward on the first evaluation (fed actions)
+  const float* per_w = d->per_w;
   cdz = G.fn([=] { return launch_td(ctx, c->ws[0].out, tc->ws[0].out, b->r, b->m, d->hp.discount, B, d->td,
-                                        c->ws[0].dz[nc - 1], d->loss_norms); }, {c0, tcH});
+                                        c->ws[0].dz[nc - 1], d->loss_norms, per_w); }, {c0, tcH});
+  if (d->per_hook) G.fn(d->per_hook, {cdz});
   for (int l = nc - 1; l >= 0; --l) {
     const FcL& L = c->fc[l];
     G.gemm(sqg(1, fc_dw_args(c, c->ws[0], l, B, c->ws[0].dz[l])), {cdz});
@@ -612,12 +620,37 @@ static int step_body(cpp_ddpg* d, cpp_replay* r, int B, int n_batches, const int
   // optimiser kernel as before, so the rows drawn are the same.  Conv trunks on f16 / u8 stores; CPP_RIDE_GATHER=0: in sequence.
   static const bool no_ride = cpp_switch_off("CPP_RIDE_GATHER");
   const bool ride_ok = !no_ride && C > 0 && (r->store_dtype == CPP_F16 || r->store_dtype == CPP_U8);
-  RC(replay_sample_device(r, B, rows_dev, seed, rows_dev ? nullptr : r->counter, C, d->step_batch, direct));
+  // Prioritized memory (per.hip): minibatch i's rows are the caller's or a stratified draw by priority, keyed by the sampler's counter as
+  // the uniform draw is; its importance weights scale the critic's loss.  As soon as its TD values are known, ONE launch writes its
+  // priorities into the tree and draws minibatch i + 1 (counter + 1: the optimiser's launch moves the counter, as before) -- before the
+  // pass that gathers i + 1, wherever that rides.  The gathers take the drawn rows as a row list.
+  const bool per = r->per_tree != nullptr;
+  auto rows_of = [&](int i) -> const int32_t* { return rows_dev ? rows_dev + (size_t)i * B : per ? r->per_rows : nullptr; };
+  struct PerScope {
+    cpp_ddpg* d;
+    PerScope(cpp_ddpg* d_, cpp_replay* r_) : d(d_) { d->per_w = r_->per_tree ? r_->per_w : nullptr; }
+    ~PerScope() { d->per_w = nullptr; d->per_hook = nullptr; }
+  } per_scope(d, r);
+  if (per) {
+    PerArgs p = per_args(r);
+    p.B = B; p.w_rows = rows_dev; p.seed = seed; p.counter = rows_dev ? nullptr : r->counter; p.out_rows = r->per_rows; p.out_w = r->per_w;
+    RC(launch_per_update_sample(ctx, p));
+  }
+  RC(replay_sample_device(r, B, rows_of(0), seed, rows_of(0) ? nullptr : r->counter, C, d->step_batch, direct));
   for (int i = 0; i < n_batches; ++i) {
     GatherArgs ga; int Cg = 0;
     const bool more = i + 1 < n_batches;
+    if (per) {
+      PerArgs p = per_args(r);
+      p.up_rows = rows_of(i); p.n_up = B; p.up_td = d->td;
+      if (more) {
+        p.B = B; p.w_rows = rows_dev ? rows_of(i + 1) : nullptr; p.seed = seed; p.counter = rows_dev ? nullptr : r->counter; p.counter_add = 1;
+        p.out_rows = r->per_rows; p.out_w = r->per_w;
+      }
+      d->per_hook = [ctx, p] { return launch_per_update_sample(ctx, p); };
+    }
     if (more && ride_ok) {
-      ga = replay_gather_args(r, B, rows_dev ? rows_dev + (size_t)(i + 1) * B : nullptr, seed, rows_dev ? nullptr : r->counter, C,
+      ga = replay_gather_args(r, B, rows_of(i + 1), seed, rows_of(i + 1) ? nullptr : r->counter, C,
                               d->step_batch, direct, &Cg);
       ga.counter_add = 1;
       // with the slots double-buffered the pass can leave as early as conv1's dW (MFMA-bound, HBM idle, and its second
@@ -637,6 +670,7 @@ static int step_body(cpp_ddpg* d, cpp_replay* r, int B, int n_batches, const int
       ctx->st_ride = &sr; ctx->st_ride_done = false;
     }
     const int rc = compute_gradients(d, d->step_batch);
+    d->per_hook = nullptr;
     const bool rode = ctx->ride != nullptr && ctx->ride_done;
     const bool tables_done = ctx->st_ride != nullptr && ctx->st_ride_done && rode;
     ctx->ride = nullptr; ctx->st_ride = nullptr;
@@ -660,7 +694,7 @@ static int step_body(cpp_ddpg* d, cpp_replay* r, int B, int n_batches, const int
     if (more) {
       if (stats_ride) { d->step_batch->B = B; d->step_batch->dtype = CPP_F16; d->step_batch->stats_C = Cg; }     // (replay_sample_finish's bookkeeping)
       else if (rode) RC(replay_sample_finish(r, B, Cg, C, d->step_batch));
-      else RC(replay_sample_device(r, B, rows_dev ? rows_dev + (size_t)(i + 1) * B : nullptr, seed, rows_dev ? nullptr : r->counter, C,
+      else RC(replay_sample_device(r, B, rows_of(i + 1), seed, rows_of(i + 1) ? nullptr : r->counter, C,
                                    d->step_batch, direct));
     }
   }
@@ -680,6 +714,7 @@ extern "C" int cpp_ddpg_train_rows(cpp_ddpg* d, cpp_replay* r, int B, const int3
   ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_train_rows: batch %d outside [1,%d]", B, d->maxB);
   ARG_CHECK(r->elems == d->actor->state_elems && r->A == d->actor->spec.action_dim, "cpp_ddpg_train_rows: replay shape does not match the networks");
   if (r->size <= 0) { cpp_set_error("cpp_ddpg_train_rows: replay memory is empty"); return CPP_ERR_STATE; }
+  ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_ddpg_train_rows: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
   route_check(d);
   cpp_ctx* ctx = d->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
@@ -709,6 +744,7 @@ extern "C" int cpp_ddpg_train_step(cpp_ddpg* d, cpp_replay* r, int B, int n_batc
   ARG_CHECK(n_batches >= 1 && (size_t)n_batches * B <= 65536, "cpp_ddpg_train_step: n_batches %d", n_batches);
   ARG_CHECK(r->elems == d->actor->state_elems && r->A == d->actor->spec.action_dim, "cpp_ddpg_train_step: replay shape does not match the networks");
   if (r->size <= 0) { cpp_set_error("cpp_ddpg_train_step: replay memory is empty"); return CPP_ERR_STATE; }
+  ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_ddpg_train_step: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
   route_check(d);
   cpp_ctx* ctx = d->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
@@ -856,6 +892,7 @@ static int half_step_checks(cpp_ddpg* d, cpp_replay* r, int B, const char* who) 
 }
 
 extern "C" int cpp_ddpg_sample_and_compute(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed) {
+  RC(per_refuse(r, "cpp_ddpg_sample_and_compute"));
   if (d) route_check(d);
   RC(half_step_checks(d, r, B, "cpp_ddpg_sample_and_compute"));
   HIP_CHECK(hipSetDevice(d->ctx->device));
@@ -897,6 +934,7 @@ extern "C" int cpp_ddpg_average_params(cpp_ddpg* d, cpp_comm* c) {
 // comm == NULL: a single learner taking the same path (tests).  Whitening statistics and target updates are local.
 extern "C" int cpp_ddpg_dp_train_step(cpp_ddpg* d, cpp_replay* r, cpp_comm* c, int B, int n_batches, uint64_t seed,
                                       int sync_every, int overlap) {
+  RC(per_refuse(r, "cpp_ddpg_dp_train_step"));
   RC(half_step_checks(d, r, B, "cpp_ddpg_dp_train_step"));
   ARG_CHECK(n_batches >= 1 && sync_every >= 1, "cpp_ddpg_dp_train_step: n_batches %d, sync_every %d", n_batches, sync_every);
   ARG_CHECK(!c || c->ctx == d->ctx, "cpp_ddpg_dp_train_step: communicator and networks live on different contexts");

@@ -133,6 +133,11 @@ struct cpp_replay {
   // host-drawn minibatch rows on their way to rows_in (cpp_ddpg_train_rows / cpp_naf_train_rows): a ring of pinned slots, so that the
   // call returns while the previous minibatch is still running (a pageable hipMemcpyAsync would wait for the stream)
   int32_t* rows_pin; hipEvent_t rows_pin_ev[CPP_ROWS_RING]; bool rows_pin_used[CPP_ROWS_RING]; int rows_pin_k;
+  // prioritized replay (cpp_replay_enable_priorities; per.hip): nullptr tree = uniform memory
+  double* per_tree; int per_L; float per_alpha, per_eps;
+  float* per_maxp; float* per_beta;                        // device scalars (written by value, in stream order)
+  int32_t* per_rows; float* per_w;                         // the rows of the last draw and the importance weights of the last minibatch
+  int32_t* per_list; float* per_vals;                      // staging of host rows / values (cpp_replay_update_priorities, write_rows)
   Arena arena;
 };
 static size_t replay_esz(const cpp_replay* r) { return r->store_dtype == CPP_U8 ? 1 : sizeof(__half); }
@@ -230,6 +235,8 @@ int replay_sample_finish(cpp_replay* r, int B, int C, int channels, cpp_batch* o
 int replay_sample_device(cpp_replay* r, int B, const int32_t* rows_dev, uint64_t seed, const uint64_t* counter_dev, int channels, cpp_batch* out, bool direct = false,
                          uint64_t* bump = nullptr, bool* bumped = nullptr);
 int replay_stage_rows(cpp_replay* r, const int32_t* idxs, int n, const char* who);
+PerArgs per_args(const cpp_replay* r);            // the memory's tree, size word, maximum and beta; nothing to write, nothing to draw
+int per_refuse(const cpp_replay* r, const char* who);   // CPP_ERR_ARG (with the message) on a prioritized memory
 const float* white_of(cpp_batch* b, int which, int C);
 bool direct_replay_ok(cpp_net* a, cpp_replay* r, int B);
 

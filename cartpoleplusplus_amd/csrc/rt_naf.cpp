@@ -537,6 +537,7 @@ static int naf_step_body(cpp_naf* f, cpp_replay* r, int B, int n_batches, const 
 }
 
 extern "C" int cpp_naf_train_step(cpp_naf* f, cpp_replay* r, int B, int n_batches, const int32_t* idxs, uint64_t seed) {
+  RC(per_refuse(r, "cpp_naf_train_step"));      // (NAF under prioritized replay: not built)
   if (f) naf_route_check(f);
   ARG_CHECK(f && r, "cpp_naf_train_step: NULL argument");
   ARG_CHECK(B >= 1 && B <= f->maxB, "cpp_naf_train_step: batch %d outside [1,%d]", B, f->maxB);
@@ -587,6 +588,7 @@ static int naf_rows_body(cpp_naf* f, cpp_replay* r, int B, bool fold = false, bo
   return ctx_route_publish(f->ctx);
 }
 extern "C" int cpp_naf_train_rows(cpp_naf* f, cpp_replay* r, int B, const int32_t* idxs, float* loss) {
+  RC(per_refuse(r, "cpp_naf_train_rows"));      // (NAF under prioritized replay: not built)
   if (f) naf_route_check(f);
   ARG_CHECK(f && r && idxs, "cpp_naf_train_rows: NULL argument");
   ARG_CHECK(B >= 1 && B <= f->maxB, "cpp_naf_train_rows: batch %d outside [1,%d]", B, f->maxB);
@@ -633,6 +635,7 @@ static int naf_rows_apply_body(cpp_naf* f, cpp_replay* r, int B) {
   return naf_apply(f, 1.0f, true, nullptr, nullptr, 0, 0, 0, true);
 }
 extern "C" int cpp_naf_train_rows_async(cpp_naf* f, cpp_replay* r, int B, const int32_t* idxs, uint64_t* ticket) {
+  RC(per_refuse(r, "cpp_naf_train_rows_async"));      // (NAF under prioritized replay: not built)
   if (f) naf_route_check(f);
   ARG_CHECK(f && r && idxs && ticket, "cpp_naf_train_rows_async: NULL argument");
   ARG_CHECK(B >= 1 && B <= f->maxB, "cpp_naf_train_rows_async: batch %d outside [1,%d]", B, f->maxB);
@@ -705,6 +708,7 @@ static int naf_half_checks(cpp_naf* f, cpp_replay* r, int B, const char* who) {
 // sample B rows on the device (Philox; the counter advances by one) and leave the gradients of the three networks in the flat
 // buffer [value | mu | l_values]; hipGraph-captured after the first call per (B, seed, replay)
 extern "C" int cpp_naf_sample_and_compute(cpp_naf* f, cpp_replay* r, int B, uint64_t seed) {
+  RC(per_refuse(r, "cpp_naf_sample_and_compute"));      // (NAF under prioritized replay: not built)
   if (f) naf_route_check(f);
   RC(naf_half_checks(f, r, B, "cpp_naf_sample_and_compute"));
   cpp_ctx* ctx = f->ctx;
@@ -765,6 +769,7 @@ extern "C" int cpp_naf_dp_status(const cpp_naf* f, int* mode, char* reason, int 
 }
 
 extern "C" int cpp_naf_dp_train_step(cpp_naf* f, cpp_replay* r, cpp_comm* c, int B, int n_batches, uint64_t seed, int sync_every) {
+  RC(per_refuse(r, "cpp_naf_dp_train_step"));      // (NAF under prioritized replay: not built)
   if (f) naf_route_check(f);
   RC(naf_half_checks(f, r, B, "cpp_naf_dp_train_step"));
   ARG_CHECK(n_batches >= 1 && sync_every >= 1, "cpp_naf_dp_train_step: n_batches %d, sync_every %d", n_batches, sync_every);

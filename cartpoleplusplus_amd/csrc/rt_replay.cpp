@@ -1,6 +1,7 @@
 // minibatches resident in HBM (cpp_batch_*) and the replay memory payload (cpp_replay_*)
 #include "rt_internal.h"
 
+static int per_write(cpp_replay* r, const int32_t* rows, int n, const float* abs_td);
 // ---------------------------------------------------------------------------------------------
 // batch
 // ---------------------------------------------------------------------------------------------
@@ -108,6 +109,8 @@ static int replay_create(cpp_ctx* ctx, int buffer_size, int state_slots, int64_t
   r->store_dtype = store_dtype;
   r->slot_stats = nullptr; r->stats_C = 0; r->stats_cap = 0; r->sampled = false; r->slot_list = nullptr; r->slot_list_cap = 0;
   r->rows_pin = nullptr; r->rows_pin_k = 0; memset(r->rows_pin_used, 0, sizeof(r->rows_pin_used)); memset(r->rows_pin_ev, 0, sizeof(r->rows_pin_ev));
+  r->per_tree = nullptr; r->per_L = 0; r->per_alpha = r->per_eps = 0.f; r->per_maxp = r->per_beta = nullptr;
+  r->per_rows = nullptr; r->per_w = nullptr; r->per_list = nullptr; r->per_vals = nullptr;
   r->stage = nullptr; r->stage_cap = 0; r->pinned = nullptr; r->pinned_cap = 0; r->pinned_busy = false; r->lut = nullptr; r->bad = nullptr;
   HIP_CHECK(hipEventCreateWithFlags(&r->pinned_free, hipEventDisableTiming));
   int rc = r->arena.alloc(&r->store, (size_t)state_slots * state_elems * replay_esz(r), false);
@@ -287,6 +290,7 @@ extern "C" int cpp_replay_write_rows(cpp_replay* r, const int32_t* rows, int n, 
     HIP_CHECK(hipMemcpyAsync(r->mask + r0, mask + i, cnt * sizeof(float), hipMemcpyHostToDevice, st));
     i = j;
   }
+  if (r->per_tree) RC(per_write(r, rows, n, nullptr));      // (new rows, FIFO overwrites included: the running maximum)
   HIP_CHECK(hipStreamSynchronize(st));
   return CPP_OK;
 }
@@ -434,8 +438,15 @@ extern "C" int cpp_replay_sample(cpp_replay* r, int B, const int32_t* idxs, uint
     rows_dev = r->rows_in;
   } else {
     HIP_CHECK(hipMemcpyAsync(r->counter_adhoc, &counter, sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (r->per_tree) {          // prioritized memory: the stratified draw (per.hip) keyed by the same (seed, counter), then a gather of its rows
+      ARG_CHECK(B <= PER_MAX_ROWS, "cpp_replay_sample: a prioritized draw takes at most %d rows", PER_MAX_ROWS);
+      PerArgs p = per_args(r);
+      p.B = B; p.seed = seed; p.counter = r->counter_adhoc; p.out_rows = r->per_rows; p.out_w = r->per_w;
+      RC(launch_per_update_sample(r->ctx, p));
+      rows_dev = r->per_rows;
+    }
   }
-  RC(replay_sample_device(r, B, rows_dev, seed, idxs ? nullptr : r->counter_adhoc, channels, out));
+  RC(replay_sample_device(r, B, rows_dev, seed, rows_dev ? nullptr : r->counter_adhoc, channels, out));
   if (idxs) HIP_CHECK(hipStreamSynchronize(st));     // the caller's index array may go away after return
   return CPP_OK;
 }
@@ -456,7 +467,149 @@ extern "C" int cpp_replay_fill_synthetic(cpp_replay* r, int n_rows, uint64_t see
                         r->action, r->reward, r->mask, n_rows, r->A, seed));
   if (r->store_dtype == CPP_U8) RC(launch_replay_fill_u8(r->ctx, (uint8_t*)r->store, r->elems * (long)r->slots, seed));
   if (r->slot_stats && r->stats_C > 0) RC(launch_slot_stats(r->ctx, r->store, r->store_dtype, r->elems, r->stats_C, r->slot_stats, nullptr, 0, r->slots, r->lut));
+  if (r->per_tree) RC(launch_per_rebuild(r->ctx, r->per_tree, r->per_L, n_rows, r->per_maxp));
   HIP_CHECK(ctx_sync_stream(r->ctx));
   return replay_set_size(r, n_rows);
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// prioritized replay (per.hip): extensions, no reference counterpart
+// ---------------------------------------------------------------------------------------------
+PerArgs per_args(const cpp_replay* r) {
+  PerArgs p; memset(&p, 0, sizeof(p));
+  p.tree = r->per_tree; p.L = r->per_L; p.size_ptr = r->size_dev; p.maxp = r->per_maxp; p.beta = r->per_beta;
+  p.alpha = r->per_alpha; p.eps = r->per_eps;
+  return p;
+}
+
+int per_refuse(const cpp_replay* r, const char* who) {
+  if (r && r->per_tree) {
+    cpp_set_error("%s: prioritized replay is supported by the DDPG learner's cpp_ddpg_train_step / cpp_ddpg_train_rows only", who);
+    return CPP_ERR_ARG;
+  }
+  return CPP_OK;
+}
+
+// host rows -> leaves, in launches of PER_MAX_ROWS rows (in order: a later occurrence of a row still wins).  abs_td == nullptr: the
+// rows take the running maximum (new rows)
+static int per_write(cpp_replay* r, const int32_t* rows, int n, const float* abs_td) {
+  hipStream_t st = r->ctx->stream;
+  for (int i0 = 0; i0 < n; i0 += PER_MAX_ROWS) {
+    const int m = n - i0 < PER_MAX_ROWS ? n - i0 : PER_MAX_ROWS;
+    HIP_CHECK(hipMemcpyAsync(r->per_list, rows + i0, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (abs_td) HIP_CHECK(hipMemcpyAsync(r->per_vals, abs_td + i0, (size_t)m * sizeof(float), hipMemcpyHostToDevice, st));
+    PerArgs p = per_args(r);
+    p.up_rows = r->per_list; p.n_up = m; p.up_td = abs_td ? r->per_vals : nullptr;
+    RC(launch_per_update_sample(r->ctx, p));
+    HIP_CHECK(hipStreamSynchronize(st));       // (the staging buffers are reused by the next chunk)
+  }
+  return CPP_OK;
+}
+
+// *dst = v, in stream order, the value travelling with the call (no host buffer that must outlive it)
+static int per_write_scalar(cpp_replay* r, float* dst, float v) {
+  int32_t bits; memcpy(&bits, &v, sizeof(bits));
+  HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)dst, bits, 1, r->ctx->stream));
+  return CPP_OK;
+}
+
+extern "C" int cpp_replay_enable_priorities(cpp_replay* r, float alpha, float eps) {
+  ARG_CHECK(r, "cpp_replay_enable_priorities: NULL argument");
+  ARG_CHECK(alpha >= 0.f && std::isfinite(alpha), "cpp_replay_enable_priorities: alpha %g (must be >= 0)", alpha);
+  ARG_CHECK(alpha == 0.f || (eps > 0.f && std::isfinite(eps)), "cpp_replay_enable_priorities: eps %g (must be > 0 unless alpha == 0)", eps);
+  HIP_CHECK(hipSetDevice(r->ctx->device));
+  if (!r->per_tree) {
+    int L = 0;
+    while ((1L << L) < (long)r->rows) ++L;
+    HIP_CHECK(ctx_sync_stream(r->ctx));
+    RC(dalloc(r->arena, &r->per_tree, (size_t)2 << L));
+    RC(dalloc(r->arena, &r->per_maxp, (size_t)1));
+    RC(dalloc(r->arena, &r->per_beta, (size_t)1));
+    RC(dalloc(r->arena, &r->per_rows, (size_t)PER_MAX_ROWS));
+    RC(dalloc(r->arena, &r->per_w, (size_t)PER_MAX_ROWS));
+    RC(dalloc(r->arena, &r->per_list, (size_t)PER_MAX_ROWS));
+    RC(dalloc(r->arena, &r->per_vals, (size_t)PER_MAX_ROWS));
+    r->per_L = L;
+  }
+  r->per_alpha = alpha; r->per_eps = alpha == 0.f ? 0.f : eps;
+  // the captured step graphs hold the uniform sequence (and alpha / eps by value): a new uid makes every one of them be captured again
+  r->uid = replay_next_uid(); r->sampled = false;
+  ++r->write_gen;
+  RC(per_write_scalar(r, r->per_maxp, 1.0f));      // the running maximum starts at 1; every row in the memory takes it
+  HIP_CHECK(hipMemsetAsync(r->per_w, 0, PER_MAX_ROWS * sizeof(float), r->ctx->stream));
+  RC(launch_per_rebuild(r->ctx, r->per_tree, r->per_L, r->size, r->per_maxp));
+  HIP_CHECK(ctx_sync_stream(r->ctx));
+  return CPP_OK;
+}
+
+extern "C" int cpp_replay_set_priority_beta(cpp_replay* r, float beta) {
+  ARG_CHECK(r && r->per_tree, "cpp_replay_set_priority_beta: not a prioritized replay memory");
+  ARG_CHECK(beta >= 0.f && std::isfinite(beta), "cpp_replay_set_priority_beta: beta %g", beta);
+  HIP_CHECK(hipSetDevice(r->ctx->device));
+  // a stream-ordered write by value: the graph replays behind it read the new value, nothing is captured again, the host does not wait
+  return per_write_scalar(r, r->per_beta, beta);
+}
+
+extern "C" int cpp_replay_update_priorities(cpp_replay* r, const int32_t* rows, int n, const float* abs_td) {
+  ARG_CHECK(r && r->per_tree, "cpp_replay_update_priorities: not a prioritized replay memory");
+  ARG_CHECK(n >= 0 && (n == 0 || (rows && abs_td)), "cpp_replay_update_priorities: NULL argument");
+  for (int i = 0; i < n; ++i) {
+    ARG_CHECK(rows[i] >= 0 && rows[i] < r->size, "cpp_replay_update_priorities: row %d outside [0,%d)", rows[i], r->size);
+    ARG_CHECK(std::isfinite(abs_td[i]), "cpp_replay_update_priorities: |td| of row %d is not finite", rows[i]);
+  }
+  HIP_CHECK(hipSetDevice(r->ctx->device));
+  return per_write(r, rows, n, abs_td);
+}
+
+extern "C" int cpp_replay_read_priorities(cpp_replay* r, const int32_t* rows, int n, float* p) {
+  ARG_CHECK(r && r->per_tree, "cpp_replay_read_priorities: not a prioritized replay memory");
+  ARG_CHECK(n >= 0 && (n == 0 || (rows && p)), "cpp_replay_read_priorities: NULL argument");
+  for (int i = 0; i < n; ++i) ARG_CHECK(rows[i] >= 0 && rows[i] < r->rows, "cpp_replay_read_priorities: row %d outside [0,%d)", rows[i], r->rows);
+  HIP_CHECK(hipSetDevice(r->ctx->device));
+  // the n leaves only: one copy per run of consecutive rows
+  std::vector<double> leaves((size_t)n);
+  const double* leaf0 = r->per_tree + ((size_t)1 << r->per_L);
+  for (int i = 0; i < n;) {
+    int j = i + 1;
+    while (j < n && rows[j] == rows[j - 1] + 1) ++j;
+    HIP_CHECK(hipMemcpyAsync(leaves.data() + i, leaf0 + rows[i], (size_t)(j - i) * sizeof(double), hipMemcpyDeviceToHost, r->ctx->stream));
+    i = j;
+  }
+  HIP_CHECK(ctx_sync_stream(r->ctx));
+  for (int i = 0; i < n; ++i) p[i] = (float)leaves[i];
+  return CPP_OK;
+}
+
+extern "C" int cpp_replay_read_priority_tree(cpp_replay* r, double* out, int64_t cap) {
+  ARG_CHECK(r && r->per_tree && out, "cpp_replay_read_priority_tree: not a prioritized replay memory");
+  const int64_t words = (int64_t)2 << r->per_L;
+  ARG_CHECK(cap >= words, "cpp_replay_read_priority_tree: %ld words needed, %ld given", (long)words, (long)cap);
+  HIP_CHECK(hipSetDevice(r->ctx->device));
+  HIP_CHECK(hipMemcpyAsync(out, r->per_tree, (size_t)words * sizeof(double), hipMemcpyDeviceToHost, r->ctx->stream));
+  HIP_CHECK(ctx_sync_stream(r->ctx));
+  return CPP_OK;
+}
+
+extern "C" int cpp_replay_last_weights(cpp_replay* r, int B, float* w) {
+  ARG_CHECK(r && r->per_tree && w, "cpp_replay_last_weights: not a prioritized replay memory");
+  ARG_CHECK(B >= 1 && B <= PER_MAX_ROWS, "cpp_replay_last_weights: batch %d outside [1,%d]", B, PER_MAX_ROWS);
+  HIP_CHECK(hipSetDevice(r->ctx->device));
+  HIP_CHECK(hipMemcpyAsync(w, r->per_w, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, r->ctx->stream));
+  HIP_CHECK(ctx_sync_stream(r->ctx));
+  return CPP_OK;
+}
+
+extern "C" int cpp_replay_draw_prioritized(cpp_replay* r, int B, uint64_t seed, int32_t* idxs, float* w) {
+  ARG_CHECK(r && r->per_tree, "cpp_replay_draw_prioritized: not a prioritized replay memory");
+  ARG_CHECK(B >= 1 && B <= PER_MAX_ROWS, "cpp_replay_draw_prioritized: batch %d outside [1,%d]", B, PER_MAX_ROWS);
+  if (r->size <= 0) { cpp_set_error("cpp_replay_draw_prioritized: replay memory is empty"); return CPP_ERR_STATE; }
+  HIP_CHECK(hipSetDevice(r->ctx->device));
+  PerArgs p = per_args(r);
+  p.B = B; p.seed = seed; p.counter = r->counter; p.bump = 1; p.out_rows = r->per_rows; p.out_w = r->per_w;
+  RC(launch_per_update_sample(r->ctx, p));
+  if (idxs) HIP_CHECK(hipMemcpyAsync(idxs, r->per_rows, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, r->ctx->stream));
+  if (w) HIP_CHECK(hipMemcpyAsync(w, r->per_w, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, r->ctx->stream));
+  HIP_CHECK(ctx_sync_stream(r->ctx));
+  return CPP_OK;
+}

@@ -121,7 +121,33 @@ def build_parser():
       help="play the episodes on a rollout thread while the learner trains back to back (training_loop.py): the learner -- and, with "
            "--data-parallel, every other rank -- never waits for this process's environment once it is past burn-in")
     a('--synthetic-env', action='store_true', help="random-frame stand-in env (pybullet stays optional)")
+    # prioritized experience replay (an extension beyond the reference: Schaul et al. 2016, proportional; the sum tree on the GPU)
+    a('--prioritized-replay', action='store_true',
+      help="draw minibatches by priority (|td| + eps)^alpha and weight the critic's loss by the importance weights")
+    a('--priority-alpha', type=float, default=0.6, help="--prioritized-replay: priority exponent alpha")
+    a('--priority-beta', type=float, default=0.4, help="--prioritized-replay: importance-weight exponent beta at the start")
+    a('--priority-beta-final', type=float, default=1.0, help="--prioritized-replay: beta after --priority-beta-steps train steps")
+    a('--priority-beta-steps', type=int, default=100000,
+      help="--prioritized-replay: outer train steps over which beta moves linearly to --priority-beta-final")
+    a('--priority-eps', type=float, default=1e-6, help="--prioritized-replay: added to |td| before the exponent")
     return parser
+
+
+def priority_beta(o, train_steps):
+    """beta of the outer train step `train_steps` (linear from --priority-beta to --priority-beta-final)"""
+    n = max(1, int(o.priority_beta_steps))
+    f = min(1.0, max(0, int(train_steps)) / float(n))
+    return float(o.priority_beta) + f * (float(o.priority_beta_final) - float(o.priority_beta))
+
+
+def check_prioritized_opts(o):
+    """--prioritized-replay's refusals at startup"""
+    if not getattr(o, "prioritized_replay", False):
+        return
+    if o.host_rng_sampling:
+        raise SystemExit("--prioritized-replay draws minibatches by priority on the device: it cannot be combined with --host-rng-sampling")
+    if o.data_parallel:
+        raise SystemExit("--prioritized-replay is not supported by the data-parallel step (per-shard trees): drop --data-parallel")
 
 
 def default_opts(**overrides):
@@ -413,6 +439,9 @@ class CriticNetwork(base_network.Network):
         trainer = self._trainer()
         if isinstance(batch, replay_memory.Batch) and trainer.train_pair(batch):
             return                  # ran together with the actor's deferred update (ActorNetwork.train)
+        if isinstance(batch, replay_memory.Batch) and batch.weights is not None:
+            raise RuntimeError("a prioritized Batch trains as the reference's pair: actor.train(batch.state_1), then critic.train(batch) "
+                               "on the same draw (the weights and the priority updates belong to that fused minibatch)")
         dev = trainer.device_batch_for(batch)
         check(lib.cpp_ddpg_train_critic(trainer.handle, dev.handle))
         if opts.print_gradients:
@@ -443,6 +472,10 @@ class DeepDeterministicPolicyGradientAgent(object):
         # replay memory: f16 state store resident in HBM (ddpg_cartpole.py:257-261)
         self.replay_memory = replay_memory.ReplayMemory(opts.replay_memory_size, state_shape, action_dim,
                                                        store_dtype=opts.replay_store)
+        if getattr(opts, "prioritized_replay", False):
+            check_prioritized_opts(opts)
+            self.replay_memory.enable_priorities(opts.priority_alpha, opts.priority_eps, seed=opts.sample_seed)
+            self.replay_memory.set_priority_beta(priority_beta(opts, 0))
         # s1 and s2 placeholders
         batched_state_shape = [None] + list(state_shape)
         s1 = base_network.Placeholder(batched_state_shape)
@@ -509,6 +542,8 @@ class DeepDeterministicPolicyGradientAgent(object):
 
     def _train_once(self, batch_size, batches_per_step):
         """the inner step ddpg_cartpole.py:331-337; returns the losses it logs (B10: the last minibatch's TD loss)."""
+        if getattr(opts, "prioritized_replay", False):
+            self.replay_memory.set_priority_beta(priority_beta(opts, self.train_steps))
         if opts.host_rng_sampling:
             for _ in range(batches_per_step):
                 batch = self.replay_memory.batch(batch_size)
@@ -609,6 +644,7 @@ def main(argv=None):
         # the host-RNG path is the reference's literal loop: local actor.train / critic.train calls with no all-reduce -- N learners
         # would agree on when to train (LoopAgreement) and silently train N different networks
         raise SystemExit("--data-parallel draws minibatches with the device sampler inside the collective step: it cannot be combined with --host-rng-sampling")
+    check_prioritized_opts(opts)
     sys.stderr.write("%s\n" % opts)
     env = make_env(opts)
     agent = DeepDeterministicPolicyGradientAgent(env=env)

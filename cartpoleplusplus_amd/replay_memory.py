@@ -113,6 +113,7 @@ class Batch(object):
         self._small = small                       # {"action", "reward", "terminal_mask"}: host arrays this Batch owns
         self._states = None                       # {"state_1", "state_2"} once downloaded
         self._gen = memory._write_gen if memory is not None else None
+        self.weights = None                       # prioritized draws: the rows' importance weights, (B,) f32 (None: uniform draw)
 
     @classmethod
     def empty(cls, state_shape, action_dim):
@@ -317,6 +318,8 @@ class ReplayMemory(object):
         self._write_gen = 0          # bumped by every write of states (add_episode, fill_synthetic)
         self._drawn = weakref.WeakSet()   # Batches drawn since the last write (preserved before the next one, see Batch)
         self._adhoc_counter = 0      # sample_on_device draws (separate from the train steps' device counter)
+        self.prioritized = False     # enable_priorities: proportional prioritized replay, the sum tree on the device
+        self.priority_seed = 0
         # pixel states (H, W, 3, cameras, repeats): channel count for the fused whitening statistics
         self.channels = int(np.prod(self.state_shape[2:])) if len(self.state_shape) == 5 else 0
         if self.channels > 0:        # per-state whitening sums, kept by the store: sampling never re-reads the pixels for them
@@ -435,8 +438,17 @@ class ReplayMemory(object):
     def batch(self, batch_size=None, idxs=None):
         """replay_memory.py:131-138.  Rows come from numpy's global RNG exactly like the reference (`idxs=` overrides, as
         replay_memory_test.py:84 expects).  No device work happens here: the returned Batch is the draw, its state columns are
-        read (or trained on) where they lie."""
+        read (or trained on) where they lie.  A prioritized memory (enable_priorities) draws on the device instead: by priority,
+        keyed by the memory's seed and the train steps' sampler counter (the rows agent.train_step would draw next); the Batch
+        carries the rows' importance weights (`weights`)."""
         self.stats[">batch"] += 1
+        if idxs is None and self.prioritized and self.size() > 0:
+            B = int(batch_size)
+            idxs, w = np.empty(B, np.int32), np.empty(B, np.float32)
+            check(lib.cpp_replay_draw_prioritized(self.handle, B, int(self.priority_seed), ptr(idxs), ptr(w)))
+            b = self._new_batch(idxs)
+            b.weights = w
+            return b
         if idxs is None:
             idxs = self.random_indexes(batch_size)
         idxs = np.ascontiguousarray(np.asarray(idxs, dtype=np.int64).astype(np.int32))
@@ -464,6 +476,44 @@ class ReplayMemory(object):
         b = self._new_batch(idxs)
         dev.set_owner(b)
         return b
+
+    # --- prioritized replay (extension: the reference samples uniformly) ---------------------------------------------------------
+    def enable_priorities(self, alpha, eps=1e-6, seed=0):
+        """proportional prioritized replay (Schaul et al. 2016) for this memory: a sum tree of the rows' priorities on the device
+        (include/cartpolepp_abi.h, DESIGN "Prioritized replay").  Every row in the memory, and every row written later, takes the
+        running maximum priority (1.0 at first).  `seed` keys batch()'s draws; use the train step's sample seed for the same stream."""
+        check(lib.cpp_replay_enable_priorities(self.handle, float(alpha), float(eps)))
+        self.prioritized, self.priority_seed = True, int(seed)
+
+    def set_priority_beta(self, beta):
+        """the importance-weight exponent of the following draws and train steps (a device scalar: no graph is captured again)"""
+        check(lib.cpp_replay_set_priority_beta(self.handle, float(beta)))
+
+    def update_priorities(self, idxs, abs_td):
+        """p = (|td| + eps)^alpha for rows `idxs` (a row listed twice takes its last value)"""
+        idxs = np.ascontiguousarray(np.asarray(idxs).reshape(-1), dtype=np.int32)
+        v = np.ascontiguousarray(np.abs(np.asarray(abs_td, np.float32).reshape(-1)))
+        assert len(idxs) == len(v), (len(idxs), len(v))
+        check(lib.cpp_replay_update_priorities(self.handle, ptr(idxs), len(idxs), ptr(v)))
+
+    def priorities(self, idxs):
+        idxs = np.ascontiguousarray(np.asarray(idxs).reshape(-1), dtype=np.int32)
+        out = np.empty(len(idxs), np.float32)
+        check(lib.cpp_replay_read_priorities(self.handle, ptr(idxs), len(idxs), ptr(out)))
+        return out
+
+    def priority_tree(self):
+        """the device's sum tree, 2^(L+1) f64 words in heap layout (node 1 = root, leaf i at 2^L + i)"""
+        L = max(0, int(self.buffer_size - 1).bit_length())
+        out = np.empty(2 << L, np.float64)
+        check(lib.cpp_replay_read_priority_tree(self.handle, ptr(out), len(out)))
+        return out
+
+    def last_weights(self, B):
+        """the importance weights of the last prioritized draw / minibatch"""
+        out = np.empty(int(B), np.float32)
+        check(lib.cpp_replay_last_weights(self.handle, int(B), ptr(out)))
+        return out
 
     def fill_synthetic(self, n_rows, seed=1234):
         """bench/test helper: synthetic transitions generated on the device.  The host bookkeeping is advanced to

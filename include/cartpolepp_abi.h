@@ -215,6 +215,42 @@ int cpp_replay_last_indexes(cpp_replay* replay, int B, int32_t* out);   /* rows 
  * states f16(k/255), k~U{0..255}; a~U(-1,1); reward 1; terminal w.p. 1/50; s2 = s1 slot + 1. */
 int cpp_replay_fill_synthetic(cpp_replay* replay, int n_rows, uint64_t seed);
 
+/* ---- prioritized experience replay (Schaul et al. 2016, proportional variant) on the device ----------------------------------
+ * Extension, no reference counterpart (the reference samples uniformly, replay_memory.py:123-129).  Opt-in per memory; a memory
+ * without cpp_replay_enable_priorities behaves exactly as before.  Semantics:
+ *  - Tree: complete binary sum tree in f64, heap layout: node 1 is the root, leaf i at node 2^L + i (2^L >= buffer_size) holds
+ *    (double)p_i, p_i row i's f32 priority; every inner node is left + right of its final children (order-independent contents).
+ *  - Priority from TD: p = powf(|td| + eps, alpha) in f32 (alpha == 1: |td| + eps exactly; alpha == 0: 1.0f exactly).
+ *  - Duplicates: a row listed twice in one update takes the priority of its LAST occurrence.
+ *  - New rows (cpp_replay_write_rows, cpp_replay_fill_synthetic, FIFO overwrites included) take the running maximum priority: a
+ *    device scalar that starts at 1.0 and is the max of every priority written since (all entries of an update, duplicates included).
+ *    Enabling gives every row already in the memory that maximum; rows >= size hold 0 and are never drawn.
+ *  - Draw (stratified) of minibatch row b: r = philox4x32_10({b, 1, lo(counter), hi(counter)}, seed) (word 1 = 1: disjoint from the
+ *    uniform sampler's stream), U = (double)(((uint64)r.x << 32 | r.y) >> 11) * 2^-53, u = ((double)b + U) * (total / (double)B);
+ *    from the root go left if u < left, else u -= left and go right.  Top-end guard: a leaf at or past `size` (rounding) is
+ *    replaced by the last row, size - 1.  The counter advances by one per minibatch, as the uniform sampler's.
+ *  - Importance weights: w_b = pow(size * leaf_b / total, -beta) in f64, divided by the batch maximum, stored as f32.  beta is a
+ *    device scalar; setting it is a stream-ordered write, captured graph replays read the new value.
+ *  - DDPG: critic loss mean(w td^2), dz_q = (td w) 2 / B (w == 1: today's bits); cpp_ddpg_last_stats()[0] is the weighted loss; the
+ *    actor's update is unweighted.  The priorities of minibatch k are in the tree before minibatch k+1 is drawn, in the fused step
+ *    (cpp_ddpg_train_step) and in the literal loop (cpp_replay_draw_prioritized + cpp_ddpg_train_rows) alike: the same rows.
+ *  - cpp_replay_sample(idxs == NULL) draws by priority (key (seed, counter) as given).  cpp_ddpg_dp_train_step,
+ *    cpp_ddpg_sample_and_compute and the cpp_naf_* train entry points return CPP_ERR_ARG on a prioritized memory, writing nothing.
+ * Batches of a prioritized memory hold at most 1024 rows. */
+/* alpha >= 0; eps > 0 unless alpha == 0.  Called again: new alpha / eps, the maximum back to 1.0 and every row at it. */
+int cpp_replay_enable_priorities(cpp_replay* replay, float alpha, float eps);
+int cpp_replay_set_priority_beta(cpp_replay* replay, float beta);           /* beta >= 0 (0 until set) */
+/* the priorities of n rows from |td| values (abs_td >= 0), the duplicate rule above */
+int cpp_replay_update_priorities(cpp_replay* replay, const int32_t* rows, int n, const float* abs_td);
+int cpp_replay_read_priorities(cpp_replay* replay, const int32_t* rows, int n, float* p);
+/* the whole tree, 2^(L+1) doubles (node 0 unused, 0): tests */
+int cpp_replay_read_priority_tree(cpp_replay* replay, double* out, int64_t cap);
+/* importance weights of the last prioritized draw or minibatch (B <= 1024) */
+int cpp_replay_last_weights(cpp_replay* replay, int B, float* w);
+/* the literal loop's draw: B rows by priority keyed (seed, the training sampler's counter), which then advances by one -- the rows
+ * cpp_ddpg_train_step would draw for its next minibatch; rows and weights come back to the host (either may be NULL) */
+int cpp_replay_draw_prioritized(cpp_replay* replay, int B, uint64_t seed, int32_t* idxs, float* w);
+
 /* ---- DDPG train ops (ddpg_cartpole.py:102-119, :186-248, :329-337) --------------------------- */
 typedef struct cpp_ddpg_hyper {
   float actor_learning_rate;     /* --actor-learning-rate  (ddpg_cartpole.py:41)  */
