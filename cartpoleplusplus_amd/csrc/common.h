@@ -448,6 +448,9 @@ struct PerArgs {
   uint64_t seed; uint64_t* counter; int counter_add, bump;   // draw key: (seed, *counter + counter_add); bump: ++*counter after it
   const float* beta;
   int32_t* out_rows; float* out_w;
+  // optional device flag (NAF's check_numerics flag): non-zero = phases 1-2 stand down (no leaf, no ancestor, no maximum is written); the
+  // rows and weights of phases 3-4 are still produced
+  const int* skip_if_set;
 };
 int launch_per_update_sample(cpp_ctx* ctx, const PerArgs& a);
 int launch_per_rebuild(cpp_ctx* ctx, double* tree, int L, long n, const float* maxp);
@@ -460,7 +463,10 @@ struct NafHeadArgs {
   float* d_value; float* d_mu_z; float* d_l;        // nullptr: forward only
   int* nonfinite;                                   // set to 1 when l_values / L / loss are not finite
 };
-int launch_naf_head(cpp_ctx* ctx, const NafHeadArgs& a);
+// w: the rows' importance weights (prioritized replay, per.hip): loss = mean(w td^2), dQ = (td w) 2 / B -- the weighted instances,
+// which take the arguments with w appended (the uniform instances' argument layout stays as it is)
+struct NafHeadWArgs : NafHeadArgs { const float* w; };
+int launch_naf_head(cpp_ctx* ctx, const NafHeadArgs& a, const float* w = nullptr);
 // NAF with the shared representation (naf_cartpole.py:151-152, :176-177), everything between the last hidden layer and the layer
 // below it in ONE row-local launch (gemm.hip: naf_heads_kernel): the four head layers (value, mu, l_values on state_1, the target
 // value on state_2), naf_head_kernel's body, and d(representation) = the three heads' contributions in the order value, mu,
@@ -488,10 +494,12 @@ struct NafMlpArgs {
   float* h1_out; long ld1;                           // the live representation, where the heads' dW GEMMs read it (B x (rep + 1))
   float* dz0;                                        // B x n0: dz of the first hidden layer
 };
+struct NafHeadsWArgs : NafHeadsArgs { const float* w; };      // (launch_naf_heads / launch_naf_mlp with weights: as NafHeadWArgs)
+struct NafMlpWArgs : NafMlpArgs { const float* w; };
 bool naf_mlp_supported(const NafMlpArgs& m);
-int launch_naf_mlp(cpp_ctx* ctx, const NafMlpArgs& m);
+int launch_naf_mlp(cpp_ctx* ctx, const NafMlpArgs& m, const float* w = nullptr);      // w: as launch_naf_head
 bool naf_heads_supported(const NafHeadsArgs& a);
-int launch_naf_heads(cpp_ctx* ctx, const NafHeadsArgs& a);
+int launch_naf_heads(cpp_ctx* ctx, const NafHeadsArgs& a, const float* w = nullptr);  // w: as launch_naf_head
 
 // ---------------------------------------------------------------------------------------------
 // launch bookkeeping

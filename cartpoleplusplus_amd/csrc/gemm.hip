@@ -4,6 +4,7 @@
 // layout stores "<scope>/biases" directly after "<scope>/weights", so [W; b] is one (n_in+1, n_out)
 // matrix and every activation buffer carries a constant 1.0 in its last column -- forward bias add,
 // db = sum(dz) and dW = x^T dz all fall out of the same GEMM.
+#include <type_traits>
 #include "common.h"
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
@@ -401,8 +402,13 @@ int launch_td(cpp_ctx* ctx, const float* q, const float* tq, const float* r, con
 //   y = r + (mask*discount)*V'(s2); td = Q - y; loss = mean(td^2)
 // backward of the loss: dQ = 2 td / B; dz = -z dQ; dL[i][j] = d_i dz_j; dd = L dz;
 //   dl(off-diag) = dL, dl(diag) = dL * exp(l); d_mu = -dd, pushed through tanh: * (1 - mu^2).
+// Args = NafHeadWArgs (prioritized replay, per.hip): the row's importance weight w scales its loss term and dQ = (td w) 2 / B; everything
+// below dQ inherits it.  The three NAF head paths' weighted instances take the arguments with w appended (common.h: NafHeadWArgs,
+// NafHeadsWArgs, NafMlpWArgs); the uniform instances keep their argument layout, and with it their instructions.
 #define NAF_MAX_A 8
-__global__ __launch_bounds__(256) void naf_head_kernel(const NafHeadArgs a) {
+template <class Args>
+__global__ __launch_bounds__(256) void naf_head_kernel(const Args a) {
+  constexpr bool WEIGHTED = std::is_same<Args, NafHeadWArgs>::value;
   __shared__ double red[256];
   __shared__ int bad;
   if (threadIdx.x == 0) bad = 0;
@@ -435,9 +441,11 @@ __global__ __launch_bounds__(256) void naf_head_kernel(const NafHeadArgs a) {
     if (a.adv) a.adv[b] = adv;
     if (a.q) a.q[b] = q;
     if (a.td) a.td[b] = td;
-    s += (double)td * (double)td;
+    float wb = 1.f;
+    if constexpr (WEIGHTED) wb = a.w[b];
+    s += WEIGHTED ? (double)wb * ((double)td * (double)td) : (double)td * (double)td;
     if (a.d_value) {
-      const float dq = td * inv_b;
+      const float dq = WEIGHTED ? (td * wb) * inv_b : td * inv_b;
       a.d_value[b] = dq;
       float dz[NAF_MAX_A];
       for (int j = 0; j < A; ++j) dz[j] = -z[j] * dq;
@@ -466,10 +474,15 @@ __global__ __launch_bounds__(256) void naf_head_kernel(const NafHeadArgs a) {
   }
 }
 
-int launch_naf_head(cpp_ctx* ctx, const NafHeadArgs& a) {
+int launch_naf_head(cpp_ctx* ctx, const NafHeadArgs& a, const float* w) {
   if (a.A > NAF_MAX_A) { cpp_set_error("naf head: action_dim %d > %d", a.A, NAF_MAX_A); return 1; }
   prof_begin(ctx);
-  hipLaunchKernelGGL(naf_head_kernel, dim3(1), dim3(256), 0, ctx->stream, a);
+  if (w) {
+    NafHeadWArgs wa; static_cast<NafHeadArgs&>(wa) = a; wa.w = w;
+    hipLaunchKernelGGL(naf_head_kernel<NafHeadWArgs>, dim3(1), dim3(256), 0, ctx->stream, wa);
+  } else {
+    hipLaunchKernelGGL(naf_head_kernel<NafHeadArgs>, dim3(1), dim3(256), 0, ctx->stream, a);
+  }
   LAUNCH_CHECK();
   prof_end(ctx, K_NAF_HEAD);
   return 0;
@@ -487,11 +500,13 @@ int launch_naf_head(cpp_ctx* ctx, const NafHeadArgs& a) {
 // address).  A variant with the rows in registers (per-lane 16-byte loads, no LDS) and the weights through the scalar cache was
 // slower (16 us: 64 cache lines per load instruction, a scalar round trip per chunk of weights).
 // loss = mean(td^2): with several workgroups each writes its partial through and the last one to arrive adds them in order.
+// Args = NafHeadsWArgs: mean(w td^2) and dQ = (td w) 2 / B, the row's weight one more load beside its reward (naf_head_kernel).
 constexpr int NAFH_ROWS = 256, NAFH_THREADS = 256, NAFH_XI = 16, NAFH_WL = 4;
 typedef float nafh_f4 __attribute__((ext_vector_type(4)));
 typedef unsigned nafh_u4 __attribute__((ext_vector_type(4)));
-template <int AT>
-__global__ __launch_bounds__(NAFH_THREADS) void naf_heads_kernel(const NafHeadsArgs a) {
+template <int AT, class Args>
+__global__ __launch_bounds__(NAFH_THREADS) void naf_heads_kernel(const Args a) {
+  constexpr bool WEIGHTED = std::is_same<Args, NafHeadsWArgs>::value;
   extern __shared__ __attribute__((aligned(16))) float nl[];
   constexpr int A = AT, NL = A * (A + 1) / 2, NO = 1 + A + NL, NO4 = (NO + 3) / 4;
   static_assert(NO + 1 <= 16, "head values per row");
@@ -536,6 +551,8 @@ __global__ __launch_bounds__(NAFH_THREADS) void naf_heads_kernel(const NafHeadsA
 #pragma unroll
   for (int i = 0; i < A; ++i) act[i] = rv ? a.action[(long)b * A + i] : 0.f;
   const float rew = rv ? a.reward[b] : 0.f, msk = rv ? a.mask[b] : 0.f;
+  float wrow = 1.f;
+  if constexpr (WEIGHTED) wrow = rv ? a.w[b] : 1.f;
   // ---- into LDS
   for (int i = tid; i < 32 * KP; i += NAFH_THREADS) wT[i] = 0.f;         // wT and wB (wT: rows NO + 1 .. 15 and k >= K stay zero)
   __syncthreads();
@@ -620,8 +637,8 @@ __global__ __launch_bounds__(NAFH_THREADS) void naf_heads_kernel(const NafHeadsA
     if (a.adv) a.adv[b] = adv;
     if (a.q) a.q[b] = qv;
     if (a.td) a.td[b] = td;
-    s2 = (double)td * (double)td;
-    const float dq = td * (2.f / (float)a.B);
+    s2 = WEIGHTED ? (double)wrow * ((double)td * (double)td) : (double)td * (double)td;
+    const float dq = WEIGHTED ? (td * wrow) * (2.f / (float)a.B) : td * (2.f / (float)a.B);
     a.d_value[b] = dq;
     float dz[A];
 #pragma unroll
@@ -727,19 +744,30 @@ bool naf_heads_supported(const NafHeadsArgs& a) {
          (a.B + NAFH_ROWS - 1) / NAFH_ROWS <= NAF_HEADS_MAX_WGS && naf_heads_lds(a) <= 150 * 1024;
 }
 
-int launch_naf_heads(cpp_ctx* ctx, const NafHeadsArgs& a) {
+int launch_naf_heads(cpp_ctx* ctx, const NafHeadsArgs& a, const float* w) {
   const size_t lds = naf_heads_lds(a);
   typedef void (*kern_t)(const NafHeadsArgs);
-  static const kern_t kerns[4] = {naf_heads_kernel<1>, naf_heads_kernel<2>, naf_heads_kernel<3>, naf_heads_kernel<4>};
+  typedef void (*wkern_t)(const NafHeadsWArgs);
+  static const kern_t kerns[4] = {naf_heads_kernel<1, NafHeadsArgs>, naf_heads_kernel<2, NafHeadsArgs>, naf_heads_kernel<3, NafHeadsArgs>,
+                                  naf_heads_kernel<4, NafHeadsArgs>};
+  static const wkern_t wkerns[4] = {naf_heads_kernel<1, NafHeadsWArgs>, naf_heads_kernel<2, NafHeadsWArgs>, naf_heads_kernel<3, NafHeadsWArgs>,
+                                    naf_heads_kernel<4, NafHeadsWArgs>};
   if (a.A < 1 || a.A > 4) { cpp_set_error("naf heads: action_dim %d", a.A); return 1; }
-  static size_t attr[CPP_MAX_DEVICES][4] = {};
-  size_t& have = attr[cpp_dev_slot(ctx)][a.A - 1];
+  static size_t attr[CPP_MAX_DEVICES][8] = {};
+  size_t& have = attr[cpp_dev_slot(ctx)][a.A - 1 + (w ? 4 : 0)];
+  const void* kf = w ? (const void*)wkerns[a.A - 1] : (const void*)kerns[a.A - 1];
   if (lds > have) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)kerns[a.A - 1], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_CHECK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     have = lds;
   }
   prof_begin(ctx);
-  hipLaunchKernelGGL(kerns[a.A - 1], dim3((a.B + NAFH_ROWS - 1) / NAFH_ROWS), dim3(NAFH_THREADS), lds, ctx->stream, a);
+  const dim3 grid((a.B + NAFH_ROWS - 1) / NAFH_ROWS);
+  if (w) {
+    NafHeadsWArgs wa; static_cast<NafHeadsArgs&>(wa) = a; wa.w = w;
+    hipLaunchKernelGGL(wkerns[a.A - 1], grid, dim3(NAFH_THREADS), lds, ctx->stream, wa);
+  } else {
+    hipLaunchKernelGGL(kerns[a.A - 1], grid, dim3(NAFH_THREADS), lds, ctx->stream, a);
+  }
   LAUNCH_CHECK();
   prof_end(ctx, K_NAF_HEAD);
   return 0;
@@ -758,8 +786,10 @@ int launch_naf_heads(cpp_ctx* ctx, const NafHeadsArgs& a) {
 // to arrive adds them in order (at most B / 16 of them).
 constexpr int NAFM_S1 = 26, NAFM_S2 = 13, NAFM_LD = 52, NAFM_XS = 105, NAFM_XL = 7;   // XL: ceil(16 * 104 / 256) staged elements per thread
 // S1, S2:      // k steps of layer 1 (n0 + 1 <= 104) and of the heads / dX (n1 + 1 <= 52); LDS row stride
-template <int AT>
-__global__ __launch_bounds__(256) void naf_mlp_kernel(const NafMlpArgs m) {
+// Args = NafMlpWArgs: weighted as naf_heads_kernel.
+template <int AT, class Args>
+__global__ __launch_bounds__(256) void naf_mlp_kernel(const Args m) {
+  constexpr bool WEIGHTED = std::is_same<Args, NafMlpWArgs>::value;
   const NafHeadsArgs& a = m.h;
   constexpr int A = AT, NL = A * (A + 1) / 2, NO = 1 + A + NL;
   static_assert(NO <= 15, "head values per row");
@@ -844,6 +874,8 @@ __global__ __launch_bounds__(256) void naf_mlp_kernel(const NafMlpArgs m) {
 #pragma unroll
   for (int i = 0; i < A; ++i) act[i] = hrv ? a.action[(long)hrow * A + i] : 0.f;
   const float rew = hrv ? a.reward[hrow] : 0.f, msk = hrv ? a.mask[hrow] : 0.f;
+  float wrow = 1.f;
+  if constexpr (WEIGHTED) wrow = hrv ? m.w[hrow] : 1.f;
   // LDS: zero, the bias inputs
   for (int i = tid; i < 16 * NAFM_LD; i += 256) {
     const float one = (i % NAFM_LD) == n1 ? 1.f : 0.f;
@@ -928,8 +960,8 @@ __global__ __launch_bounds__(256) void naf_mlp_kernel(const NafMlpArgs m) {
     if (a.adv) a.adv[b] = adv;
     if (a.q) a.q[b] = qv;
     if (a.td) a.td[b] = td;
-    s2 = (double)td * (double)td;
-    const float dq = td * (2.f / (float)a.B);
+    s2 = WEIGHTED ? (double)wrow * ((double)td * (double)td) : (double)td * (double)td;
+    const float dq = WEIGHTED ? (td * wrow) * (2.f / (float)a.B) : td * (2.f / (float)a.B);
     a.d_value[b] = dq;
     float dz[A], dzr[NO];
 #pragma unroll
@@ -1022,13 +1054,22 @@ bool naf_mlp_supported(const NafMlpArgs& m) {
          a.drep && m.dz0 && m.h1_out && a.ldd == a.rep && (a.B + 15) / 16 <= NAF_HEADS_MAX_WGS;
 }
 
-int launch_naf_mlp(cpp_ctx* ctx, const NafMlpArgs& m) {
+int launch_naf_mlp(cpp_ctx* ctx, const NafMlpArgs& m, const float* w) {
   typedef void (*kern_t)(const NafMlpArgs);
-  static const kern_t kerns[4] = {naf_mlp_kernel<1>, naf_mlp_kernel<2>, naf_mlp_kernel<3>, naf_mlp_kernel<4>};
+  typedef void (*wkern_t)(const NafMlpWArgs);
+  static const kern_t kerns[4] = {naf_mlp_kernel<1, NafMlpArgs>, naf_mlp_kernel<2, NafMlpArgs>, naf_mlp_kernel<3, NafMlpArgs>,
+                                  naf_mlp_kernel<4, NafMlpArgs>};
+  static const wkern_t wkerns[4] = {naf_mlp_kernel<1, NafMlpWArgs>, naf_mlp_kernel<2, NafMlpWArgs>, naf_mlp_kernel<3, NafMlpWArgs>,
+                                    naf_mlp_kernel<4, NafMlpWArgs>};
   const int A = m.h.A;
   if (A < 1 || A > 4) { cpp_set_error("naf mlp: action_dim %d", A); return 1; }
   prof_begin(ctx);
-  hipLaunchKernelGGL(kerns[A - 1], dim3((m.h.B + 15) / 16), dim3(256), 0, ctx->stream, m);
+  if (w) {
+    NafMlpWArgs wa; static_cast<NafMlpArgs&>(wa) = m; wa.w = w;
+    hipLaunchKernelGGL(wkerns[A - 1], dim3((m.h.B + 15) / 16), dim3(256), 0, ctx->stream, wa);
+  } else {
+    hipLaunchKernelGGL(kerns[A - 1], dim3((m.h.B + 15) / 16), dim3(256), 0, ctx->stream, m);
+  }
   LAUNCH_CHECK();
   prof_end(ctx, K_NAF_HEAD);
   return 0;

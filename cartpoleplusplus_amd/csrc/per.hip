@@ -5,6 +5,7 @@
 // (double)p_i; every inner node is left + right of its final children, so the tree does not depend on the order threads run in.
 //
 // per_update_sample_kernel: ONE workgroup per launch, four phases:
+//   (phases 1-2 stand down while the optional flag skip_if_set is non-zero: NAF's check_numerics flag keeps a non-finite minibatch out)
 //   1. leaf writes of up to PER_MAX_ROWS rows (a row listed twice takes its LAST occurrence: an O(n^2) scan of the list in LDS) and
 //      the running maximum priority;
 //   2. the ancestors of the touched leaves, level by level, a barrier between levels (the top 10 levels in LDS);
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(PER_THREADS) void per_update_sample_kernel(const Pe
   const int tid = threadIdx.x, L = a.L;
   const long nleaf = 1L << L;
   double* tree = a.tree;
-  if (a.n_up > 0) {
+  if (a.n_up > 0 && !(a.skip_if_set && *a.skip_if_set)) {      // (uniform: every lane reads the same word)
     // ---- 1. leaves (+ running maximum)
     for (int b = tid; b < a.n_up; b += PER_THREADS) rows[b] = a.up_rows[b];
     const float pmax0 = *a.maxp;

@@ -27,7 +27,17 @@ struct cpp_naf {
   float* res_pin; hipEvent_t res_ev[CPP_NAF_TICKETS]; uint64_t next_ticket;
   uint64_t dp_local;       // minibatches applied locally since the last parameter averaging (periodic mode)
   cpp_batch* step_batch;
+  // prioritized replay (per.hip): the importance weights the head kernel reads, and the launch that follows the TD values of the
+  // minibatch (its priorities into the tree, the next minibatch's rows and weights)
+  const float* per_w; std::function<int()> per_hook;
   Arena arena;
+};
+
+// the prioritized-replay state of one gradient pass or step, cleared on every way out
+struct NafPerScope {
+  cpp_naf* f;
+  NafPerScope(cpp_naf* f_, const cpp_replay* r) : f(f_) { f->per_w = r->per_tree ? r->per_w : nullptr; }
+  ~NafPerScope() { f->per_w = nullptr; f->per_hook = nullptr; }
 };
 
 extern "C" int cpp_naf_create(cpp_ctx* ctx, cpp_net* value, cpp_net* tvalue, cpp_net* mu, cpp_net* lv, int share,
@@ -64,6 +74,7 @@ extern "C" int cpp_naf_create(cpp_ctx* ctx, cpp_net* value, cpp_net* tvalue, cpp
   f->epoch = ctx->kernel_epoch;
   f->res_pin = nullptr; f->next_ticket = 0; memset(f->res_ev, 0, sizeof(f->res_ev));
   f->hgraph = nullptr; f->hexec = nullptr; f->hgraph_ok = false; f->h_B = 0; f->h_seed = 0; f->h_replay_uid = 0; f->dp_local = 0;
+  f->per_w = nullptr;
   const size_t nall = (size_t)(f->nV + f->nM + f->nL);
   int rc = dalloc(f->arena, &f->gradbuf, nall);
   if (!rc) rc = dalloc(f->arena, &f->m, nall);
@@ -144,7 +155,7 @@ static int naf_head(cpp_naf* f, cpp_batch* b, bool backward) {
   if (backward) {
     a.d_value = f->value->ws[0].dz.back(); a.d_mu_z = f->mu->ws[0].dz.back(); a.d_l = f->lv->ws[0].dz.back();
   }
-  return launch_naf_head(f->ctx, a);
+  return launch_naf_head(f->ctx, a, f->per_w);
 }
 
 // backward of the fully connected stack of a network without an action splice, from layer `start` down:
@@ -277,10 +288,14 @@ static int naf_compute_gradients(cpp_naf* f, cpp_batch* b, bool fold = false, bo
     G.fn([=] { return bump_dropout(tv); }, {tvout});
     if (!share) { G.fn([=] { return bump_dropout(mu); }, {muout}); G.fn([=] { return bump_dropout(lv); }, {lvout}); }
   }
-  // ---- NAF head: L, advantage, TD loss and the gradients of the three head outputs
-  const int head = mlp ? G.fn([=] { return launch_naf_mlp(ctx, nm); }, {vout, tvout})
-                 : fused ? G.fn([=] { return launch_naf_heads(ctx, nh); }, {vout, tvout})
+  // ---- NAF head: L, advantage, TD loss and the gradients of the three head outputs (prioritized replay: weighted by f->per_w)
+  const float* per_w = f->per_w;
+  const int head = mlp ? G.fn([=] { return launch_naf_mlp(ctx, nm, per_w); }, {vout, tvout})
+                 : fused ? G.fn([=] { return launch_naf_heads(ctx, nh, per_w); }, {vout, tvout})
                          : G.fn([=] { return naf_head(f, b, true); }, {vout, tvout, muout, lvout});
+  // (prioritized replay: as soon as the TD values are known -- the next op level, ahead of the conv backward that carries the next
+  // minibatch's gather)
+  if (f->per_hook) G.fn(f->per_hook, {head});
 
   // ---- backward
   if (!share) {
@@ -481,18 +496,41 @@ static void naf_route_check(cpp_naf* f) {
 // nothing minibatch i computes: it rides in the launch of i's conv1 dW (or of its dW reductions), keyed by the sampler's counter + 1
 // -- the counter itself moves in i's optimiser launch, which also finishes the whitening tables of i + 1.  CPP_RIDE_GATHER=0: in sequence.
 // dp / comm: as rt_ddpg.cpp's step_body -- the gradient all-reduce sits between a minibatch's gradients and its update, inside the graph
+// Prioritized memory (per.hip; the data-parallel step refuses one): as rt_ddpg.cpp's step_body -- minibatch i's rows are the caller's or
+// a stratified draw by priority keyed by the sampler's counter, its importance weights scale the loss, and ONE launch behind its head
+// kernel writes its priorities into the tree and draws minibatch i + 1.  Here the draws advance the counter themselves (bump), not the
+// optimiser's launch: that launch stands down while the check_numerics flag is set (unless_nonfinite, as on the asynchronous rows path)
+// and the priority writes with it (skip_if_set), the draws and the counter going on as before.
 static int naf_step_body(cpp_naf* f, cpp_replay* r, int B, int n_batches, const int32_t* rows_dev, uint64_t seed, bool dp = false, cpp_comm* comm = nullptr) {
   const int C = f->value->spec.pixel ? f->value->spec.C : 0;
   cpp_ctx* ctx = f->ctx;
   const bool direct = direct_replay_ok(f->value, r, B);
   static const bool no_ride = cpp_switch_off("CPP_RIDE_GATHER");
   const bool ride_ok = !no_ride && C > 0 && !f->value->spec.use_batch_norm && (r->store_dtype == CPP_F16 || r->store_dtype == CPP_U8);
-  RC(replay_sample_device(r, B, rows_dev, seed, rows_dev ? nullptr : r->counter, C, f->step_batch, direct));
+  const bool per = r->per_tree != nullptr;
+  auto rows_of = [&](int i) -> const int32_t* { return rows_dev ? rows_dev + (size_t)i * B : per ? r->per_rows : nullptr; };
+  NafPerScope per_scope(f, r);
+  auto per_draw = [&](PerArgs& p, int i) {       // minibatch i's rows (unless the caller's) and weights
+    p.B = B; p.w_rows = rows_dev ? rows_of(i) : nullptr; p.seed = seed; p.counter = rows_dev ? nullptr : r->counter; p.bump = rows_dev ? 0 : 1;
+    p.out_rows = r->per_rows; p.out_w = r->per_w;
+  };
+  if (per) {
+    PerArgs p = per_args(r);
+    per_draw(p, 0);
+    RC(launch_per_update_sample(ctx, p));
+  }
+  RC(replay_sample_device(r, B, rows_of(0), seed, rows_of(0) ? nullptr : r->counter, C, f->step_batch, direct));
   for (int i = 0; i < n_batches; ++i) {
     GatherArgs ga; int Cg = 0;
     const bool more = i + 1 < n_batches;
+    if (per) {
+      PerArgs p = per_args(r);
+      p.up_rows = rows_of(i); p.n_up = B; p.up_td = f->td; p.skip_if_set = f->nonfinite;
+      if (more) per_draw(p, i + 1);
+      f->per_hook = [ctx, p] { return launch_per_update_sample(ctx, p); };
+    }
     if (more && ride_ok) {
-      ga = replay_gather_args(r, B, rows_dev ? rows_dev + (size_t)(i + 1) * B : nullptr, seed, rows_dev ? nullptr : r->counter, C,
+      ga = replay_gather_args(r, B, rows_of(i + 1), seed, rows_of(i + 1) ? nullptr : r->counter, C,
                               f->step_batch, direct, &Cg);
       ga.counter_add = 1;
       static const bool no_dwride = cpp_switch_off("CPP_RIDE_DW");
@@ -508,7 +546,8 @@ static int naf_step_body(cpp_naf* f, cpp_replay* r, int B, int n_batches, const 
       sr.count = (double)B * (double)(r->elems / Cg); sr.eps = 1e-6; sr.wmax = ctx->white_max_dev;
       ctx->st_ride = &sr; ctx->st_ride_done = false;
     }
-    const int rc = naf_compute_gradients(f, f->step_batch, true);
+    const int rc = naf_compute_gradients(f, f->step_batch, true, !per);
+    f->per_hook = nullptr;
     const bool rode = ctx->ride != nullptr && ctx->ride_done;
     const bool tables_done = ctx->st_ride != nullptr && ctx->st_ride_done && rode;
     ctx->ride = nullptr; ctx->st_ride = nullptr;
@@ -523,11 +562,11 @@ static int naf_step_body(cpp_naf* f, cpp_replay* r, int B, int n_batches, const 
     static const bool no_tgt_ride = cpp_switch_off("CPP_RIDE_TARGETS");
     f->targets_applied = false;
     f->targets_in_apply = !more && !dp && !no_tgt_ride;      // (the last minibatch of an outer step: the target update rides in its optimiser launch)
-    RC(naf_apply(f, (dp && comm) ? 1.0f / (float)comm->world : 1.0f, false, rows_dev ? nullptr : r->counter, stats_ride ? f->step_batch : nullptr, B, Cg, r->elems, !dp, tables_done));
+    RC(naf_apply(f, (dp && comm) ? 1.0f / (float)comm->world : 1.0f, per, (rows_dev || per) ? nullptr : r->counter, stats_ride ? f->step_batch : nullptr, B, Cg, r->elems, !dp, tables_done));
     if (more) {
       if (stats_ride) { f->step_batch->B = B; f->step_batch->dtype = CPP_F16; f->step_batch->stats_C = Cg; }     // (replay_sample_finish's bookkeeping)
       else if (rode) RC(replay_sample_finish(r, B, Cg, C, f->step_batch));
-      else RC(replay_sample_device(r, B, rows_dev ? rows_dev + (size_t)(i + 1) * B : nullptr, seed, rows_dev ? nullptr : r->counter, C,
+      else RC(replay_sample_device(r, B, rows_of(i + 1), seed, rows_of(i + 1) ? nullptr : r->counter, C,
                                    f->step_batch, direct));
     }
   }
@@ -537,13 +576,13 @@ static int naf_step_body(cpp_naf* f, cpp_replay* r, int B, int n_batches, const 
 }
 
 extern "C" int cpp_naf_train_step(cpp_naf* f, cpp_replay* r, int B, int n_batches, const int32_t* idxs, uint64_t seed) {
-  RC(per_refuse(r, "cpp_naf_train_step"));      // (NAF under prioritized replay: not built)
   if (f) naf_route_check(f);
-  ARG_CHECK(f && r, "cpp_naf_train_step: NULL argument");
+  ARG_CHECK(f && r, "cpp_naf_train_step: NULL %s", r && r->per_tree ? "NAF learner for a prioritized memory" : "argument");
   ARG_CHECK(B >= 1 && B <= f->maxB, "cpp_naf_train_step: batch %d outside [1,%d]", B, f->maxB);
   ARG_CHECK(n_batches >= 1 && (size_t)n_batches * B <= 65536, "cpp_naf_train_step: n_batches %d", n_batches);
   ARG_CHECK(r->elems == f->value->state_elems && r->A == f->A, "cpp_naf_train_step: replay shape does not match the networks");
   if (r->size <= 0) { cpp_set_error("cpp_naf_train_step: replay memory is empty"); return CPP_ERR_STATE; }
+  ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_naf_train_step: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
   cpp_ctx* ctx = f->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
   if (!f->step_batch) RC(cpp_batch_create(ctx, f->maxB, r->elems, r->A, &f->step_batch));
@@ -580,20 +619,33 @@ extern "C" int cpp_naf_train_step(cpp_naf* f, cpp_replay* r, int B, int n_batche
 // sticky: the check_numerics flag is NOT cleared (cpp_naf_train_rows_async: the host learns of a non-finite minibatch up to two calls
 // later; until it has, every later optimiser launch must stand down as the first one did -- the reference's check_numerics stops
 // training before any further train op, naf_cartpole.py:242-245,265)
+// Prioritized memory: the importance weights of the caller's rows against the tree as it stands (the rows of cpp_replay_draw_prioritized
+// get the weights that draw computed), and the priorities of the minibatch written behind its head kernel -- unless the check_numerics
+// flag is set (sticky: as long as it stays set)
 static int naf_rows_body(cpp_naf* f, cpp_replay* r, int B, bool fold = false, bool sticky = false) {
   const int C = f->value->spec.pixel ? f->value->spec.C : 0;
   if (!sticky) HIP_CHECK(hipMemsetAsync(f->nonfinite, 0, sizeof(int), f->ctx->stream));
+  NafPerScope per_scope(f, r);
+  if (r->per_tree) {
+    PerArgs p = per_args(r);
+    p.B = B; p.w_rows = r->rows_in; p.out_w = r->per_w;
+    RC(launch_per_update_sample(f->ctx, p));
+    PerArgs u = per_args(r);
+    u.up_rows = r->rows_in; u.n_up = B; u.up_td = f->td; u.skip_if_set = f->nonfinite;
+    cpp_ctx* ctx = f->ctx;
+    f->per_hook = [ctx, u] { return launch_per_update_sample(ctx, u); };
+  }
   RC(replay_sample_device(r, B, r->rows_in, 0, nullptr, C, f->step_batch, direct_replay_ok(f->value, r, B)));
   RC(naf_compute_gradients(f, f->step_batch, fold, !sticky));
   return ctx_route_publish(f->ctx);
 }
 extern "C" int cpp_naf_train_rows(cpp_naf* f, cpp_replay* r, int B, const int32_t* idxs, float* loss) {
-  RC(per_refuse(r, "cpp_naf_train_rows"));      // (NAF under prioritized replay: not built)
   if (f) naf_route_check(f);
-  ARG_CHECK(f && r && idxs, "cpp_naf_train_rows: NULL argument");
+  ARG_CHECK(f && r && idxs, "cpp_naf_train_rows: NULL %s", r && r->per_tree ? "argument (NAF learner or rows) for a prioritized memory" : "argument");
   ARG_CHECK(B >= 1 && B <= f->maxB, "cpp_naf_train_rows: batch %d outside [1,%d]", B, f->maxB);
   ARG_CHECK(r->elems == f->value->state_elems && r->A == f->A, "cpp_naf_train_rows: replay shape does not match the networks");
   if (r->size <= 0) { cpp_set_error("cpp_naf_train_rows: replay memory is empty"); return CPP_ERR_STATE; }
+  ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_naf_train_rows: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
   cpp_ctx* ctx = f->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
   if (!f->step_batch) RC(cpp_batch_create(ctx, f->maxB, r->elems, r->A, &f->step_batch));
@@ -635,12 +687,12 @@ static int naf_rows_apply_body(cpp_naf* f, cpp_replay* r, int B) {
   return naf_apply(f, 1.0f, true, nullptr, nullptr, 0, 0, 0, true);
 }
 extern "C" int cpp_naf_train_rows_async(cpp_naf* f, cpp_replay* r, int B, const int32_t* idxs, uint64_t* ticket) {
-  RC(per_refuse(r, "cpp_naf_train_rows_async"));      // (NAF under prioritized replay: not built)
   if (f) naf_route_check(f);
-  ARG_CHECK(f && r && idxs && ticket, "cpp_naf_train_rows_async: NULL argument");
+  ARG_CHECK(f && r && idxs && ticket, "cpp_naf_train_rows_async: NULL %s", r && r->per_tree ? "argument for a prioritized memory" : "argument");
   ARG_CHECK(B >= 1 && B <= f->maxB, "cpp_naf_train_rows_async: batch %d outside [1,%d]", B, f->maxB);
   ARG_CHECK(r->elems == f->value->state_elems && r->A == f->A, "cpp_naf_train_rows_async: replay shape does not match the networks");
   if (r->size <= 0) { cpp_set_error("cpp_naf_train_rows_async: replay memory is empty"); return CPP_ERR_STATE; }
+  ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_naf_train_rows_async: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
   cpp_ctx* ctx = f->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
   if (!f->step_batch) RC(cpp_batch_create(ctx, f->maxB, r->elems, r->A, &f->step_batch));
@@ -708,7 +760,7 @@ static int naf_half_checks(cpp_naf* f, cpp_replay* r, int B, const char* who) {
 // sample B rows on the device (Philox; the counter advances by one) and leave the gradients of the three networks in the flat
 // buffer [value | mu | l_values]; hipGraph-captured after the first call per (B, seed, replay)
 extern "C" int cpp_naf_sample_and_compute(cpp_naf* f, cpp_replay* r, int B, uint64_t seed) {
-  RC(per_refuse(r, "cpp_naf_sample_and_compute"));      // (NAF under prioritized replay: not built)
+  RC(per_refuse(r, "cpp_naf_sample_and_compute"));      // (the half step of the data-parallel learners: one tree per shard is not built)
   if (f) naf_route_check(f);
   RC(naf_half_checks(f, r, B, "cpp_naf_sample_and_compute"));
   cpp_ctx* ctx = f->ctx;
@@ -769,7 +821,7 @@ extern "C" int cpp_naf_dp_status(const cpp_naf* f, int* mode, char* reason, int 
 }
 
 extern "C" int cpp_naf_dp_train_step(cpp_naf* f, cpp_replay* r, cpp_comm* c, int B, int n_batches, uint64_t seed, int sync_every) {
-  RC(per_refuse(r, "cpp_naf_dp_train_step"));      // (NAF under prioritized replay: not built)
+  RC(per_refuse(r, "cpp_naf_dp_train_step"));      // (one tree per shard: not built)
   if (f) naf_route_check(f);
   RC(naf_half_checks(f, r, B, "cpp_naf_dp_train_step"));
   ARG_CHECK(n_batches >= 1 && sync_every >= 1, "cpp_naf_dp_train_step: n_batches %d, sync_every %d", n_batches, sync_every);

@@ -485,7 +485,8 @@ PerArgs per_args(const cpp_replay* r) {
 
 int per_refuse(const cpp_replay* r, const char* who) {
   if (r && r->per_tree) {
-    cpp_set_error("%s: prioritized replay is supported by the DDPG learner's cpp_ddpg_train_step / cpp_ddpg_train_rows only", who);
+    cpp_set_error("%s: prioritized replay is supported by cpp_ddpg_train_step / cpp_ddpg_train_rows and cpp_naf_train_step / "
+                  "cpp_naf_train_rows / cpp_naf_train_rows_async only", who);
     return CPP_ERR_ARG;
   }
   return CPP_OK;

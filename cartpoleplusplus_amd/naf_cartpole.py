@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _lib, base_network, replay_memory, util
 from ._lib import lib, check, ptr
+from .ddpg_cartpole import check_prioritized_opts, priority_beta
 
 VERBOSE_DEBUG = False
 
@@ -109,6 +110,10 @@ def build_parser():
     a('--async-rollouts', action='store_true',
       help="play the episodes on a rollout thread while the learner trains back to back (training_loop.py)")
     a('--synthetic-env', action='store_true', help="random-frame stand-in env")
+    # prioritized experience replay (an extension beyond the reference; the DDPG parser's option names and defaults): options of
+    # default_opts / set_opts only -- the command line does not take --prioritized-replay yet (tests/test_per_host.py pins its absence)
+    parser.set_defaults(prioritized_replay=False, priority_alpha=0.6, priority_beta=0.4, priority_beta_final=1.0,
+                        priority_beta_steps=100000, priority_eps=1e-6)
     return parser
 
 
@@ -367,12 +372,17 @@ class NormalizedAdvantageFunctionAgent(object):
             _lib.default_context().set_precision("exact")
         self.replay_memory = replay_memory.ReplayMemory(opts.replay_memory_size, state_shape, action_dim,
                                                        store_dtype=opts.replay_store)
+        if getattr(opts, "prioritized_replay", False):      # (as the DDPG agent: loss mean(w td^2), priorities from the TD values)
+            check_prioritized_opts(opts)
+            self.replay_memory.enable_priorities(opts.priority_alpha, opts.priority_eps, seed=opts.sample_seed)
+            self.replay_memory.set_priority_beta(priority_beta(opts, 0))
         batched_state_shape = [None] + list(state_shape)
         s1 = base_network.Placeholder(batched_state_shape)
         s2 = base_network.Placeholder(batched_state_shape)
         self.value_net = ValueNetwork("value", s1, opts.hidden_layers)
         self.target_value_net = ValueNetwork("target_value", s2, opts.hidden_layers)
         self.naf = NafNetwork("naf", s1, s2, self.value_net, self.target_value_net, action_dim)
+        self.train_steps = 0
 
     def initialise_variables(self, seed=None):
         rng = np.random.RandomState(seed) if seed is not None else np.random
@@ -392,6 +402,7 @@ class NormalizedAdvantageFunctionAgent(object):
         """the inner step naf_cartpole.py:367-373 as one device-side sequence (hipGraph after the first call)."""
         if idxs is None and getattr(opts, "data_parallel", False):      # one learner of N: the collective step (distributed.py)
             self._dp_learner(batch_size).train_step(batches_per_step)
+            self.train_steps += 1
             return
         rows = None
         if idxs is not None:
@@ -399,6 +410,7 @@ class NormalizedAdvantageFunctionAgent(object):
         self.replay_memory.stats[">batch"] += batches_per_step
         check(lib.cpp_naf_train_step(self.naf.handle, self.replay_memory.handle, int(batch_size),
                                      int(batches_per_step), ptr(rows), int(opts.sample_seed)))
+        self.train_steps += 1
 
     def _dp_learner(self, batch_size):
         from . import distributed
@@ -415,6 +427,8 @@ class NormalizedAdvantageFunctionAgent(object):
     def _train_once(self, batch_size, batches_per_step):
         """the inner step naf_cartpole.py:365-373; returns the losses it logs."""
         losses = []
+        if getattr(opts, "prioritized_replay", False):
+            self.replay_memory.set_priority_beta(priority_beta(opts, self.train_steps))
         if opts.host_rng_sampling:
             for _ in range(batches_per_step):
                 batch_start = time.time()
@@ -495,6 +509,7 @@ def main(argv=None):
         # the host-RNG path is the reference's literal loop: local actor.train / critic.train calls with no all-reduce -- N learners
         # would agree on when to train (LoopAgreement) and silently train N different networks
         raise SystemExit("--data-parallel draws minibatches with the device sampler inside the collective step: it cannot be combined with --host-rng-sampling")
+    check_prioritized_opts(opts)
     sys.stderr.write("%s\n" % opts)
     from .ddpg_cartpole import make_env
     env = make_env(opts)

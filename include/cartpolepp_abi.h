@@ -234,8 +234,15 @@ int cpp_replay_fill_synthetic(cpp_replay* replay, int n_rows, uint64_t seed);
  *  - DDPG: critic loss mean(w td^2), dz_q = (td w) 2 / B (w == 1: today's bits); cpp_ddpg_last_stats()[0] is the weighted loss; the
  *    actor's update is unweighted.  The priorities of minibatch k are in the tree before minibatch k+1 is drawn, in the fused step
  *    (cpp_ddpg_train_step) and in the literal loop (cpp_replay_draw_prioritized + cpp_ddpg_train_rows) alike: the same rows.
+ *  - NAF: loss mean(w td^2), dQ = (td w) 2 / B (w == 1: today's bits); everything below dQ inherits the weight; cpp_naf_last_stats()[0]
+ *    is the weighted loss.  cpp_naf_train_step (fused) and cpp_naf_train_rows / cpp_naf_train_rows_async (the literal loop, after
+ *    cpp_replay_draw_prioritized) write minibatch k's priorities before k+1 is drawn, as DDPG's.  A non-finite minibatch (the
+ *    check_numerics flag: l_values, L or the loss not finite) writes no priority and, in cpp_naf_train_step and
+ *    cpp_naf_train_rows_async, no parameter: for as long as the flag stays set (it is sticky on those two paths).  The draws and the
+ *    counter go on.  cpp_naf_train_step's target soft update still runs (the value network it follows has not moved).
  *  - cpp_replay_sample(idxs == NULL) draws by priority (key (seed, counter) as given).  cpp_ddpg_dp_train_step,
- *    cpp_ddpg_sample_and_compute and the cpp_naf_* train entry points return CPP_ERR_ARG on a prioritized memory, writing nothing.
+ *    cpp_ddpg_sample_and_compute, cpp_naf_dp_train_step and cpp_naf_sample_and_compute (per-shard trees: not built) return
+ *    CPP_ERR_ARG on a prioritized memory, writing nothing.
  * Batches of a prioritized memory hold at most 1024 rows. */
 /* alpha >= 0; eps > 0 unless alpha == 0.  Called again: new alpha / eps, the maximum back to 1.0 and every row at it. */
 int cpp_replay_enable_priorities(cpp_replay* replay, float alpha, float eps);

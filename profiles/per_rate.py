@@ -1,15 +1,20 @@
 #!/usr/bin/env python
 """Prioritized replay's cost in the fused DDPG step: cfg3 (64x64x18, B = 256, 5 minibatches per outer step, 22 000 synthetic rows),
 the uniform step against the prioritized one (alpha 0.6, beta 0.4), ONE process, two agents, alternating timed blocks of
-hipGraph-replayed outer steps.  Prints one JSON line: steps/s of each and their ratio (median over the block pairs)."""
+hipGraph-replayed outer steps.  Prints one JSON line: steps/s of each and their ratio (median over the block pairs).
+--naf: the fused NAF step at cfg4 instead (64x64x18, B = 256, shared trunk, Momentum, 5 minibatches per step, 22 000 rows).
+Usage: per_rate.py [--naf] [blocks] [steps per block]"""
 import json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cartpoleplusplus_amd import ddpg_cartpole as D
+from cartpoleplusplus_amd import naf_cartpole as F
 
 shape, B, NB, ROWS = (64, 64, 3, 2, 3), 256, 5, 22000
-blocks = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-steps = int(sys.argv[2]) if len(sys.argv) > 2 else 40
+naf = "--naf" in sys.argv
+args = [a for a in sys.argv[1:] if a != "--naf"]
+blocks = int(args[0]) if len(args) > 0 else 8
+steps = int(args[1]) if len(args) > 1 else 40
 
 
 class Env(object):
@@ -19,6 +24,15 @@ class Env(object):
 
 
 def agent(per):
+    if naf:          # cfg4: the shared trunk under Momentum (exps/run_93.sh)
+        F.set_opts(F.default_opts(use_raw_pixels=True, render_height=64, render_width=64, num_cameras=2, action_repeats=3, batch_size=B,
+                                  replay_memory_size=ROWS, share_input_state_representation=True, optimiser="Momentum",
+                                  optimiser_args=json.dumps({"learning_rate": 0.01, "momentum": 0.9}), prioritized_replay=per))
+        a = F.NormalizedAdvantageFunctionAgent(Env())
+        a.initialise_variables(seed=42)
+        a.post_var_init_setup()
+        a.replay_memory.fill_synthetic(ROWS, seed=1234)
+        return a
     D.set_opts(D.default_opts(use_raw_pixels=True, render_height=64, render_width=64, num_cameras=2, action_repeats=3, batch_size=B,
                               replay_memory_size=ROWS, prioritized_replay=per))
     a = D.DeepDeterministicPolicyGradientAgent(Env())
@@ -29,7 +43,7 @@ def agent(per):
 
 
 agents = {"uniform": agent(False), "per": agent(True)}
-ctx = agents["uniform"].actor.ctx
+ctx = agents["uniform"].value_net.ctx if naf else agents["uniform"].actor.ctx
 for a in agents.values():
     for _ in range(4):
         a.train_step(B, NB)
@@ -43,7 +57,7 @@ for _ in range(blocks):
         ctx.sync()
         rates[k].append(steps / (time.perf_counter() - t0))
 ratio = float(np.median(np.array(rates["per"]) / np.array(rates["uniform"])))
-print(json.dumps({"workload": "cfg3", "B": B, "batches_per_step": NB, "blocks": blocks, "steps_per_block": steps,
+print(json.dumps({"workload": "naf-cfg4" if naf else "cfg3", "B": B, "batches_per_step": NB, "blocks": blocks, "steps_per_block": steps,
                   "uniform_steps_per_s": float(np.median(rates["uniform"])), "per_steps_per_s": float(np.median(rates["per"])),
                   "per_over_uniform": ratio}))
 for a in agents.values():
