@@ -111,6 +111,8 @@ SIGNATURES = {
     "cpp_replay_read_priority_tree": (_I, [_P, _P, _L]),
     "cpp_replay_last_weights": (_I, [_P, _I, _P]),
     "cpp_replay_draw_prioritized": (_I, [_P, _I, _U64, _P, _P]),
+    "cpp_replay_set_n_step": (_I, [_P, _I, _F]),
+    "cpp_replay_get_n_step": (_I, [_P, C.POINTER(_I), C.POINTER(_F)]),
     "cpp_ddpg_create": (_I, [_P, _P, _P, _P, _P, C.POINTER(DdpgHyper), _PP]),
     "cpp_ddpg_destroy": (_I, [_P]),
     "cpp_ddpg_train_actor": (_I, [_P, _P]),

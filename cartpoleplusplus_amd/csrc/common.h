@@ -299,7 +299,14 @@ struct GatherArgs {
   long elems; int B; int size; int action_dim; int C;
   const int32_t* size_ptr;      // non-null: the sampler's range is read from here (device word kept by cpp_replay_set_size), so
                                 // that a captured launch keeps sampling the whole memory as it grows; `size` otherwise
+  // n-step memory (cpp_replay_set_n_step; appended, so that the uniform instances keep their argument layout): non-null selects the
+  // launchers' NSTEP instances, which walk up to n rows from the drawn one and fold the return into the reward / mask columns
+  // (gather_body.h: nstep_walk).  The words are written by value in stream order: captured launches read the current n and discount.
+  const struct NStepWords* nstep;
+  int rows_cap;                 // buffer_size R of the memory (the walk wraps modulo R once the memory is full)
 };
+struct NStepWords { int32_t n; float discount; };
+constexpr int NSTEP_MAX = 64;   // one wavefront: lane k holds row (i + k) mod R
 int launch_gather_stats(cpp_ctx* ctx, const GatherArgs& a, int dtype);
 // per-state sufficient statistics of store rows [first, first + n) (slots == nullptr) or of the n rows listed in `slots` (device): the very
 // sums a gather of that state would leave in GatherArgs::part, computed once when the state is written

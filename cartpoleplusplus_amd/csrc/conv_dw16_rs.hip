@@ -4,7 +4,7 @@
 #include "conv_dw16_rs.h"
 #include "gather_body.h"
 
-template <int CIN>
+template <int CIN, bool NSTEP>
 __global__ __launch_bounds__(CONV_THREADS, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_dw16_rs_kernel(const ConvArgsN batch, int nbands, int band, int gx, const GatherArgs g) {
   const int ndw = gx * (batch.n / 2);
   if ((int)blockIdx.x < ndw) {
@@ -15,22 +15,28 @@ __global__ __launch_bounds__(CONV_THREADS, 2) __attribute__((amdgpu_waves_per_eu
     float* sh = reinterpret_cast<float*>(lds_raw + CPP_MAX_CHANNELS * 16 * 8);
     float* lut = sh + 256 * GATHER_SH;
     const int i = (int)blockIdx.x - ndw;
-    gather_stats_body<__half>(g, i % g.B, i / g.B, sh, dsh, lut);
+    gather_stats_body<__half, NSTEP>(g, i % g.B, i / g.B, sh, dsh, lut);
   }
 }
 
 template <int CIN>
 static int conv_dw16_rs_launch(cpp_ctx* ctx, const ConvArgsN& a, int nbands, int band, int gx, int pairs) {
   constexpr int lds = Dw16RsGeom<CIN>::LDS_BYTES > GATHER_LDS_BYTES ? Dw16RsGeom<CIN>::LDS_BYTES : GATHER_LDS_BYTES;      // (the rider's workgroups share the allocation)
-  static bool attr_done[CPP_MAX_DEVICES] = {};
-  if (!attr_done[cpp_dev_slot(ctx)]) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)conv_dw16_rs_kernel<CIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_done[cpp_dev_slot(ctx)] = true;
+  static bool attr_done[CPP_MAX_DEVICES][2] = {};
+  if (!attr_done[cpp_dev_slot(ctx)][0]) {
+    HIP_CHECK(hipFuncSetAttribute((const void*)conv_dw16_rs_kernel<CIN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    attr_done[cpp_dev_slot(ctx)][0] = true;
   }
   GatherArgs g; memset(&g, 0, sizeof(g));
   int nride = 0;
   if (ctx->ride && !ctx->ride_done && ctx->ride_at_dw && ctx->ride_dtype == 1) { g = *ctx->ride; ctx->ride_done = true; nride = 2 * g.B; }
-  hipLaunchKernelGGL(conv_dw16_rs_kernel<CIN>, dim3(gx * pairs + nride), dim3(CONV_THREADS), lds, ctx->stream, a, nbands, band, gx, g);
+  if (g.nstep) {           // (the rider walks an n-step memory: its own instance, the uniform one is left as it was)
+    if (!attr_done[cpp_dev_slot(ctx)][1]) {
+      HIP_CHECK(hipFuncSetAttribute((const void*)conv_dw16_rs_kernel<CIN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      attr_done[cpp_dev_slot(ctx)][1] = true;
+    }
+    hipLaunchKernelGGL((conv_dw16_rs_kernel<CIN, true>), dim3(gx * pairs + nride), dim3(CONV_THREADS), lds, ctx->stream, a, nbands, band, gx, g);
+  } else hipLaunchKernelGGL((conv_dw16_rs_kernel<CIN, false>), dim3(gx * pairs + nride), dim3(CONV_THREADS), lds, ctx->stream, a, nbands, band, gx, g);
   LAUNCH_CHECK();
   return 0;
 }

@@ -67,8 +67,51 @@ template <> __device__ __forceinline__ __half elem_convert<uint8_t, __half>(uint
 
 __host__ __device__ inline int gcd_int(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
 
-// (b, which): the workgroup's place in the (B, 2) grid -- blockIdx for a launch of its own
-template <typename T>
+// f32 product / sum, each rounded on its own: never contracted into an FMA (the n-step return's fixed operation order, which the
+// host's numpy restatement in replay_memory.py repeats bit for bit)
+__device__ __forceinline__ float nstep_mul(float x, float y) {
+#pragma clang fp contract(off)
+  return x * y;
+}
+__device__ __forceinline__ float nstep_add(float x, float y) {
+#pragma clang fp contract(off)
+  return x + y;
+}
+
+// n-step walk (include/cartpolepp_abi.h, "n-step returns"), by every lane of a wave for the wave-uniform drawn row i: lane k < n loads
+// the four columns of row j_k = (i + k) mod R in ONE round of loads (the only memory trip between the row and the state's slot, as the
+// uniform gather's row -> slot load); lane k links to k + 1 if mask[j_k] != 0, row j_{k+1} exists (j_k + 1 < size, or the memory is
+// full and j_{k+1} != i) and s2_idx[j_k] == s1_idx[j_{k+1}].  The first lane that does not link is the last row walked, m - 1.
+// which == 1: the slot of s2_idx[j_{m-1}]; which == 0: the slot of s1_idx[i] and the folded reward / mask, added in the fixed order
+// g_k = g_{k-1} * discount, R_k = R_{k-1} + r[j_k] * g_k, mask = mask[j_{m-1}] * g_{m-1} (n = 1: the stored values).
+__device__ __forceinline__ void nstep_walk(const GatherArgs& a, const int row, const int which, const int lane, int* slot, float* reward,
+                                           float* mask) {
+  const int n = a.nstep->n;
+  const float discount = a.nstep->discount;
+  const int size = a.size_ptr ? *a.size_ptr : a.size, R = a.rows_cap;
+  const bool full = size >= R;
+  const bool have = lane < n && (full ? lane < R : row + lane < size);      // (row < size <= R: every j below is a row of the memory)
+  const int j = full ? (row + lane) % R : row + lane;
+  float m = 0.f, r = 0.f; int s1 = -1, s2 = -1;
+  if (have) { m = a.mask[j]; r = a.reward[j]; s1 = a.s_idx[0][j]; s2 = a.s_idx[1][j]; }
+  const int s1_next = __shfl_down(s1, 1);
+  const bool have_next = __shfl_down((int)have, 1) != 0 && lane < 63;
+  const bool link = have && m != 0.f && have_next && s2 == s1_next;
+  const int last = __ffsll((unsigned long long)__ballot(!link)) - 1;        // (lane n - 1 never links: 0 <= last < n)
+  if (which == 1) { *slot = __builtin_amdgcn_readlane(s2, last); return; }
+  *slot = __builtin_amdgcn_readlane(s1, 0);
+  float g = 1.f, ret = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r), 0));
+  for (int k = 1; k <= last; ++k) {
+    g = nstep_mul(g, discount);
+    ret = nstep_add(ret, nstep_mul(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(r), k)), g));
+  }
+  *reward = ret;
+  *mask = nstep_mul(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(m), last)), g);
+}
+
+// (b, which): the workgroup's place in the (B, 2) grid -- blockIdx for a launch of its own.  NSTEP: the memory's n-step instance
+// (GatherArgs::nstep non-null); the uniform instances (false) compile to the instructions they had before the walk existed.
+template <typename T, bool NSTEP = false>
 __device__ __forceinline__ void gather_stats_body(const GatherArgs& a, const int b, const int which, float* sh, double* dsh, float* lut) {
   // (lut: CPP_U8 store, f16(k/255) as float)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -82,18 +125,20 @@ __device__ __forceinline__ void gather_stats_body(const GatherArgs& a, const int
     if (a.s_idx[0] == nullptr) { row = b; slot = b; }       // statistics over an already gathered batch
     else {
       row = a.rows ? a.rows[b] : sample_row(a.seed, (a.counter ? *a.counter : 0) + (uint64_t)a.counter_add, b, a.size_ptr ? *a.size_ptr : a.size);
-      slot = a.s_idx[which][row];
+      if (!NSTEP) slot = a.s_idx[which][row];
     }
   }
   row = __shfl(row, 0);
   slot = __shfl(slot, 0);
+  float nreward = 0.f, nmask = 0.f;
+  if (NSTEP && a.s_idx[0] != nullptr) nstep_walk(a, row, which, lane, &slot, &nreward, &nmask);
 
   if (tid == 0 && a.out_slot[which]) a.out_slot[which][b] = slot;
   if (which == 0 && a.s_idx[0] != nullptr) {
     if (tid == 0 && a.rows_out) a.rows_out[b] = row;
     if (tid < a.action_dim) a.out_action[(long)b * a.action_dim + tid] = a.action[(long)row * a.action_dim + tid];
-    if (tid == 64) a.out_reward[b] = a.reward[row];
-    if (tid == 65) a.out_mask[b] = a.mask[row];
+    if (tid == 64) a.out_reward[b] = NSTEP ? nreward : a.reward[row];
+    if (tid == 65) a.out_mask[b] = NSTEP ? nmask : a.mask[row];
   }
 
   const T* src = (const T*)a.store[which] + (long)slot * a.elems;

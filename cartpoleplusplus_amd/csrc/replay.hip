@@ -14,19 +14,19 @@
 #include "gather_body.h"
 #include "stats_body.h"
 
-template <typename T>
+template <typename T, bool NSTEP>
 __global__ __launch_bounds__(256) void gather_stats_kernel(const GatherArgs a) {
   __shared__ float sh[256 * GATHER_SH];
   __shared__ double dsh[CPP_MAX_CHANNELS * 16];
   __shared__ float lut[256];
-  gather_stats_body<T>(a, (int)blockIdx.x, (int)blockIdx.y, sh, dsh, lut);
+  gather_stats_body<T, NSTEP>(a, (int)blockIdx.x, (int)blockIdx.y, sh, dsh, lut);
 }
 
 // The dW reductions that end a minibatch's backward pass and the sample + statistics pass that starts the next minibatch in ONE
 // launch: the gather depends on nothing the step computes (its draw is keyed by the sampler's counter + 1), the reduction
 // is a latency chain on a handful of workgroups -- back to back they cost 8.8 + 19.8 us, together the longer of the two.
 // Workgroups [0, reduction blocks) reduce (4 slices of 64 lanes: its own fixed order, the same for every store type), the rest gather.
-template <typename T>
+template <typename T, bool NSTEP>
 __global__ __launch_bounds__(256) void reduce_gather_kernel(const DwReduceBatch rb, const GatherArgs a) {
   const int nred = rb.block_start[rb.n];
   if ((int)blockIdx.x < nred) {
@@ -37,15 +37,18 @@ __global__ __launch_bounds__(256) void reduce_gather_kernel(const DwReduceBatch 
     __shared__ double dsh[CPP_MAX_CHANNELS * 16];
     __shared__ float lut[256];
     const int i = (int)blockIdx.x - nred;
-    gather_stats_body<T>(a, i % a.B, i / a.B, sh, dsh, lut);
+    gather_stats_body<T, NSTEP>(a, i % a.B, i / a.B, sh, dsh, lut);
   }
 }
 
 int launch_reduce_gather(cpp_ctx* ctx, const DwReduceBatch& rb, const GatherArgs& a, int dtype) {
   prof_begin(ctx);
   const dim3 grid(rb.block_start[rb.n] + 2 * a.B);
-  if (dtype == 2) hipLaunchKernelGGL(reduce_gather_kernel<uint8_t>, grid, dim3(256), 0, ctx->stream, rb, a);
-  else hipLaunchKernelGGL(reduce_gather_kernel<__half>, grid, dim3(256), 0, ctx->stream, rb, a);
+  if (a.nstep) {          // (an n-step memory's walk: its own instances, the uniform ones are left as they were)
+    if (dtype == 2) hipLaunchKernelGGL((reduce_gather_kernel<uint8_t, true>), grid, dim3(256), 0, ctx->stream, rb, a);
+    else hipLaunchKernelGGL((reduce_gather_kernel<__half, true>), grid, dim3(256), 0, ctx->stream, rb, a);
+  } else if (dtype == 2) hipLaunchKernelGGL((reduce_gather_kernel<uint8_t, false>), grid, dim3(256), 0, ctx->stream, rb, a);
+  else hipLaunchKernelGGL((reduce_gather_kernel<__half, false>), grid, dim3(256), 0, ctx->stream, rb, a);
   LAUNCH_CHECK();
   prof_end(ctx, K_REDUCE_GATHER);
   return 0;
@@ -83,9 +86,12 @@ int launch_gather_stats(cpp_ctx* ctx, const GatherArgs& a, int dtype) {
     return 1;
   }
   prof_begin(ctx);
-  if (dtype == 2) hipLaunchKernelGGL(gather_stats_kernel<uint8_t>, dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
-  else if (dtype == 1) hipLaunchKernelGGL(gather_stats_kernel<__half>, dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(gather_stats_kernel<float>, dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
+  if (a.nstep) {          // (replay memories hold f16 or 8-bit states)
+    if (dtype == 2) hipLaunchKernelGGL((gather_stats_kernel<uint8_t, true>), dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((gather_stats_kernel<__half, true>), dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
+  } else if (dtype == 2) hipLaunchKernelGGL((gather_stats_kernel<uint8_t, false>), dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
+  else if (dtype == 1) hipLaunchKernelGGL((gather_stats_kernel<__half, false>), dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((gather_stats_kernel<float, false>), dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
   LAUNCH_CHECK();
   prof_end(ctx, K_GATHER_STATS);
   return 0;

@@ -713,6 +713,7 @@ extern "C" int cpp_ddpg_train_rows(cpp_ddpg* d, cpp_replay* r, int B, const int3
   ARG_CHECK(d && r && idxs, "cpp_ddpg_train_rows: NULL argument");
   ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_train_rows: batch %d outside [1,%d]", B, d->maxB);
   ARG_CHECK(r->elems == d->actor->state_elems && r->A == d->actor->spec.action_dim, "cpp_ddpg_train_rows: replay shape does not match the networks");
+  RC(nstep_refuse(r, d->hp.discount, "cpp_ddpg_train_rows"));
   if (r->size <= 0) { cpp_set_error("cpp_ddpg_train_rows: replay memory is empty"); return CPP_ERR_STATE; }
   ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_ddpg_train_rows: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
   route_check(d);
@@ -743,6 +744,7 @@ extern "C" int cpp_ddpg_train_step(cpp_ddpg* d, cpp_replay* r, int B, int n_batc
   ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_train_step: batch %d outside [1,%d]", B, d->maxB);
   ARG_CHECK(n_batches >= 1 && (size_t)n_batches * B <= 65536, "cpp_ddpg_train_step: n_batches %d", n_batches);
   ARG_CHECK(r->elems == d->actor->state_elems && r->A == d->actor->spec.action_dim, "cpp_ddpg_train_step: replay shape does not match the networks");
+  RC(nstep_refuse(r, d->hp.discount, "cpp_ddpg_train_step"));
   if (r->size <= 0) { cpp_set_error("cpp_ddpg_train_step: replay memory is empty"); return CPP_ERR_STATE; }
   ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_ddpg_train_step: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
   route_check(d);
@@ -895,6 +897,7 @@ extern "C" int cpp_ddpg_sample_and_compute(cpp_ddpg* d, cpp_replay* r, int B, ui
   RC(per_refuse(r, "cpp_ddpg_sample_and_compute"));
   if (d) route_check(d);
   RC(half_step_checks(d, r, B, "cpp_ddpg_sample_and_compute"));
+  RC(nstep_refuse(r, d->hp.discount, "cpp_ddpg_sample_and_compute"));
   HIP_CHECK(hipSetDevice(d->ctx->device));
   return half_step(d, r, B, seed, false, nullptr);
 }
@@ -936,6 +939,7 @@ extern "C" int cpp_ddpg_dp_train_step(cpp_ddpg* d, cpp_replay* r, cpp_comm* c, i
                                       int sync_every, int overlap) {
   RC(per_refuse(r, "cpp_ddpg_dp_train_step"));
   RC(half_step_checks(d, r, B, "cpp_ddpg_dp_train_step"));
+  RC(nstep_refuse(r, d->hp.discount, "cpp_ddpg_dp_train_step"));
   ARG_CHECK(n_batches >= 1 && sync_every >= 1, "cpp_ddpg_dp_train_step: n_batches %d, sync_every %d", n_batches, sync_every);
   ARG_CHECK(!c || c->ctx == d->ctx, "cpp_ddpg_dp_train_step: communicator and networks live on different contexts");
   route_check(d);

@@ -138,6 +138,9 @@ struct cpp_replay {
   float* per_maxp; float* per_beta;                        // device scalars (written by value, in stream order)
   int32_t* per_rows; float* per_w;                         // the rows of the last draw and the importance weights of the last minibatch
   int32_t* per_list; float* per_vals;                      // staging of host rows / values (cpp_replay_update_priorities, write_rows)
+  // n-step returns (cpp_replay_set_n_step; gather_body.h: nstep_walk): nullptr = never set, the uniform gathers.  Host copies of the
+  // device words for the trainers' discount check
+  NStepWords* nstep_dev; int nstep_n; float nstep_discount;
   Arena arena;
 };
 static size_t replay_esz(const cpp_replay* r) { return r->store_dtype == CPP_U8 ? 1 : sizeof(__half); }
@@ -230,6 +233,7 @@ GemmArgs fc_dx_args(cpp_net* n, int l, int B, const float* dz, long dz_ld, int c
 int batch_stats(cpp_ctx* ctx, const void* s0, const void* s1, int dtype, long elems, int B, int C, double* part, float* white);
 int batch_ensure_stats(cpp_batch* b, int C);
 uint64_t replay_next_uid();      // graph keys: a fresh uid per cpp_replay_create and per change of a sampled memory's statistics setting
+int nstep_refuse(const cpp_replay* r, float discount, const char* who);      // CPP_ERR_ARG: an n-step memory folded with another discount
 GatherArgs replay_gather_args(cpp_replay* r, int B, const int32_t* rows_dev, uint64_t seed, const uint64_t* counter_dev, int channels, cpp_batch* out, bool direct, int* C_out);
 int replay_sample_finish(cpp_replay* r, int B, int C, int channels, cpp_batch* out, uint64_t* bump = nullptr, bool* bumped = nullptr);
 int replay_sample_device(cpp_replay* r, int B, const int32_t* rows_dev, uint64_t seed, const uint64_t* counter_dev, int channels, cpp_batch* out, bool direct = false,

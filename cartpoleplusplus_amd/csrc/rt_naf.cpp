@@ -581,6 +581,7 @@ extern "C" int cpp_naf_train_step(cpp_naf* f, cpp_replay* r, int B, int n_batche
   ARG_CHECK(B >= 1 && B <= f->maxB, "cpp_naf_train_step: batch %d outside [1,%d]", B, f->maxB);
   ARG_CHECK(n_batches >= 1 && (size_t)n_batches * B <= 65536, "cpp_naf_train_step: n_batches %d", n_batches);
   ARG_CHECK(r->elems == f->value->state_elems && r->A == f->A, "cpp_naf_train_step: replay shape does not match the networks");
+  RC(nstep_refuse(r, f->hp.discount, "cpp_naf_train_step"));
   if (r->size <= 0) { cpp_set_error("cpp_naf_train_step: replay memory is empty"); return CPP_ERR_STATE; }
   ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_naf_train_step: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
   cpp_ctx* ctx = f->ctx;
@@ -644,6 +645,7 @@ extern "C" int cpp_naf_train_rows(cpp_naf* f, cpp_replay* r, int B, const int32_
   ARG_CHECK(f && r && idxs, "cpp_naf_train_rows: NULL %s", r && r->per_tree ? "argument (NAF learner or rows) for a prioritized memory" : "argument");
   ARG_CHECK(B >= 1 && B <= f->maxB, "cpp_naf_train_rows: batch %d outside [1,%d]", B, f->maxB);
   ARG_CHECK(r->elems == f->value->state_elems && r->A == f->A, "cpp_naf_train_rows: replay shape does not match the networks");
+  RC(nstep_refuse(r, f->hp.discount, "cpp_naf_train_rows"));
   if (r->size <= 0) { cpp_set_error("cpp_naf_train_rows: replay memory is empty"); return CPP_ERR_STATE; }
   ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_naf_train_rows: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
   cpp_ctx* ctx = f->ctx;
@@ -691,6 +693,7 @@ extern "C" int cpp_naf_train_rows_async(cpp_naf* f, cpp_replay* r, int B, const 
   ARG_CHECK(f && r && idxs && ticket, "cpp_naf_train_rows_async: NULL %s", r && r->per_tree ? "argument for a prioritized memory" : "argument");
   ARG_CHECK(B >= 1 && B <= f->maxB, "cpp_naf_train_rows_async: batch %d outside [1,%d]", B, f->maxB);
   ARG_CHECK(r->elems == f->value->state_elems && r->A == f->A, "cpp_naf_train_rows_async: replay shape does not match the networks");
+  RC(nstep_refuse(r, f->hp.discount, "cpp_naf_train_rows_async"));
   if (r->size <= 0) { cpp_set_error("cpp_naf_train_rows_async: replay memory is empty"); return CPP_ERR_STATE; }
   ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_naf_train_rows_async: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
   cpp_ctx* ctx = f->ctx;
@@ -763,6 +766,7 @@ extern "C" int cpp_naf_sample_and_compute(cpp_naf* f, cpp_replay* r, int B, uint
   RC(per_refuse(r, "cpp_naf_sample_and_compute"));      // (the half step of the data-parallel learners: one tree per shard is not built)
   if (f) naf_route_check(f);
   RC(naf_half_checks(f, r, B, "cpp_naf_sample_and_compute"));
+  RC(nstep_refuse(r, f->hp.discount, "cpp_naf_sample_and_compute"));
   cpp_ctx* ctx = f->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
   if (!f->step_batch) RC(cpp_batch_create(ctx, f->maxB, r->elems, r->A, &f->step_batch));
@@ -824,6 +828,7 @@ extern "C" int cpp_naf_dp_train_step(cpp_naf* f, cpp_replay* r, cpp_comm* c, int
   RC(per_refuse(r, "cpp_naf_dp_train_step"));      // (one tree per shard: not built)
   if (f) naf_route_check(f);
   RC(naf_half_checks(f, r, B, "cpp_naf_dp_train_step"));
+  RC(nstep_refuse(r, f->hp.discount, "cpp_naf_dp_train_step"));
   ARG_CHECK(n_batches >= 1 && sync_every >= 1, "cpp_naf_dp_train_step: n_batches %d, sync_every %d", n_batches, sync_every);
   ARG_CHECK(!c || c->ctx == f->ctx, "cpp_naf_dp_train_step: communicator and networks live on different contexts");
   const float inv = c ? 1.0f / (float)c->world : 1.0f;

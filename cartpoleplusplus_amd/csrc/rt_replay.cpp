@@ -111,6 +111,7 @@ static int replay_create(cpp_ctx* ctx, int buffer_size, int state_slots, int64_t
   r->rows_pin = nullptr; r->rows_pin_k = 0; memset(r->rows_pin_used, 0, sizeof(r->rows_pin_used)); memset(r->rows_pin_ev, 0, sizeof(r->rows_pin_ev));
   r->per_tree = nullptr; r->per_L = 0; r->per_alpha = r->per_eps = 0.f; r->per_maxp = r->per_beta = nullptr;
   r->per_rows = nullptr; r->per_w = nullptr; r->per_list = nullptr; r->per_vals = nullptr;
+  r->nstep_dev = nullptr; r->nstep_n = 1; r->nstep_discount = 0.f;
   r->stage = nullptr; r->stage_cap = 0; r->pinned = nullptr; r->pinned_cap = 0; r->pinned_busy = false; r->lut = nullptr; r->bad = nullptr;
   HIP_CHECK(hipEventCreateWithFlags(&r->pinned_free, hipEventDisableTiming));
   int rc = r->arena.alloc(&r->store, (size_t)state_slots * state_elems * replay_esz(r), false);
@@ -395,6 +396,7 @@ GatherArgs replay_gather_args(cpp_replay* r, int B, const int32_t* rows_dev, uin
   a.out_action = out->a; a.out_reward = out->r; a.out_mask = out->m;
   a.part = out->part; a.seed = seed; a.counter = counter_dev;
   a.elems = r->elems; a.B = B; a.size = r->size; a.size_ptr = r->size_dev; a.action_dim = r->A; a.C = C;
+  a.nstep = r->nstep_dev; a.rows_cap = r->rows;
   *C_out = C;
   return a;
 }
@@ -612,5 +614,45 @@ extern "C" int cpp_replay_draw_prioritized(cpp_replay* r, int B, uint64_t seed, 
   if (idxs) HIP_CHECK(hipMemcpyAsync(idxs, r->per_rows, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, r->ctx->stream));
   if (w) HIP_CHECK(hipMemcpyAsync(w, r->per_w, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, r->ctx->stream));
   HIP_CHECK(ctx_sync_stream(r->ctx));
+  return CPP_OK;
+}
+
+
+// ---------------------------------------------------------------------------------------------
+// n-step returns (gather_body.h: nstep_walk): extension, no reference counterpart
+// ---------------------------------------------------------------------------------------------
+extern "C" int cpp_replay_set_n_step(cpp_replay* r, int n, float discount) {
+  ARG_CHECK(r, "cpp_replay_set_n_step: NULL argument");
+  ARG_CHECK(n >= 1 && n <= NSTEP_MAX, "cpp_replay_set_n_step: n %d outside [1,%d]", n, NSTEP_MAX);
+  ARG_CHECK(std::isfinite(discount) && discount >= 0.f, "cpp_replay_set_n_step: discount %g (must be finite and >= 0)", discount);
+  HIP_CHECK(hipSetDevice(r->ctx->device));
+  if (!r->nstep_dev) {
+    // the captured step graphs hold the uniform gather instances: a new uid makes every one of them be captured again (with the
+    // n-step instances, which read n and the discount from the words below at every replay)
+    HIP_CHECK(ctx_sync_stream(r->ctx));
+    RC(dalloc(r->arena, &r->nstep_dev, (size_t)1));
+    r->uid = replay_next_uid(); r->sampled = false;
+  }
+  ++r->write_gen;          // (a minibatch presampled under the old setting is stale)
+  r->nstep_n = n; r->nstep_discount = discount;
+  // stream-ordered writes by value (as the priority beta): the next minibatch, also of an already captured graph, walks with them
+  RC(per_write_scalar(r, reinterpret_cast<float*>(&r->nstep_dev->discount), discount));
+  float nbits; memcpy(&nbits, &n, sizeof(nbits));
+  return per_write_scalar(r, reinterpret_cast<float*>(&r->nstep_dev->n), nbits);
+}
+
+extern "C" int cpp_replay_get_n_step(cpp_replay* r, int* n, float* discount) {
+  ARG_CHECK(r, "cpp_replay_get_n_step: NULL argument");
+  if (n) *n = r->nstep_n;
+  if (discount) *discount = r->nstep_discount;
+  return CPP_OK;
+}
+
+int nstep_refuse(const cpp_replay* r, float discount, const char* who) {
+  if (r && r->nstep_n > 1 && memcmp(&r->nstep_discount, &discount, sizeof(float)) != 0) {
+    cpp_set_error("%s: the memory folds %d-step returns with discount %.9g, the trainer's discount is %.9g (cpp_replay_set_n_step)", who,
+                  r->nstep_n, (double)r->nstep_discount, (double)discount);
+    return CPP_ERR_ARG;
+  }
   return CPP_OK;
 }

@@ -34,6 +34,30 @@ def _delegate(name):
     return op
 
 
+def n_step_columns(idxs, state_1_idx, state_2_idx, reward, terminal_mask, size, buffer_size, n, discount):
+    """The n-step walk of the device gather (include/cartpolepp_abi.h "n-step returns"; csrc/gather_body.h nstep_walk) on the host
+    columns: for every drawn row, (reward, terminal_mask, state_2_idx) of its n-step transition, in the gather's f32 operation order
+    (g_k = g_{k-1} * discount, R_k = R_{k-1} + r[j_k] * g_k, mask[j_{m-1}] * g_{m-1}; numpy rounds every f32 operation on its own)."""
+    idxs = np.asarray(idxs, np.int64).reshape(-1)
+    s1, s2 = np.asarray(state_1_idx).reshape(-1), np.asarray(state_2_idx).reshape(-1)
+    r, m = np.asarray(reward, np.float32).reshape(-1), np.asarray(terminal_mask, np.float32).reshape(-1)
+    size, R, d = int(size), int(buffer_size), np.float32(discount)
+    full = size == R
+    j = idxs.copy()
+    ret, g = r[j].copy(), np.ones(len(j), np.float32)
+    live = np.ones(len(j), bool)
+    for _ in range(1, int(n)):
+        nxt = (j + 1) % R if full else j + 1
+        go = live & (m[j] != 0) & ((j + 1 < size) | full) & (nxt != idxs)
+        nxt = np.where(go, nxt, j)                   # (rows that stop index themselves: no row outside the memory is read)
+        go &= s2[j] == s1[nxt]
+        j = np.where(go, nxt, j)
+        g = np.where(go, g * d, g)
+        ret = np.where(go, ret + r[j] * g, ret)
+        live = go
+    return ret.reshape(-1, 1), (m[j] * g).reshape(-1, 1), s2[j].astype(np.int32)
+
+
 class StateColumn(object):
     """`batch.state_1` / `batch.state_2`: the (B, *state_shape) f16 column of a Batch, still resident in HBM.
 
@@ -320,6 +344,7 @@ class ReplayMemory(object):
         self._adhoc_counter = 0      # sample_on_device draws (separate from the train steps' device counter)
         self.prioritized = False     # enable_priorities: proportional prioritized replay, the sum tree on the device
         self.priority_seed = 0
+        self.n_step, self.n_step_discount = 1, 0.0     # enable_n_step: the gathers fold n-step returns into reward / terminal_mask
         # pixel states (H, W, 3, cameras, repeats): channel count for the fused whitening statistics
         self.channels = int(np.prod(self.state_shape[2:])) if len(self.state_shape) == 5 else 0
         if self.channels > 0:        # per-state whitening sums, kept by the store: sampling never re-reads the pixels for them
@@ -425,7 +450,12 @@ class ReplayMemory(object):
         """the draw `idxs` as a Batch: slots and the three small columns are copied from the host mirrors now (np.copy semantics of
         replay_memory.py:134-138 for everything that is cheap), the states stay where they are."""
         small = {"action": self.action[idxs], "reward": self.reward[idxs], "terminal_mask": self.terminal_mask[idxs]}
-        b = Batch(self, self.state_shape, idxs, self.state_1_idx[idxs], self.state_2_idx[idxs], small)
+        s2_idx = self.state_2_idx[idxs]
+        if self.n_step > 1:          # the n-step transitions the device gathers of these rows form (from the mirrors: no device round trip)
+            small["reward"], small["terminal_mask"], s2_idx = n_step_columns(
+                idxs, self.state_1_idx, self.state_2_idx, self.reward, self.terminal_mask, self.size(), self.buffer_size,
+                self.n_step, self.n_step_discount)
+        b = Batch(self, self.state_shape, idxs, self.state_1_idx[idxs], s2_idx, small)
         self._drawn.add(b)
         return b
 
@@ -514,6 +544,20 @@ class ReplayMemory(object):
         out = np.empty(int(B), np.float32)
         check(lib.cpp_replay_last_weights(self.handle, int(B), ptr(out)))
         return out
+
+    # --- n-step returns (extension: the reference trains on one-step targets) ------------------------------------------------------
+    def enable_n_step(self, n, discount):
+        """n-step transitions for every minibatch of this memory (include/cartpolepp_abi.h, DESIGN "n-step returns"): each drawn row
+        walks up to n rows along its episode; reward becomes the discounted n-step return, terminal_mask discount^(m-1) * mask of the
+        last row walked and state_2 that row's.  `discount` must be the trainer's (opts.discount): the trainers refuse another one.
+        n = 1 is the one-step memory.  Takes effect at the next minibatch, in captured step graphs too."""
+        n, discount = int(n), float(discount)
+        if not 1 <= n <= 64:
+            raise ValueError("enable_n_step: n %d outside [1, 64]" % n)
+        if not (np.isfinite(discount) and discount >= 0.0):
+            raise ValueError("enable_n_step: discount %r (must be finite and >= 0)" % discount)
+        check(lib.cpp_replay_set_n_step(self.handle, n, discount))
+        self.n_step, self.n_step_discount = n, float(np.float32(discount))
 
     def fill_synthetic(self, n_rows, seed=1234):
         """bench/test helper: synthetic transitions generated on the device.  The host bookkeeping is advanced to

@@ -258,6 +258,30 @@ int cpp_replay_last_weights(cpp_replay* replay, int B, float* w);
  * cpp_ddpg_train_step would draw for its next minibatch; rows and weights come back to the host (either may be NULL) */
 int cpp_replay_draw_prioritized(cpp_replay* replay, int B, uint64_t seed, int32_t* idxs, float* w);
 
+/* ---- n-step returns (D4PG, Rainbow) in the gather ---------------------------------------------------------------------------
+ * Extension, no reference counterpart (the reference trains on r + mask * discount * Q'(s2), ddpg_cartpole.py:397).  Opt-in per
+ * memory with cpp_replay_set_n_step(replay, n, discount); n = 1 is the default and means exactly the one-step behaviour, bit for bit,
+ * on every path.  For a drawn row i, in a memory of R = buffer_size rows and current `size`:
+ *  - Walk: j_0 = i.  For k = 0 .. n-2 the walk goes on to j_{k+1} only if mask[j_k] != 0; the next row exists (j_k + 1 < size, or
+ *    the memory is full (size == R), in which case j_{k+1} = (j_k + 1) mod R); j_{k+1} != i; and s2_idx[j_k] == s1_idx[j_{k+1}].
+ *    Otherwise it stops.  m is the number of rows walked, 1 <= m <= n.
+ *  - The contiguity test is sound at the FIFO write head: a live row's state slots are in use, and a newly written row's s2 comes
+ *    from the free list, so the newest row (whose s2 is a slot no live row's s1 can hold) never appears to continue into the oldest
+ *    one.  For memories filled by add_episode (whole episodes, the last row of each with mask 0) the walk gives the exact n-step return.
+ *  - Arithmetic, all f32, every operation rounded on its own (no contraction): g_0 = 1, g_k = g_{k-1} * discount; R_0 = r[j_0],
+ *    R_k = R_{k-1} + r[j_k] * g_k.  The gathered reward is R_{m-1}, the gathered terminal_mask is mask[j_{m-1}] * g_{m-1}, the
+ *    gathered state_2 (and its whitening statistics) is the state in slot s2_idx[j_{m-1}]; state_1 and action come from j_0.  The
+ *    head kernels' target reward + (mask * discount) * Q'(s2) is then the n-step target.  At n = 1 these are the stored values.
+ *  - Trainers: cpp_ddpg_train_step, cpp_ddpg_train_rows, cpp_ddpg_sample_and_compute, cpp_ddpg_dp_train_step, cpp_naf_train_step,
+ *    cpp_naf_train_rows, cpp_naf_train_rows_async, cpp_naf_sample_and_compute and cpp_naf_dp_train_step return CPP_ERR_ARG, writing
+ *    nothing, on a memory with n > 1 whose discount is not bit-equal to their own hyper.discount.  A cpp_batch gathered by
+ *    cpp_replay_sample carries the folded columns: training it under another discount is the caller's affair.
+ *  - Prioritized replay combines unchanged: a drawn row's priority comes from its n-step TD; the draws and weights are as before.
+ *  - 1 <= n <= 64 (one wavefront); discount finite and >= 0.  n and the discount are device words written in stream order: a change
+ *    takes effect at the next minibatch, also inside already captured step graphs. */
+int cpp_replay_set_n_step(cpp_replay* replay, int n, float discount);
+int cpp_replay_get_n_step(cpp_replay* replay, int* n, float* discount);       /* (1, 0) until set; either output may be NULL */
+
 /* ---- DDPG train ops (ddpg_cartpole.py:102-119, :186-248, :329-337) --------------------------- */
 typedef struct cpp_ddpg_hyper {
   float actor_learning_rate;     /* --actor-learning-rate  (ddpg_cartpole.py:41)  */
