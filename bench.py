@@ -11,7 +11,8 @@ minibatches; in front of it run --warmup untimed ones and as many more as it tak
 JSON line): the chip's clock needs tens of milliseconds of load to settle, and a 20-step region started 10 steps after idle
 reports the ramp, not the rate (measured 3-7 % low).
 
-Prints ONE JSON line (rank 0).  Besides the contract keys it carries
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set up, warm up, time the --steps minibatches, write
+--dump-outputs if asked, print the line (contract keys, `config` without the measured extras below).  Everything else runs behind --full:
   roofline       : the dominant kernel (conv1 forward) against the matrix-pipe peak of the instruction it issues, launch
                    durations measured with HIP events on the stream the kernel runs on (a profiled pass of the same step
                    sequence, run right after the timed region; the timed region itself is one hipGraph replay per 5
@@ -24,7 +25,9 @@ Prints ONE JSON line (rank 0).  Besides the contract keys it carries
                    CPP_CONV_K16=0 CPP_CONV_B16=0): the f32 twin of the f16x2 / bf16x6 numbers
   control_exact_products : the same step with --precision exact (three f16 pieces, nine bf16 products: every product exact)
   extra          : short runs of the other BASELINE configs (cfg2, cfg4 = NAF, cfg5), steps/s each
-(N = 1, rank 0 only for the last three; --quick skips them.)
+  config.data_parallel, config.dp_vs_fused_same_process : data-parallel runs (N > 1 or --force-dp): how the step ran on every rank,
+                   replica digests, the exposed all-reduce; the two graphs in alternating blocks at world size 1
+(N = 1, rank 0 only for cpu_baseline, control and extra; --full --quick skips those three.)
 
 --dump-outputs DIR writes what the timed region's last train-step call computed (rank 0) as DIR/<name>.npy: see dump_outputs.
 """
@@ -55,6 +58,7 @@ SETTLE_STEPS = 200                       # untimed minibatches in front of the t
 PEAK_F32_MFMA_TFLOPS = 157.3             # MI355X_MICROARCH.md: dense f32-input MFMA peak
 PEAK_F16_MFMA_TFLOPS = 2500.0            # MI355X_MICROARCH.md: dense f16 / bf16 MFMA peak
 CONV_DEFS = ((5, 10), (5, 10), (3, 10))
+TRUNKS = {"ddpg": (4, 2), "naf": (2, 1)}  # conv-trunk forwards, backwards per minibatch (NAF shared trunk: value on s1, target on s2)
 # matrix pipe of a profiled kernel name -> (peak TFLOP/s for ALGORITHMIC flops, description)
 SUSTAINED_F16_MFMA_TFLOPS_RANDOM_OPERANDS = 2000      # measured 1914-2056 on two boxes: profiles/r02_mfma_rate_probe.txt (informational, see roofline["sustained"])
 # --precision: the release library multiplies two f16 pieces of conv1's f32 operand and six bf16 piece products in conv2 ("fast", the
@@ -148,7 +152,7 @@ def cpu_baseline_torch(shape, B, budget_s=25.0):
 
 def sub_bench(extra_args, env=None, timeout=420):
     """one more bench.py process (another workload, or the ablation library); returns its parsed JSON line or an error."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--quick"] + list(extra_args)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--quick"] + list(extra_args)
     try:
         r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, **(env or {})), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                            timeout=timeout)
@@ -200,6 +204,118 @@ def self_launch(n):
     return subprocess.call(cmd, cwd=ROOT, env=env)
 
 
+def kernel_profile(args, ctx, agent, shape, B, kind, ms_per_step):
+    """--full: a HIP-event pass of --profile-steps minibatches behind the timed region.  Returns the line's roofline, layers,
+    non_conv_us_per_step, conv_kernels_without_a_layers_row and kernels keys, and config's conv_bound_frac_whole_step / _basis."""
+    # ---- per-kernel HIP-event pass (rank 0 reports) -> roofline of the dominant kernel, per-layer table
+    ctx.prof_reset()
+    ctx.prof_enable(True)
+    pgroups = max(1, args.profile_steps // BATCHES_PER_STEP)
+    for _ in range(pgroups):
+        agent.train_step(B, BATCHES_PER_STEP)
+    ctx.sync()
+    ctx.prof_enable(False)
+    prof = ctx.prof_read()
+    pm = pgroups * BATCHES_PER_STEP
+
+    per_layer = conv_macs(shape)[2]
+    nfwd, nbwd = TRUNKS[kind]
+    gf = lambda macs, nets: 2.0 * B * macs * nets          # algorithmic FLOPs of one launch over the whole minibatch
+
+    # One row per conv launch of the fused step.  A row may be served by several profiled kernel names (the same kernel with
+    # and without the next minibatch's sample pass riding along: conv1_dw_f16 / conv1_dw_gather): their times and launches
+    # are merged, and the FLOPs per launch are a constant of the launch (2 * B * MACs * networks), never derived from counts.
+    # parts: [(algorithmic flops per launch, pipe)] -- a paired launch (dW + dX) is bounded by the sum of its parts' times.
+    def row(label, names, parts):
+        ms = sum(prof.get(n, (0.0, 0))[0] for n in names)
+        n = sum(prof.get(n, (0.0, 0))[1] for n in names)
+        if n == 0:
+            return None
+        avg_us = 1e3 * ms / n
+        flops = sum(p[0] for p in parts)
+        bound_us = sum(1e6 * p[0] / (PIPES[p[1]][0] * 1e12) for p in parts)
+        return {"layer": label, "kernels": [k for k in names if k in prof], "launches_per_step": round(n / pm, 2),
+                "gflop_per_launch": round(flops / 1e9, 3), "avg_launch_us": round(avg_us, 2), "us_per_step": round(1e3 * ms / pm, 2),
+                "pipe": "+".join(p[1] for p in parts), "achieved_tflops": round(flops / (avg_us * 1e-6) / 1e12, 2),
+                "bound_us": round(bound_us, 2), "frac": round(bound_us / avg_us, 4)}
+    L1, L2, L3 = per_layer
+    nb = nbwd
+    fast = "conv1_fwd_f16" in prof and not os.environ.get("CPP_CONV_DXRS") and not os.environ.get("CPP_CONV_DWRS")      # (the f16 / bf16 pipes are on)
+    bn = bool(getattr(args, "use_batch_norm", False))
+    rs2 = fast and not bn and shape[1] // 2 in (32, 64) and shape[0] % 4 == 0
+    rs3 = fast and not bn and shape[1] // 4 in (16, 32, 64) and shape[0] % 8 == 0 and shape[0] // 4 >= 8
+    rows = [r for r in (
+        row("conv1 forward", ["conv1_fwd_f16"], [(gf(L1, nfwd), F16_PIPE)]),
+        row("conv1 forward (f32 MFMA)", ["conv1_fwd"], [(gf(L1, nfwd), "f32")]),
+        row("conv1 dW", ["conv1_dw_f16", "conv1_dw_gather"], [(gf(L1, nb), F16_PIPE)]),
+        row("conv1 dW (f32 MFMA)", ["conv1_dw"], [(gf(L1, nb), "f32")]),
+        # (when conv3 + pool3 ride as the tail of conv2's workgroups there is no conv3_fwd launch: its FLOPs belong to this row)
+        row("conv2 forward" + ("" if "conv3_fwd" in prof else " + conv3 forward"), ["conv2_fwd"],
+            [(gf(L2, nfwd), B16_PIPE if "conv1_fwd_f16" in prof else "f32")] + ([] if "conv3_fwd" in prof else [(gf(L3, nfwd), "f32")])),
+        # (round 5: conv2's dX -- and conv3's dW / dX -- run on the bf16 pipes' row-streaming bodies, conv_dx_rs.h / conv_dw_rs.h, where
+        # the rows are 32 or 64 pixels wide (conv3's pair launch: 16 too); other widths keep the f32-input kernels)
+        row("conv2 dW + dX", ["conv2_bwd"], [(gf(L2, nb), B16_PIPE), (gf(L2, nb), B16_PIPE if rs2 else "f32")]),
+        # (conv2's dW on its own launch -- cfg5's 64 x 64 conv2 has no pair instance -- runs conv_dwb16_kernel, bf16 pieces, whenever conv1 /
+        # conv2 are on the f16 / bf16 pipes; round 4's line priced it against the f32 pipe)
+        row("conv2 dW", ["conv2_dw"], [(gf(L2, nb), B16_PIPE if "conv1_fwd_f16" in prof else "f32")]),
+        row("conv2 dX", ["conv2_dx"], [(gf(L2, nb), B16_PIPE if rs2 else "f32")]),
+        row("conv3 forward", ["conv3_fwd"], [(gf(L3, nfwd), B16_PIPE if rs3 and shape[1] // 4 >= 32 else "f32")]),      # (conv_fw_rs.h at rows of 32 / 64 pixels)
+        row("conv3 dW + dX", ["conv3_bwd"], [(gf(L3, nb), B16_PIPE if rs3 else "f32"), (gf(L3, nb), B16_PIPE if rs3 else "f32")]),
+        row("conv3 dW", ["conv3_dw"], [(gf(L3, nb), B16_PIPE if rs3 and shape[1] // 4 >= 32 else "f32")]),
+        row("conv3 dX", ["conv3_dx"], [(gf(L3, nb), B16_PIPE if rs3 and shape[1] // 4 >= 32 else "f32")])) if r]
+    for r in rows:
+        assert r["frac"] <= 1.0, "roofline accounting error: %r" % (r,)
+    mapped = {k for r in rows for k in r["kernels"]}
+    # ("conv1_image": conv1's operand images as a launch of their own -- the first minibatch of an outer step; the others' ride in the
+    # optimiser's launch.  No convolution FLOPs: it counts under non_conv_us_per_step)
+    unmapped_conv = sorted(k for k in prof if k.startswith("conv") and k not in mapped and k != "conv1_image")
+    # (reported, not asserted: a kernel id without a `layers` row understates conv_bound_frac_whole_step, it does not invalidate the line)
+    conv_us = sum(r["us_per_step"] for r in rows)
+    bound_us_step = sum(r["bound_us"] * r["launches_per_step"] for r in rows)
+    kernels = {k: {"ms_per_step": round(v[0] / pm, 4), "launches_per_step": round(v[1] / pm, 2)}
+               for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])}
+    other_us = 1e3 * sum(v[0] for v in prof.values()) / pm - conv_us
+
+    dom = max(rows, key=lambda r: r["us_per_step"]) if rows else None
+    roofline = None
+    if dom:
+        pipe = dom["pipe"].split("+")[0]
+        # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process; they come from separate
+        # rocprofv3 --pmc passes of this same command (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE), committed under profiles/
+        traffic, traffic_src = None, None
+        for rnd in ("r06", "r05", "r04", "r03", "r02", "r01"):
+            try:
+                with open(os.path.join(ROOT, "profiles", "%s_pmc.json" % rnd)) as f:
+                    pmc = json.load(f)
+                if args.workload == "cfg3" and dom["kernels"][0] in pmc["kernels"]:
+                    traffic = pmc["kernels"][dom["kernels"][0]]["hbm_bytes_per_launch"]
+                    traffic_src = "profiles/%s_pmc.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of bench.py, bytes per launch)" % rnd
+                    break
+            except Exception:
+                pass
+        roofline = {"bound": "mfma", "kernel": dom["kernels"][0], "layer": dom["layer"], "achieved": dom["achieved_tflops"],
+                    "peak": round(PIPES[pipe][0], 1), "unit": "TFLOP/s", "frac": dom["frac"], "peak_basis": PIPES[pipe][1],
+                    # SURVEY 8(d) named the f32-input MFMA peak as the bounding roofline before conv1 moved to exact f16 pieces: the
+                    # same achieved rate against THAT denominator (> 1 is possible and means nothing but "not an f32-MFMA kernel")
+                    "frac_vs_f32_mfma": round(dom["achieved_tflops"] / PEAK_F32_MFMA_TFLOPS, 4),
+                    "flops_per_launch": dom["gflop_per_launch"] * 1e9, "avg_launch_ms": round(dom["avg_launch_us"] / 1e3, 5),
+                    "launches_per_step": dom["launches_per_step"], "traffic": traffic, "traffic_source": traffic_src}
+        if pipe == F16_PIPE:
+            # informational, next to (never instead of) `peak` / `frac`: what the f16 pipes sustain on operands that toggle like image
+            # data -- the chip clocks to its power budget (profiles/diag/mfma_rate_probe.hip, profiles/r02_mfma_rate_probe.txt)
+            npieces = 3 if EXACT_PRODUCTS else 2
+            sus = SUSTAINED_F16_MFMA_TFLOPS_RANDOM_OPERANDS / float(npieces)
+            roofline["sustained"] = {"peak": round(sus, 1), "frac": round(dom["achieved_tflops"] / sus, 4),
+                                     "basis": "v_mfma_f32_16x16x32_f16 issued back to back by every SIMD with pseudo-random operands: 1914-2056 TFLOP/s at "
+                                              "1.9-2.0 GHz on two boxes, %d taken (2354-2453 at 2.4 GHz with constant operands; 32x32x16: 1595-1719), "
+                                              "/ %d pieces; profiles/r02_mfma_rate_probe.txt" % (SUSTAINED_F16_MFMA_TFLOPS_RANDOM_OPERANDS, npieces)}
+    return {"roofline": roofline, "layers": rows, "non_conv_us_per_step": round(other_us, 2),
+            "conv_kernels_without_a_layers_row": unmapped_conv, "kernels": kernels,
+            "conv_bound_frac_whole_step": round(bound_us_step / (1e3 * ms_per_step), 4),
+            "conv_bound_frac_basis": "sum over the conv launches of (algorithmic FLOPs / peak of the pipe the launch runs on) / measured "
+                                     "step time; pipes: " + "; ".join("%s = %.1f TFLOP/s (%s)" % (k, v[0], v[1]) for k, v in PIPES.items())}
+
+
 def main():
     global BATCHES_PER_STEP
     ap = argparse.ArgumentParser()
@@ -210,9 +326,12 @@ def main():
     ap.add_argument("--replay-rows", type=int, default=0, help="rows of the replay shard (default: 22000; cfg5: 6000)")
     ap.add_argument("--batches-per-step", type=int, default=BATCHES_PER_STEP,
                     help="minibatches per train-step call = per target soft update (ddpg_cartpole.py:30; 1: the per-minibatch-target-update variant of SURVEY 8d)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the per-kernel pass (roofline, layers, kernels), the data-parallel diagnostics and, "
+                         "unless --quick, the cpu baseline, control and extra runs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="headline + roofline only: no cpu baseline, control or extra runs")
-    ap.add_argument("--profile-steps", type=int, default=10, help="minibatches of the per-kernel HIP-event pass")
+    ap.add_argument("--quick", action="store_true", help="with --full: headline + roofline only, no cpu baseline, control or extra runs")
+    ap.add_argument("--profile-steps", type=int, default=10, help="minibatches of the per-kernel HIP-event pass (--full)")
     ap.add_argument("--use-batch-norm", action="store_true", help="informational: the networks of exps/run_8x / run_9x (--use-batch-norm)")
     ap.add_argument("--precision", default="fast", choices=["fast", "exact"],
                     help="arithmetic contract of conv1 / conv2 on the f16 / bf16 pipes (cpp_ctx_set_precision): operands to within one f32 ulp "
@@ -383,9 +502,9 @@ def main():
     # every rank (one hipGraph with the all-reduce inside, or the same launches on the stream because the capture was refused -- and why),
     # whether the replicas still hold the same bits after the timed region (identical inputs to every update: they must), and what the
     # all-reduce costs where nothing hides it (between the gradient kernels and the update: HIP events around the collective, one
-    # profiled pass, per minibatch)
+    # profiled pass, per minibatch).  --full only, like everything below that is not the headline
     dp_diag = None
-    if use_dp and learner is not None:
+    if args.full and use_dp and learner is not None:
         import hashlib
         st = learner.dp_status() if hasattr(learner, "dp_status") else {"path": "torch-collective", "reason": ""}
         nets_ = [n for n in (getattr(agent, "actor", None), getattr(agent, "critic", None), getattr(agent, "target_actor", None),
@@ -421,7 +540,7 @@ def main():
     # blocks (the two bench lines of a profile run come from two processes on a chip whose clock state drifts by a few per cent: paired
     # runs gave 0.957 ... 0.990; the kernels differ by one sumsq launch, rocprof: 1782 vs 1770 us per five minibatches)
     dp_vs_fused = None
-    if use_dp and world == 1 and learner is not None and args.sync_every == 1 and not args.overlap and hasattr(agent, "train_step"):
+    if args.full and use_dp and world == 1 and learner is not None and args.sync_every == 1 and not args.overlap and hasattr(agent, "train_step"):
         agent.train_step(B, BATCHES_PER_STEP); agent.train_step(B, BATCHES_PER_STEP)      # (captures the fused graph)
         blocks, bg = 8, max(20, groups)
         t_dp, t_fused = [], []
@@ -442,109 +561,10 @@ def main():
                        "blocks": blocks, "minibatches_per_block": n_blk,
                        "how": "alternating blocks of the two hipGraphs on the same trainer, replay and stream, order swapped every pair"}
 
-    # ---- per-kernel HIP-event pass (rank 0 reports) -> roofline of the dominant kernel, per-layer table
-    ctx.prof_reset()
-    ctx.prof_enable(True)
-    pgroups = max(1, args.profile_steps // BATCHES_PER_STEP)
-    for _ in range(pgroups):
-        agent.train_step(B, BATCHES_PER_STEP)
-    ctx.sync()
-    ctx.prof_enable(False)
-    prof = ctx.prof_read()
-    pm = pgroups * BATCHES_PER_STEP
-
-    F, Bk, per_layer = conv_macs(shape)
-    nfwd, nbwd = (4, 2) if kind == "ddpg" else (2, 1)      # trunks per minibatch (NAF shared trunk: value on s1, target on s2)
+    F, Bk, _ = conv_macs(shape)
+    nfwd, nbwd = TRUNKS[kind]
     conv_flops_step = 2.0 * B * (nfwd * F + nbwd * Bk)
-    gf = lambda macs, nets: 2.0 * B * macs * nets          # algorithmic FLOPs of one launch over the whole minibatch
-
-    # One row per conv launch of the fused step.  A row may be served by several profiled kernel names (the same kernel with
-    # and without the next minibatch's sample pass riding along: conv1_dw_f16 / conv1_dw_gather): their times and launches
-    # are merged, and the FLOPs per launch are a constant of the launch (2 * B * MACs * networks), never derived from counts.
-    # parts: [(algorithmic flops per launch, pipe)] -- a paired launch (dW + dX) is bounded by the sum of its parts' times.
-    def row(label, names, parts):
-        ms = sum(prof.get(n, (0.0, 0))[0] for n in names)
-        n = sum(prof.get(n, (0.0, 0))[1] for n in names)
-        if n == 0:
-            return None
-        avg_us = 1e3 * ms / n
-        flops = sum(p[0] for p in parts)
-        bound_us = sum(1e6 * p[0] / (PIPES[p[1]][0] * 1e12) for p in parts)
-        return {"layer": label, "kernels": [k for k in names if k in prof], "launches_per_step": round(n / pm, 2),
-                "gflop_per_launch": round(flops / 1e9, 3), "avg_launch_us": round(avg_us, 2), "us_per_step": round(1e3 * ms / pm, 2),
-                "pipe": "+".join(p[1] for p in parts), "achieved_tflops": round(flops / (avg_us * 1e-6) / 1e12, 2),
-                "bound_us": round(bound_us, 2), "frac": round(bound_us / avg_us, 4)}
-    L1, L2, L3 = per_layer
-    nb = nbwd
-    fast = "conv1_fwd_f16" in prof and not os.environ.get("CPP_CONV_DXRS") and not os.environ.get("CPP_CONV_DWRS")      # (the f16 / bf16 pipes are on)
-    bn = bool(getattr(args, "use_batch_norm", False))
-    rs2 = fast and not bn and shape[1] // 2 in (32, 64) and shape[0] % 4 == 0
-    rs3 = fast and not bn and shape[1] // 4 in (16, 32, 64) and shape[0] % 8 == 0 and shape[0] // 4 >= 8
-    rows = [r for r in (
-        row("conv1 forward", ["conv1_fwd_f16"], [(gf(L1, nfwd), F16_PIPE)]),
-        row("conv1 forward (f32 MFMA)", ["conv1_fwd"], [(gf(L1, nfwd), "f32")]),
-        row("conv1 dW", ["conv1_dw_f16", "conv1_dw_gather"], [(gf(L1, nb), F16_PIPE)]),
-        row("conv1 dW (f32 MFMA)", ["conv1_dw"], [(gf(L1, nb), "f32")]),
-        # (when conv3 + pool3 ride as the tail of conv2's workgroups there is no conv3_fwd launch: its FLOPs belong to this row)
-        row("conv2 forward" + ("" if "conv3_fwd" in prof else " + conv3 forward"), ["conv2_fwd"],
-            [(gf(L2, nfwd), B16_PIPE if "conv1_fwd_f16" in prof else "f32")] + ([] if "conv3_fwd" in prof else [(gf(L3, nfwd), "f32")])),
-        # (round 5: conv2's dX -- and conv3's dW / dX -- run on the bf16 pipes' row-streaming bodies, conv_dx_rs.h / conv_dw_rs.h, where
-        # the rows are 32 or 64 pixels wide (conv3's pair launch: 16 too); other widths keep the f32-input kernels)
-        row("conv2 dW + dX", ["conv2_bwd"], [(gf(L2, nb), B16_PIPE), (gf(L2, nb), B16_PIPE if rs2 else "f32")]),
-        # (conv2's dW on its own launch -- cfg5's 64 x 64 conv2 has no pair instance -- runs conv_dwb16_kernel, bf16 pieces, whenever conv1 /
-        # conv2 are on the f16 / bf16 pipes; round 4's line priced it against the f32 pipe)
-        row("conv2 dW", ["conv2_dw"], [(gf(L2, nb), B16_PIPE if "conv1_fwd_f16" in prof else "f32")]),
-        row("conv2 dX", ["conv2_dx"], [(gf(L2, nb), B16_PIPE if rs2 else "f32")]),
-        row("conv3 forward", ["conv3_fwd"], [(gf(L3, nfwd), B16_PIPE if rs3 and shape[1] // 4 >= 32 else "f32")]),      # (conv_fw_rs.h at rows of 32 / 64 pixels)
-        row("conv3 dW + dX", ["conv3_bwd"], [(gf(L3, nb), B16_PIPE if rs3 else "f32"), (gf(L3, nb), B16_PIPE if rs3 else "f32")]),
-        row("conv3 dW", ["conv3_dw"], [(gf(L3, nb), B16_PIPE if rs3 and shape[1] // 4 >= 32 else "f32")]),
-        row("conv3 dX", ["conv3_dx"], [(gf(L3, nb), B16_PIPE if rs3 and shape[1] // 4 >= 32 else "f32")])) if r]
-    for r in rows:
-        assert r["frac"] <= 1.0, "roofline accounting error: %r" % (r,)
-    mapped = {k for r in rows for k in r["kernels"]}
-    # ("conv1_image": conv1's operand images as a launch of their own -- the first minibatch of an outer step; the others' ride in the
-    # optimiser's launch.  No convolution FLOPs: it counts under non_conv_us_per_step)
-    unmapped_conv = sorted(k for k in prof if k.startswith("conv") and k not in mapped and k != "conv1_image")
-    # (reported, not asserted: a kernel id without a `layers` row understates conv_bound_frac_whole_step, it does not invalidate the line)
-    conv_us = sum(r["us_per_step"] for r in rows)
-    bound_us_step = sum(r["bound_us"] * r["launches_per_step"] for r in rows)
-    kernels = {k: {"ms_per_step": round(v[0] / pm, 4), "launches_per_step": round(v[1] / pm, 2)}
-               for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])}
-    other_us = 1e3 * sum(v[0] for v in prof.values()) / pm - conv_us
-
-    dom = max(rows, key=lambda r: r["us_per_step"]) if rows else None
-    roofline = None
-    if dom:
-        pipe = dom["pipe"].split("+")[0]
-        # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process; they come from separate
-        # rocprofv3 --pmc passes of this same command (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE), committed under profiles/
-        traffic, traffic_src = None, None
-        for rnd in ("r06", "r05", "r04", "r03", "r02", "r01"):
-            try:
-                with open(os.path.join(ROOT, "profiles", "%s_pmc.json" % rnd)) as f:
-                    pmc = json.load(f)
-                if args.workload == "cfg3" and dom["kernels"][0] in pmc["kernels"]:
-                    traffic = pmc["kernels"][dom["kernels"][0]]["hbm_bytes_per_launch"]
-                    traffic_src = "profiles/%s_pmc.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of bench.py, bytes per launch)" % rnd
-                    break
-            except Exception:
-                pass
-        roofline = {"bound": "mfma", "kernel": dom["kernels"][0], "layer": dom["layer"], "achieved": dom["achieved_tflops"],
-                    "peak": round(PIPES[pipe][0], 1), "unit": "TFLOP/s", "frac": dom["frac"], "peak_basis": PIPES[pipe][1],
-                    # SURVEY 8(d) named the f32-input MFMA peak as the bounding roofline before conv1 moved to exact f16 pieces: the
-                    # same achieved rate against THAT denominator (> 1 is possible and means nothing but "not an f32-MFMA kernel")
-                    "frac_vs_f32_mfma": round(dom["achieved_tflops"] / PEAK_F32_MFMA_TFLOPS, 4),
-                    "flops_per_launch": dom["gflop_per_launch"] * 1e9, "avg_launch_ms": round(dom["avg_launch_us"] / 1e3, 5),
-                    "launches_per_step": dom["launches_per_step"], "traffic": traffic, "traffic_source": traffic_src}
-        if pipe == F16_PIPE:
-            # informational, next to (never instead of) `peak` / `frac`: what the f16 pipes sustain on operands that toggle like image
-            # data -- the chip clocks to its power budget (profiles/diag/mfma_rate_probe.hip, profiles/r02_mfma_rate_probe.txt)
-            npieces = 3 if EXACT_PRODUCTS else 2
-            sus = SUSTAINED_F16_MFMA_TFLOPS_RANDOM_OPERANDS / float(npieces)
-            roofline["sustained"] = {"peak": round(sus, 1), "frac": round(dom["achieved_tflops"] / sus, 4),
-                                     "basis": "v_mfma_f32_16x16x32_f16 issued back to back by every SIMD with pseudo-random operands: 1914-2056 TFLOP/s at "
-                                              "1.9-2.0 GHz on two boxes, %d taken (2354-2453 at 2.4 GHz with constant operands; 32x32x16: 1595-1719), "
-                                              "/ %d pieces; profiles/r02_mfma_rate_probe.txt" % (SUSTAINED_F16_MFMA_TFLOPS_RANDOM_OPERANDS, npieces)}
+    prof_out = kernel_profile(args, ctx, agent, shape, B, kind, ms_per_step) if args.full else None
 
     # the fully connected heads (reported separately, never in a roofline numerator): per image and minibatch the actor's
     # layers run forward once and backward twice (dX, dW), the critic's forward twice and backward twice, each target network forward once
@@ -585,19 +605,15 @@ def main():
                    "data_parallel": dp_diag,
                    "conv_gflop_per_step": round(conv_flops_step / 1e9, 3),
                    "conv_gflop_per_step_as_the_reference_executes_it": (round(2.0 * B * (5 * F + 2 * Bk) / 1e9, 3) if kind == "ddpg" else None),
-                   "mlp_gflop_per_step": mlp_gflop,
-                   "conv_bound_frac_whole_step": round(bound_us_step / (1e3 * ms_per_step), 4),
-                   "conv_bound_frac_basis": "sum over the conv launches of (algorithmic FLOPs / peak of the pipe the launch runs on) / measured "
-                                            "step time; pipes: " + "; ".join("%s = %.1f TFLOP/s (%s)" % (k, v[0], v[1]) for k, v in PIPES.items())},
-        "roofline": roofline,
-        "layers": rows,
-        "non_conv_us_per_step": round(other_us, 2),
-        "conv_kernels_without_a_layers_row": unmapped_conv,
-        "kernels": kernels,
+                   "mlp_gflop_per_step": mlp_gflop},
     }
+    if prof_out is not None:
+        for k in ("conv_bound_frac_whole_step", "conv_bound_frac_basis"):
+            out["config"][k] = prof_out.pop(k)
+        out.update(prof_out)
     if dumped is not None:
         out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-    side = rank == 0 and world == 1 and not args.quick
+    side = args.full and rank == 0 and world == 1 and not args.quick
     if side and not args.no_cpu_baseline and kind == "ddpg":
         out["cpu_baseline"] = cpu_baseline_torch(shape, B)
         out["cpu_baseline_numpy"] = cpu_baseline_numpy(shape, B)

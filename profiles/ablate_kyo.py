@@ -29,7 +29,7 @@ def run(kernel, names):
         env = dict(os.environ)
         if name != "BASE":
             env["CARTPOLEPP_ABLATION"] = "ablate_%s" % name
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--quick", "--steps", "100", "--warmup", "10"],
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--quick", "--steps", "100", "--warmup", "10"],
                              env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode()
         try:
             d = json.loads(out.strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 L=cartpoleplusplus_amd/lib
 cp $L/libcartpolepp_hip_ablation.so /tmp/abl_keep.so
 export CARTPOLEPP_ABLATION=1
-run() { lib=$1; shift; cp $L/$lib $L/libcartpolepp_hip_ablation.so; echo "== $lib $*"; env "$@" python bench.py --quick --steps 200 --warmup 20 2>/dev/null | python -c "
+run() { lib=$1; shift; cp $L/$lib $L/libcartpolepp_hip_ablation.so; echo "== $lib $*"; env "$@" python bench.py --full --quick --steps 200 --warmup 20 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -7,7 +7,7 @@ for round in 1 2; do
 for v in $L/libexp_*.so; do
   cp $v $L/libcartpolepp_hip_ablation.so
   echo "== $(basename $v)"
-  python bench.py --quick --workload $1 --steps $2 --warmup 10 2>/dev/null | python -c "
+  python bench.py --full --quick --workload $1 --steps $2 --warmup 10 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

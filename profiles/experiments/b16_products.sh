@@ -15,7 +15,7 @@ for v in "nine 1 1" "f32 1 0" "six six 1"; do
 done
 for i in 1 2; do
   for v in 1 six; do
-    echo "== bench ABLATION=$v"; CARTPOLEPP_ABLATION=$v python bench.py --quick --steps 200 --warmup 20 2>/dev/null | python -c "
+    echo "== bench ABLATION=$v"; CARTPOLEPP_ABLATION=$v python bench.py --full --quick --steps 200 --warmup 20 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], [(l['layer'], l['avg_launch_us']) for l in d['layers']])"
   done

@@ -4,7 +4,7 @@
 export CARTPOLEPP_ABLATION=1
 run() {
   echo "== $*"
-  env "$@" python bench.py --quick --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "
+  env "$@" python bench.py --full --quick --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

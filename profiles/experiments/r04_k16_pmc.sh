@@ -6,7 +6,7 @@ OUT=$PWD/gpurun_out/k16pmc
 REPO=$PWD
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-PB="python $REPO/bench.py --quick --steps 10 --warmup 5 --profile-steps 5"
+PB="python $REPO/bench.py --full --quick --steps 10 --warmup 5 --profile-steps 5"
 pass() {  # name, counters...
   local n=$1; shift
   rm -rf $OUT/$n

@@ -1,7 +1,7 @@
 #!/bin/bash
-# bench.py --quick on each experimental library; prints the value and the five conv layers' launch times
+# bench.py --full --quick on each experimental library; prints the value and the five conv layers' launch times
 for v in "$@"; do
-  env CARTPOLEPP_ABLATION=$v python bench.py --quick --steps 200 --warmup 20 2>/tmp/err_$v.txt | python -c "
+  env CARTPOLEPP_ABLATION=$v python bench.py --full --quick --steps 200 --warmup 20 2>/tmp/err_$v.txt | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 # multiplied with both networks' dY) against the shipped one network per workgroup (two per CU); ablation build, CPP_DW16_PAIR30=1.
 for i in 1 2 3; do
   for v in 0 1; do
-    CARTPOLEPP_ABLATION=1 CPP_DW16_PAIR30=$v python bench.py --quick --workload cfg5 --steps 100 --warmup 10 2>/dev/null | python -c "
+    CARTPOLEPP_ABLATION=1 CPP_DW16_PAIR30=$v python bench.py --full --quick --workload cfg5 --steps 100 --warmup 10 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['kernels']

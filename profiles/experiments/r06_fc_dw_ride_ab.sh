@@ -3,7 +3,7 @@
 for w in cfg3 cfg2; do
 for i in 1 2 3; do
   for v in 1 0; do
-    CARTPOLEPP_ABLATION=1 CPP_RIDE_FC_DW=$v python bench.py --quick --workload $w --steps 200 --warmup 10 2>/dev/null | python -c "
+    CARTPOLEPP_ABLATION=1 CPP_RIDE_FC_DW=$v python bench.py --full --quick --workload $w --steps 200 --warmup 10 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['kernels']

@@ -4,7 +4,7 @@
 for w in cfg3 cfg5 r50; do
   for i in 1 2; do
     for v in "" counted; do
-      CARTPOLEPP_ABLATION=$v python bench.py --quick --workload $w --steps 60 --warmup 10 2>/dev/null | python -c "
+      CARTPOLEPP_ABLATION=$v python bench.py --full --quick --workload $w --steps 60 --warmup 10 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$w variant=%-8s' % '$v', d['value'], [(l['layer'], l['avg_launch_us']) for l in d['layers'][:3]])"

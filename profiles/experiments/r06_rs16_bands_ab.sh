@@ -2,7 +2,7 @@
 # (512 workgroups) against the previous commit's whole images (lib/libcartpolepp_hip_prev.so), alternating on one box
 for i in 1 2 3; do
   for v in "" prev; do
-    CARTPOLEPP_ABLATION=$v python bench.py --quick --workload cfg4 --steps 200 --warmup 10 2>/dev/null | python -c "
+    CARTPOLEPP_ABLATION=$v python bench.py --full --quick --workload cfg4 --steps 200 --warmup 10 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['kernels']

@@ -3,7 +3,7 @@
 for w in cfg3 cfg2 cfg4; do
 for i in 1 2 3; do
   for v in "" r05; do
-    CARTPOLEPP_ABLATION=$v python bench.py --quick --workload $w --steps 200 --warmup 10 2>/dev/null | python -c "
+    CARTPOLEPP_ABLATION=$v python bench.py --full --quick --workload $w --steps 200 --warmup 10 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$w lib=%-4s' % ('$v' or 'r06'), d['value'], [(l['layer'][:13], l['avg_launch_us']) for l in d['layers'][:4]], 'non_conv', d['non_conv_us_per_step'])"

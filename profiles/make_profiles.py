@@ -65,7 +65,7 @@ def other_configs(rnd):
     with open(os.path.join(ROOT, "profiles", "%s_configs.md" % rnd), "w") as f:
         f.write("# Round %s: the other configurations (profiles/run_profiles.sh), one MI355X\n\n" % rnd[1:])
         f.write("Every number quoted in README.md / DESIGN.md for a configuration other than cfg3 comes from this file.  Per\n"
-                "configuration: the `bench.py --quick` JSON line (un-profiled run) and the `rocprofv3 --kernel-trace --stats` kernel\n"
+                "configuration: the `bench.py --full --quick` JSON line (un-profiled run) and the `rocprofv3 --kernel-trace --stats` kernel\n"
                 "table of the same command.\n\n")
         for name in names:
             line = open(os.path.join(ROOT, "gpurun_out", "bench_%s_%s.json" % (rnd, name))).read().strip()
@@ -114,7 +114,7 @@ def main(rnd):
     with open(os.path.join(ROOT, "profiles", "%s_kernel_stats.md" % rnd), "w") as f:
         f.write("# Round %s profile: bench.py (cfg3, 64x64x18, B=256), MI355X\n\n" % rnd[1:])
         f.write("Command (profiles/run_profiles.sh): `rocprofv3 --kernel-trace --stats -d gpurun_out/prof_%s -o k -- python bench.py "
-                "--quick --steps 50 --warmup 10 --profile-steps 5`\n\n" % rnd)
+                "--full --quick --steps 50 --warmup 10 --profile-steps 5`\n\n" % rnd)
         f.write("70 minibatch steps in total (warm-up, hipGraph-replayed timed steps, and the eager HIP-event pass); durations in\n"
                 "microseconds, from the rocpd database's `top_kernels` view (profiles/make_profiles.py).  One `conv_fwd_rs16_kernel<18>` (round 5;\n"
                 "rounds 2-4: `conv_fwd_k16_kernel<18,5,2,2>`) launch computes conv1 of all four networks of a minibatch (blockIdx.y = network); likewise conv2/conv3 forward;\n"
@@ -127,7 +127,7 @@ def main(rnd):
         f.write("| kernel | calls | total us | avg us | % |\n|---|---|---|---|---|\n")
         for name, calls, tot, avg, pct in rows:
             f.write("| `%s` | %d | %.1f | %.3f | %.2f |\n" % (name, calls, tot, avg, pct))
-        f.write("\n## bench.py JSON line of the same build (un-profiled default run, same box)\n\n```\n%s\n```\n" % bench_line)
+        f.write("\n## bench.py JSON line of the same build (`bench.py --full` outside the profiler, same box)\n\n```\n%s\n```\n" % bench_line)
     sq, fe, wr = counters(pmc_of("pmc_%s_sq" % rnd)), counters(pmc_of("pmc_%s_fetch" % rnd)), counters(pmc_of("pmc_%s_write" % rnd))
     kernels = {}
     for k in sq:
@@ -149,7 +149,7 @@ def main(rnd):
             e["hbm_write_bytes"] = 1024.0 * e["WRITE_SIZE_KB"]
             e["hbm_bytes_per_launch"] = e["hbm_read_bytes_corrected"] + e["hbm_write_bytes"]
         kernels[k] = e
-    blob = {"source": "profiles/run_profiles.sh: rocprofv3 --kernel-trace --pmc <counters> -- python bench.py --quick --steps 10 --warmup 5 "
+    blob = {"source": "profiles/run_profiles.sh: rocprofv3 --kernel-trace --pmc <counters> -- python bench.py --full --quick --steps 10 --warmup 5 "
                       "--profile-steps 5 (three separate passes: SQ_*, FETCH_SIZE, WRITE_SIZE)",
             "note": "means per dispatch; FETCH_SIZE (KB) doubled per the gfx950 correction for 16-byte coalesced reads; conv*_fwd "
                     "launches carry four networks, conv*_dw / conv*_dx launches two",

@@ -1,9 +1,11 @@
-"""bench.py prints ONE JSON line with the contract's keys (the driver parses it): run the quick variant on the GPU and check the
-line's shape.  (The full variant adds cpu_baseline / control / extra and takes minutes; profiles/r02_kernel_stats.md keeps one.)"""
+"""bench.py prints ONE JSON line with the contract's keys (the driver parses it): run it on the GPU and check the line's shape.  A plain
+run carries the headline alone; --full --quick adds the per-kernel pass (roofline, layers), and --full alone also cpu_baseline / control /
+extra, which take minutes (profiles/r02_kernel_stats.md keeps one)."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -12,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_quick_line_has_the_contract_keys():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "5", "--quick"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "5", "--full", "--quick"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
@@ -37,6 +39,29 @@ def test_bench_quick_line_has_the_contract_keys():
     assert d["cpu_baseline"] is None                            # --quick
 
 
+def test_bench_plain_line_is_the_headline_alone():
+    """`bench.py --gpus 1 --steps N --warmup W`: set up, warm up, time, print.  The line has the contract keys and none of what --full
+    measures (no per-kernel pass, no side runs, no cpu baseline), and the run spends little time outside its minibatches."""
+    t0 = time.time()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "5"],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    wall = time.time() - t0
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == "DDPG training steps/sec, 64x64x18 pixel obs, batch=256" and d["unit"] == "steps/s"
+    assert d["n_gpus"] == 1 and d["steps"] == 10 and d["warmup"] == 5 and d["warmup_steps_run"] >= 200
+    assert d["higher_is_better"] is True and d["dtype"] == "f32-acc/f16x2,bf16x6"
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-3
+    for k in ("roofline", "layers", "kernels", "non_conv_us_per_step", "cpu_baseline_numpy", "control", "control_exact_products", "extra"):
+        assert k not in d, k
+    assert d["cpu_baseline"] is None and "conv_bound_frac_whole_step" not in d["config"]
+    assert d["config"]["data_parallel"] is None and d["config"]["dp_vs_fused_same_process"] is None
+    outside = wall - (d["steps"] + d["warmup_steps_run"]) * d["ms_per_step"] / 1e3
+    assert outside < 30.0, outside
+
+
 def test_bench_gpus_2_as_a_plain_command_launches_its_own_ranks():
     """`python bench.py --gpus N` with no WORLD_SIZE in the environment is the driver's form: it must start its N ranks itself
     (torch.distributed.run), and rank 0's ONE JSON line must say n_gpus = N with the whole-job rate.  On a one-GPU box the two ranks
@@ -59,7 +84,8 @@ def test_bench_force_dp_compares_the_two_graphs_in_one_process():
     """the data-parallel step (ncclAllReduce, norm and optimiser inside ONE hipGraph per outer step) against the single
     learner's fused graph at world size 1 -- alternating blocks in the SAME process (two processes on one chip differ by its clock state).
     The bar is the verdict's 0.98; measured 0.992-0.994 (profiles/r04_configs.md cfg3_dp1)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--quick", "--force-dp"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--quick",
+                        "--force-dp"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]

@@ -42,7 +42,8 @@ def test_bench_at_n_gpus_reports_one_graph_per_step_identical_replicas_and_even_
     same parameter bits after the timed region, the exposed all-reduce must be reported, and no rank may lag the others by 10 %."""
     if _gpus() < n:
         pytest.skip("needs %d GPUs on this node (found %d)" % (n, _gpus()))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "40", "--warmup", "5", "--quick"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "40", "--warmup", "5", "--full",
+                        "--quick"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500, env=_clean_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
