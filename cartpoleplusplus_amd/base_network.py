@@ -155,6 +155,8 @@ class Network(object):
             spec.pixel, (spec.H, spec.W, spec.C) = 1, self._conv_input
         else:
             spec.pixel, spec.state_elems = 0, int(self._state_elems)
+        if len(self._hidden) > len(spec.hidden):
+            raise ValueError("%s: %d hidden layers, at most %d" % (self.namespace, len(self._hidden), len(spec.hidden)))
         spec.n_hidden = len(self._hidden)
         for i, h in enumerate(self._hidden):
             spec.hidden[i] = h

@@ -60,7 +60,8 @@ __global__ __launch_bounds__(HEADS_THREADS) void ddpg_heads_kernel(const DdpgHea
   float* wq = W3t + wfl;           float* wqt = wq + (N3P + 4);       // [0, N3P): weights (zero padded); N3P: the bias
   float* Wo = wqt + (N3P + 4);     float* Wot = Wo + (n2a + 1) * A;
   const int n1a = h.n1a, n1ap = (n1a + 3) & ~3;
-  const int w2fl = n1a ? (((n1a + 1) * n2a + HEADS_WSLACK + 3) & ~3) : 0;
+  // rows [0, n1ap] of [W2; b2]: the loop below reads rows up to n1ap - 1, which lie past the bias row n1a unless n1a % 4 == 0
+  const int w2fl = n1a ? (((n1ap + 1) * n2a + HEADS_WSLACK + 3) & ~3) : 0;
   float* W2 = hl + ((2 * wfl + 2 * (N3P + 4) + 2 * (n2a + 1) * A + 3) & ~3); float* W2t = W2 + w2fl;
   float* rowbase = W2t + w2fl;
   const int rowf0 = N3P + 2 * n2cp + ((2 * n2a + 3) & ~3);  // per row: dz3 scratch, xc, xtc (16-byte aligned), xa, xta
@@ -158,7 +159,8 @@ __global__ __launch_bounds__(HEADS_THREADS) void ddpg_heads_kernel(const DdpgHea
   __syncthreads();
   HCK();
   if (n1a) {   // ---- the actors' last hidden layer: lane t owns unit t (units >= n2a read on into finite weights and are zeroed)
-    // (x is zero from n1a to n1ap and the rows it meets there -- the bias row, then the zero slack -- are finite: no bounds in the loop)
+    // (x is zero from n1a to n1ap and the rows it meets there -- the bias row, then zeros: w2fl covers n1ap + 1 rows -- are finite: no
+    // bounds in the loop; a row past the image would be the next one's, or the uninitialised row scratch behind W2t)
     float p2 = W2[n1a * n2a + t], p2t = W2t[n1a * n2a + t], q2 = 0.f, q2t = 0.f;
 #pragma unroll 4
     for (int k = 0; k < n1ap; k += 4) {
@@ -284,7 +286,7 @@ __global__ __launch_bounds__(HEADS_THREADS) void ddpg_heads_kernel(const DdpgHea
 size_t ddpg_heads_lds_bytes(const DdpgHeadsArgs& h) {
   const size_t k3 = h.n2c + h.A + 1, n3p = HEADS_N3P, n2cp = (h.n2c + 3) & ~3;
   const size_t wfl = (k3 * h.n3 + HEADS_WSLACK + 3) & ~(size_t)3;
-  const size_t w2fl = h.n1a ? (((size_t)(h.n1a + 1) * h.n2a + HEADS_WSLACK + 3) & ~(size_t)3) : 0, n1ap = (h.n1a + 3) & ~3;
+  const size_t n1ap = (h.n1a + 3) & ~3, w2fl = h.n1a ? (((n1ap + 1) * h.n2a + HEADS_WSLACK + 3) & ~(size_t)3) : 0;
   const size_t w = ((2 * wfl + 2 * (n3p + 4) + 2 * (size_t)(h.n2a + 1) * h.A + 3) & ~(size_t)3) + 2 * w2fl;
   const size_t f = w + (size_t)HEADS_ROWS * (n3p + 2 * n2cp + ((2 * h.n2a + 3) & ~3) + (h.n1a ? HEADS_TEAM + 2 * n1ap : 0));
   return f * sizeof(float);
@@ -292,7 +294,7 @@ size_t ddpg_heads_lds_bytes(const DdpgHeadsArgs& h) {
 
 bool ddpg_heads_supported(const DdpgHeadsArgs& h) {
   if (h.n1a && !(h.n1a <= HEADS_N1MAX && (h.n2a & 1) == 0 &&
-                 (h.n1a + 1) * h.n2a + HEADS_WSLACK + 4 <= 4 * HEADS_NW4P * HEADS_THREADS)) return false;
+                 (((h.n1a + 3) & ~3) + 1) * h.n2a + HEADS_WSLACK + 4 <= 4 * HEADS_NW4P * HEADS_THREADS)) return false;
   return h.A <= HEADS_AMAX && h.n3 <= HEADS_N3P && h.n2a <= HEADS_TEAM && h.n2c <= HEADS_TEAM &&
          (h.n2a + 1) * h.A <= 2 * HEADS_THREADS && (h.n2c + h.A + 1) * h.n3 + HEADS_WSLACK + 4 <= 4 * HEADS_NW4 * HEADS_THREADS && (h.n3 & 1) == 0 && ddpg_heads_lds_bytes(h) <= 120 * 1024 && (h.B + HEADS_ROWS - 1) / HEADS_ROWS <= DDPG_HEADS_MAX_WGS;
 }

@@ -47,7 +47,8 @@ extern "C" int cpp_naf_create(cpp_ctx* ctx, cpp_net* value, cpp_net* tvalue, cpp
   ARG_CHECK(value->spec.head_out == 1 && tvalue->spec.head_out == 1 && value->nparams == tvalue->nparams,
             "cpp_naf_create: value / target_value shapes");
   const int A = mu->spec.head_out;
-  ARG_CHECK(A >= 1 && A <= 8 && lv->spec.head_out == A * (A + 1) / 2, "cpp_naf_create: mu has %d outputs, l_values %d (want A and A(A+1)/2)",
+  ARG_CHECK(A >= 1 && A <= 8, "cpp_naf_create: action_dim %d outside [1, 8] (the NAF head's L matrix is at most 8 x 8)", A);
+  ARG_CHECK(lv->spec.head_out == A * (A + 1) / 2, "cpp_naf_create: mu has %d outputs, l_values %d (want A and A(A+1)/2)",
             A, lv->spec.head_out);
   ARG_CHECK(mu->spec.head_act == 2 && lv->spec.head_act == 0 && value->spec.head_act == 0, "cpp_naf_create: head activations");
   ARG_CHECK(hp->optimiser >= CPP_OPT_SGD && hp->optimiser <= CPP_OPT_ADAM, "cpp_naf_create: optimiser %d", hp->optimiser);

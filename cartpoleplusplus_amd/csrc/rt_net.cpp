@@ -95,8 +95,13 @@ extern "C" int cpp_net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_ba
   ARG_CHECK(spec->kind == CPP_ACTOR || spec->kind == CPP_CRITIC || spec->kind == CPP_HEAD, "cpp_net_create: kind %d", spec->kind);
   if (spec->kind == CPP_HEAD) ARG_CHECK(spec->head_out >= 1 && spec->head_out <= 64 && (spec->head_act == 0 || spec->head_act == 2),
                                         "cpp_net_create: head_out %d head_act %d", spec->head_out, spec->head_act);
-  ARG_CHECK(spec->action_dim >= 1 && spec->action_dim <= 16, "cpp_net_create: action_dim %d", spec->action_dim);
-  ARG_CHECK(spec->n_hidden >= 0 && spec->n_hidden <= 8, "cpp_net_create: n_hidden %d", spec->n_hidden);
+  // (a head network's action_dim is its output width -- NAF's l_values head has A (A + 1) / 2 outputs, up to 36 -- and shapes nothing)
+  if (spec->kind != CPP_HEAD)
+    ARG_CHECK(spec->action_dim >= 1 && spec->action_dim <= 16, "cpp_net_create: action_dim %d outside [1, 16]", spec->action_dim);
+  else ARG_CHECK(spec->action_dim >= 1, "cpp_net_create: action_dim %d", spec->action_dim);
+  ARG_CHECK(spec->n_hidden >= 0 && spec->n_hidden <= 8, "cpp_net_create: n_hidden %d outside [0, 8]", spec->n_hidden);
+  for (int i = 0; i < spec->n_hidden; ++i)
+    ARG_CHECK(spec->hidden[i] >= 1, "cpp_net_create: hidden layer %d has width %d (at least 1)", i, spec->hidden[i]);
   if (spec->pixel) ARG_CHECK(spec->H >= 8 && spec->W >= 8 && spec->C >= 1 && spec->C <= CPP_MAX_CHANNELS,
                              "cpp_net_create: pixel dims %dx%dx%d", spec->H, spec->W, spec->C);
   else ARG_CHECK(spec->state_elems >= 1, "cpp_net_create: state_elems %d", spec->state_elems);

@@ -20,19 +20,24 @@ class FakeEnv(object):
         def __init__(self, shape):
             self.shape = tuple(shape)
 
-    def __init__(self, shape):
-        self.observation_space, self.action_space = self._S(shape), self._S((1, 2))
+    def __init__(self, shape, action_dim=2):
+        self.observation_space, self.action_space = self._S(shape), self._S((1, action_dim))
 
 
-def make_pair(shape, B, pixel, seed=0, replay_size=64, perturb=True, dt=np.float64, **optkw):
+def make_pair(shape, B, pixel, seed=0, replay_size=64, perturb=True, dt=np.float64, actor_hidden=None, critic_hidden=None,
+              action_dim=2, **optkw):
     """returns (agent, oracle DDPG, specs).  Parameters are perturbed away from the near-zero actor
-    head / zero biases so every path carries signal."""
+    head / zero biases so every path carries signal.  actor_hidden / critic_hidden: lists of widths
+    (--actor-hidden-layers / --critic-hidden-layers; None: the defaults), action_dim: the env's action size."""
     import os
     from cartpoleplusplus_amd import ddpg_cartpole as D
     if os.environ.get("TEST_EXACT_PRODUCTS") == "1":      # (test snippets run in subprocesses: the TEST's switch for --exact-products)
         optkw.setdefault("exact_products", True)
+    for key, widths in (("actor_hidden_layers", actor_hidden), ("critic_hidden_layers", critic_hidden)):
+        if widths is not None:
+            optkw[key] = ",".join(str(int(w)) for w in widths)
     make_opts(D, shape, B, pixel, replay_memory_size=replay_size, **optkw)
-    agent = D.DeepDeterministicPolicyGradientAgent(FakeEnv(shape))
+    agent = D.DeepDeterministicPolicyGradientAgent(FakeEnv(shape, action_dim))
     agent.initialise_variables(seed=seed)
     rng = np.random.default_rng(seed + 100)
     if perturb:
@@ -48,8 +53,8 @@ def make_pair(shape, B, pixel, seed=0, replay_size=64, perturb=True, dt=np.float
         kw = dict(pixel=True, H=shape[0], W=shape[1], C=int(np.prod(shape[2:])), batch_norm=bool(optkw.get("use_batch_norm", False)))
     else:
         kw = dict(pixel=False, state_elems=int(np.prod(shape)))
-    aspec = O.NetSpec("actor", 2, [100, 100, 50], dropout=bool(optkw.get("use_dropout", False)), **kw)
-    cspec = O.NetSpec("critic", 2, [100, 100, 50], **kw)
+    aspec = O.NetSpec("actor", action_dim, D._hidden(D.opts.actor_hidden_layers), dropout=bool(optkw.get("use_dropout", False)), **kw)
+    cspec = O.NetSpec("critic", action_dim, D._hidden(D.opts.critic_hidden_layers), **kw)
     ref = O.DDPG(aspec, cspec, agent.actor.get_params(), agent.critic.get_params(), dt)
     ref.set_targets(agent.target_actor.get_params(), agent.target_critic.get_params())
     return agent, ref, (aspec, cspec)
@@ -210,19 +215,91 @@ def fill_with_rendered_episodes(agent, shape, rows, seed=0, blind_camera=False, 
 F32_GRAD_FACTOR = 1.5
 
 
+# ---- which kernels ran the heads: one eager, profiled minibatch, its launch counts against the ones the layer lists imply
+def ddpg_gemm_levels(path, actor_hidden, critic_hidden, pixel):
+    """GEMM launches of one DDPG minibatch (rt_ddpg.cpp compute_gradients: the op graph launches every GEMM that is ready at
+    once, so this is the number of levels that hold one).  na = actor layers with the head.  Fused heads (pixel critic: two
+    levels in front of its action splice): the forward of the actors' first na - 1 - pre layers and the critics' prefix side by
+    side, the heads kernel, then their backward chains side by side -- pre, the actor's last hidden layer in the heads kernel,
+    takes one level off each actor chain.  GEMM levels: the actors, the critics' prefix, the concat layer and q three times over
+    (fed actions, a = mu(s1), the target), dQ/da back to the splice, the actor's head gradient, the two backward chains."""
+    na = len(actor_hidden) + 1
+    if path in ("heads", "heads+pre"):
+        assert pixel, "the fused heads need the pixel critic's prefix"
+        return 2 * max(na - 1 - (path == "heads+pre"), 2)
+    if pixel:
+        return max(2 * na + 4, na + 7)
+    return 2 * na + 2 * (len(critic_hidden) + 1)
+
+
+def naf_gemm_levels(path, hidden, share):
+    """the same for one NAF minibatch (rt_naf.cpp naf_compute_gradients, pixel trunk).  nh hidden layers.  heads: the nh layers
+    forward, naf_heads_kernel (the head layers, d(representation)), nh levels of dW / dX; mlp (nh = 2): the second layer joins the
+    kernel both ways; gemm: the three head layers and the target value's last layer take a level, naf_head_kernel, the heads' dW
+    and the three accumulating d(representation) GEMMs, then the hidden stack; own trunks: three stacks side by side."""
+    nh = len(hidden)
+    if not share:
+        assert path == "gemm"
+        return 2 * nh + 2
+    return {"mlp": 2, "heads": 2 * nh, "gemm": 2 * nh + 4}[path]
+
+
+def _profiled_step(agent, ctx, B):
+    ctx.sync()
+    ctx.prof_reset()
+    ctx.prof_enable(True)
+    try:
+        agent.train_step(B, 1)                 # (profiling: the eager launch sequence, no graph capture)
+        ctx.sync()
+    finally:
+        ctx.prof_enable(False)
+    prof = ctx.prof_read()
+    ctx.prof_reset()
+    return {k: n for k, (_ms, n) in prof.items()}
+
+
+def ddpg_path(agent, B, actor_hidden, critic_hidden, pixel):
+    """one eager minibatch on the replay memory's rows, profiled: 'heads+pre', 'heads' or 'gemm' ('heads+pre|heads' where the
+    two launch the same number of GEMM levels: an actor of two hidden layers, whose folded layer is hidden behind the critics'
+    two-level prefix).  Raises if the counts fit none of them."""
+    n = _profiled_step(agent, agent.actor.ctx, B)
+    heads, gemm = n.get("heads", 0), n.get("gemm", 0)
+    cand = ["heads+pre", "heads"] if heads == 1 else ["gemm"] if heads == 0 else []
+    if "heads+pre" in cand and len(actor_hidden) < 2:
+        cand.remove("heads+pre")
+    fit = [p for p in cand if ddpg_gemm_levels(p, actor_hidden, critic_hidden, pixel) == gemm]
+    assert fit, "launch counts %s fit no DDPG head path (actor %s, critic %s)" % (n, actor_hidden, critic_hidden)
+    return "|".join(fit)
+
+
+def naf_path(agent, B, hidden, share):
+    """the same for NAF: 'mlp' (naf_mlp_kernel), 'heads' (naf_heads_kernel) or 'gemm' (GEMM levels + naf_head_kernel)."""
+    n = _profiled_step(agent, agent.value_net.ctx, B)
+    gemm = n.get("gemm", 0)
+    assert n.get("naf_head", 0) == 1, n
+    cand = (["mlp"] if len(hidden) == 2 else []) + ["heads", "gemm"] if share else ["gemm"]
+    fit = [p for p in cand if naf_gemm_levels(p, hidden, share) == gemm]
+    assert len(fit) == 1, "launch counts %s fit %s of the NAF head paths (hidden %s, share %s)" % (n, fit, hidden, share)
+    return fit[0]
+
+
 def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_size=None, seed=0, graph=True,
                                   atol=1e-5, grad_rel=2e-5, param_rel=2e-6, warm="philox", report_only=False,
-                                  fill="noise", f32_twin=False, flip_tol=1e-5):
+                                  fill="noise", f32_twin=False, flip_tol=1e-5, probe=False, before_step=None, pixel=True, **pair_kw):
     """ONE minibatch of the fused inner step (cpp_ddpg_train_step, default kernels: f16-pipe conv1 reading the replay store
     through the sampled slots, bf16-pipe conv2, fused heads, paired launches) -- with graph=True the hipGraph REPLAY of it,
     on rows drawn by the device's Philox sampler -- against oracle.DDPG(float64) on the same rows and the same starting
     parameters: actions / Q / TD / dQ/da at `atol` (north_star: 1e-5), both pre-clip gradient lists per variable at
-    `grad_rel` (pool routes: the device's, accepted only at near ties), the clipped SGD result and the target updates."""
+    `grad_rel` (pool routes: the device's, accepted only at near ties), the clipped SGD result and the target updates.
+    pair_kw: make_pair's widths, action size and options (--use-dropout: the oracle draws the device's masks).  probe: one
+    profiled minibatch first, report["path"] = ddpg_path().  before_step(): called right before the minibatch that is checked.
+    pixel=False: a low-dimensional state of `shape` (no trunk: the pool and ReLU routes are not compared)."""
     import ctypes
     from cartpoleplusplus_amd import _lib
-    agent, _ref, (aspec, cspec) = make_pair(shape, B, True, seed=seed, replay_size=replay_size or rows + 50,
-                                           replay_store=replay_store)
+    agent, _ref, (aspec, cspec) = make_pair(shape, B, pixel, seed=seed, replay_size=replay_size or rows + 50,
+                                           replay_store=replay_store, **pair_kw)
     report = {}
+    steps = 0                                             # training-mode forwards before the one checked (dropout masks)
     try:
         rm = agent.replay_memory
         if fill == "noise":
@@ -231,12 +308,19 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
             assert fill in ("render", "render-blind", "render-glint"), fill
             fill_with_rendered_episodes(agent, shape, rows, seed=seed, blind_camera=(fill != "render"),
                                         glint=0.02 if fill == "render-glint" else 0.0)
+        if probe:
+            report["path"] = ddpg_path(agent, B, aspec.hidden, cspec.hidden, pixel)
+            steps += 1
         if graph or warm == "philox-eager":
             agent.train_step(B, 1)                        # eager pass + capture
+            steps += 1
         elif warm == "rows":
             agent.train_step(B, 1, idxs=np.random.default_rng(seed + 77).integers(0, rows, B).astype(np.int32))
+            steps += 1
         nets = (agent.actor, agent.critic, agent.target_actor, agent.target_critic)
         P = [n.get_params() for n in nets]
+        if before_step is not None:
+            before_step()
         if graph:
             agent.train_step(B, 1)                        # hipGraph replay, device-drawn rows
             idxs = np.empty(B, np.int32)
@@ -249,9 +333,12 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
         g_a, g_c = agent.actor.get_grads(), agent.critic.get_grads()
         stats = agent.trainer.last_stats()
         Pn = [n.get_params() for n in nets]
-        codes_a, codes_c = device_pool_codes(agent.actor, B), device_pool_codes(agent.critic, B)
-        relu_a, relu_c = device_relu_active(agent.actor, B), device_relu_active(agent.critic, B)
-        pools_c = [getattr(agent.critic, "pool%d" % i).eval(B) for i in (1, 2, 3)]
+        if pixel:
+            codes_a, codes_c = device_pool_codes(agent.actor, B), device_pool_codes(agent.critic, B)
+            relu_a, relu_c = device_relu_active(agent.actor, B), device_relu_active(agent.critic, B)
+            pools_c = [getattr(agent.critic, "pool%d" % i).eval(B) for i in (1, 2, 3)]
+        else:
+            codes_a = codes_c = relu_a = relu_c = None
         # the minibatch, read back through paths that do not involve the gather kernel's state copy
         s1, s2 = rm.state[rm.state_1_idx[idxs]], rm.state[rm.state_2_idx[idxs]]
         hb = rm.batch(idxs=idxs)
@@ -261,6 +348,9 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
         agent.close()
     ref = O.DDPG(aspec, cspec, P[0], P[1], np.float64)
     ref.set_targets(P[2], P[3])
+    if aspec.dropout:
+        ref.actor.drop_masks = dropout_masks("actor", aspec.hidden, B, steps)
+        ref.target_actor.drop_masks = dropout_masks("target_actor", aspec.hidden, B, steps)
     # the two discontinuities of the trunk's gradient -- which element of a 2x2 window carries it, and whether the ReLU lets it
     # through -- are taken from the device and must coincide with the oracle's own except at rounding-level ties
     ref.actor.amax_override, ref.critic.amax_override = codes_a, codes_c
@@ -271,7 +361,7 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
     for key, fn, args in (("flips_actor", pool_flips_are_near_ties, (ag["cache_actor"], codes_a)),
                           ("flips_critic", pool_flips_are_near_ties, (cg["cache_critic"], codes_c)),
                           ("relu_flips_actor", relu_flips_are_at_the_boundary, (ag["cache_actor"], relu_a)),
-                          ("relu_flips_critic", relu_flips_are_at_the_boundary, (cg["cache_critic"], relu_c))):
+                          ("relu_flips_critic", relu_flips_are_at_the_boundary, (cg["cache_critic"], relu_c))) if pixel else ():
         try:
             report[key] = fn(*args, flip_tol, what=key.split("_")[-1])
         except AssertionError as e:
@@ -283,7 +373,7 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
     report["err_q"] = float(np.abs(q - cg["q"]).max())
     report["err_td"] = float(np.abs(td - cg["td"]).max())
     report["q_scale"] = float(np.abs(cg["q"]).max())
-    for i, (name, _k, _co) in enumerate(O.CONV_DEFS):
+    for i, (name, _k, _co) in enumerate(O.CONV_DEFS if pixel else ()):
         want = cg["cache_critic"][name][1]
         report["err_pool%d" % (i + 1)] = float(np.abs(pools_c[i].reshape(want.shape) - want).max())
         report["mag_pool%d" % (i + 1)] = float(np.abs(want).max())
@@ -292,6 +382,8 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
         # entitled to): how far IT sits from the float64 values on these inputs
         ref32 = O.DDPG(aspec, cspec, P[0], P[1], np.float32)
         ref32.set_targets(P[2], P[3])
+        if aspec.dropout:
+            ref32.actor.drop_masks, ref32.target_actor.drop_masks = ref.actor.drop_masks, ref.target_actor.drop_masks
         ref32.actor.amax_override, ref32.critic.amax_override = codes_a, codes_c      # (the same routes: rounding is what is compared)
         ref32.actor.relu_override, ref32.critic.relu_override = relu_a, relu_c
         ag32, cg32 = ref32.actor_gradients(s1), ref32.critic_gradients(t)
@@ -303,7 +395,7 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
         report["f32_err_dq_da"] = float(np.abs(ag32["dq_da"] - ag["dq_da"]).max())
         report["f32_err_q"] = float(np.abs(cg32["q"] - cg["q"]).max())
         report["f32_err_td"] = float(np.abs(cg32["td"] - cg["td"]).max())
-        for i, (name, _k, _co) in enumerate(O.CONV_DEFS):
+        for i, (name, _k, _co) in enumerate(O.CONV_DEFS if pixel else ()):
             report["f32_err_pool%d" % (i + 1)] = float(np.abs(cg32["cache_critic"][name][1] - cg["cache_critic"][name][1]).max())
         report["white_scale_max"] = float(np.max(cg["cache_critic"]["white"][0]))
         report["white_scale_min"] = float(np.min(cg["cache_critic"]["white"][0]))

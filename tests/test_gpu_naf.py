@@ -20,19 +20,23 @@ class HB(object):
 
 
 def make_naf(shape, B, share, optimiser="GradientDescent", optimiser_args=None, seed=0, replay_size=64, clip=5.0,
-             use_batch_norm=False, use_dropout=False):
+             use_batch_norm=False, use_dropout=False, hidden=None, action_dim=2):
+    """hidden: list of widths (--hidden-layers; None: the default 100,50), action_dim: the env's action size"""
     from cartpoleplusplus_amd import naf_cartpole as F
     pixel = len(shape) == 5
+    hidden = [100, 50] if hidden is None else [int(h) for h in hidden]
+    A = int(action_dim)
     kw = dict(batch_size=B, replay_memory_size=replay_size, share_input_state_representation=share,
               optimiser=optimiser, optimiser_args=json.dumps(optimiser_args or {"learning_rate": 0.01}),
-              gradient_clip=clip, use_batch_norm=use_batch_norm, use_dropout=use_dropout)
+              gradient_clip=clip, use_batch_norm=use_batch_norm, use_dropout=use_dropout,
+              hidden_layers=",".join(str(h) for h in hidden))
     if pixel:
         kw.update(use_raw_pixels=True, render_height=shape[0], render_width=shape[1], num_cameras=shape[3],
                   action_repeats=shape[4])
     else:
         kw.update(use_raw_pixels=False, action_repeats=shape[0])
     F.set_opts(F.default_opts(**kw))
-    agent = F.NormalizedAdvantageFunctionAgent(FakeEnv(shape))
+    agent = F.NormalizedAdvantageFunctionAgent(FakeEnv(shape, A))
     agent.initialise_variables(seed=seed)
     rng = np.random.default_rng(seed + 5)
     for net in (agent.value_net, agent.naf.mu_net, agent.naf.l_net):
@@ -44,14 +48,14 @@ def make_naf(shape, B, share, optimiser="GradientDescent", optimiser_args=None, 
     skw = dict(pixel=True, H=shape[0], W=shape[1], C=int(np.prod(shape[2:])), batch_norm=use_batch_norm) if pixel else \
         dict(pixel=False, state_elems=int(np.prod(shape)))
     skw["dropout"] = use_dropout
-    vspec = N.HeadSpec(1, "linear", [100, 50], **skw)
+    vspec = N.HeadSpec(1, "linear", hidden, **skw)
     if share:
-        mspec = N.HeadSpec(2, "tanh", [], False, state_elems=50, head_only=True)
-        lspec = N.HeadSpec(3, "linear", [], False, state_elems=50, head_only=True)
+        mspec = N.HeadSpec(A, "tanh", [], False, state_elems=hidden[-1], head_only=True)
+        lspec = N.HeadSpec(N.num_l_values(A), "linear", [], False, state_elems=hidden[-1], head_only=True)
     else:
-        mspec, lspec = N.HeadSpec(2, "tanh", [100, 50], **skw), N.HeadSpec(3, "linear", [100, 50], **skw)
+        mspec, lspec = N.HeadSpec(A, "tanh", hidden, **skw), N.HeadSpec(N.num_l_values(A), "linear", hidden, **skw)
     ref = N.NAF(vspec, mspec, lspec, agent.value_net.get_params(), agent.naf.mu_net.get_params(),
-                agent.naf.l_net.get_params(), share, 2, np.float64, gradient_clip=clip,
+                agent.naf.l_net.get_params(), share, A, np.float64, gradient_clip=clip,
                 optimiser=N.make_optimiser(optimiser, optimiser_args or {"learning_rate": 0.01}))
     ref.target_value = O.Net(vspec, agent.target_value_net.get_params(), np.float64)
     return agent, ref, (vspec, mspec, lspec)
@@ -269,19 +273,20 @@ def test_cfg4_B256_graph_replayed_naf_step_against_f64_oracle(shape, B, share):
     naf_fused_step_against_f64_oracle(shape, B, share)
 
 
-def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise"):
+def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, probe=False, **naf_kw):
     """cfg4 at the size the metric is quoted on (64x64x18, B = 256, shared trunk, Momentum as in exps/run_93.sh): the hipGraph REPLAY
     of the fused NAF step (naf_cartpole.py:365-373) on rows drawn by the device's sampler against oracle.NAF(float64) started from the
     same parameters and Momentum slots: loss at 1e-5, the pre-clip gradient list per variable at 2e-5 (the trunk's two
     discontinuities -- pool route, ReLU -- taken from the device and accepted only at rounding-level ties), the clipped Momentum
     update and the target update.  Second case: the reference's own defaults (50 x 50 x 6 render, batch 128,
-    naf_cartpole.py's three networks on trunks of their own)."""
+    naf_cartpole.py's three networks on trunks of their own).  naf_kw: make_naf's widths and action size; probe: one profiled
+    minibatch first, its head path (tests.helpers.naf_path) returned."""
     import ctypes
     from cartpoleplusplus_amd import _lib
-    from tests.helpers import (device_pool_codes, device_relu_active, pool_flips_are_near_ties, relu_flips_are_at_the_boundary)
-    rows = 700
+    from tests.helpers import (device_pool_codes, device_relu_active, naf_path, pool_flips_are_near_ties, relu_flips_are_at_the_boundary)
     oargs = {"learning_rate": 0.01, "momentum": 0.9}
-    agent, _ref, specs = make_naf(shape, B, share, "Momentum", oargs, seed=4, replay_size=rows + 50)
+    agent, _ref, specs = make_naf(shape, B, share, "Momentum", oargs, seed=4, replay_size=rows + 50, **naf_kw)
+    path = None
     try:
         rm = agent.replay_memory
         if fill == "noise":
@@ -290,6 +295,8 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise"):
             from cartpoleplusplus_amd import naf_cartpole as F
             from tests.helpers import fill_with_rendered_episodes
             fill_with_rendered_episodes(agent, shape, rows, seed=33, blind_camera=(fill == "render-blind"), opts=F.opts)
+        if probe:
+            path = naf_path(agent, B, specs[0].hidden, share)
         agent.train_step(B, 1)                                    # eager pass + capture (also fills the Momentum slots)
         nets = (agent.value_net, agent.naf.mu_net, agent.naf.l_net, agent.target_value_net)
         P = [n.get_params() for n in nets]
@@ -308,7 +315,7 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise"):
     finally:
         agent.close()
     vspec, mspec, lspec = specs
-    ref = N.NAF(vspec, mspec, lspec, P[0], P[1], P[2], share, 2, np.float64, gradient_clip=5.0,
+    ref = N.NAF(vspec, mspec, lspec, P[0], P[1], P[2], share, mspec.head_out, np.float64, gradient_clip=5.0,
                 optimiser=N.make_optimiser("Momentum", oargs))
     ref.target_value = O.Net(vspec, P[3], np.float64)
     ref.m = opt["m"].astype(np.float64)
@@ -332,6 +339,7 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise"):
     assert_flat_close(vspec, Pn[3], ref.target_value.flat(), rel=1e-6, what="target value net")
     d_got, d_want = got.astype(np.float64) - before, ref.flat() - before
     assert np.linalg.norm(d_got - d_want) < 2.0 ** -23 * np.linalg.norm(before) + 5e-5 * np.linalg.norm(d_want)
+    return path
 
 
 @pytest.mark.parametrize("switch", ["CPP_NAF_MLP", "CPP_NAF_HEADS"])

@@ -24,10 +24,12 @@ PER = dict(prioritized_replay=True, priority_alpha=0.6, priority_beta=0.4, prior
 MOMENTUM = ("Momentum", {"learning_rate": 0.01, "momentum": 0.9})
 
 
-def make_naf(shape, B, share, optimiser="Momentum", optimiser_args=None, seed=0, replay_size=64, **extra):
+def make_naf(shape, B, share, optimiser="Momentum", optimiser_args=None, seed=0, replay_size=64, hidden=None, action_dim=2, **extra):
     """tests/test_gpu_naf.py's make_naf with options of its own (the prioritized-replay keys)"""
     from cartpoleplusplus_amd import naf_cartpole as F
     pixel = len(shape) == 5
+    hidden, A = ([100, 50] if hidden is None else [int(h) for h in hidden]), int(action_dim)
+    extra.setdefault("hidden_layers", ",".join(str(h) for h in hidden))
     kw = dict(batch_size=B, replay_memory_size=replay_size, share_input_state_representation=share, optimiser=optimiser,
               optimiser_args=json.dumps(optimiser_args or MOMENTUM[1]), gradient_clip=5.0)
     if pixel:
@@ -36,7 +38,7 @@ def make_naf(shape, B, share, optimiser="Momentum", optimiser_args=None, seed=0,
         kw.update(use_raw_pixels=False, action_repeats=shape[0])
     kw.update(extra)
     F.set_opts(F.default_opts(**kw))
-    agent = F.NormalizedAdvantageFunctionAgent(FakeEnv(shape))
+    agent = F.NormalizedAdvantageFunctionAgent(FakeEnv(shape, A))
     agent.initialise_variables(seed=seed)
     rng = np.random.default_rng(seed + 5)
     for net in (agent.value_net, agent.naf.mu_net, agent.naf.l_net):
@@ -46,12 +48,12 @@ def make_naf(shape, B, share, optimiser="Momentum", optimiser_args=None, seed=0,
     p = agent.target_value_net.get_params()
     agent.target_value_net.set_params(p + rng.normal(0, 0.01, p.shape).astype(np.float32))
     skw = dict(pixel=True, H=shape[0], W=shape[1], C=int(np.prod(shape[2:]))) if pixel else dict(pixel=False, state_elems=int(np.prod(shape)))
-    vspec = N.HeadSpec(1, "linear", [100, 50], **skw)
+    vspec = N.HeadSpec(1, "linear", hidden, **skw)
     if share:
-        mspec = N.HeadSpec(2, "tanh", [], False, state_elems=50, head_only=True)
-        lspec = N.HeadSpec(3, "linear", [], False, state_elems=50, head_only=True)
+        mspec = N.HeadSpec(A, "tanh", [], False, state_elems=hidden[-1], head_only=True)
+        lspec = N.HeadSpec(N.num_l_values(A), "linear", [], False, state_elems=hidden[-1], head_only=True)
     else:
-        mspec, lspec = N.HeadSpec(2, "tanh", [100, 50], **skw), N.HeadSpec(3, "linear", [100, 50], **skw)
+        mspec, lspec = N.HeadSpec(A, "tanh", hidden, **skw), N.HeadSpec(N.num_l_values(A), "linear", hidden, **skw)
     return agent, (vspec, mspec, lspec)
 
 
@@ -77,20 +79,24 @@ def last_rows(agent, B):
     return rows
 
 
-def per_naf_step_against_f64_oracle(shape, B, share, rows=2500, replay_store="f16", seed=0, alpha=0.6, eps=1e-6, grad_rel=2e-5):
+def per_naf_step_against_f64_oracle(shape, B, share, rows=2500, replay_store="f16", seed=0, alpha=0.6, eps=1e-6, grad_rel=2e-5,
+                                    probe=False, **naf_kw):
     """ONE hipGraph-replayed minibatch of the fused NAF step on a prioritized memory (rows drawn by priority, priorities spread over three
     decades) against WeightedNAF(float64) on the same rows, parameters and Momentum slots: w.max() == 1 and w.min() < 0.5, the loss
     mean(w td^2) at 1e-5, the pre-clip gradients at 2e-5 (the trunk's pool routes and ReLUs taken from the device, accepted only at
     rounding-level ties), the unweighted gradient far away, the priorities written (|td| + eps)^alpha (held to the oracle's td, which
     the device's matches at 1e-5 relative to max(1, |td|): the tolerance carries alpha times that), and the clipped Momentum update."""
     from cartpoleplusplus_amd import naf_cartpole as F
-    from tests.helpers import device_pool_codes, device_relu_active, pool_flips_are_near_ties, relu_flips_are_at_the_boundary
+    from tests.helpers import device_pool_codes, device_relu_active, naf_path, pool_flips_are_near_ties, relu_flips_are_at_the_boundary
     pixel = len(shape) == 5
     agent, specs = make_naf(shape, B, share, seed=seed, replay_size=rows + 50, replay_store=replay_store, priority_alpha=alpha,
-                            priority_eps=eps, **{k: v for k, v in PER.items() if k not in ("priority_alpha", "priority_eps")})
+                            priority_eps=eps, **dict({k: v for k, v in PER.items() if k not in ("priority_alpha", "priority_eps")}, **naf_kw))
+    path = None
     try:
         rm = agent.replay_memory
         rm.fill_synthetic(rows, seed=33 + seed)
+        if probe:
+            path = naf_path(agent, B, specs[0].hidden, share)
         agent.train_step(B, 1)                                    # eager pass + capture (also fills the Momentum slots)
         rm.update_priorities(np.arange(rows), np.random.default_rng(seed + 9).lognormal(0.0, 2.0, rows).astype(np.float32))
         nets = (agent.value_net, agent.naf.mu_net, agent.naf.l_net, agent.target_value_net)
@@ -113,7 +119,7 @@ def per_naf_step_against_f64_oracle(shape, B, share, rows=2500, replay_store="f1
     finally:
         agent.close()
     vspec, mspec, lspec = specs
-    ref = WeightedNAF(vspec, mspec, lspec, Pm[0], Pm[1], Pm[2], share, 2, np.float64, gradient_clip=5.0,
+    ref = WeightedNAF(vspec, mspec, lspec, Pm[0], Pm[1], Pm[2], share, mspec.head_out, np.float64, gradient_clip=5.0,
                       optimiser=N.make_optimiser(*MOMENTUM))
     ref.target_value = O.Net(vspec, Pm[3], np.float64)
     ref.m = opt["m"].astype(np.float64)
@@ -144,6 +150,7 @@ def per_naf_step_against_f64_oracle(shape, B, share, rows=2500, replay_store="f1
     assert_flat_close(cat, np.concatenate(Pn[:3]), ref.flat(), rel=2e-6, what="NAF params after the prioritized step")
     assert_flat_close(vspec, Pn[3], ref.target_value.flat(), rel=1e-6, what="target value net")
     assert np.abs(ref.flat() - before).max() > 0
+    return path
 
 
 PARITY = [

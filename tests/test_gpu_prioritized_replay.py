@@ -210,16 +210,20 @@ def test_reference_loop_is_the_fused_step(shape, B, pixel, per_step):
 
 
 def _per_step_against_f64_oracle(shape, B, rows, pixel=True, replay_store="f16", seed=0, alpha=0.6, beta=0.4, eps=1e-6,
-                                 atol=1e-5, grad_rel=2e-5, flip_tol=1e-5):
+                                 atol=1e-5, grad_rel=2e-5, flip_tol=1e-5, probe=False, **pair_kw):
     """ONE graph-replayed minibatch of the fused step on a prioritized memory (rows drawn by priority, importance weights w) against
     oracle.DDPG(float64) on the same rows and parameters: actions / Q / TD at `atol`, the actor's pre-clip gradients at `grad_rel`
     (unweighted), the critic's at `grad_rel` against the oracle's backward pass of w * td_dev -- the weighted gradient, the critic's
     gradient being linear in TD --, the weighted loss mean(w td^2), and the priorities written: (|td_dev| + eps)^alpha."""
     agent, _ref, (aspec, cspec) = make_pair(shape, B, pixel, seed=seed, replay_size=rows + 50, replay_store=replay_store,
-                                           prioritized_replay=True, priority_alpha=alpha, priority_beta=beta, priority_eps=eps)
+                                           prioritized_replay=True, priority_alpha=alpha, priority_beta=beta, priority_eps=eps, **pair_kw)
+    path = None
     try:
         rm = agent.replay_memory
         rm.fill_synthetic(rows, seed=21 + seed)
+        if probe:
+            from tests.helpers import ddpg_path
+            path = ddpg_path(agent, B, aspec.hidden, cspec.hidden, pixel)
         agent.train_step(B, 1)                            # eager pass + capture
         # priorities spread over three decades: the next draw's importance weights are far from 1
         rm.update_priorities(np.arange(rows), np.random.default_rng(seed + 9).lognormal(0.0, 2.0, rows).astype(np.float32))
@@ -268,6 +272,7 @@ def _per_step_against_f64_oracle(shape, B, rows, pixel=True, replay_store="f16",
     assert float(np.linalg.norm(g_c - cg["grads"]) / np.linalg.norm(cg["grads"])) > 100 * grad_rel
     want = P.priority(td.reshape(-1)[[last[k] for k in keys]], alpha, eps)
     assert np.abs(written / want - 1).max() < 2e-6
+    return path
 
 
 @pytest.mark.parametrize("shape,store,seed", [((64, 64, 3, 2, 3), "f16", 0), ((64, 64, 3, 2, 3), "u8", 2), ((64, 64, 3, 1, 3), "f16", 1)],
