@@ -5,6 +5,12 @@ import numpy as np
 from oracle import ddpg_np as O
 
 
+def hyper_options(hyper):
+    """an O.Hyper as the command line options of ddpg_cartpole.py (make_pair's **optkw)"""
+    return dict(actor_learning_rate=hyper.actor_lr, critic_learning_rate=hyper.critic_lr, discount=hyper.discount,
+                gradient_clip=hyper.gradient_clip, target_update_rate=hyper.target_update_rate)
+
+
 def make_opts(D, shape, B, pixel, **kw):
     if pixel:
         o = D.default_opts(use_raw_pixels=True, render_height=shape[0], render_width=shape[1],
@@ -244,18 +250,23 @@ def naf_gemm_levels(path, hidden, share):
     return {"mlp": 2, "heads": 2 * nh, "gemm": 2 * nh + 4}[path]
 
 
-def _profiled_step(agent, ctx, B):
+def _profiled_calls(ctx, fn):
+    """launch counts per kernel family of fn() (profiling: the eager launch sequence, no graph capture)"""
     ctx.sync()
     ctx.prof_reset()
     ctx.prof_enable(True)
     try:
-        agent.train_step(B, 1)                 # (profiling: the eager launch sequence, no graph capture)
+        fn()
         ctx.sync()
     finally:
         ctx.prof_enable(False)
     prof = ctx.prof_read()
     ctx.prof_reset()
     return {k: n for k, (_ms, n) in prof.items()}
+
+
+def _profiled_step(agent, ctx, B):
+    return _profiled_calls(ctx, lambda: agent.train_step(B, 1))
 
 
 def ddpg_path(agent, B, actor_hidden, critic_hidden, pixel):
@@ -285,7 +296,8 @@ def naf_path(agent, B, hidden, share):
 
 def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_size=None, seed=0, graph=True,
                                   atol=1e-5, grad_rel=2e-5, param_rel=2e-6, warm="philox", report_only=False,
-                                  fill="noise", f32_twin=False, flip_tol=1e-5, probe=False, before_step=None, pixel=True, **pair_kw):
+                                  fill="noise", f32_twin=False, flip_tol=1e-5, probe=False, before_step=None, pixel=True, hyper=None,
+                                  **pair_kw):
     """ONE minibatch of the fused inner step (cpp_ddpg_train_step, default kernels: f16-pipe conv1 reading the replay store
     through the sampled slots, bf16-pipe conv2, fused heads, paired launches) -- with graph=True the hipGraph REPLAY of it,
     on rows drawn by the device's Philox sampler -- against oracle.DDPG(float64) on the same rows and the same starting
@@ -293,9 +305,12 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
     `grad_rel` (pool routes: the device's, accepted only at near ties), the clipped SGD result and the target updates.
     pair_kw: make_pair's widths, action size and options (--use-dropout: the oracle draws the device's masks).  probe: one
     profiled minibatch first, report["path"] = ddpg_path().  before_step(): called right before the minibatch that is checked.
-    pixel=False: a low-dimensional state of `shape` (no trunk: the pool and ReLU routes are not compared)."""
+    pixel=False: a low-dimensional state of `shape` (no trunk: the pool and ReLU routes are not compared).  hyper: an O.Hyper the
+    device agent and the oracle are both built with (None: the reference's defaults)."""
     import ctypes
     from cartpoleplusplus_amd import _lib
+    if hyper is not None:
+        pair_kw.update(hyper_options(hyper))
     agent, _ref, (aspec, cspec) = make_pair(shape, B, pixel, seed=seed, replay_size=replay_size or rows + 50,
                                            replay_store=replay_store, **pair_kw)
     report = {}
@@ -332,6 +347,7 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
         actions, dq_da, q, td = agent.trainer.last_values(B)
         g_a, g_c = agent.actor.get_grads(), agent.critic.get_grads()
         stats = agent.trainer.last_stats()
+        report["norms"] = (float(stats[1]), float(stats[2]))  # (pre-clip, actor's and critic's lists: which side of a clip they fall on)
         Pn = [n.get_params() for n in nets]
         if pixel:
             codes_a, codes_c = device_pool_codes(agent.actor, B), device_pool_codes(agent.critic, B)
@@ -346,7 +362,7 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
         assert np.array_equal(m[:, 0], rm.terminal_mask[idxs, 0]) and np.array_equal(r[:, 0], rm.reward[idxs, 0])
     finally:
         agent.close()
-    ref = O.DDPG(aspec, cspec, P[0], P[1], np.float64)
+    ref = O.DDPG(aspec, cspec, P[0], P[1], np.float64, **({} if hyper is None else {"hyper": hyper}))
     ref.set_targets(P[2], P[3])
     if aspec.dropout:
         ref.actor.drop_masks = dropout_masks("actor", aspec.hidden, B, steps)
@@ -380,7 +396,7 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
     if f32_twin:
         # the same evaluation in float32 numpy (the rounding an f32 implementation such as the reference's TF CPU kernels is
         # entitled to): how far IT sits from the float64 values on these inputs
-        ref32 = O.DDPG(aspec, cspec, P[0], P[1], np.float32)
+        ref32 = O.DDPG(aspec, cspec, P[0], P[1], np.float32, **({} if hyper is None else {"hyper": hyper}))
         ref32.set_targets(P[2], P[3])
         if aspec.dropout:
             ref32.actor.drop_masks, ref32.target_actor.drop_masks = ref.actor.drop_masks, ref.target_actor.drop_masks
@@ -429,7 +445,7 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
     nc_ref = nc_dev if report.get("critic_grads_checked_at_device_td") else nc
     assert abs(stats[1] - na) < 1e-4 * max(1.0, na) and abs(stats[2] - nc_ref) < 1e-4 * max(1.0, nc_ref), (stats, na, nc, nc_ref)
     # clip + SGD (util.py:47-50, ddpg_cartpole.py:118-119,218) and the target updates (:336-337) on top of them
-    hp = O.DEFAULT_HYPER
+    hp = O.DEFAULT_HYPER if hyper is None else hyper
     ca, _ = O.clip_by_global_norm(ag["grads"], hp.gradient_clip, np.float64)
     cc, _ = O.clip_by_global_norm(cg["grads"], hp.gradient_clip, np.float64)
     want_a, want_c = P[0] - hp.actor_lr * ca, P[1] - hp.critic_lr * cc
@@ -447,6 +463,15 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
         rel_d = max(5e-5, F32_GRAD_FACTOR * report["f32_rel_%s_grads" % name]) if f32_twin else 5e-5
         bound = 2.0 ** -23 * np.linalg.norm(old) + rel_d * np.linalg.norm(d_want)
         assert np.linalg.norm(d_got - d_want) < bound, (name, report, bound)
+    # ... and the soft update's own delta, -tau * (target - new source): the rel=1e-6 asserts above are relative to the target,
+    # 1 / tau times larger than what the update adds to it.  Same form: f32 storage rounding of the target plus the relative bar
+    for name, new, old, src in (("target_actor", Pn[2], P[2], want_a), ("target_critic", Pn[3], P[3], want_c)):
+        d_got = new.astype(np.float64) - old
+        d_want = O.soft_update(old, src, hp.target_update_rate, np.float64) - old
+        err, size = float(np.linalg.norm(d_got - d_want)), float(np.linalg.norm(d_want))
+        report["rel_delta_" + name] = err / size if size > 0 else err
+        bound = 2.0 ** -23 * np.linalg.norm(old) + 5e-5 * size
+        assert err < bound, (name, report, bound)
     return report
 
 
@@ -472,3 +497,167 @@ def synthetic_state_codes(slot, elems, seed):
     by = np.stack([(w[e >> 2] >> np.uint64(8 * (e & 3))) & np.uint64(0xFF) for e in range(16)], axis=1).astype(np.uint8).ravel()
     off = first - int(blocks[0]) * 16
     return by[off:off + elems]
+
+
+# ---- several minibatches at chosen hyperparameters: inputs made on the host, so that the oracle-only sensitivity test and the GPU
+# ---- test compute from the same numbers (tests/test_hyper_sensitivity.py, tests/test_gpu_hyperparameters.py)
+DEFAULT_ACTOR_HIDDEN = (100, 100, 50)          # --actor-hidden-layers' default (the pixel critic's stack is fixed: NetSpec._fc_layers)
+
+
+def delta_bound(theta, d_want, r, nb=1):
+    """how far a float32 update may sit from the float64 one: every one of `nb` stores of theta rounds at 2^-24 |theta| per element
+    (2^-23 covers the fused multiply-add in front of it), and the update itself is held to `r` of its own size"""
+    return 2.0 ** -23 * nb * float(np.linalg.norm(np.asarray(theta, np.float64))) + r * float(np.linalg.norm(d_want))
+
+
+def host_case(shape, B, nb, seed, rows=24, action_dim=2):
+    """specs, starting parameters of the four DDPG networks (xavier + make_pair's perturbations), `rows` transitions as episodes
+    (pixel: codes k / 255 in f16, what the replay store holds exactly) and nb * B row numbers with the minibatches they select."""
+    from oracle.replay_np import OracleReplayMemory
+    pixel = len(shape) == 5
+    kw = dict(pixel=True, H=shape[0], W=shape[1], C=int(np.prod(shape[2:]))) if pixel else dict(pixel=False, state_elems=int(np.prod(shape)))
+    aspec, cspec = O.NetSpec("actor", action_dim, DEFAULT_ACTOR_HIDDEN, **kw), O.NetSpec("critic", action_dim, DEFAULT_ACTOR_HIDDEN, **kw)
+    rng = np.random.default_rng(1000 + seed)
+    P = []
+    for spec in (aspec, cspec):
+        p = O.init_params(spec, rng)
+        P.append(p + rng.normal(0, 0.05, p.shape).astype(np.float32))
+    for p in list(P):
+        P.append(p + rng.normal(0, 0.01, p.shape).astype(np.float32))
+    orm = OracleReplayMemory(rows, shape, action_dim)
+    mk = (lambda: rng.integers(0, 256, shape).astype(np.float16) / np.float16(255)) if pixel else \
+         (lambda: rng.standard_normal(shape).astype(np.float32))
+    episodes, left = [], rows
+    while left > 0:
+        n = min(left, int(rng.integers(2, 7)))
+        episodes.append((mk(), [(rng.uniform(-1, 1, (1, action_dim)).astype(np.float32), float(rng.integers(0, 3)), mk()) for _ in range(n)]))
+        orm.add_episode(*episodes[-1])
+        left -= n
+    idxs = rng.integers(0, rows, nb * B).astype(np.int32)
+    batches = []
+    for i in range(nb):
+        ob = orm.batch(idxs=idxs[i * B:(i + 1) * B])
+        batches.append((ob.state_1, ob.action, ob.reward, ob.terminal_mask, ob.state_2))
+    return (aspec, cspec), P, episodes, idxs, batches
+
+
+def oracle_of(specs, P, dt, hyper):
+    ref = O.DDPG(specs[0], specs[1], P[0], P[1], dt, hyper=hyper)
+    ref.set_targets(P[2], P[3])
+    return ref
+
+
+def four_vectors(ref):
+    return [np.asarray(n.flat(), np.float64) for n in (ref.actor, ref.critic, ref.target_actor, ref.target_critic)]
+
+
+def oracle_minibatch(ref, batch):
+    """DDPG.train_minibatch, returning what the tests look at besides: both pre-clip norms and the trunk's routes -- per conv layer
+    the 2x2 windows' arg-max where the window carries gradient (255 elsewhere), which is also the ReLU's decision"""
+    dt, hp = ref.dt, ref.hp
+    ag, cg = ref.actor_gradients(batch[0]), ref.critic_gradients(batch)
+    routes = []
+    for cache in (ag["cache_actor"], cg["cache_critic"]):
+        for name, _k, _co in O.CONV_DEFS if ref.actor.spec.pixel else ():
+            routes.append(np.where(cache[name][1] > 0, cache[name + ":amax_own"], 255).astype(np.uint8))
+    a_clip, a_norm = O.clip_by_global_norm(ag["grads"], hp.gradient_clip, dt)
+    c_clip, c_norm = O.clip_by_global_norm(cg["grads"], hp.gradient_clip, dt)
+    ref.actor = O.Net(ref.actor.spec, (ref.actor.flat() - dt(hp.actor_lr) * a_clip).astype(dt), dt)
+    ref.critic = O.Net(ref.critic.spec, (ref.critic.flat() - dt(hp.critic_lr) * c_clip).astype(dt), dt)
+    return {"actor_norm": float(a_norm), "critic_norm": float(c_norm), "routes": routes, "td": cg["td"], "loss": float(cg["loss"])}
+
+
+def oracle_train_step(ref, batches):
+    outs = [oracle_minibatch(ref, b) for b in batches]
+    ref.update_targets()
+    return outs
+
+
+def f32_twin_case(specs, P, batches, hyper):
+    """the float64 oracle and its float32 numpy twin over the same minibatches + target update.  Returns (final f64 vectors, per vector
+    r = max(5e-5, F32_GRAD_FACTOR x the twin's relative delta error), the f64 per-minibatch outputs, whether both took the same pool
+    and ReLU routes in every minibatch)."""
+    ref, ref32 = oracle_of(specs, P, np.float64, hyper), oracle_of(specs, P, np.float32, hyper)
+    o64, o32 = oracle_train_step(ref, batches), oracle_train_step(ref32, batches)
+    same = all(np.array_equal(x, y) for a, b in zip(o64, o32) for x, y in zip(a["routes"], b["routes"]))
+    want, twin = four_vectors(ref), four_vectors(ref32)
+    rs = []
+    for w, t, p in zip(want, twin, P):
+        d = np.linalg.norm(w - p)
+        rs.append(max(5e-5, F32_GRAD_FACTOR * float(np.linalg.norm(t - w) / d) if d > 0 else 5e-5))
+    return want, rs, o64, same
+
+
+# the hyperparameter sets of tests/test_gpu_hyperparameters.py (each one's power is checked in tests/test_hyper_sensitivity.py)
+LOUD = O.Hyper(1e-2, 5e-2, 0.9, 0.5, 0.25)                 # clip engaged on both lists
+HYPER_SETS = {"LOUD": LOUD,
+              "UNCLIPPED_NONE": LOUD._replace(gradient_clip=None),          # the kernel's clip <= 0
+              "UNCLIPPED_1E4": LOUD._replace(gradient_clip=1e4),            # clip > 0 with a scale of exactly 1
+              "SPLIT": LOUD._replace(gradient_clip=15.0)}                   # between the two lists' norms: one clipped, one not
+ACTOR_LOUD = LOUD._replace(actor_lr=0.1)                   # an actor update as large as the critic's: a stale ACTOR image shows in the actor
+RIDER_CASES = {"LOUD": ((64, 64, 3, 2, 3), 8, 1, LOUD), "ACTOR_LOUD": ((64, 64, 3, 2, 3), 8, 2, ACTOR_LOUD)}      # shape, B, host_case seed, set
+SENS_SHAPE, SENS_B, SENS_SEED = (16, 16, 3, 1, 2), 16, 3
+STALE_TARGET_CASE = ((64, 64, 3, 2, 3), 8, 2)              # shape, B, host_case seed
+NAF_HYPER = dict(discount=0.9, target_update_rate=0.25, clip=0.5)
+NAF_OPTIMISERS = {"momentum-0.5": ("Momentum", {"learning_rate": 0.01, "momentum": 0.5}, 1),       # name, args, warm-up steps
+                  "momentum-0.0": ("Momentum", {"learning_rate": 0.01, "momentum": 0.0}, 1),
+                  "adam-third-step": ("Adam", {"learning_rate": 0.01, "beta1": 0.8, "beta2": 0.9, "epsilon": 1e-3}, 2)}
+NAF_RIDER_CASE = ((64, 64, 3, 2, 3), 8, 3, 30, 5)         # shape, B, minibatches, rows, seed: the shared trunk, conv1 on the operand image
+
+
+def naf_host_case(shape, B, nb, rows, seed, hidden=(100, 50), action_dim=2):
+    """host_case for the shared-trunk NAF agent: (value, mu, l) specs, the three parameter vectors + the target value network's,
+    episodes, rows and the minibatches they select"""
+    from oracle import naf_np as N
+    from oracle.replay_np import OracleReplayMemory
+    kw = dict(pixel=True, H=shape[0], W=shape[1], C=int(np.prod(shape[2:])))
+    specs = (N.HeadSpec(1, "linear", list(hidden), **kw),
+             N.HeadSpec(action_dim, "tanh", [], False, state_elems=hidden[-1], head_only=True),
+             N.HeadSpec(N.num_l_values(action_dim), "linear", [], False, state_elems=hidden[-1], head_only=True))
+    rng = np.random.default_rng(2000 + seed)
+    flats = []
+    for sp in specs:
+        p = N.init_head_params(sp, rng)
+        flats.append(p + rng.normal(0, 0.05, p.shape).astype(np.float32))
+    flats.append(flats[0] + rng.normal(0, 0.01, flats[0].shape).astype(np.float32))
+    orm = OracleReplayMemory(rows, shape, action_dim)
+    mk = lambda: rng.integers(0, 256, shape).astype(np.float16) / np.float16(255)
+    episodes, left = [], rows
+    while left > 0:
+        n = min(left, int(rng.integers(2, 6)))
+        episodes.append((mk(), [(rng.uniform(-1, 1, (1, action_dim)).astype(np.float32), float(rng.integers(0, 3)), mk()) for _ in range(n)]))
+        orm.add_episode(*episodes[-1])
+        left -= n
+    idxs = rng.integers(0, rows, nb * B).astype(np.int32)
+    batches = []
+    for i in range(nb):
+        ob = orm.batch(idxs=idxs[i * B:(i + 1) * B])
+        batches.append((ob.state_1, ob.action, ob.reward, ob.terminal_mask, ob.state_2))
+    return specs, flats, episodes, idxs, batches
+
+
+def naf_twin_case(specs, flats, batches, optimiser, optimiser_args, action_dim=2):
+    """oracle.NAF.train_step (shared trunk, NAF_HYPER) in float64 and in float32 numpy.  Returns ((params, target) of the float64
+    run, their r = max(5e-5, F32_GRAD_FACTOR x the twin's relative delta error), the float64 norms per minibatch, whether both took
+    the same pool / ReLU routes in the value trunk in every minibatch)."""
+    from oracle import naf_np as N
+    refs, routes = {}, {}
+    for dt in (np.float32, np.float64):
+        r = N.NAF(specs[0], specs[1], specs[2], flats[0], flats[1], flats[2], True, action_dim, dt, discount=NAF_HYPER["discount"],
+                  gradient_clip=NAF_HYPER["clip"], target_update_rate=NAF_HYPER["target_update_rate"],
+                  optimiser=N.make_optimiser(optimiser, optimiser_args))
+        r.target_value = O.Net(specs[0], flats[3], dt)
+        routes[dt], norms = [], []
+        for b in batches:
+            cv = r._forward(b[0])[0]
+            routes[dt] += [np.where(cv[c][1] > 0, cv[c + ":amax_own"], 255) for c, _k, _co in O.CONV_DEFS]
+            norms.append(float(r.train(b)["norm"]))
+        r.update_targets()
+        refs[dt] = r
+    same = all(np.array_equal(x, y) for x, y in zip(routes[np.float32], routes[np.float64]))
+    want, rs = [], []
+    for get, start in ((lambda r: r.flat(), np.concatenate(flats[:3])), (lambda r: r.target_value.flat(), flats[3])):
+        w, t = np.asarray(get(refs[np.float64]), np.float64), np.asarray(get(refs[np.float32]), np.float64)
+        want.append(w)
+        rs.append(max(5e-5, F32_GRAD_FACTOR * float(np.linalg.norm(t - w) / np.linalg.norm(w - start))))
+    return want, rs, norms, same

@@ -20,8 +20,9 @@ class HB(object):
 
 
 def make_naf(shape, B, share, optimiser="GradientDescent", optimiser_args=None, seed=0, replay_size=64, clip=5.0,
-             use_batch_norm=False, use_dropout=False, hidden=None, action_dim=2):
-    """hidden: list of widths (--hidden-layers; None: the default 100,50), action_dim: the env's action size"""
+             use_batch_norm=False, use_dropout=False, hidden=None, action_dim=2, discount=0.99, target_update_rate=1e-4):
+    """hidden: list of widths (--hidden-layers; None: the default 100,50), action_dim: the env's action size; clip (None: no clipping),
+    discount, target_update_rate: --gradient-clip, --discount, --target-update-rate for the agent and the oracle alike"""
     from cartpoleplusplus_amd import naf_cartpole as F
     pixel = len(shape) == 5
     hidden = [100, 50] if hidden is None else [int(h) for h in hidden]
@@ -29,7 +30,7 @@ def make_naf(shape, B, share, optimiser="GradientDescent", optimiser_args=None, 
     kw = dict(batch_size=B, replay_memory_size=replay_size, share_input_state_representation=share,
               optimiser=optimiser, optimiser_args=json.dumps(optimiser_args or {"learning_rate": 0.01}),
               gradient_clip=clip, use_batch_norm=use_batch_norm, use_dropout=use_dropout,
-              hidden_layers=",".join(str(h) for h in hidden))
+              hidden_layers=",".join(str(h) for h in hidden), discount=discount, target_update_rate=target_update_rate)
     if pixel:
         kw.update(use_raw_pixels=True, render_height=shape[0], render_width=shape[1], num_cameras=shape[3],
                   action_repeats=shape[4])
@@ -55,8 +56,8 @@ def make_naf(shape, B, share, optimiser="GradientDescent", optimiser_args=None, 
     else:
         mspec, lspec = N.HeadSpec(A, "tanh", hidden, **skw), N.HeadSpec(N.num_l_values(A), "linear", hidden, **skw)
     ref = N.NAF(vspec, mspec, lspec, agent.value_net.get_params(), agent.naf.mu_net.get_params(),
-                agent.naf.l_net.get_params(), share, A, np.float64, gradient_clip=clip,
-                optimiser=N.make_optimiser(optimiser, optimiser_args or {"learning_rate": 0.01}))
+                agent.naf.l_net.get_params(), share, A, np.float64, gradient_clip=clip, discount=discount,
+                target_update_rate=target_update_rate, optimiser=N.make_optimiser(optimiser, optimiser_args or {"learning_rate": 0.01}))
     ref.target_value = O.Net(vspec, agent.target_value_net.get_params(), np.float64)
     return agent, ref, (vspec, mspec, lspec)
 
@@ -273,7 +274,8 @@ def test_cfg4_B256_graph_replayed_naf_step_against_f64_oracle(shape, B, share):
     naf_fused_step_against_f64_oracle(shape, B, share)
 
 
-def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, probe=False, **naf_kw):
+def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, probe=False, optimiser="Momentum", optimiser_args=None,
+                                      warm_steps=1, clip=5.0, discount=0.99, target_update_rate=1e-4, report=None, **naf_kw):
     """cfg4 at the size the metric is quoted on (64x64x18, B = 256, shared trunk, Momentum as in exps/run_93.sh): the hipGraph REPLAY
     of the fused NAF step (naf_cartpole.py:365-373) on rows drawn by the device's sampler against oracle.NAF(float64) started from the
     same parameters and Momentum slots: loss at 1e-5, the pre-clip gradient list per variable at 2e-5 (the trunk's two
@@ -284,8 +286,9 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, p
     import ctypes
     from cartpoleplusplus_amd import _lib
     from tests.helpers import (device_pool_codes, device_relu_active, naf_path, pool_flips_are_near_ties, relu_flips_are_at_the_boundary)
-    oargs = {"learning_rate": 0.01, "momentum": 0.9}
-    agent, _ref, specs = make_naf(shape, B, share, "Momentum", oargs, seed=4, replay_size=rows + 50, **naf_kw)
+    oargs = {"learning_rate": 0.01, "momentum": 0.9} if optimiser_args is None else optimiser_args
+    agent, _ref, specs = make_naf(shape, B, share, optimiser, oargs, seed=4, replay_size=rows + 50, clip=clip, discount=discount,
+                                  target_update_rate=target_update_rate, **naf_kw)
     path = None
     try:
         rm = agent.replay_memory
@@ -297,7 +300,8 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, p
             fill_with_rendered_episodes(agent, shape, rows, seed=33, blind_camera=(fill == "render-blind"), opts=F.opts)
         if probe:
             path = naf_path(agent, B, specs[0].hidden, share)
-        agent.train_step(B, 1)                                    # eager pass + capture (also fills the Momentum slots)
+        for _ in range(warm_steps):
+            agent.train_step(B, 1)                                # eager pass + capture (also fills the Momentum slots)
         nets = (agent.value_net, agent.naf.mu_net, agent.naf.l_net, agent.target_value_net)
         P = [n.get_params() for n in nets]
         opt = agent.naf.get_optimiser_state()
@@ -315,10 +319,13 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, p
     finally:
         agent.close()
     vspec, mspec, lspec = specs
-    ref = N.NAF(vspec, mspec, lspec, P[0], P[1], P[2], share, mspec.head_out, np.float64, gradient_clip=5.0,
-                optimiser=N.make_optimiser("Momentum", oargs))
+    ref = N.NAF(vspec, mspec, lspec, P[0], P[1], P[2], share, mspec.head_out, np.float64, gradient_clip=clip, discount=discount,
+                target_update_rate=target_update_rate, optimiser=N.make_optimiser(optimiser, oargs))
     ref.target_value = O.Net(vspec, P[3], np.float64)
     ref.m = opt["m"].astype(np.float64)
+    if optimiser == "Adam":
+        ref.v, ref.t = opt["v"].astype(np.float64), int(opt["step"])
+        assert ref.t == warm_steps + (1 if probe else 0), (ref.t, warm_steps)
     rnets = [ref.value] if share else [ref.value, ref.mu, ref.l]
     for net, cd, rl in zip(rnets, codes, relu):
         net.amax_override, net.relu_override = cd, rl
@@ -332,13 +339,23 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, p
     cat = CatSpec(specs)
     assert_flat_close(cat, grads, out["grads"], rel=2e-5, what="NAF pre-clip grads vs f64 oracle (flips %d / %d)" % (flips, rflips))
     before = ref.flat()
-    ref.apply(out["grads"])
+    target_before = ref.target_value.flat()
+    norm = ref.apply(out["grads"])
     ref.update_targets()
     got = np.concatenate(Pn[:3])
+    assert abs(stats[1] - norm) < 1e-4 * max(1.0, norm), (stats, norm)
     assert_flat_close(cat, got, ref.flat(), rel=2e-6, what="NAF params after the step")
     assert_flat_close(vspec, Pn[3], ref.target_value.flat(), rel=1e-6, what="target value net")
     d_got, d_want = got.astype(np.float64) - before, ref.flat() - before
+    if report is not None:
+        report.update(params=got, target=Pn[3], norm=float(norm), device_norm=float(stats[1]),
+                      rel_delta_params=float(np.linalg.norm(d_got - d_want) / np.linalg.norm(d_want)))
     assert np.linalg.norm(d_got - d_want) < 2.0 ** -23 * np.linalg.norm(before) + 5e-5 * np.linalg.norm(d_want)
+    # the target's own delta, -tau * (target - new value network): same form (the rel=1e-6 above is relative to the target itself)
+    t_got, t_want = Pn[3].astype(np.float64) - target_before, ref.target_value.flat() - target_before
+    if report is not None:
+        report["rel_delta_target"] = float(np.linalg.norm(t_got - t_want) / np.linalg.norm(t_want))
+    assert np.linalg.norm(t_got - t_want) < 2.0 ** -23 * np.linalg.norm(target_before) + 5e-5 * np.linalg.norm(t_want)
     return path
 
 

@@ -122,12 +122,15 @@ def test_explicit_n1_is_the_one_step_memory():
         b.close()
 
 
-def _ddpg_nstep_against_f64_oracle(shape, B, rows, pixel=True, seed=0, per=False, atol=1e-5, grad_rel=2e-5, flip_tol=1e-5):
+def _ddpg_nstep_against_f64_oracle(shape, B, rows, pixel=True, seed=0, per=False, atol=1e-5, grad_rel=2e-5, flip_tol=1e-5, hyper=None):
     """ONE graph-replayed minibatch of the fused DDPG step on an n = 3 memory against oracle.DDPG(float64), unmodified, on the n-step
     columns (reward, terminal_mask, state_2 of the last row walked): actions / Q / TD at `atol`, the pre-clip gradients at `grad_rel`.
     per: a prioritized memory as well -- the critic's gradient against the oracle's backward pass of w * td_dev, and the priorities
-    written from the n-step TD."""
+    written from the n-step TD.  hyper: an O.Hyper for the agent and the oracle (None: the defaults)."""
     kw = dict(prioritized_replay=True, priority_alpha=0.6, priority_beta=0.4, priority_eps=1e-6) if per else {}
+    if hyper is not None:
+        from tests.helpers import hyper_options
+        kw.update(hyper_options(hyper))
     agent, _ref, (aspec, cspec) = make_pair(shape, B, pixel, seed=seed, replay_size=rows + 50, **kw)
     from cartpoleplusplus_amd import ddpg_cartpole as D
     try:
@@ -159,7 +162,7 @@ def _ddpg_nstep_against_f64_oracle(shape, B, rows, pixel=True, seed=0, per=False
         assert (hb.state_2_idx != rm.state_2_idx[idxs]).any() and (m != rm.terminal_mask[idxs]).any()
     finally:
         agent.close()
-    ref = O.DDPG(aspec, cspec, Pm[0], Pm[1], np.float64)
+    ref = O.DDPG(aspec, cspec, Pm[0], Pm[1], np.float64, **({} if hyper is None else {"hyper": hyper}))
     ref.set_targets(Pm[2], Pm[3])
     if pixel:
         ref.actor.amax_override, ref.critic.amax_override = codes_a, codes_c
