@@ -113,6 +113,10 @@ SIGNATURES = {
     "cpp_replay_draw_prioritized": (_I, [_P, _I, _U64, _P, _P]),
     "cpp_replay_set_n_step": (_I, [_P, _I, _F]),
     "cpp_replay_get_n_step": (_I, [_P, C.POINTER(_I), C.POINTER(_F)]),
+    "cpp_replay_set_random_shift": (_I, [_P, _I, _I, _I, _U64]),
+    "cpp_replay_get_random_shift": (_I, [_P, C.POINTER(_I), C.POINTER(_U64), C.POINTER(_U64)]),
+    "cpp_replay_last_shifts": (_I, [_P, _I, _P]),
+    "cpp_replay_gather_shifted": (_I, [_P, _I, _P, _I, _P]),
     "cpp_ddpg_create": (_I, [_P, _P, _P, _P, _P, C.POINTER(DdpgHyper), _PP]),
     "cpp_ddpg_destroy": (_I, [_P]),
     "cpp_ddpg_train_actor": (_I, [_P, _P]),

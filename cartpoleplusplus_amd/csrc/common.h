@@ -304,8 +304,20 @@ struct GatherArgs {
   // (gather_body.h: nstep_walk).  The words are written by value in stream order: captured launches read the current n and discount.
   const struct NStepWords* nstep;
   int rows_cap;                 // buffer_size R of the memory (the walk wraps modulo R once the memory is full)
+  // random shift (cpp_replay_set_random_shift; appended likewise): non-null selects the launchers' shifting instances, which write
+  // every gathered image shifted by its own (dy, dx) (gather_body.h: gather_shifted_rows).  The draw is keyed by the memory's
+  // augmentation counter, a device word the gather itself advances (ShiftWords); pad, seed and the image geometry travel by value --
+  // a change of any of them re-issues the memory's uid, so no captured launch keeps an old one.
+  struct ShiftWords* shift;
+  int32_t* shifts_out;          // [2][B][2]: (dy, dx) of every gathered state, next to rows_out
+  uint64_t shift_seed;
+  int shift_pad, shift_H, shift_W, shift_C;      // H x W pixels of shift_C interleaved channels: H * W * shift_C == elems
 };
 struct NStepWords { int32_t n; float discount; };
+// counter: minibatches gathered with augmentation so far.  ticket: workgroups of the running gather that have read the counter; the one
+// that takes the last ticket advances the counter and clears the tickets (gather_body.h)
+struct ShiftWords { uint64_t counter; uint32_t ticket; uint32_t reserved; };
+constexpr int SHIFT_MAX_PAD = 16;
 constexpr int NSTEP_MAX = 64;   // one wavefront: lane k holds row (i + k) mod R
 int launch_gather_stats(cpp_ctx* ctx, const GatherArgs& a, int dtype);
 // per-state sufficient statistics of store rows [first, first + n) (slots == nullptr) or of the n rows listed in `slots` (device): the very

@@ -109,9 +109,115 @@ __device__ __forceinline__ void nstep_walk(const GatherArgs& a, const int row, c
   *mask = nstep_mul(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(m), last)), g);
 }
 
+// ---- random shift (include/cartpolepp_abi.h, "Random shift"): out[y, x, c] = in[clamp(y + dy), clamp(x + dx), c] ------------------
+// An output vector (8 elements, 16-byte aligned in the gathered copy) that lies inside one image row and whose 8 source elements are
+// all inside the source row is 8 CONTIGUOUS source elements at element offset clamp(y + dy) * L + x0 + dx * C (L = W * C elements per
+// row) -- 2-byte aligned in general, not 16.  It is read as the two ALIGNED vectors that cover it and realigned in registers: a mux by
+// the dword part of the offset, then one v_alignbit per output dword for the sub-dword part.  The other vectors -- the |dx| pixels at
+// one end of a row that repeat the edge pixel, and vectors that straddle two rows when L % 8 != 0 -- take their 8 elements one by one
+// (`slow`); their loads are issued with the batch's, not behind it.  The lane -> channel-class structure is the output's, i.e. the
+// unshifted gather's: a lane's vectors still hold the same 8 channels, so the statistics below are untouched.
+template <typename T> struct ShiftElem { typedef uint16_t E; };
+template <> struct ShiftElem<uint8_t> { typedef uint8_t E; };
+struct ShiftGeom { int L, H, C, dy, dxC, ch[8]; long nvec; };      // ch[e]: channel of a lane's element e (the same for all its vectors)
+
+template <typename T> struct ShiftVec {
+  static constexpr int NW = (int)sizeof(T) * 2;      // dwords per vector of 8 elements
+  uint32_t w[2 * NW];                                // the two aligned vectors that cover the source elements
+  uint32_t el[8];                                    // slow: the 8 source elements
+  int t; bool slow;
+
+  __device__ __forceinline__ void issue(const T* src, const ShiftGeom& g, const long v) {
+    const unsigned e0 = (unsigned)v * 8u;
+    const int y = (int)(e0 / (unsigned)g.L), xe0 = (int)e0 - y * g.L;
+    const int s0 = xe0 + g.dxC;
+    slow = (xe0 + 8 > g.L) | (s0 < 0) | (s0 + 8 > g.L);
+    const int sy = min(max(y + g.dy, 0), g.H - 1);
+    const int base = slow ? 0 : sy * g.L + s0;
+    t = base & 7;
+    const long v0 = base >> 3, v1 = v0 + 1 < g.nvec ? v0 + 1 : v0;      // (v1 is read only when t != 0: then it is inside the state)
+    if constexpr (NW == 4) {
+      const uint4 lo = *reinterpret_cast<const uint4*>(src + v0 * 8), hi = *reinterpret_cast<const uint4*>(src + v1 * 8);
+      w[0] = lo.x; w[1] = lo.y; w[2] = lo.z; w[3] = lo.w; w[NW] = hi.x; w[NW + 1] = hi.y; w[2 * NW - 2] = hi.z; w[2 * NW - 1] = hi.w;
+    } else {
+      const uint2 lo = *reinterpret_cast<const uint2*>(src + v0 * 8), hi = *reinterpret_cast<const uint2*>(src + v1 * 8);
+      w[0] = lo.x; w[1] = lo.y; w[NW] = hi.x; w[NW + 1] = hi.y;
+    }
+    if (slow) {
+      const typename ShiftElem<T>::E* s = reinterpret_cast<const typename ShiftElem<T>::E*>(src);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        int xe = xe0 + e, yy = y;
+        if (xe >= g.L) { xe -= g.L; ++yy; }                     // (L >= 8: at most one row further; 8 v + e < elems: yy < H)
+        const int c = g.ch[e];                                  // the element's channel (L % C == 0)
+        const int xs = xe + g.dxC;
+        const int col = xs < 0 ? c : (xs >= g.L ? g.L - g.C + c : xs);
+        el[e] = (uint32_t)s[(long)min(max(yy + g.dy, 0), g.H - 1) * g.L + col];
+      }
+    }
+  }
+
+  __device__ __forceinline__ void finish(Vec8<T>& x) const {
+    uint32_t o[NW];
+    if (slow) {
+#pragma unroll
+      for (int j = 0; j < NW; ++j)
+        o[j] = NW == 4 ? (el[2 * j] | (el[2 * j + 1] << 16))
+                       : (el[(4 * j) & 7] | (el[(4 * j + 1) & 7] << 8) | (el[(4 * j + 2) & 7] << 16) | (el[(4 * j + 3) & 7] << 24));
+    } else {
+      const int tb = t * (int)sizeof(T), k = tb >> 2;          // byte offset inside the first vector: dword part, sub-dword part
+      const uint32_t bits = (uint32_t)(tb & 3) * 8u;
+      // (the mux as bit selects, v_bfi_b32: written as a choice between two array elements the compiler turns it into ONE load at a
+      // run-time index, which puts the whole window into scratch memory)
+      const uint32_t k1 = 0u - (uint32_t)(k & 1), k2 = 0u - (uint32_t)((k >> 1) & 1);
+      uint32_t m[NW + 1];
+      if constexpr (NW == 4) {
+        uint32_t u[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) u[i] = (w[i + 2] & k2) | (w[i] & ~k2);
+#pragma unroll
+        for (int i = 0; i < 5; ++i) m[i] = (u[i + 1] & k1) | (u[i] & ~k1);
+      } else {
+#pragma unroll
+        for (int i = 0; i < NW + 1; ++i) m[i] = (w[i + 1] & k1) | (w[i] & ~k1);
+      }
+#pragma unroll
+      for (int j = 0; j < NW; ++j) o[j] = __builtin_amdgcn_alignbit(m[j + 1], m[j], bits);
+    }
+    set_raw(x, o);
+  }
+  static __device__ __forceinline__ void set_raw(Vec8<__half>& x, const uint32_t* o) { x.raw = make_uint4(o[0], o[1], o[2], o[3]); }
+  static __device__ __forceinline__ void set_raw(Vec8<uint8_t>& x, const uint32_t* o) { x.raw = make_uint2(o[0], o[1]); }
+};
+
+// The (dy, dx) of gathered state (b, which) and the augmentation counter's advance.  Thread 0 of the workgroup reads the counter n,
+// draws r = philox4x32_10({b, 2 + which, n_lo, n_hi}, seed) and takes a ticket (release: the read is complete before the ticket
+// counts); the workgroup that takes the last of the launch's 2 B tickets writes n + 1 and clears the tickets.  Nobody reads the counter
+// after its own ticket, so every workgroup of the launch has read n before n + 1 is written; the next gather is a later launch on the
+// stream.  `shw`: two ints of LDS nothing else touches before the barrier below.
+__device__ __forceinline__ void shift_draw(const GatherArgs& a, const int b, const int which, int* shw, int* dy, int* dx) {
+  if (threadIdx.x == 0) {
+    const uint64_t n = __hip_atomic_load(&a.shift->counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    u32x4 c = {(uint32_t)b, 2u + (uint32_t)which, (uint32_t)n, (uint32_t)(n >> 32)};
+    const u32x4 r = philox4x32_10(c, (uint32_t)a.shift_seed, (uint32_t)(a.shift_seed >> 32));
+    const uint64_t span = 2u * (uint32_t)a.shift_pad + 1u;
+    const int y = (int)(((uint64_t)r.x * span) >> 32) - a.shift_pad, x = (int)(((uint64_t)r.y * span) >> 32) - a.shift_pad;
+    shw[0] = y; shw[1] = x;
+    a.shifts_out[((long)which * a.B + b) * 2] = y; a.shifts_out[((long)which * a.B + b) * 2 + 1] = x;
+    const uint32_t ticket = __hip_atomic_fetch_add(&a.shift->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (ticket == 2u * (uint32_t)a.B - 1u) {
+      __hip_atomic_store(&a.shift->counter, n + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&a.shift->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  __syncthreads();
+  *dy = shw[0]; *dx = shw[1];
+}
+
 // (b, which): the workgroup's place in the (B, 2) grid -- blockIdx for a launch of its own.  NSTEP: the memory's n-step instance
-// (GatherArgs::nstep non-null); the uniform instances (false) compile to the instructions they had before the walk existed.
-template <typename T, bool NSTEP = false>
+// (GatherArgs::nstep non-null); the uniform instances (false) compile to the instructions they had before the walk existed.  SHIFT: the
+// random-shift instance (GatherArgs::shift non-null; a materialising pixel gather: out_state set, C > 0), likewise.
+template <typename T, bool NSTEP = false, bool SHIFT = false>
 __device__ __forceinline__ void gather_stats_body(const GatherArgs& a, const int b, const int which, float* sh, double* dsh, float* lut) {
   // (lut: CPP_U8 store, f16(k/255) as float)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -132,6 +238,8 @@ __device__ __forceinline__ void gather_stats_body(const GatherArgs& a, const int
   slot = __shfl(slot, 0);
   float nreward = 0.f, nmask = 0.f;
   if (NSTEP && a.s_idx[0] != nullptr) nstep_walk(a, row, which, lane, &slot, &nreward, &nmask);
+  int shift_dy = 0, shift_dx = 0;
+  if constexpr (SHIFT) shift_draw(a, b, which, reinterpret_cast<int*>(dsh), &shift_dy, &shift_dx);
 
   if (tid == 0 && a.out_slot[which]) a.out_slot[which][b] = slot;
   if (which == 0 && a.s_idx[0] != nullptr) {
@@ -164,7 +272,44 @@ __device__ __forceinline__ void gather_stats_body(const GatherArgs& a, const int
   double s[8], ss[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) { s[e] = 0.0; ss[e] = 0.0; }
-  if (lane < act) {
+  if constexpr (SHIFT) {
+    if (lane < act) {
+      // as the loop below: GU output vectors per thread in flight (two aligned loads each), the same vectors per lane in the same order
+      constexpr int GU = 6;
+      ShiftGeom g;
+      g.L = a.shift_W * a.shift_C; g.H = a.shift_H; g.C = a.shift_C; g.dy = shift_dy; g.dxC = shift_dx * a.shift_C; g.nvec = nvec;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g.ch[e] = (8 * (wave * act + lane) + e) % a.shift_C;
+      long v = wave * act + lane;
+      const long stride = 4 * act;
+      for (; v + (GU - 1) * stride < nvec; v += GU * stride) {
+        ShiftVec<T> s0, s1, s2, s3, s4, s5;       // (named, not an array: each stays in registers)
+        static_assert(GU == 6, "one ShiftVec per vector in flight");
+        s0.issue(src, g, v); s1.issue(src, g, v + stride); s2.issue(src, g, v + 2 * stride);
+        s3.issue(src, g, v + 3 * stride); s4.issue(src, g, v + 4 * stride); s5.issue(src, g, v + 5 * stride);
+        auto finish = [&](const ShiftVec<T>& sv, const long vo) __attribute__((always_inline)) {
+          Vec8<T> x;
+          vec_init(x, lut);
+          sv.finish(x);
+          x.store(dst + vo * 8);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) { const double f = (double)x.get(e); s[e] += f; ss[e] = fma(f, f, ss[e]); }
+        };
+        finish(s0, v); finish(s1, v + stride); finish(s2, v + 2 * stride);
+        finish(s3, v + 3 * stride); finish(s4, v + 4 * stride); finish(s5, v + 5 * stride);
+      }
+      for (; v < nvec; v += stride) {
+        ShiftVec<T> sv;
+        sv.issue(src, g, v);
+        Vec8<T> x;
+        vec_init(x, lut);
+        sv.finish(x);
+        x.store(dst + v * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { const double f = (double)x.get(e); s[e] += f; ss[e] = fma(f, f, ss[e]); }
+      }
+    }
+  } else if (lane < act) {
     // GU row vectors per thread in flight (one 16-byte load each is far too little to cover the HBM latency with two
     // workgroups per CU); the accumulation order per lane is unchanged
     constexpr int GU = 6;

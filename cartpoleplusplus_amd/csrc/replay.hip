@@ -41,10 +41,48 @@ __global__ __launch_bounds__(256) void reduce_gather_kernel(const DwReduceBatch 
   }
 }
 
+// the random-shift instances of the two kernels above (GatherArgs::shift non-null: a memory with cpp_replay_set_random_shift on); kernels
+// of their own, so that the instances above keep their names and their instructions
+template <typename T, bool NSTEP>
+__global__ __launch_bounds__(256) void gather_shift_kernel(const GatherArgs a) {
+  __shared__ float sh[256 * GATHER_SH];
+  __shared__ double dsh[CPP_MAX_CHANNELS * 16];
+  __shared__ float lut[256];
+  gather_stats_body<T, NSTEP, true>(a, (int)blockIdx.x, (int)blockIdx.y, sh, dsh, lut);
+}
+template <typename T, bool NSTEP>
+__global__ __launch_bounds__(256) void reduce_gather_shift_kernel(const DwReduceBatch rb, const GatherArgs a) {
+  const int nred = rb.block_start[rb.n];
+  if ((int)blockIdx.x < nred) {
+    __shared__ float red[4][64];
+    conv_dw_reduce_body<4>(rb, (int)blockIdx.x, red);
+  } else {
+    __shared__ float sh[256 * GATHER_SH];
+    __shared__ double dsh[CPP_MAX_CHANNELS * 16];
+    __shared__ float lut[256];
+    const int i = (int)blockIdx.x - nred;
+    gather_stats_body<T, NSTEP, true>(a, i % a.B, i / a.B, sh, dsh, lut);
+  }
+}
+// a shifting gather materialises a pixel minibatch from an f16 / u8 store (replay_gather_args sets `shift` only then)
+static bool shift_args_ok(const GatherArgs& a, int dtype) {
+  if (a.out_state[0] && a.out_state[1] && a.s_idx[0] && a.C > 0 && a.shifts_out && (dtype == 1 || dtype == 2) &&
+      (long)a.shift_H * a.shift_W * a.shift_C == a.elems && a.elems < (1L << 31)) return true;
+  cpp_set_error("gather: random shift needs a materialising pixel gather (H %d W %d C %d, %ld elements)", a.shift_H, a.shift_W, a.shift_C, a.elems);
+  return false;
+}
+
 int launch_reduce_gather(cpp_ctx* ctx, const DwReduceBatch& rb, const GatherArgs& a, int dtype) {
+  if (a.shift && !shift_args_ok(a, dtype)) return 1;
   prof_begin(ctx);
   const dim3 grid(rb.block_start[rb.n] + 2 * a.B);
-  if (a.nstep) {          // (an n-step memory's walk: its own instances, the uniform ones are left as they were)
+  if (a.shift) {
+    if (a.nstep) {
+      if (dtype == 2) hipLaunchKernelGGL((reduce_gather_shift_kernel<uint8_t, true>), grid, dim3(256), 0, ctx->stream, rb, a);
+      else hipLaunchKernelGGL((reduce_gather_shift_kernel<__half, true>), grid, dim3(256), 0, ctx->stream, rb, a);
+    } else if (dtype == 2) hipLaunchKernelGGL((reduce_gather_shift_kernel<uint8_t, false>), grid, dim3(256), 0, ctx->stream, rb, a);
+    else hipLaunchKernelGGL((reduce_gather_shift_kernel<__half, false>), grid, dim3(256), 0, ctx->stream, rb, a);
+  } else if (a.nstep) {          // (an n-step memory's walk: its own instances, the uniform ones are left as they were)
     if (dtype == 2) hipLaunchKernelGGL((reduce_gather_kernel<uint8_t, true>), grid, dim3(256), 0, ctx->stream, rb, a);
     else hipLaunchKernelGGL((reduce_gather_kernel<__half, true>), grid, dim3(256), 0, ctx->stream, rb, a);
   } else if (dtype == 2) hipLaunchKernelGGL((reduce_gather_kernel<uint8_t, false>), grid, dim3(256), 0, ctx->stream, rb, a);
@@ -85,8 +123,15 @@ int launch_gather_stats(cpp_ctx* ctx, const GatherArgs& a, int dtype) {
                   a.elems, a.C);
     return 1;
   }
+  if (a.shift && !shift_args_ok(a, dtype)) return 1;
   prof_begin(ctx);
-  if (a.nstep) {          // (replay memories hold f16 or 8-bit states)
+  if (a.shift) {
+    if (a.nstep) {
+      if (dtype == 2) hipLaunchKernelGGL((gather_shift_kernel<uint8_t, true>), dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
+      else hipLaunchKernelGGL((gather_shift_kernel<__half, true>), dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
+    } else if (dtype == 2) hipLaunchKernelGGL((gather_shift_kernel<uint8_t, false>), dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((gather_shift_kernel<__half, false>), dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
+  } else if (a.nstep) {          // (replay memories hold f16 or 8-bit states)
     if (dtype == 2) hipLaunchKernelGGL((gather_stats_kernel<uint8_t, true>), dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL((gather_stats_kernel<__half, true>), dim3(a.B, 2), dim3(256), 0, ctx->stream, a);
   } else if (dtype == 2) hipLaunchKernelGGL((gather_stats_kernel<uint8_t, false>), dim3(a.B, 2), dim3(256), 0, ctx->stream, a);

@@ -595,10 +595,11 @@ extern "C" int cpp_ddpg_update_targets(cpp_ddpg* d) {
 
 // The fused step does not need a gathered copy of the minibatch when conv1 runs on the f16-pipe kernels: they take the
 // replay store plus the sampled slots (the gather kernel then only reads -- statistics -- and writes 2 B ints).
-// CPP_DIRECT_REPLAY=0 keeps the copy.
+// CPP_DIRECT_REPLAY=0 keeps the copy.  So does a memory with random shift on (cpp_replay_set_random_shift): the shifted images exist
+// only in the gathered copy.
 bool direct_replay_ok(cpp_net* a, cpp_replay* r, int B) {
   static const bool off = cpp_switch_off("CPP_DIRECT_REPLAY");
-  if (off || !a->spec.pixel || r->store_dtype != CPP_F16) return false;
+  if (off || !a->spec.pixel || r->store_dtype != CPP_F16 || r->shift_pad > 0) return false;
   const int C = a->spec.C;
   int g = 8, c = C; while (c) { int t = g % c; g = c; c = t; }
   if (r->elems % 8 != 0 || C / g > 16 || r->elems % C != 0) return false;       // statistics come from the gather kernel

@@ -141,6 +141,9 @@ struct cpp_replay {
   // n-step returns (cpp_replay_set_n_step; gather_body.h: nstep_walk): nullptr = never set, the uniform gathers.  Host copies of the
   // device words for the trainers' discount check
   NStepWords* nstep_dev; int nstep_n; float nstep_discount;
+  // random shift (cpp_replay_set_random_shift; gather_body.h): pad 0 = off.  shift_dev: the augmentation counter and the gathers'
+  // tickets; shift_out: the (2, B, 2) shifts of the last augmented gather.  Both allocated at the first enable.
+  ShiftWords* shift_dev; int32_t* shift_out; int shift_pad, shift_H, shift_W; uint64_t shift_seed;
   Arena arena;
 };
 static size_t replay_esz(const cpp_replay* r) { return r->store_dtype == CPP_U8 ? 1 : sizeof(__half); }
@@ -234,10 +237,11 @@ int batch_stats(cpp_ctx* ctx, const void* s0, const void* s1, int dtype, long el
 int batch_ensure_stats(cpp_batch* b, int C);
 uint64_t replay_next_uid();      // graph keys: a fresh uid per cpp_replay_create and per change of a sampled memory's statistics setting
 int nstep_refuse(const cpp_replay* r, float discount, const char* who);      // CPP_ERR_ARG: an n-step memory folded with another discount
-GatherArgs replay_gather_args(cpp_replay* r, int B, const int32_t* rows_dev, uint64_t seed, const uint64_t* counter_dev, int channels, cpp_batch* out, bool direct, int* C_out);
+GatherArgs replay_gather_args(cpp_replay* r, int B, const int32_t* rows_dev, uint64_t seed, const uint64_t* counter_dev, int channels, cpp_batch* out, bool direct, int* C_out,
+                              bool augment = true);      // augment: a memory with random shift on gathers shifted (false: cpp_replay_sample, the stored pixels)
 int replay_sample_finish(cpp_replay* r, int B, int C, int channels, cpp_batch* out, uint64_t* bump = nullptr, bool* bumped = nullptr);
 int replay_sample_device(cpp_replay* r, int B, const int32_t* rows_dev, uint64_t seed, const uint64_t* counter_dev, int channels, cpp_batch* out, bool direct = false,
-                         uint64_t* bump = nullptr, bool* bumped = nullptr);
+                         uint64_t* bump = nullptr, bool* bumped = nullptr, bool augment = true);
 int replay_stage_rows(cpp_replay* r, const int32_t* idxs, int n, const char* who);
 PerArgs per_args(const cpp_replay* r);            // the memory's tree, size word, maximum and beta; nothing to write, nothing to draw
 int per_refuse(const cpp_replay* r, const char* who);   // CPP_ERR_ARG (with the message) on a prioritized memory

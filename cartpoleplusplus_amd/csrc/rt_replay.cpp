@@ -112,6 +112,7 @@ static int replay_create(cpp_ctx* ctx, int buffer_size, int state_slots, int64_t
   r->per_tree = nullptr; r->per_L = 0; r->per_alpha = r->per_eps = 0.f; r->per_maxp = r->per_beta = nullptr;
   r->per_rows = nullptr; r->per_w = nullptr; r->per_list = nullptr; r->per_vals = nullptr;
   r->nstep_dev = nullptr; r->nstep_n = 1; r->nstep_discount = 0.f;
+  r->shift_dev = nullptr; r->shift_out = nullptr; r->shift_pad = r->shift_H = r->shift_W = 0; r->shift_seed = 0;
   r->stage = nullptr; r->stage_cap = 0; r->pinned = nullptr; r->pinned_cap = 0; r->pinned_busy = false; r->lut = nullptr; r->bad = nullptr;
   HIP_CHECK(hipEventCreateWithFlags(&r->pinned_free, hipEventDisableTiming));
   int rc = r->arena.alloc(&r->store, (size_t)state_slots * state_elems * replay_esz(r), false);
@@ -377,7 +378,7 @@ int replay_stage_rows(cpp_replay* r, const int32_t* idxs, int n, const char* who
 // device-only part of sampling (graph-capturable when rows_dev == nullptr or already resident)
 // descriptor of the fused sample + gather + statistics pass into `out` (C_out: channels of the vector statistics path, 0: none)
 GatherArgs replay_gather_args(cpp_replay* r, int B, const int32_t* rows_dev, uint64_t seed, const uint64_t* counter_dev,
-                                     int channels, cpp_batch* out, bool direct, int* C_out) {
+                                     int channels, cpp_batch* out, bool direct, int* C_out, bool augment) {
   int C = channels;
   r->sampled = true;
   if (C > 0) {
@@ -397,6 +398,11 @@ GatherArgs replay_gather_args(cpp_replay* r, int B, const int32_t* rows_dev, uin
   a.part = out->part; a.seed = seed; a.counter = counter_dev;
   a.elems = r->elems; a.B = B; a.size = r->size; a.size_ptr = r->size_dev; a.action_dim = r->A; a.C = C;
   a.nstep = r->nstep_dev; a.rows_cap = r->rows;
+  // random shift: the materialising pixel gathers of a memory that has it on (direct_replay_ok refuses such a memory the direct path)
+  if (augment && r->shift_pad > 0 && !direct && C > 0) {
+    a.shift = r->shift_dev; a.shifts_out = r->shift_out; a.shift_seed = r->shift_seed;
+    a.shift_pad = r->shift_pad; a.shift_H = r->shift_H; a.shift_W = r->shift_W; a.shift_C = r->stats_C;
+  }
   *C_out = C;
   return a;
 }
@@ -416,9 +422,9 @@ int replay_sample_finish(cpp_replay* r, int B, int C, int channels, cpp_batch* o
   return CPP_OK;
 }
 int replay_sample_device(cpp_replay* r, int B, const int32_t* rows_dev, uint64_t seed, const uint64_t* counter_dev,
-                                int channels, cpp_batch* out, bool direct, uint64_t* bump, bool* bumped) {
+                                int channels, cpp_batch* out, bool direct, uint64_t* bump, bool* bumped, bool augment) {
   int C = 0;
-  const GatherArgs a = replay_gather_args(r, B, rows_dev, seed, counter_dev, channels, out, direct, &C);
+  const GatherArgs a = replay_gather_args(r, B, rows_dev, seed, counter_dev, channels, out, direct, &C, augment);
   RC(launch_gather_stats(r->ctx, a, r->store_dtype));      // a CPP_U8 store gathers to f16 as well
   return replay_sample_finish(r, B, C, channels, out, bump, bumped);
 }
@@ -448,7 +454,8 @@ extern "C" int cpp_replay_sample(cpp_replay* r, int B, const int32_t* idxs, uint
       rows_dev = r->per_rows;
     }
   }
-  RC(replay_sample_device(r, B, rows_dev, seed, rows_dev ? nullptr : r->counter_adhoc, channels, out));
+  // (the stored pixels, also on a memory with random shift on: the augmentation belongs to the trainers' gathers and cpp_replay_gather_shifted)
+  RC(replay_sample_device(r, B, rows_dev, seed, rows_dev ? nullptr : r->counter_adhoc, channels, out, false, nullptr, nullptr, false));
   if (idxs) HIP_CHECK(hipStreamSynchronize(st));     // the caller's index array may go away after return
   return CPP_OK;
 }
@@ -654,5 +661,74 @@ int nstep_refuse(const cpp_replay* r, float discount, const char* who) {
                   r->nstep_n, (double)r->nstep_discount, (double)discount);
     return CPP_ERR_ARG;
   }
+  return CPP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// random shift (gather_body.h: ShiftVec, shift_draw): extension, no reference counterpart
+// ---------------------------------------------------------------------------------------------
+extern "C" int cpp_replay_set_random_shift(cpp_replay* r, int H, int W, int pad, uint64_t seed) {
+  ARG_CHECK(r, "cpp_replay_set_random_shift: NULL argument");
+  ARG_CHECK(r->stats_C > 0, "cpp_replay_set_random_shift: not a pixel memory (cpp_replay_set_stats_channels has not been called with channels > 0)");
+  ARG_CHECK(H >= 1 && W >= 1 && (double)H * (double)W * (double)r->stats_C == (double)r->elems,
+            "cpp_replay_set_random_shift: H %d x W %d x %d channels is not the state's %ld elements", H, W, r->stats_C, r->elems);
+  ARG_CHECK(pad >= 0 && pad <= SHIFT_MAX_PAD && pad < (H < W ? H : W), "cpp_replay_set_random_shift: pad %d outside [0,%d] or >= min(H, W) = %d", pad,
+            SHIFT_MAX_PAD, H < W ? H : W);
+  ARG_CHECK((long)W * r->stats_C >= 8 && r->elems < (1L << 31), "cpp_replay_set_random_shift: rows of %ld elements (8 at least), states of %ld (2^31 at most)",
+            (long)W * r->stats_C, r->elems);
+  HIP_CHECK(hipSetDevice(r->ctx->device));
+  if (pad == 0 && r->shift_pad == 0) return CPP_OK;          // off stays off: nothing changes, no graph is captured again
+  if (pad > 0 && !r->shift_dev) {
+    HIP_CHECK(ctx_sync_stream(r->ctx));
+    RC(dalloc(r->arena, &r->shift_dev, (size_t)1));
+    RC(dalloc(r->arena, &r->shift_out, (size_t)4 * 65536));
+  }
+  // the captured step graphs hold the gather instances, the direct-store decision, pad, seed and the geometry by value: a new uid makes
+  // every one of them be captured again
+  r->uid = replay_next_uid(); r->sampled = false;
+  ++r->write_gen;              // (a minibatch presampled under the old setting is stale)
+  r->shift_pad = pad; r->shift_H = pad ? H : 0; r->shift_W = pad ? W : 0; r->shift_seed = pad ? seed : 0;
+  if (pad > 0) {               // the counter starts at 0, no ticket is out: in stream order behind every gather launched so far
+    HIP_CHECK(hipMemsetAsync(r->shift_dev, 0, sizeof(ShiftWords), r->ctx->stream));
+    HIP_CHECK(hipMemsetAsync(r->shift_out, 0, (size_t)4 * 65536 * sizeof(int32_t), r->ctx->stream));
+  }
+  return CPP_OK;
+}
+
+extern "C" int cpp_replay_get_random_shift(cpp_replay* r, int* pad, uint64_t* seed, uint64_t* counter) {
+  ARG_CHECK(r, "cpp_replay_get_random_shift: NULL argument");
+  if (pad) *pad = r->shift_pad;
+  if (seed) *seed = r->shift_seed;
+  if (counter) {
+    *counter = 0;
+    if (r->shift_pad > 0) {
+      HIP_CHECK(hipSetDevice(r->ctx->device));
+      HIP_CHECK(hipMemcpyAsync(counter, &r->shift_dev->counter, sizeof(uint64_t), hipMemcpyDeviceToHost, r->ctx->stream));
+      HIP_CHECK(ctx_sync_stream(r->ctx));
+    }
+  }
+  return CPP_OK;
+}
+
+extern "C" int cpp_replay_last_shifts(cpp_replay* r, int B, int32_t* out) {
+  ARG_CHECK(r && out && B >= 1 && B <= 65536, "cpp_replay_last_shifts: bad argument");
+  if (r->shift_pad <= 0) { cpp_set_error("cpp_replay_last_shifts: random shift is not enabled on this memory"); return CPP_ERR_STATE; }
+  HIP_CHECK(hipSetDevice(r->ctx->device));
+  HIP_CHECK(hipMemcpyAsync(out, r->shift_out, (size_t)4 * B * sizeof(int32_t), hipMemcpyDeviceToHost, r->ctx->stream));
+  HIP_CHECK(ctx_sync_stream(r->ctx));
+  return CPP_OK;
+}
+
+extern "C" int cpp_replay_gather_shifted(cpp_replay* r, int B, const int32_t* idxs, int channels, cpp_batch* out) {
+  ARG_CHECK(r && out && idxs, "cpp_replay_gather_shifted: NULL argument");
+  ARG_CHECK(B >= 1 && B <= out->maxB && B <= 65536, "cpp_replay_gather_shifted: batch %d outside [1,%d]", B, out->maxB);
+  ARG_CHECK(out->elems == r->elems && out->A == r->A, "cpp_replay_gather_shifted: batch/replay shapes differ");
+  if (r->shift_pad <= 0) { cpp_set_error("cpp_replay_gather_shifted: random shift is not enabled on this memory"); return CPP_ERR_STATE; }
+  ARG_CHECK(channels == r->stats_C, "cpp_replay_gather_shifted: channels %d, the memory's images have %d", channels, r->stats_C);
+  if (r->size <= 0) { cpp_set_error("cpp_replay_gather_shifted: replay memory is empty"); return CPP_ERR_STATE; }
+  HIP_CHECK(hipSetDevice(r->ctx->device));
+  RC(replay_stage_rows(r, idxs, B, "cpp_replay_gather_shifted"));
+  RC(replay_sample_device(r, B, r->rows_in, 0, nullptr, channels, out));
+  HIP_CHECK(ctx_sync_stream(r->ctx));
   return CPP_OK;
 }

@@ -58,6 +58,26 @@ def n_step_columns(idxs, state_1_idx, state_2_idx, reward, terminal_mask, size, 
     return ret.reshape(-1, 1), (m[j] * g).reshape(-1, 1), s2[j].astype(np.int32)
 
 
+RANDOM_SHIFT_MAX_PAD = 16
+
+
+def check_random_shift(state_shape, pad):
+    """the argument check of ReplayMemory.enable_random_shift (include/cartpolepp_abi.h "Random shift"): a pixel memory
+    (H, W, 3, cameras, repeats) and 0 <= pad <= 16, pad < min(H, W).  Returns (H, W, pad); raises ValueError otherwise."""
+    shape = tuple(int(d) for d in state_shape)
+    if len(shape) != 5:
+        raise ValueError("enable_random_shift: state shape %r is not a pixel memory (H, W, 3, cameras, repeats)" % (shape,))
+    H, W = shape[0], shape[1]
+    if int(pad) != pad:
+        raise ValueError("enable_random_shift: pad %r is not an integer" % (pad,))
+    pad = int(pad)
+    if not 0 <= pad <= RANDOM_SHIFT_MAX_PAD:
+        raise ValueError("enable_random_shift: pad %d outside [0, %d]" % (pad, RANDOM_SHIFT_MAX_PAD))
+    if pad >= min(H, W):
+        raise ValueError("enable_random_shift: pad %d >= min(H, W) = %d" % (pad, min(H, W)))
+    return H, W, pad
+
+
 class StateColumn(object):
     """`batch.state_1` / `batch.state_2`: the (B, *state_shape) f16 column of a Batch, still resident in HBM.
 
@@ -345,6 +365,7 @@ class ReplayMemory(object):
         self.prioritized = False     # enable_priorities: proportional prioritized replay, the sum tree on the device
         self.priority_seed = 0
         self.n_step, self.n_step_discount = 1, 0.0     # enable_n_step: the gathers fold n-step returns into reward / terminal_mask
+        self.random_shift = (0, 0)   # enable_random_shift: (pad, seed); pad 0 = off
         # pixel states (H, W, 3, cameras, repeats): channel count for the fused whitening statistics
         self.channels = int(np.prod(self.state_shape[2:])) if len(self.state_shape) == 5 else 0
         if self.channels > 0:        # per-state whitening sums, kept by the store: sampling never re-reads the pixels for them
@@ -558,6 +579,42 @@ class ReplayMemory(object):
             raise ValueError("enable_n_step: discount %r (must be finite and >= 0)" % discount)
         check(lib.cpp_replay_set_n_step(self.handle, n, discount))
         self.n_step, self.n_step_discount = n, float(np.float32(discount))
+
+    # --- random shift (extension: the reference trains on the stored renders) -----------------------------------------------------
+    def enable_random_shift(self, pad, seed=0):
+        """DrQ's random shift for every minibatch the trainers gather from this memory (include/cartpolepp_abi.h, DESIGN "Random
+        shift"): each gathered state_1 / state_2 image is padded by `pad` pixels of its own edge and cropped back at an offset drawn
+        per image and per minibatch (Philox keyed by `seed` and the memory's augmentation counter, which starts at 0 here).  pad = 0
+        switches it off.  Applies to agent.train_step and to the literal loop while the Batch is still in the replay (its rows are
+        gathered by the train call); `batch.state_1` read on the host, `Batch.device`, sample_on_device and a Batch that was preserved
+        or uploaded show / train the stored pixels.  Data-parallel learners: give every rank's memory its own seed."""
+        H, W, pad = check_random_shift(self.state_shape, pad)
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        check(lib.cpp_replay_set_random_shift(self.handle, H, W, pad, seed))
+        self.random_shift = (pad, seed if pad else 0)
+
+    def shift_counter(self):
+        """minibatches gathered with augmentation since enable_random_shift (waits for the stream)"""
+        n = C.c_uint64()
+        check(lib.cpp_replay_get_random_shift(self.handle, None, None, C.byref(n)))
+        return int(n.value)
+
+    def last_shifts(self, B):
+        """the (2, B, 2) int32 shifts [which][b][dy, dx] of the last augmented gather"""
+        out = np.empty((2, int(B), 2), np.int32)
+        check(lib.cpp_replay_last_shifts(self.handle, int(B), ptr(out)))
+        return out
+
+    def gather_shifted(self, idxs):
+        """rows `idxs` gathered with augmentation (one minibatch: the counter advances by one): (state_1, state_2, shifts) on the host"""
+        idxs = np.ascontiguousarray(np.asarray(idxs).reshape(-1), dtype=np.int32)
+        B = len(idxs)
+        dev = self._device_batch(B)
+        dev.evict_owner()
+        check(lib.cpp_replay_gather_shifted(self.handle, B, ptr(idxs), self.channels, dev.handle))
+        s1, s2 = np.empty((B,) + self.state_shape, np.float16), np.empty((B,) + self.state_shape, np.float16)
+        check(lib.cpp_batch_download(dev.handle, ptr(s1), ptr(s2), None, None, None))
+        return s1, s2, self.last_shifts(B)
 
     def fill_synthetic(self, n_rows, seed=1234):
         """bench/test helper: synthetic transitions generated on the device.  The host bookkeeping is advanced to

@@ -282,6 +282,44 @@ int cpp_replay_draw_prioritized(cpp_replay* replay, int B, uint64_t seed, int32_
 int cpp_replay_set_n_step(cpp_replay* replay, int n, float discount);
 int cpp_replay_get_n_step(cpp_replay* replay, int* n, float* discount);       /* (1, 0) until set; either output may be NULL */
 
+/* ---- Random shift (DrQ, DrQ-v2) in the gather ---------------------------------------------------------------------------------
+ * Extension, no reference counterpart (the reference trains on the stored renders).  Opt-in per memory with
+ * cpp_replay_set_random_shift(replay, H, W, pad, seed); a memory on which it was never enabled, or with pad = 0, behaves bit for bit
+ * as before on every path.  Pixel memories only: state shape (H, W, 3, cameras, repeats) with the C = 3 * cameras * repeats channels
+ * innermost, i.e. a memory for which cpp_replay_set_stats_channels was called with C > 0, and H * W * C == state_elems.
+ *  - The shifted image.  For gathered state (b, which) -- which = 0: state_1, 1: state_2 -- with shift (dy, dx), each in [-pad, pad]:
+ *      out[y, x, c] = in[clamp(y + dy, 0, H-1), clamp(x + dx, 0, W-1), c]
+ *    i.e. replicate padding by `pad` followed by a crop at offset (pad + dy, pad + dx): DrQ-v2's RandomShiftsAug at integer shifts.
+ *    The same rule for the f16 and the 8-bit store (which gathers to f16 through its table, as without the shift).  The whitening
+ *    statistics of the minibatch are those of the shifted images: what the networks see.
+ *  - The draw.  r = philox4x32_10(ctr = {b, 2 + which, n_lo, n_hi}, key = {seed_lo, seed_hi}); `seed` is the augmentation's own, n
+ *    the memory's augmentation counter.  (ctr.y is 0 for the uniform row draw and 1 for the prioritized draw: 2 and 3 keep the shift
+ *    streams disjoint from both, even under equal seeds.)  dy = (int)(((uint64)r.x * (2 pad + 1)) >> 32) - pad, dx likewise from r.y.
+ *  - The counter.  A 64-bit device word per memory, 0 when the augmentation is enabled (every call of cpp_replay_set_random_shift
+ *    with pad > 0 resets it).  It advances by exactly one per minibatch gathered with augmentation, in stream order, inside the
+ *    gather's own launch, on every path that trains: cpp_ddpg_train_step / cpp_naf_train_step (eager or replayed from a captured
+ *    graph), cpp_ddpg_train_rows / cpp_naf_train_rows / cpp_naf_train_rows_async (the literal loop: rows from the host),
+ *    cpp_ddpg_sample_and_compute / cpp_naf_sample_and_compute and the data-parallel steps.  It does not depend on the sampler's
+ *    counter (which stands still when the host draws the rows).
+ *  - Where it applies: to the trainers' own gathers, listed above, and to cpp_replay_gather_shifted.  cpp_replay_sample keeps
+ *    returning the stored pixels and does not move the counter, so a cpp_batch it filled is trained as it is.
+ *  - A memory with pad > 0 always materialises its minibatch (the gathered-copy route of the 8-bit store); conv1 never reads the store
+ *    directly.  n-step: the shift is applied to the state in the slot the walk ends on.  Prioritized replay, batch norm and dropout
+ *    are unaffected.  Data-parallel learners: each rank's memory has its own seed and counter; distinct seeds per rank are the
+ *    caller's business.
+ *  - cpp_replay_set_random_shift returns CPP_ERR_ARG and writes nothing if the memory is not a pixel memory, if H * W * C !=
+ *    state_elems (C: the memory's statistics channels), if pad is outside [0, 16] or >= min(H, W), or if a row holds fewer than 8
+ *    elements (W * C < 8).  pad = 0 switches the feature off (the direct path again).  Every effective change re-issues the memory's
+ *    graph key: the trainers capture their step graphs again at the next call, none replays the old form. */
+int cpp_replay_set_random_shift(cpp_replay* replay, int H, int W, int pad, uint64_t seed);
+/* synchronises the stream for the counter; (0, 0, 0) when off; any output may be NULL */
+int cpp_replay_get_random_shift(cpp_replay* replay, int* pad, uint64_t* seed, uint64_t* counter);
+/* the (2, B, 2) shifts [which][b][dy, dx] of the last augmented gather of B rows (written by the gather next to its rows) */
+int cpp_replay_last_shifts(cpp_replay* replay, int B, int32_t* out);
+/* cpp_replay_sample(idxs != NULL)'s contract with the augmentation applied: the B host-given rows gathered, shifted, into `out`,
+ * the counter advancing by one (inspection / tests).  CPP_ERR_STATE on a memory without the augmentation. */
+int cpp_replay_gather_shifted(cpp_replay* replay, int B, const int32_t* idxs, int channels, cpp_batch* out);
+
 /* ---- DDPG train ops (ddpg_cartpole.py:102-119, :186-248, :329-337) --------------------------- */
 typedef struct cpp_ddpg_hyper {
   float actor_learning_rate;     /* --actor-learning-rate  (ddpg_cartpole.py:41)  */
