@@ -127,6 +127,10 @@ SIGNATURES = {
     "cpp_ddpg_grad_buffer": (_I, [_P, _PP, C.POINTER(_L)]),
     "cpp_ddpg_apply_gradients": (_I, [_P, _F]),
     "cpp_ddpg_update_targets": (_I, [_P]),
+    "cpp_ddpg_set_optimiser": (_I, [_P, _I, _F, _F, _F, _F]),
+    "cpp_ddpg_opt_state_size": (_L, [_P]),
+    "cpp_ddpg_get_opt_state": (_I, [_P, _P, _P, _L, _P]),
+    "cpp_ddpg_set_opt_state": (_I, [_P, _P, _P, _L, _P]),
     "cpp_ddpg_train_step": (_I, [_P, _P, _I, _I, _P, _U64]),
     "cpp_ddpg_train_rows": (_I, [_P, _P, _I, _P]),
     "cpp_ddpg_sample_and_compute": (_I, [_P, _P, _I, _U64]),

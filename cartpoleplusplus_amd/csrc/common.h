@@ -385,6 +385,8 @@ struct OptSegs {
   int nseg; int kind; float momentum, beta1, beta2, epsilon;
   const double* sq; int sq_begin[2], sq_count[2];   // sq != nullptr: group g's squared norm = sum of sq[sq_begin[g] .. + sq_count[g]) instead of `part`
   const uint64_t* step;        // Adam: number of applies so far INCLUDING this one (device counter)
+  const uint64_t* step_seg[OPT_MAX_SEGS];      // optional, per segment: the segment's own count instead of `step` (DDPG: the actor's and the
+                               // critic's optimisers count their own applies, ddpg_cartpole.py:118-119, :218).  Nobody writes it in this launch.
   uint64_t* bump;              // optional: device counter incremented once by this launch (the replay sampler's Philox counter)
   // optional (tgt[seg] != nullptr): this launch closes an OUTER step -- a segment's target network takes its soft update from
   // the parameter values this launch writes (ddpg_cartpole.py:336-337 behind the last minibatch: soft_update_kernel's launch disappears)
@@ -403,7 +405,7 @@ struct OptSegs {
   int img_n; int img_cin;        // img_cin: conv1's input channels (the image body's instance)
   long img_skip[OPT_MAX_SEGS];   // leading parameters of a segment (conv1's weights and biases) that its image workgroup updates itself
   struct { float* w; float* bias; const float* gw; const float* gb; unsigned char* rec; int seg, col, nout;
-           const float* white; float* mw; float* mb; } img[4];      // mw / mb: the Momentum slots of those parameters (OPT_MOMENTUM)      // white != nullptr: the column's table is already in memory (the dW reductions' launch computed it)
+           const float* white; float* mw; float* mb; float* vw; float* vb; } img[4];      // mw / mb: the Momentum slots of those parameters (OPT_MOMENTUM), Adam's first moments (OPT_ADAM); vw / vb: Adam's second moments      // white != nullptr: the column's table is already in memory (the dW reductions' launch computed it)
 };
 // the SGD update of one parameter, p - lr * (g * scale), with its roundings pinned (one product, one fused multiply-add): opt_apply_kernel
 // writes it, the conv1 image rider of the same launch recomputes it, and both must hold the same bits whatever the compiler contracts
@@ -411,6 +413,24 @@ __host__ __device__ inline float sgd_update(float p, float g, float scale, float
 // ... and Momentum's pair (util.py:73-76: accum = momentum * accum + g; p -= lr * accum), pinned the same way
 __host__ __device__ inline float momentum_accum(float m, float g, float scale, float momentum) { return __builtin_fmaf(momentum, m, g * scale); }
 __host__ __device__ inline float momentum_step(float p, float accum, float lr) { return __builtin_fmaf(-lr, accum, p); }
+// ... and Adam's element (util.py:73-76, tf.train.AdamOptimizer: m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g^2; p -= lr_t m / (sqrt(v) + eps)),
+// pinned the same way: g * scale is one product; each moment is one fused multiply-add on a rounded product, (1 - b1) * g and
+// ((1 - b2) * g) * g; lr_t * m is one product; sqrtf and the division are the correctly rounded ones; the last step is a plain
+// subtraction.  lr_t is adam_rate's value.  opt_apply_kernel writes these, the conv1 image rider recomputes them.
+struct AdamElem { float p, m, v; };
+__host__ __device__ inline AdamElem adam_update(float p, float g, float m, float v, float scale, float lr_t, float beta1, float beta2, float epsilon) {
+  const float gi = g * scale;
+  AdamElem e;
+  e.m = __builtin_fmaf(beta1, m, (1.f - beta1) * gi);
+  e.v = __builtin_fmaf(beta2, v, ((1.f - beta2) * gi) * gi);
+  e.p = p - (lr_t * e.m) / (sqrtf(e.v) + epsilon);
+  return e;
+}
+// the bias-corrected rate of apply number t (t >= 1, counted INCLUDING the apply it serves): lr sqrt(1 - b2^t) / (1 - b1^t), in f64, rounded once
+__host__ __device__ inline float adam_rate(float lr, float beta1, float beta2, uint64_t t) {
+  const double td = (double)t;
+  return (float)((double)lr * sqrt(1.0 - pow((double)beta2, td)) / (1.0 - pow((double)beta1, td)));
+}
 // ... and the target networks' update, target - coeff * (target - source) (base_network.py:31), pinned the same way: soft_update_kernel
 // writes it, and so does the optimiser's launch when it closes an outer step (OptSegs::tgt)
 __host__ __device__ inline float soft_update_value(float t, float s, float coeff) { return __builtin_fmaf(-coeff, t - s, t); }
@@ -441,6 +461,8 @@ struct DdpgHeadsArgs {
   float *h2a_out, *dz_h1a;                         // B x ld_h2a (first n2a columns), B x n1a
   // optional: importance weights of the rows (prioritized replay, per.hip): loss = mean(w td^2), dz_q = (td w) 2 / B
   const float* w;
+  // optional: the two optimisers' step counters (Momentum / Adam: rt_ddpg.cpp), both += 1 -- nobody reads them before the optimiser's launch
+  unsigned long long* step_bump;
 };
 #define DDPG_HEADS_MAX_WGS 256
 size_t ddpg_heads_lds_bytes(const DdpgHeadsArgs& h);

@@ -55,13 +55,17 @@ struct Conv1ImageArgs {
   const float* gw; const float* gb; float lr, gscale;
   float* mw; float* mb; float momentum;      // OPT_MOMENTUM: the parameters' accumulator slots (read, advanced and written back here)
   float* w_out; float* b_out;     // ... and written by THIS workgroup (the update's own workgroups leave these parameters alone: no one reads a half-updated tensor)
+  float* vw; float* vb; float beta1, beta2, epsilon;      // OPT_ADAM (vw != nullptr): mw / mb are the first moments, vw / vb the second; lr is replaced by pre()'s bias-corrected rate
 };
 struct Conv1ImageArgsN { Conv1ImageArgs a[CONV_BATCH_MAX]; int n; };
 
 // pre(): called once the loads of the weights (gradients, accumulators) are in flight, returns the gradient scale of the update that
 // rides here -- optim.hip's rider adds up the clipping norm and fetches the whitening table in there, under the loads' latency
-struct Conv1ImageNoPre { __device__ __forceinline__ float operator()(float gscale) const { return gscale; } };
-template <int CIN, int NPCS = F16_PIECES, typename Pre = Conv1ImageNoPre>
+// (lr: the update's rate, which pre() may replace -- Adam's bias-corrected rate comes from a device counter)
+struct Conv1ImageNoPre { __device__ __forceinline__ float operator()(float gscale, float&) const { return gscale; } };
+// ADAM: the instances that know Adam's element (a.vw / a.vb) -- only opt_apply_kernel<true> has them; every other instance carries
+// none of that code
+template <int CIN, int NPCS = F16_PIECES, typename Pre = Conv1ImageNoPre, bool ADAM = false>
 __device__ __forceinline__ void conv1_image_body(const Conv1ImageArgs& a, unsigned char* lds_raw, Pre pre = Pre()) {
   typedef Rs16Geom<CIN, NPCS> G;
   constexpr int KS = G::KS, P = G::P, NO = G::NO, NCH = G::NCH, NPC = G::NPC, RK = G::RK;
@@ -84,7 +88,7 @@ __device__ __forceinline__ void conv1_image_body(const Conv1ImageArgs& a, unsign
   // floats -- a thread fetching its own 24 (ky, k, o) values asked for 40-byte strides, 2.6 us of this workgroup (6.5 with the gradients)
   float* wst = reinterpret_cast<float*>(lds_raw);              // [KS * KROW * nout] -- in the record's place, which is written later
   const int nwts = KS * G::KROW * nout;
-  float gscale_b = a.gscale;
+  float gscale_b = a.gscale, lr = a.lr;
   {
     constexpr int NWT = (KS * G::KROW * NO + CONV_THREADS - 1) / CONV_THREADS;      // (every load in flight before the first use)
     float wr[NWT], gr[NWT];
@@ -94,13 +98,36 @@ __device__ __forceinline__ void conv1_image_body(const Conv1ImageArgs& a, unsign
     if (a.gw) {
 #pragma unroll
       for (int n = 0; n < NWT; ++n) { const int i = tid + n * CONV_THREADS; gr[n] = a.gw[i < nwts ? i : 0]; }
-      if (a.mw) {
+      if (a.mw && !(ADAM && a.vw)) {
 #pragma unroll
         for (int n = 0; n < NWT; ++n) { const int i = tid + n * CONV_THREADS; mr[n] = a.mw[i < nwts ? i : 0]; }
       }
     }
-    const float gscale = pre(a.gscale);
+    const float gscale = pre(a.gscale, lr);
     gscale_b = gscale;
+    if (ADAM && a.gw && a.vw) {
+      // Adam (opt_apply_kernel's own expressions).  The moments are fetched behind pre(), whose own registers are free by now -- in
+      // front of it they would be live across it -- and the elements are finished four at a time: left alone the scheduler runs all
+      // the divisions side by side, and the kernel's register count is what EVERY workgroup of the optimiser's launch is allocated.
+      float vr[NWT];
+      int i0 = 0;
+      asm volatile("" : "+v"(i0));      // (opaque: the clamped indices are recomputed here -- reused from the loads above they would live across pre() too)
+#pragma unroll
+      for (int n = 0; n < NWT; ++n) { const int i = tid + n * CONV_THREADS; mr[n] = a.mw[i < nwts ? i : i0]; }
+#pragma unroll
+      for (int n = 0; n < NWT; ++n) { const int i = tid + n * CONV_THREADS; vr[n] = a.vw[i < nwts ? i : i0]; }
+#pragma unroll
+      for (int n = 0; n < NWT; ++n) {
+        const int i = tid + n * CONV_THREADS;
+        if (i < nwts) {
+          const AdamElem e = adam_update(wr[n], gr[n], mr[n], vr[n], gscale, lr, a.beta1, a.beta2, a.epsilon);
+          a.mw[i] = e.m; a.vw[i] = e.v;
+          wst[i] = e.p;
+          if (a.w_out) a.w_out[i] = e.p;
+        }
+        if ((n & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
 #pragma unroll
     for (int n = 0; n < NWT; ++n) {
       const int i = tid + n * CONV_THREADS;
@@ -109,11 +136,12 @@ __device__ __forceinline__ void conv1_image_body(const Conv1ImageArgs& a, unsign
         if (a.gw && a.mw) {                                    // (opt_apply_kernel's own expressions)
           const float acc = momentum_accum(mr[n], gr[n], gscale, a.momentum);
           a.mw[i] = acc;
-          w = momentum_step(w, acc, a.lr);
-        } else if (a.gw) w = sgd_update(w, gr[n], gscale, a.lr);
+          w = momentum_step(w, acc, lr);
+        } else if (a.gw) w = sgd_update(w, gr[n], gscale, lr);
         wst[i] = w;
         if (a.gw && a.w_out) a.w_out[i] = w;
       }
+    }
     }
   }
   __syncthreads();
@@ -134,8 +162,9 @@ __device__ __forceinline__ void conv1_image_body(const Conv1ImageArgs& a, unsign
   if (tid < 16) {
     float bo = (a.bias && tid < nout) ? a.bias[tid] : 0.f;
     if (a.bias && a.gb && tid < nout) {
-      if (a.mb) { const float acc = momentum_accum(a.mb[tid], a.gb[tid], gscale_b, a.momentum); a.mb[tid] = acc; bo = momentum_step(bo, acc, a.lr); }
-      else bo = sgd_update(bo, a.gb[tid], gscale_b, a.lr);
+      if (ADAM && a.vb) { const AdamElem e = adam_update(bo, a.gb[tid], a.mb[tid], a.vb[tid], gscale_b, lr, a.beta1, a.beta2, a.epsilon); a.mb[tid] = e.m; a.vb[tid] = e.v; bo = e.p; }
+      else if (a.mb) { const float acc = momentum_accum(a.mb[tid], a.gb[tid], gscale_b, a.momentum); a.mb[tid] = acc; bo = momentum_step(bo, acc, lr); }
+      else bo = sgd_update(bo, a.gb[tid], gscale_b, lr);
       if (a.b_out) a.b_out[tid] = bo;
     }
     biasn[tid] = bo;

@@ -276,6 +276,7 @@ __global__ __launch_bounds__(HEADS_THREADS) void ddpg_heads_kernel(const DdpgHea
     double s = 0.0;
     for (int i = 0; i < HEADS_ROWS; ++i) s += lred[i];
     h.loss_part[blockIdx.x] = s;
+    if (blockIdx.x == 0 && h.step_bump) { h.step_bump[0] += 1ull; h.step_bump[1] += 1ull; }
   }
 #ifdef HEADS_CLOCK
   HCK();

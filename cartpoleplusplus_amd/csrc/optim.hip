@@ -66,6 +66,10 @@ __device__ __forceinline__ double lane_sum_f64(const double* q, const int count,
 //   SGD      : p -= lr * g
 //   Momentum : m = momentum * m + g;  p -= lr * m
 //   Adam     : lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t);  m, v moments;  p -= lr_t * m / (sqrt(v) + eps)
+// Two instances.  ADAM = false serves GradientDescent and Momentum and holds no Adam code at all, neither in the update's workgroups nor
+// in the image rider: it is the kernel on bench.py's headline step, and what it executes does not depend on Adam existing.  ADAM = true
+// serves OPT_ADAM alone.
+template <bool ADAM>
 __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(const OptSegs s, float grad_scale,
                                                                 float clip, const double* part,
                                                                 int nparts, float* norms_out) {
@@ -77,7 +81,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(const OptSegs s,
     __shared__ float wh[2 * CPP_MAX_CHANNELS];
     const int j = blockIdx.x, ws = s.img[j].seg;
     // (run by conv1_image_body once its weight / gradient loads are in flight)
-    auto pre = [&](float) __attribute__((always_inline)) -> float {
+    auto pre = [&](float, float& lr_io) __attribute__((always_inline)) -> float {
     // the update's scale, as the workgroups of segment ws compute it below (same partials, same order)
       if (s.img[j].gw) {
         double tot = 0.0;
@@ -98,6 +102,8 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(const OptSegs s,
           float sc = 1.f;
           if (clip > 0.f) sc = clip * fminf(1.f / norm, 1.f / clip);
           sh_scale = sc * grad_scale;
+          // (Adam: the bias-corrected rate of segment ws, from the same counter by the same function as its workgroups below)
+          if (ADAM) sh_lr = adam_rate(s.lr[ws], s.beta1, s.beta2, *(s.step_seg[ws] ? s.step_seg[ws] : s.step));
         }
       }
       // the whitening table of the network's state column, as the first rider's waves compute it (stats_finalize_wave: a lane's rows in
@@ -136,19 +142,22 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(const OptSegs s,
         }
       }
       __syncthreads();
+      if (ADAM && s.img[j].gw) lr_io = sh_lr;
       return s.img[j].gw ? sh_scale : 0.f;
     };
     Conv1ImageArgs ia;
     ia.w = s.img[j].w; ia.bias = s.img[j].bias; ia.scale = wh; ia.shift = wh + s.img_cin; ia.wscale = 0.f; ia.nout = s.img[j].nout; ia.rec = s.img[j].rec;
     ia.gw = s.img[j].gw; ia.gb = s.img[j].gb; ia.lr = s.img[j].gw ? s.lr[ws] : 0.f; ia.gscale = 0.f;      // (the scale: pre's return value)
     ia.w_out = s.img[j].gw ? s.img[j].w : nullptr; ia.b_out = s.img[j].gw ? s.img[j].bias : nullptr;
-    ia.mw = (s.img[j].gw && s.kind == OPT_MOMENTUM) ? s.img[j].mw : nullptr; ia.mb = (s.img[j].gw && s.kind == OPT_MOMENTUM) ? s.img[j].mb : nullptr; ia.momentum = s.momentum;
+    const bool slots = s.img[j].gw && (ADAM || s.kind == OPT_MOMENTUM), adam = ADAM && s.img[j].gw;
+    ia.mw = slots ? s.img[j].mw : nullptr; ia.mb = slots ? s.img[j].mb : nullptr; ia.momentum = s.momentum;
+    ia.vw = adam ? s.img[j].vw : nullptr; ia.vb = adam ? s.img[j].vb : nullptr; ia.beta1 = s.beta1; ia.beta2 = s.beta2; ia.epsilon = s.epsilon;
     switch (s.img_cin) {                                // (uniform: one of conv_fwd_rs16.hip's instances)
-      case 3: conv1_image_body<3, F16_PIECES>(ia, img_lds, pre); break;
-      case 6: conv1_image_body<6, F16_PIECES>(ia, img_lds, pre); break;
-      case 9: conv1_image_body<9, F16_PIECES>(ia, img_lds, pre); break;
-      case 12: conv1_image_body<12, F16_PIECES>(ia, img_lds, pre); break;
-      default: conv1_image_body<18, F16_PIECES>(ia, img_lds, pre); break;
+      case 3: conv1_image_body<3, F16_PIECES, decltype(pre), ADAM>(ia, img_lds, pre); break;
+      case 6: conv1_image_body<6, F16_PIECES, decltype(pre), ADAM>(ia, img_lds, pre); break;
+      case 9: conv1_image_body<9, F16_PIECES, decltype(pre), ADAM>(ia, img_lds, pre); break;
+      case 12: conv1_image_body<12, F16_PIECES, decltype(pre), ADAM>(ia, img_lds, pre); break;
+      default: conv1_image_body<18, F16_PIECES, decltype(pre), ADAM>(ia, img_lds, pre); break;
     }
     return;
   }
@@ -179,10 +188,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(const OptSegs s,
     if (clip > 0.f) sc = clip * fminf(1.f / norm, 1.f / clip);
     sh_scale = sc * grad_scale;
     float lr = s.lr[seg];
-    if (s.kind == OPT_ADAM) {
-      const double t = (double)(*s.step);
-      lr = (float)((double)lr * sqrt(1.0 - pow((double)s.beta2, t)) / (1.0 - pow((double)s.beta1, t)));
-    }
+    if (ADAM) lr = adam_rate(lr, s.beta1, s.beta2, *(s.step_seg[seg] ? s.step_seg[seg] : s.step));
     sh_lr = lr;
     if (blockIdx.x == 0 && norms_out && s.n[seg] > 0) norms_out[s.group[seg]] = norm;
     if (blockIdx.x == 0 && seg == 0 && s.bump) *s.bump += 1;
@@ -198,7 +204,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(const OptSegs s,
   const long stride = (long)gridDim.x * OPT_THREADS;
   float* tp = s.tgt[seg] ? s.tgt[seg] + skip : nullptr;      // (uniform) the segment's target network: updated from the new values
   const float tc = s.tgt_coeff;
-  if (s.kind == OPT_SGD) {
+  if (!ADAM && s.kind == OPT_SGD) {
     long i = (long)blockIdx.x * OPT_THREADS + threadIdx.x;
     for (; i + 3 * stride < n; i += 4 * stride) {
       float pv[4], gv[4], tv[4];
@@ -216,7 +222,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(const OptSegs s,
       p[i] = pn;
       if (tp) tp[i] = soft_update_value(tp[i], pn, tc);
     }
-  } else if (s.kind == OPT_MOMENTUM) {
+  } else if (!ADAM) {
     float* m = s.m[seg] + skip;
     for (long i = (long)blockIdx.x * OPT_THREADS + threadIdx.x; i < n; i += stride) {
       const float acc = momentum_accum(m[i], g[i], sc, s.momentum);
@@ -229,14 +235,27 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(const OptSegs s,
     float* m = s.m[seg] + skip;
     float* v = s.v[seg] + skip;
     const float b1 = s.beta1, b2 = s.beta2;
-    for (long i = (long)blockIdx.x * OPT_THREADS + threadIdx.x; i < n; i += stride) {
-      const float gi = g[i] * sc;
-      const float mi = b1 * m[i] + (1.f - b1) * gi;
-      const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-      m[i] = mi; v[i] = vi;
-      const float pn = p[i] - lr * mi / (sqrtf(vi) + s.epsilon);
-      p[i] = pn;
-      if (tp) tp[i] = soft_update_value(tp[i], pn, tc);
+    // five streams per element (p, g, m, v, target): four elements' loads in flight, as in the SGD branch (one element at a time this
+    // loop waited a memory round trip per element -- it carries both conv trunks now, not only NAF's head vectors)
+    long i = (long)blockIdx.x * OPT_THREADS + threadIdx.x;
+    for (; i + 3 * stride < n; i += 4 * stride) {
+      float pv[4], gv[4], mv[4], vv[4], tv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        pv[u] = p[i + u * stride]; gv[u] = g[i + u * stride]; mv[u] = m[i + u * stride]; vv[u] = v[i + u * stride];
+        if (tp) tv[u] = tp[i + u * stride];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const AdamElem e = adam_update(pv[u], gv[u], mv[u], vv[u], sc, lr, b1, b2, s.epsilon);
+        m[i + u * stride] = e.m; v[i + u * stride] = e.v; p[i + u * stride] = e.p;
+        if (tp) tp[i + u * stride] = soft_update_value(tv[u], e.p, tc);
+      }
+    }
+    for (; i < n; i += stride) {
+      const AdamElem e = adam_update(p[i], g[i], m[i], v[i], sc, lr, b1, b2, s.epsilon);
+      m[i] = e.m; v[i] = e.v; p[i] = e.p;
+      if (tp) tp[i] = soft_update_value(tp[i], e.p, tc);
     }
   }
 }
@@ -249,16 +268,17 @@ int launch_opt_apply(cpp_ctx* ctx, const OptSegs& s, float grad_scale, float cli
   const bool img = s.img_n > 0 && (s.st_part || s.img[0].white);
   const size_t lds = img ? (size_t)Rs16ImageLds<18>::BYTES : 0;
   if (img) {
-    if ((s.kind != OPT_SGD && s.kind != OPT_MOMENTUM) || (s.st_part && s.st_C != s.img_cin) || !conv_rs16_channels_ok(s.img_cin) || s.skip_if) {
-      cpp_set_error("opt_apply: the conv1 image rider needs SGD or Momentum and a channel count conv_rs16.h is instantiated for (%d)", s.img_cin); return 1;
+    if ((s.kind != OPT_SGD && s.kind != OPT_MOMENTUM && s.kind != OPT_ADAM) || (s.st_part && s.st_C != s.img_cin) || !conv_rs16_channels_ok(s.img_cin) || s.skip_if) {
+      cpp_set_error("opt_apply: the conv1 image rider needs a known optimiser kind and a channel count conv_rs16.h is instantiated for (%d)", s.img_cin); return 1;
     }
     static bool attr_done[CPP_MAX_DEVICES] = {};
     if (!attr_done[cpp_dev_slot(ctx)]) {
-      HIP_CHECK(hipFuncSetAttribute((const void*)opt_apply_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Rs16ImageLds<18>::BYTES));
+      HIP_CHECK(hipFuncSetAttribute((const void*)opt_apply_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Rs16ImageLds<18>::BYTES));
+      HIP_CHECK(hipFuncSetAttribute((const void*)opt_apply_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Rs16ImageLds<18>::BYTES));
       attr_done[cpp_dev_slot(ctx)] = true;
     }
   }
-  hipLaunchKernelGGL(opt_apply_kernel, dim3(128, s.nseg + (s.st_part ? 1 : 0) + (img ? 1 : 0)), dim3(OPT_THREADS), lds, ctx->stream, s, grad_scale,
+  hipLaunchKernelGGL(s.kind == OPT_ADAM ? opt_apply_kernel<true> : opt_apply_kernel<false>, dim3(128, s.nseg + (s.st_part ? 1 : 0) + (img ? 1 : 0)), dim3(OPT_THREADS), lds, ctx->stream, s, grad_scale,
                      clip, part, nparts, norms_out);
   LAUNCH_CHECK();
   prof_end(ctx, K_CLIP_SGD);

@@ -36,6 +36,13 @@ struct cpp_ddpg {
   // prioritized replay (step_body, per.hip): the importance weights the gradient pass reads, and the launch that follows the TD values
   // of the minibatch (its priorities into the tree, the next minibatch's rows and weights)
   const float* per_w; std::function<int()> per_hook;
+  // the update rule of the two 'optimiser' scopes (ddpg_cartpole.py:118-119, :218; cpp_ddpg_set_optimiser).  GradientDescent has no state.
+  // Momentum / Adam: slots over gradbuf's layout [actor | critic], and one step count per list on the device (captured graphs replay
+  // them): [0] counts the actor's applies, [1] the critic's.
+  int opt_kind; float opt_momentum, opt_beta1, opt_beta2, opt_epsilon;
+  float *opt_m, *opt_v; uint64_t* opt_step;
+  bool bump_in_heads;      // step_body: the gradient pass in front of an apply() of both lists advances both counts in its heads kernel ...
+  bool step_bumped;        // ... and has (the next apply must not)
   Arena arena;
 };
 
@@ -62,6 +69,8 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   memset(d->slot_set, 0, sizeof(d->slot_set));
   d->heads_grid = d->heads_B = d->loss_parts = d->loss_B = 0;
   d->per_w = nullptr;
+  d->opt_kind = OPT_SGD; d->opt_momentum = 0.f; d->opt_beta1 = 0.9f; d->opt_beta2 = 0.999f; d->opt_epsilon = 1e-8f;
+  d->opt_m = d->opt_v = nullptr; d->opt_step = nullptr; d->bump_in_heads = d->step_bumped = false;
   const int A = actor->spec.action_dim;
   int rc = dalloc(d->arena, &d->gradbuf, (size_t)(d->nA + d->nC));
   if (!rc) rc = dalloc(d->arena, &d->dq_da, (size_t)d->maxB * A);
@@ -238,7 +247,20 @@ static int apply(cpp_ddpg* d, bool do_actor, bool do_critic, float grad_scale, u
     s.st_count = (double)next_B * (double)(elems / next_C); s.st_eps = 1e-6; s.st_wmax = d->ctx->white_max_dev;
   }
   d->actor->wimg_key = nullptr; d->critic->wimg_key = nullptr;      // (the parameters change)
-  s.nseg = 2; s.kind = OPT_SGD;
+  s.nseg = 2; s.kind = d->opt_kind;
+  const bool bumped = d->step_bumped;
+  d->step_bumped = false;
+  if (s.kind != OPT_SGD) {
+    s.momentum = d->opt_momentum; s.beta1 = d->opt_beta1; s.beta2 = d->opt_beta2; s.epsilon = d->opt_epsilon;
+    s.m[0] = d->opt_m; s.m[1] = d->opt_m + d->nA; s.v[0] = d->opt_v; s.v[1] = d->opt_v ? d->opt_v + d->nA : nullptr;
+    s.step_seg[0] = d->opt_step; s.step_seg[1] = d->opt_step + 1;
+    // a list's count moves with its own applies only (actor.train / critic.train: two optimisers).  Not in the optimiser's launch, whose
+    // other workgroups read the counts: in the heads kernel of the gradient pass (step_body) or, on the other paths, a launch in front
+    if (!bumped) {
+      if (do_actor) RC(launch_counter_add(d->ctx, d->opt_step, 1));
+      if (do_critic) RC(launch_counter_add(d->ctx, d->opt_step + 1, 1));
+    }
+  }
   s.p[0] = d->actor->params; s.g[0] = d->gradbuf; s.n[0] = do_actor ? d->nA : 0; s.lr[0] = d->hp.actor_learning_rate; s.group[0] = 0;
   s.p[1] = d->critic->params; s.g[1] = d->gradbuf + d->nA; s.n[1] = do_critic ? d->nC : 0; s.lr[1] = d->hp.critic_learning_rate; s.group[1] = 1;
   if (folded && do_actor && do_critic && grad_scale == 1.0f && d->sq_cnt[0] > 0 && d->sq_cnt[1] > 0) {
@@ -250,8 +272,11 @@ static int apply(cpp_ddpg* d, bool do_actor, bool do_critic, float grad_scale, u
   // this launch, the next minibatch's statistics are, conv1 of all four networks will run on that kernel
   cpp_net* inets[4] = {d->actor, d->critic, d->tactor, d->tcritic};
   const ConvL* L0 = d->actor->spec.pixel ? &d->actor->conv[0] : nullptr;
+  // (CPP_RIDE_IMAGE_UPDATE=0, ablation build: no image workgroups at all -- conv1's parameters and slots are advanced by the update's
+  // plain workgroups and the forward builds its image by a launch of its own: what the rider's restated update is compared with)
+  static const bool no_img = cpp_switch_off("CPP_RIDE_IMAGE_UPDATE");
   const bool img = next && next_C > 0 && do_actor && do_critic && L0 && !d->actor->spec.use_batch_norm && !d->critic->spec.use_batch_norm &&
-                   conv_rs16_ok(d->ctx, L0->Cin, L0->H, L0->W, kConvOut) && next_B >= 2;
+                   conv_rs16_ok(d->ctx, L0->Cin, L0->H, L0->W, kConvOut) && next_B >= 2 && !no_img;
   if (img) {
     s.img_n = 4; s.img_cin = L0->Cin;
     for (int k = 0; k < 2; ++k) {      // conv1's weights and biases open the flat buffers (cpp_net_var_info order): [w_off, b_off + nout)
@@ -266,6 +291,8 @@ static int apply(cpp_ddpg* d, bool do_actor, bool do_critic, float grad_scale, u
       const ConvL& L = n->conv[0];
       s.img[j].w = n->params + L.w_off; s.img[j].bias = n->params + L.b_off;
       s.img[j].gw = j < 2 ? s.g[j] + L.w_off : nullptr; s.img[j].gb = j < 2 ? s.g[j] + L.b_off : nullptr;
+      if (j < 2 && s.kind != OPT_SGD) { s.img[j].mw = s.m[j] + L.w_off; s.img[j].mb = s.m[j] + L.b_off; }
+      if (j < 2 && s.kind == OPT_ADAM) { s.img[j].vw = s.v[j] + L.w_off; s.img[j].vb = s.v[j] + L.b_off; }
       s.img[j].rec = reinterpret_cast<unsigned char*>(n->wimg); s.img[j].seg = j < 2 ? j : 0; s.img[j].col = j < 2 ? 0 : 1; s.img[j].nout = kConvOut;
       s.img[j].white = tables_done ? next->white + (long)s.img[j].col * 2 * next_C : nullptr;
     }
@@ -418,6 +445,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     hd.dz3 = c->ws[0].dz[cat]; hd.dz2c = c->ws[0].dz[cat - 1];
     hd.loss_part = d->heads_part;
     hd.w = d->per_w;
+    hd.step_bump = (d->bump_in_heads && d->opt_kind != OPT_SGD && phase == 0) ? (unsigned long long*)d->opt_step : nullptr;
     fused = ddpg_heads_supported(hd);
     // the actors are one layer deeper than the critics' prefix (100-100-50 against 200-50): their last hidden layer joins the
     // heads kernel so that both stacks reach it, and leave it, in the same number of GEMM levels.  CPP_HEADS_PRE=0: GEMMs.
@@ -432,6 +460,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     }
   }
   const int pre = (fused && hd.n1a > 0) ? 1 : 0;
+  d->step_bumped = fused && hd.step_bump != nullptr;
   d->heads_grid = fused ? (B + 3) / 4 : 0; d->heads_B = B;
   d->loss_parts = d->heads_grid; d->loss_B = B;
   int adz, cdz;
@@ -585,6 +614,63 @@ extern "C" int cpp_ddpg_apply_gradients(cpp_ddpg* d, float grad_scale) {
   return apply(d, true, true, grad_scale);
 }
 
+// ddpg_cartpole.py:118-119 and :218 build the two train ops with tf.train.GradientDescentOptimizer; util.py:73-76 is the reference's
+// rule for every other optimiser (tf.train.<name>Optimizer): Momentum and Adam with TensorFlow's semantics, one optimiser per list.
+// Allocates and zeroes the slots (m; v for Adam) over gradbuf's layout, zeroes both step counts, drops the cached graphs.
+extern "C" int cpp_ddpg_set_optimiser(cpp_ddpg* d, int kind, float momentum, float beta1, float beta2, float epsilon) {
+  ARG_CHECK(d, "cpp_ddpg_set_optimiser: NULL argument");
+  ARG_CHECK(kind >= CPP_OPT_SGD && kind <= CPP_OPT_ADAM, "cpp_ddpg_set_optimiser: optimiser %d", kind);
+  ARG_CHECK(kind != CPP_OPT_MOMENTUM || (momentum >= 0.f && momentum < 1e30f), "cpp_ddpg_set_optimiser: momentum %g", (double)momentum);
+  ARG_CHECK(kind != CPP_OPT_ADAM || (beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && epsilon > 0.f && epsilon < 1e30f),
+            "cpp_ddpg_set_optimiser: beta1 %g, beta2 %g (both in [0, 1)), epsilon %g (> 0)", (double)beta1, (double)beta2, (double)epsilon);
+  cpp_ctx* ctx = d->ctx;
+  HIP_CHECK(hipSetDevice(ctx->device));
+  HIP_CHECK(ctx_sync_stream(ctx));
+  const size_t n = (size_t)(d->nA + d->nC);
+  if (kind != CPP_OPT_SGD && !d->opt_m) RC(dalloc(d->arena, &d->opt_m, n));
+  if (kind == CPP_OPT_ADAM && !d->opt_v) RC(dalloc(d->arena, &d->opt_v, n));
+  if (kind != CPP_OPT_SGD && !d->opt_step) RC(dalloc(d->arena, &d->opt_step, (size_t)2));
+  if (d->opt_m) HIP_CHECK(hipMemsetAsync(d->opt_m, 0, n * sizeof(float), ctx->stream));
+  if (d->opt_v) HIP_CHECK(hipMemsetAsync(d->opt_v, 0, n * sizeof(float), ctx->stream));
+  if (d->opt_step) HIP_CHECK(hipMemsetAsync(d->opt_step, 0, 2 * sizeof(uint64_t), ctx->stream));
+  HIP_CHECK(ctx_sync_stream(ctx));
+  d->opt_kind = kind; d->opt_momentum = momentum; d->opt_beta1 = beta1; d->opt_beta2 = beta2; d->opt_epsilon = epsilon;
+  d->step_bumped = false;
+  d->graph_ok = false; d->rgraph_ok = false; d->dgraph_ok = false;      // (the captured launches carry the old rule)
+  drop_half_graphs(d);
+  d->pre_variant = 0;
+  return CPP_OK;
+}
+
+// the slots and the two step counts for checkpoints (util.py:88-90: tf.train.Saver saves the slot variables of both 'optimiser' scopes,
+// ddpg_cartpole.py:118, :218).  n = actor + critic parameters; m / v: the actor's list, then the critic's; v is left alone unless Adam.
+extern "C" int64_t cpp_ddpg_opt_state_size(const cpp_ddpg* d) { return d ? (int64_t)(d->nA + d->nC) : -1; }
+extern "C" int cpp_ddpg_get_opt_state(cpp_ddpg* d, float* m, float* v, int64_t n, uint64_t steps[2]) {
+  ARG_CHECK(d && steps, "cpp_ddpg_get_opt_state: NULL argument");
+  ARG_CHECK(d->opt_kind != OPT_SGD, "cpp_ddpg_get_opt_state: GradientDescent has no slots");
+  ARG_CHECK(n == d->nA + d->nC, "cpp_ddpg_get_opt_state: asked %ld values, the optimisers have %ld", (long)n, d->nA + d->nC);
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  hipStream_t st = d->ctx->stream;
+  if (m) HIP_CHECK(hipMemcpyAsync(m, d->opt_m, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (v && d->opt_kind == OPT_ADAM) HIP_CHECK(hipMemcpyAsync(v, d->opt_v, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(steps, d->opt_step, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(ctx_sync_stream(d->ctx));
+  return CPP_OK;
+}
+extern "C" int cpp_ddpg_set_opt_state(cpp_ddpg* d, const float* m, const float* v, int64_t n, const uint64_t steps[2]) {
+  ARG_CHECK(d && m && steps, "cpp_ddpg_set_opt_state: NULL argument");
+  ARG_CHECK(d->opt_kind != OPT_SGD, "cpp_ddpg_set_opt_state: GradientDescent has no slots");
+  ARG_CHECK(d->opt_kind != OPT_ADAM || v, "cpp_ddpg_set_opt_state: Adam needs v");
+  ARG_CHECK(n == d->nA + d->nC, "cpp_ddpg_set_opt_state: got %ld values, the optimisers have %ld", (long)n, d->nA + d->nC);
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  hipStream_t st = d->ctx->stream;
+  HIP_CHECK(hipMemcpyAsync(d->opt_m, m, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+  if (d->opt_kind == OPT_ADAM) HIP_CHECK(hipMemcpyAsync(d->opt_v, v, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(d->opt_step, steps, 2 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  HIP_CHECK(ctx_sync_stream(d->ctx));
+  return CPP_OK;
+}
+
 extern "C" int cpp_ddpg_update_targets(cpp_ddpg* d) {
   ARG_CHECK(d, "cpp_ddpg_update_targets: NULL argument");
   HIP_CHECK(hipSetDevice(d->ctx->device));
@@ -670,7 +756,10 @@ static int step_body(cpp_ddpg* d, cpp_replay* r, int B, int n_batches, const int
       sr.count = (double)B * (double)(r->elems / Cg); sr.eps = 1e-6; sr.wmax = ctx->white_max_dev;
       ctx->st_ride = &sr; ctx->st_ride_done = false;
     }
+    d->bump_in_heads = true;      // (the apply() below takes both lists)
     const int rc = compute_gradients(d, d->step_batch);
+    d->bump_in_heads = false;
+    if (rc) d->step_bumped = false;
     d->per_hook = nullptr;
     const bool rode = ctx->ride != nullptr && ctx->ride_done;
     const bool tables_done = ctx->st_ride != nullptr && ctx->st_ride_done && rode;
@@ -925,6 +1014,9 @@ extern "C" int cpp_ddpg_average_params(cpp_ddpg* d, cpp_comm* c) {
   NCCL_CHECK(ncclGroupStart());
   for (cpp_net* n : nets)
     NCCL_CHECK(ncclAllReduce(n->params, n->params, (size_t)n->nparams, ncclFloat, ncclAvg, c->comm, d->ctx->stream));
+  // (the optimiser slots meet at their mean too, as rt_naf.cpp's: the step counts are equal on every rank)
+  if (d->opt_kind != OPT_SGD) NCCL_CHECK(ncclAllReduce(d->opt_m, d->opt_m, (size_t)(d->nA + d->nC), ncclFloat, ncclAvg, c->comm, d->ctx->stream));
+  if (d->opt_kind == OPT_ADAM) NCCL_CHECK(ncclAllReduce(d->opt_v, d->opt_v, (size_t)(d->nA + d->nC), ncclFloat, ncclAvg, c->comm, d->ctx->stream));
   NCCL_CHECK(ncclGroupEnd());
   d->dp_local = 0;
   return CPP_OK;

@@ -130,7 +130,43 @@ def build_parser():
     a('--priority-beta-steps', type=int, default=100000,
       help="--prioritized-replay: outer train steps over which beta moves linearly to --priority-beta-final")
     a('--priority-eps', type=float, default=1e-6, help="--prioritized-replay: added to |td| before the exponent")
+    # the update rule of the actor's and the critic's train ops (an extension beyond the reference, whose DDPG is GradientDescent only,
+    # ddpg_cartpole.py:118-119, :218): TensorFlow's Momentum / Adam per list, each with its own slots and step count
+    # (both are absent from the parsed options unless given -- the options of a command line that does not name them are exactly what they
+    # were, key for key; ddpg_optimiser() reads them with their defaults, default_opts() fills them in)
+    a('--ddpg-optimiser', type=str, default=argparse.SUPPRESS, choices=list(DDPG_OPTIMISERS),
+      help="update rule of both DDPG train ops (default GradientDescent); the learning rates stay --actor-learning-rate and "
+           "--critic-learning-rate")
+    a('--ddpg-optimiser-args', type=str, default=argparse.SUPPRESS,
+      help="json object with any of momentum (0.0), beta1 (0.9), beta2 (0.999), epsilon (1e-8) for --ddpg-optimiser")
     return parser
+
+
+DDPG_OPTIMISERS = {"GradientDescent": _lib.CPP_OPT_SGD, "Momentum": _lib.CPP_OPT_MOMENTUM, "Adam": _lib.CPP_OPT_ADAM}
+_DDPG_OPTIMISER_DEFAULTS = {"momentum": 0.0, "beta1": 0.9, "beta2": 0.999, "epsilon": 1e-8}      # tf.train.AdamOptimizer's defaults
+
+
+def ddpg_optimiser(o):
+    """(kind, momentum, beta1, beta2, epsilon) of --ddpg-optimiser / --ddpg-optimiser-args; refuses what cannot be meant."""
+    import json
+    name = getattr(o, "ddpg_optimiser", "GradientDescent")
+    if name not in DDPG_OPTIMISERS:
+        raise SystemExit("--ddpg-optimiser %r is not one of %s" % (name, ", ".join(DDPG_OPTIMISERS)))
+    try:
+        args = json.loads(getattr(o, "ddpg_optimiser_args", None) or "{}")
+    except ValueError as e:
+        raise SystemExit("--ddpg-optimiser-args is not json: %s" % e)
+    if not isinstance(args, dict):
+        raise SystemExit("--ddpg-optimiser-args must be a json object")
+    if "learning_rate" in args:
+        raise SystemExit("--ddpg-optimiser-args takes no learning_rate: the two lists' rates are --actor-learning-rate and "
+                         "--critic-learning-rate")
+    unknown = sorted(set(args) - set(_DDPG_OPTIMISER_DEFAULTS))
+    if unknown:
+        raise SystemExit("--ddpg-optimiser-args: unknown key(s) %s (momentum, beta1, beta2, epsilon)" % ", ".join(unknown))
+    v = dict(_DDPG_OPTIMISER_DEFAULTS)
+    v.update({k: float(x) for k, x in args.items()})
+    return (DDPG_OPTIMISERS[name], v["momentum"], v["beta1"], v["beta2"], v["epsilon"])
 
 
 def priority_beta(o, train_steps):
@@ -152,6 +188,7 @@ def check_prioritized_opts(o):
 
 def default_opts(**overrides):
     o = build_parser().parse_args([])
+    o.ddpg_optimiser, o.ddpg_optimiser_args = "GradientDescent", "{}"
     for k, v in overrides.items():
         assert hasattr(o, k), k
         setattr(o, k, v)
@@ -273,6 +310,12 @@ class _Trainer(object):
         check(lib.cpp_ddpg_create(actor.ctx.handle, actor.handle, critic.handle, target_actor.handle,
                                   target_critic.handle, C.byref(hp), C.byref(h)))
         self._h, self.ctx = h, actor.ctx
+        # (the default rule needs no call: cpp_ddpg_create's trainer is GradientDescent, and stays what it was before the rule could be chosen;
+        # the rule is the one parsed when the critic's train op was declared, not whatever the module's options say by now)
+        rule = getattr(critic, "_optimiser", None) or ddpg_optimiser(opts)
+        self.optimiser_kind = rule[0]
+        if self.optimiser_kind != _lib.CPP_OPT_SGD:
+            check(lib.cpp_ddpg_set_optimiser(h, *rule))
         self.nets = (actor, critic, target_actor, target_critic)
         self.state_elems = int(actor._state_elems)
         self.action_dim = int(actor.action_dim)
@@ -354,6 +397,26 @@ class _Trainer(object):
         check(lib.cpp_ddpg_grad_buffer(self.handle, C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def has_optimiser_slots(self):
+        return self.optimiser_kind != _lib.CPP_OPT_SGD
+
+    def get_optimiser_state(self):
+        """the two optimisers' slot variables {m, v, step} (what tf.train.Saver checkpoints besides the weights, util.py:88-90): m and v
+        hold the actor's list, then the critic's; step = (actor's count, critic's count).  Momentum leaves v zero."""
+        assert self.has_optimiser_slots(), "GradientDescent has no slots"
+        n = int(lib.cpp_ddpg_opt_state_size(self.handle))
+        m, v, step = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(2, np.uint64)
+        check(lib.cpp_ddpg_get_opt_state(self.handle, ptr(m), ptr(v), n, ptr(step)))
+        return {"m": m, "v": v, "step": step}
+
+    def set_optimiser_state(self, state):
+        assert self.has_optimiser_slots(), "GradientDescent has no slots"
+        m = np.ascontiguousarray(state["m"], dtype=np.float32)
+        v = np.ascontiguousarray(state["v"], dtype=np.float32)
+        step = np.ascontiguousarray(np.asarray(state["step"]).reshape(2), dtype=np.uint64)
+        assert len(m) == len(v)
+        check(lib.cpp_ddpg_set_opt_state(self.handle, ptr(m), ptr(v), len(m), ptr(step)))
+
     def close(self):
         if self._h:
             self.flush()
@@ -397,6 +460,7 @@ class CriticNetwork(base_network.Network):
         # bellman: Q(s1, a) = reward + terminal_mask * discount * Q'(s2, A'(s2)); squared TD loss;
         # clip by global norm; SGD (ddpg_cartpole.py:186-218)
         self.target_critic = target_critic
+        self._optimiser = ddpg_optimiser(opts)      # (kind, momentum, beta1, beta2, epsilon) of this train op and the actor's
         self.reward = base_network.Placeholder([None, 1], name="critic_reward")
         self.terminal_mask = base_network.Placeholder([None, 1], name="critic_terminal_mask")
         self.input_state_2 = target_critic.input_state
@@ -488,6 +552,7 @@ class DeepDeterministicPolicyGradientAgent(object):
         # training ops
         self.actor.init_ops_for_training(self.critic)
         self.critic.init_ops_for_training(self.target_critic)
+        self.ddpg_optimiser_kind = self.critic._optimiser[0]      # (util.optimiser_slot_owner: who holds slots is a fact about this agent)
         self.train_steps = 0
 
     def initialise_variables(self, seed=None):

@@ -399,7 +399,8 @@ def sync_replicas_from_rank0(agent, dist, device=None):
     every rank once, as host arrays through torch.distributed (a few MB)."""
     rank = dist.get_rank()
     nets = list(agent.networks())
-    opt_owner = getattr(agent, "naf", None)
+    from . import util
+    opt_owner = util.optimiser_slot_owner(agent)      # (NAF's trainer, or the DDPG trainer under Momentum / Adam)
     payload = [None]
     if rank == 0:
         payload = [{"params": [n.get_params() for n in nets],

@@ -19,7 +19,7 @@ def add_opts(parser):
     parser.add_argument('--print-gradients', action='store_true',
                         help="print the (pre-clip) global l2 norm of each gradient list per train op")
     parser.add_argument('--optimiser', type=str, default="GradientDescent",
-                        help="optimiser name (DDPG ignores it, as in the reference)")
+                        help="optimiser name (DDPG ignores it, as in the reference: its rule is --ddpg-optimiser)")
     parser.add_argument('--optimiser-args', type=str, default="{\"learning_rate\": 0.001}",
                         help="json serialised args for optimiser constructor")
     parser.add_argument('--use-dropout', action='store_true',
@@ -109,6 +109,19 @@ def shape_and_product_of(shape):
     return "%s #%s" % (tuple(shape), int(np.prod(dims)) if dims else 1)
 
 
+def optimiser_slot_owner(agent):
+    """whoever holds the agent's optimiser slot variables, or None: NAF's trainer (`agent.naf`), or the DDPG trainer when its rule is
+    Momentum / Adam (--ddpg-optimiser, recorded on the agent when it was built) -- under GradientDescent there is nothing to keep, and
+    the trainer is not even built for asking."""
+    naf = getattr(agent, "naf", None)
+    if naf is not None:
+        return naf
+    if getattr(agent, "ddpg_optimiser_kind", 0) == 0:
+        return None
+    t = agent.trainer
+    return t if t.has_optimiser_slots() else None
+
+
 class SaverUtil(object):
     """checkpoint save / restore with the behaviour of the reference's util.SaverUtil (util.py:88-131): on start,
     restore the latest checkpoint named in `<dir>/checkpoint` or initialise the variables and save at once;
@@ -116,7 +129,8 @@ class SaverUtil(object):
     checkpointed (util.py:91).  The reference hands a tf.Session to tf.train.Saver; here the first argument is
     the agent (anything with `.networks()` -> [Network] and `.initialise_variables()`), and a checkpoint is one
     `.npz` with the flat f32 buffer of every namespace (variable names and shapes stored alongside and checked
-    on restore) plus, for agents whose optimiser has slot variables (NAF with Momentum / Adam: `agent.naf`), those slots
+    on restore) plus, for agents whose optimiser has slot variables (NAF with Momentum / Adam: `agent.naf`; DDPG with
+    --ddpg-optimiser Momentum / Adam: its trainer, two step counts), those slots
     and the update count -- tf.train.Saver saves them too (util.py:88-90), and a resumed run must not restart Adam's bias
     correction.  The `checkpoint` index file keeps TF's `model_checkpoint_path: "<name>"` line.  Both files are written to
     a temporary name and renamed, so a crash never leaves the index pointing at a partial checkpoint.  The format is this
@@ -144,7 +158,7 @@ class SaverUtil(object):
                 layout = "|".join("%s%s" % (v.name, tuple(v.shape)) for v in net.trainable_model_vars())
                 assert str(data[net.namespace + "::layout"]) == layout, "checkpoint does not match %s" % net.namespace
                 net.set_params(data[net.namespace])
-            opt = getattr(self.agent, "naf", None)
+            opt = optimiser_slot_owner(self.agent)
             if opt is not None and "optimiser::m" in data:
                 opt.set_optimiser_state({"m": data["optimiser::m"], "v": data["optimiser::v"], "step": data["optimiser::step"]})
             elif opt is not None:
@@ -165,7 +179,7 @@ class SaverUtil(object):
             blob[net.namespace] = net.get_params()
             blob[net.namespace + "::layout"] = np.array(
                 "|".join("%s%s" % (v.name, tuple(v.shape)) for v in net.trainable_model_vars()))
-        opt = getattr(self.agent, "naf", None)
+        opt = optimiser_slot_owner(self.agent)
         if opt is not None:
             for k, v in opt.get_optimiser_state().items():
                 blob["optimiser::" + k] = v

@@ -353,6 +353,22 @@ int cpp_ddpg_grad_buffer(cpp_ddpg* ddpg, void** device_ptr, int64_t* n_floats);
 int cpp_ddpg_apply_gradients(cpp_ddpg* ddpg, float grad_scale);
 /* target_actor.update_weights(); target_critic.update_weights() (:336-337). */
 int cpp_ddpg_update_targets(cpp_ddpg* ddpg);
+/* The update rule of the two train ops.  ddpg_cartpole.py:118-119 and :218 build them with tf.train.GradientDescentOptimizer (the
+ * default here, and the only rule until this call); util.py:73-76 is the reference's rule for any other optimiser,
+ * tf.train.<name>Optimizer -- CPP_OPT_MOMENTUM: accum = momentum accum + g, p -= lr accum; CPP_OPT_ADAM: lr_t = lr sqrt(1 - beta2^t) /
+ * (1 - beta1^t), m = beta1 m + (1 - beta1) g, v = beta2 v + (1 - beta2) g^2, p -= lr_t m / (sqrt(v) + epsilon).  g is the list's
+ * gradient after its own global-norm clip (util.py:45-50); the learning rates stay cpp_ddpg_hyper's.  The actor's and the critic's
+ * optimisers are separate (the reference's two 'optimiser' scopes): each list has its own slots and its own step count t, and a call
+ * that applies one list (cpp_ddpg_train_actor, cpp_ddpg_train_critic) advances that list's t only.  The call allocates and zeroes the
+ * slots (actor + critic parameters, the gradient buffer's layout), zeroes both step counts and drops the captured graphs.  Bad kinds
+ * and ranges (momentum < 0, a beta outside [0, 1), epsilon <= 0) are refused. */
+int cpp_ddpg_set_optimiser(cpp_ddpg* ddpg, int kind, float momentum, float beta1, float beta2, float epsilon);
+/* The slot variables tf.train.Saver checkpoints besides the weights (util.py:88-90; the slots of ddpg_cartpole.py:118 and :218's
+ * optimisers): m and v hold the actor's list, then the critic's (n = cpp_ddpg_opt_state_size values each; v only under Adam);
+ * steps[0] is the actor's step count, steps[1] the critic's.  Refused under GradientDescent, which has no slots. */
+int64_t cpp_ddpg_opt_state_size(const cpp_ddpg* ddpg);
+int cpp_ddpg_get_opt_state(cpp_ddpg* ddpg, float* m, float* v, int64_t n, uint64_t steps[2]);
+int cpp_ddpg_set_opt_state(cpp_ddpg* ddpg, const float* m, const float* v, int64_t n, const uint64_t steps[2]);
 /* The whole inner step :331-337 on device-resident replay: n_batches x {sample B, both updates},
  * then the target updates.  idxs: NULL (device Philox, counter advances by one per minibatch) or
  * n_batches*B caller-chosen rows.  Captured into a hipGraph after the first call per (B, n_batches)
