@@ -297,7 +297,7 @@ def naf_path(agent, B, hidden, share):
 def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_size=None, seed=0, graph=True,
                                   atol=1e-5, grad_rel=2e-5, param_rel=2e-6, warm="philox", report_only=False,
                                   fill="noise", f32_twin=False, flip_tol=1e-5, probe=False, before_step=None, pixel=True, hyper=None,
-                                  **pair_kw):
+                                  prepare=None, host_seed=None, **pair_kw):
     """ONE minibatch of the fused inner step (cpp_ddpg_train_step, default kernels: f16-pipe conv1 reading the replay store
     through the sampled slots, bf16-pipe conv2, fused heads, paired launches) -- with graph=True the hipGraph REPLAY of it,
     on rows drawn by the device's Philox sampler -- against oracle.DDPG(float64) on the same rows and the same starting
@@ -306,18 +306,36 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
     pair_kw: make_pair's widths, action size and options (--use-dropout: the oracle draws the device's masks).  probe: one
     profiled minibatch first, report["path"] = ddpg_path().  before_step(): called right before the minibatch that is checked.
     pixel=False: a low-dimensional state of `shape` (no trunk: the pool and ReLU routes are not compared).  hyper: an O.Hyper the
-    device agent and the oracle are both built with (None: the reference's defaults)."""
+    device agent and the oracle are both built with (None: the reference's defaults).  prepare(agent): called on the fresh agent, before
+    anything runs (edge-case parameters).  host_seed: parameters, episodes and (graph=False) rows are host_case(shape, B, 1, host_seed,
+    rows)'s, so that a CPU-only test can compute from the same numbers (tests/test_batchnorm_sensitivity.py).  use_batch_norm=True
+    (pair_kw): the pool codes and ReLU decisions read back are bn_relu_pool_kernel's, the oracle normalises with the batch moments in
+    all four networks.  report["grads"]: the device's two pre-clip lists."""
     import ctypes
     from cartpoleplusplus_amd import _lib
     if hyper is not None:
         pair_kw.update(hyper_options(hyper))
+    case = None
+    if host_seed is not None:
+        case = host_case(shape, B, 1, host_seed, rows=rows, batch_norm=bool(pair_kw.get("use_batch_norm", False)))
+        pair_kw = dict(pair_kw, perturb=False)
     agent, _ref, (aspec, cspec) = make_pair(shape, B, pixel, seed=seed, replay_size=replay_size or rows + 50,
                                            replay_store=replay_store, **pair_kw)
     report = {}
     steps = 0                                             # training-mode forwards before the one checked (dropout masks)
     try:
         rm = agent.replay_memory
-        if fill == "noise":
+        if case is not None:
+            for net, p in zip(agent.networks(), case[1]):
+                assert net.get_params().shape == p.shape
+                net.set_params(p)
+        if prepare is not None:
+            prepare(agent)
+        if case is not None:
+            for ep in case[2]:
+                rm.add_episode(*ep)
+            assert rm.size() == rows
+        elif fill == "noise":
             rm.fill_synthetic(rows, seed=21 + seed)
         else:
             assert fill in ("render", "render-blind", "render-glint"), fill
@@ -341,11 +359,12 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
             idxs = np.empty(B, np.int32)
             _lib.check(_lib.lib.cpp_replay_last_indexes(rm.handle, B, idxs.ctypes.data_as(ctypes.c_void_p)))
         else:
-            idxs = np.random.default_rng(seed + 5).integers(0, rows, B).astype(np.int32)
+            idxs = np.random.default_rng(seed + 5).integers(0, rows, B).astype(np.int32) if case is None else case[3]
             agent.train_step(B, 1, idxs=idxs)             # same launch sequence, eager, caller's rows
         assert idxs.min() >= 0 and idxs.max() < rows and len(np.unique(idxs)) > B // 2
         actions, dq_da, q, td = agent.trainer.last_values(B)
         g_a, g_c = agent.actor.get_grads(), agent.critic.get_grads()
+        report["grads"] = (g_a, g_c)
         stats = agent.trainer.last_stats()
         report["norms"] = (float(stats[1]), float(stats[2]))  # (pre-clip, actor's and critic's lists: which side of a clip they fall on)
         Pn = [n.get_params() for n in nets]
@@ -510,12 +529,13 @@ def delta_bound(theta, d_want, r, nb=1):
     return 2.0 ** -23 * nb * float(np.linalg.norm(np.asarray(theta, np.float64))) + r * float(np.linalg.norm(d_want))
 
 
-def host_case(shape, B, nb, seed, rows=24, action_dim=2):
+def host_case(shape, B, nb, seed, rows=24, action_dim=2, batch_norm=False):
     """specs, starting parameters of the four DDPG networks (xavier + make_pair's perturbations), `rows` transitions as episodes
-    (pixel: codes k / 255 in f16, what the replay store holds exactly) and nb * B row numbers with the minibatches they select."""
+    (pixel: codes k / 255 in f16, what the replay store holds exactly) and nb * B row numbers with the minibatches they select.
+    batch_norm: --use-batch-norm networks (the same numbers: the conv bias slots then hold BatchNorm/beta)."""
     from oracle.replay_np import OracleReplayMemory
     pixel = len(shape) == 5
-    kw = dict(pixel=True, H=shape[0], W=shape[1], C=int(np.prod(shape[2:]))) if pixel else dict(pixel=False, state_elems=int(np.prod(shape)))
+    kw = dict(pixel=True, H=shape[0], W=shape[1], C=int(np.prod(shape[2:])), batch_norm=batch_norm) if pixel else dict(pixel=False, state_elems=int(np.prod(shape)))
     aspec, cspec = O.NetSpec("actor", action_dim, DEFAULT_ACTOR_HIDDEN, **kw), O.NetSpec("critic", action_dim, DEFAULT_ACTOR_HIDDEN, **kw)
     rng = np.random.default_rng(1000 + seed)
     P = []
@@ -598,6 +618,13 @@ ACTOR_LOUD = LOUD._replace(actor_lr=0.1)                   # an actor update as 
 RIDER_CASES = {"LOUD": ((64, 64, 3, 2, 3), 8, 1, LOUD), "ACTOR_LOUD": ((64, 64, 3, 2, 3), 8, 2, ACTOR_LOUD)}      # shape, B, host_case seed, set
 SENS_SHAPE, SENS_B, SENS_SEED = (16, 16, 3, 1, 2), 16, 3
 STALE_TARGET_CASE = ((64, 64, 3, 2, 3), 8, 2)              # shape, B, host_case seed
+# batch-norm cases that tests/test_gpu_batchnorm_training.py runs on the device and tests/test_batchnorm_sensitivity.py plants faults in:
+# shape, B, rows, host_case seed (batch_norm=True)
+BN_B1_CASE = ((16, 16, 3, 1, 2), 1, 24, 41)               # a 2x2 conv3 output: four samples per channel
+BN_B7_CASE = ((64, 64, 3, 1, 2), 7, 24, 42)               # bn_bwd_reduce_kernel's second pass
+BN_PER_CASE = ((32, 32, 3, 2, 3), 8, 200, 1)              # the prioritized-replay case (the device draws its own rows: same shape, B, rows)
+BN_HYPER_CASES = {"16x16x6": ((16, 16, 3, 1, 2), 8, 3), "64x64x18": ((64, 64, 3, 2, 3), 8, 1)}          # shape, B, host_case seed (64x64x18: the first seed
+                                                                                                         # whose float32 twin keeps the float64 routes under all three sets); three minibatches
 NAF_HYPER = dict(discount=0.9, target_update_rate=0.25, clip=0.5)
 NAF_OPTIMISERS = {"momentum-0.5": ("Momentum", {"learning_rate": 0.01, "momentum": 0.5}, 1),       # name, args, warm-up steps
                   "momentum-0.0": ("Momentum", {"learning_rate": 0.01, "momentum": 0.0}, 1),

@@ -23,7 +23,7 @@ VECTORS = ("actor", "critic", "target_actor", "target_critic")
 def _pair_from_host_case(shape, B, nb, seed, hyper, rows=24, fill=True, **kw):
     """a device agent holding host_case's parameters and episodes, and the case itself"""
     from cartpoleplusplus_amd import ddpg_cartpole as D
-    specs, P, episodes, idxs, batches = host_case(shape, B, nb, seed, rows=rows)
+    specs, P, episodes, idxs, batches = host_case(shape, B, nb, seed, rows=rows, batch_norm=bool(kw.get("use_batch_norm", False)))
     agent, _ref, (aspec, _cspec) = make_pair(shape, B, len(shape) == 5, seed=seed, replay_size=rows, perturb=False,
                                              **dict(hyper_options(hyper), **kw))
     try:

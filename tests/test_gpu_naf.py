@@ -275,14 +275,15 @@ def test_cfg4_B256_graph_replayed_naf_step_against_f64_oracle(shape, B, share):
 
 
 def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, probe=False, optimiser="Momentum", optimiser_args=None,
-                                      warm_steps=1, clip=5.0, discount=0.99, target_update_rate=1e-4, report=None, **naf_kw):
+                                      warm_steps=1, clip=5.0, discount=0.99, target_update_rate=1e-4, report=None, grad_rel=2e-5, **naf_kw):
     """cfg4 at the size the metric is quoted on (64x64x18, B = 256, shared trunk, Momentum as in exps/run_93.sh): the hipGraph REPLAY
     of the fused NAF step (naf_cartpole.py:365-373) on rows drawn by the device's sampler against oracle.NAF(float64) started from the
     same parameters and Momentum slots: loss at 1e-5, the pre-clip gradient list per variable at 2e-5 (the trunk's two
     discontinuities -- pool route, ReLU -- taken from the device and accepted only at rounding-level ties), the clipped Momentum
     update and the target update.  Second case: the reference's own defaults (50 x 50 x 6 render, batch 128,
     naf_cartpole.py's three networks on trunks of their own).  naf_kw: make_naf's widths and action size; probe: one profiled
-    minibatch first, its head path (tests.helpers.naf_path) returned."""
+    minibatch first, its head path (tests.helpers.naf_path) returned.  grad_rel: the bar of the gradient list (batch-norm networks:
+    tests/test_gpu_batchnorm.py's 5e-5)."""
     import ctypes
     from cartpoleplusplus_amd import _lib
     from tests.helpers import (device_pool_codes, device_relu_active, naf_path, pool_flips_are_near_ties, relu_flips_are_at_the_boundary)
@@ -337,7 +338,7 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, p
         rflips += relu_flips_are_at_the_boundary(cache, rl, what=what + " trunk")
     assert abs(stats[0] - out["loss"]) < ATOL * max(1.0, abs(out["loss"])) and stats[2] == 0, (stats, out["loss"])
     cat = CatSpec(specs)
-    assert_flat_close(cat, grads, out["grads"], rel=2e-5, what="NAF pre-clip grads vs f64 oracle (flips %d / %d)" % (flips, rflips))
+    assert_flat_close(cat, grads, out["grads"], rel=grad_rel, what="NAF pre-clip grads vs f64 oracle (flips %d / %d)" % (flips, rflips))
     before = ref.flat()
     target_before = ref.target_value.flat()
     norm = ref.apply(out["grads"])

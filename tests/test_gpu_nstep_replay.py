@@ -122,15 +122,17 @@ def test_explicit_n1_is_the_one_step_memory():
         b.close()
 
 
-def _ddpg_nstep_against_f64_oracle(shape, B, rows, pixel=True, seed=0, per=False, atol=1e-5, grad_rel=2e-5, flip_tol=1e-5, hyper=None):
+def _ddpg_nstep_against_f64_oracle(shape, B, rows, pixel=True, seed=0, per=False, atol=1e-5, grad_rel=2e-5, flip_tol=1e-5, hyper=None, **pair_kw):
     """ONE graph-replayed minibatch of the fused DDPG step on an n = 3 memory against oracle.DDPG(float64), unmodified, on the n-step
     columns (reward, terminal_mask, state_2 of the last row walked): actions / Q / TD at `atol`, the pre-clip gradients at `grad_rel`.
     per: a prioritized memory as well -- the critic's gradient against the oracle's backward pass of w * td_dev, and the priorities
-    written from the n-step TD.  hyper: an O.Hyper for the agent and the oracle (None: the defaults)."""
+    written from the n-step TD.  hyper: an O.Hyper for the agent and the oracle (None: the defaults).  pair_kw: make_pair's options
+    (use_batch_norm)."""
     kw = dict(prioritized_replay=True, priority_alpha=0.6, priority_beta=0.4, priority_eps=1e-6) if per else {}
     if hyper is not None:
         from tests.helpers import hyper_options
         kw.update(hyper_options(hyper))
+    kw.update(pair_kw)
     agent, _ref, (aspec, cspec) = make_pair(shape, B, pixel, seed=seed, replay_size=rows + 50, **kw)
     from cartpoleplusplus_amd import ddpg_cartpole as D
     try:

@@ -144,13 +144,16 @@ def test_counter_moves_once_per_augmented_minibatch_and_never_otherwise():
 
 
 # ---- 3. one fused minibatch against the float64 oracles ---------------------------------------------------------------------------
-def _ddpg_shift_against_f64_oracle(shape, B, rows, seed=0, per=False, nstep=1, store="f16", pad=4):
+def _ddpg_shift_against_f64_oracle(shape, B, rows, seed=0, per=False, nstep=1, store="f16", pad=4, grad_rel=None, **pair_kw):
     """ONE graph-replayed minibatch of the fused DDPG step on a memory with random shift on against oracle.DDPG(float64), unmodified,
     fed the shifted minibatch rebuilt on the host: actions / Q / TD at ATOL, the pre-clip gradients at GRAD_REL; the same oracle fed
-    the stored (unshifted) pixels must miss the device's Q by more than 100 x ATOL."""
+    the stored (unshifted) pixels must miss the device's Q by more than 100 x ATOL.  grad_rel (None: GRAD_REL), pair_kw: the bar of the
+    gradient lists and make_pair's options for other networks (use_batch_norm)."""
+    grad_rel = GRAD_REL if grad_rel is None else grad_rel
     from cartpoleplusplus_amd import ddpg_cartpole as D
     from tests import per_np as P
     kw = dict(prioritized_replay=True, priority_alpha=0.6, priority_beta=0.4, priority_eps=1e-6) if per else {}
+    kw.update(pair_kw)
     agent, _ref, (aspec, cspec) = make_pair(shape, B, True, seed=seed, replay_size=rows + 50, replay_store=store, **kw)
     try:
         rm = agent.replay_memory
@@ -191,12 +194,12 @@ def _ddpg_shift_against_f64_oracle(shape, B, rows, seed=0, per=False, nstep=1, s
     print("random shift vs f64 oracle: |actions| %.2e |q| %.2e |td| %.2e; unshifted oracle misses q by %.2e" % (err + (miss,)))
     assert max(err) < ATOL, err
     assert miss > 100 * ATOL, miss
-    assert_flat_close(aspec, g_a, ag["grads"], rel=GRAD_REL, what="actor pre-clip grads vs f64 oracle (random shift)")
+    assert_flat_close(aspec, g_a, ag["grads"], rel=grad_rel, what="actor pre-clip grads vs f64 oracle (random shift)")
     if per:
         cw = ref.critic_gradients(t, td_override=w.astype(np.float64).reshape(-1, 1) * td.astype(np.float64))
-        assert_flat_close(cspec, g_c, cw["grads"], rel=GRAD_REL, what="weighted critic pre-clip grads vs f64 oracle (random shift)")
+        assert_flat_close(cspec, g_c, cw["grads"], rel=grad_rel, what="weighted critic pre-clip grads vs f64 oracle (random shift)")
     else:
-        assert_flat_close(cspec, g_c, cg["grads"], rel=GRAD_REL, what="critic pre-clip grads vs f64 oracle (random shift)")
+        assert_flat_close(cspec, g_c, cg["grads"], rel=grad_rel, what="critic pre-clip grads vs f64 oracle (random shift)")
 
 
 def test_shifted_fused_step_against_f64_oracle_cfg3():
