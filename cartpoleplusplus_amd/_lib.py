@@ -128,6 +128,8 @@ SIGNATURES = {
     "cpp_ddpg_apply_gradients": (_I, [_P, _F]),
     "cpp_ddpg_update_targets": (_I, [_P]),
     "cpp_ddpg_set_optimiser": (_I, [_P, _I, _F, _F, _F, _F]),
+    "cpp_ddpg_set_target_smoothing": (_I, [_P, _F, _F, _U64]),
+    "cpp_ddpg_last_target_noise": (_I, [_P, _I, _P, C.POINTER(_U64)]),
     "cpp_ddpg_opt_state_size": (_L, [_P]),
     "cpp_ddpg_get_opt_state": (_I, [_P, _P, _P, _L, _P]),
     "cpp_ddpg_set_opt_state": (_I, [_P, _P, _P, _L, _P]),

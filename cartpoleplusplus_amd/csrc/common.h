@@ -406,6 +406,9 @@ struct OptSegs {
   long img_skip[OPT_MAX_SEGS];   // leading parameters of a segment (conv1's weights and biases) that its image workgroup updates itself
   struct { float* w; float* bias; const float* gw; const float* gb; unsigned char* rec; int seg, col, nout;
            const float* white; float* mw; float* mb; float* vw; float* vb; } img[4];      // mw / mb: the Momentum slots of those parameters (OPT_MOMENTUM), Adam's first moments (OPT_ADAM); vw / vb: Adam's second moments      // white != nullptr: the column's table is already in memory (the dW reductions' launch computed it)
+  // optional, appended (every argument above keeps its offset): a second counter this launch advances by one -- target policy
+  // smoothing's count of gradient passes, which the pass in front has read and nobody in this launch does
+  uint64_t* bump2;
 };
 // the SGD update of one parameter, p - lr * (g * scale), with its roundings pinned (one product, one fused multiply-add): opt_apply_kernel
 // writes it, the conv1 image rider of the same launch recomputes it, and both must hold the same bits whatever the compiler contracts
@@ -440,6 +443,28 @@ int launch_opt_apply(cpp_ctx* ctx, const OptSegs& s, float grad_scale, float cli
 int launch_soft_update(cpp_ctx* ctx, float* t0, const float* s0, long n0, float* t1, const float* s1,
                        long n1, float coeff);
 
+// Target policy smoothing (TD3: Fujimoto et al. 2018, section 5.3; an extension of the target of ddpg_cartpole.py:199-209): the target
+// critic reads a' = clamp(mu'(s2) + clamp(sigma z, -c, c), -1, 1) with z ~ N(0, 1), a fresh draw per row and component in every
+// minibatch.  z is Box-Muller on two 24-bit uniforms of philox4x32_10({row, 0x100 + component, n_lo, n_hi}, seed) -- words 0..3 in that
+// place are the sampler's, prioritized replay's and the random shift's -- where n counts the target-forming gradient passes since the
+// feature was configured: a device word, so that a replayed graph draws fresh noise.  The launch that reads n never writes it.
+struct TpsArgs {
+  const unsigned long long* n;                     // nullptr: off
+  float sigma, clip; unsigned seed_lo, seed_hi;
+  float* eps;                                      // [B][A]: the clipped noise, kept for inspection (cpp_ddpg_last_target_noise)
+  unsigned long long* n_out;                       // the count the noise was drawn at
+};
+__device__ __forceinline__ float tps_noise(const TpsArgs& s, unsigned long long n, unsigned row, unsigned comp) {
+  const u32x4 r = philox4x32_10(u32x4{row, 0x100u + comp, (uint32_t)n, (uint32_t)(n >> 32)}, s.seed_lo, s.seed_hi);
+  const float u1 = (float)((r.x >> 8) + 1u) * 0x1p-24f;      // (0, 1]: exact
+  const float u2 = (float)(r.y >> 8) * 0x1p-24f;             // [0, 1): exact
+  const float z = sqrtf(-2.f * logf(u1)) * cospif(2.f * u2); // the accurate logf / cospif: |z| <= 5.77
+  return fminf(fmaxf(s.sigma * z, -s.clip), s.clip);
+}
+__device__ __forceinline__ float tps_apply(float a, float eps) { return fminf(fmaxf(a + eps, -1.f), 1.f); }
+// the GEMM-level path's form: out[b][i] = tps_apply(in[b][i], noise) over B x A columns (row strides ld_in, ld_out; in == out is fine)
+int launch_tps_smooth(cpp_ctx* ctx, const TpsArgs& s, const float* in, int ld_in, float* out, int ld_out, int B, int A);
+
 // fused DDPG heads (heads.hip): actor heads, the critic's concat layer + q on three inputs, TD, dQ/da, one backward layer
 struct DdpgHeadsArgs {
   int B, A; float discount;
@@ -463,6 +488,9 @@ struct DdpgHeadsArgs {
   const float* w;
   // optional: the two optimisers' step counters (Momentum / Adam: rt_ddpg.cpp), both += 1 -- nobody reads them before the optimiser's launch
   unsigned long long* step_bump;
+  // optional (tps.n != nullptr: the SMOOTH instances, which alone read it): target policy smoothing of the target actor's action.
+  // Appended: every argument above keeps its offset, the instances without it their instructions.
+  TpsArgs tps;
 };
 #define DDPG_HEADS_MAX_WGS 256
 size_t ddpg_heads_lds_bytes(const DdpgHeadsArgs& h);

@@ -47,7 +47,10 @@ __device__ __forceinline__ float team_sum(float v) {
 // AT: compile-time bound of the action loops; EXACT: A == AT (the loops then carry no branches that keep the compiler from
 // batching their LDS reads and interleaving the team sums)
 // WEIGHTED: prioritized replay's importance weight of the row scales its loss term and dz_q (the uniform instances never read h.w)
-template <int AT, bool EXACT, bool WEIGHTED>
+// SMOOTH: target policy smoothing (common.h, TpsArgs): the target critic reads a' + clipped noise, clamped to [-1, 1].  Lane t of a
+// team draws component t of its row (one Philox call, one logf, one cospif per wave), the team reads the A values by lane
+// broadcast; the instances without it never read h.tps and are, instruction for instruction, what they were before it existed
+template <int AT, bool EXACT, bool WEIGHTED, bool SMOOTH>
 __global__ __launch_bounds__(HEADS_THREADS) void ddpg_heads_kernel(const DdpgHeadsArgs h) {
   extern __shared__ __attribute__((aligned(16))) float hl[];
   constexpr int N3P = HEADS_N3P;
@@ -124,6 +127,8 @@ __global__ __launch_bounds__(HEADS_THREADS) void ddpg_heads_kernel(const DdpgHea
   for (int i = 0; i < AT; ++i) abv[i] = (rv && i < A) ? h.act[(long)row * A + i] : 0.f;
   const float rrow = rv ? h.r[row] : 0.f, mrow = rv ? h.mask[row] : 0.f;
   const float wrow = (WEIGHTED && rv) ? h.w[row] : 1.f;
+  unsigned long long tps_n = 0ull;
+  if (SMOOTH) tps_n = h.tps.n[0];                      // (read only: the count moves in a later launch of the pass)
   static_assert(N3P + 1 <= HEADS_THREADS, "one q-layer weight per thread");
   const float wq_a = tid < n3 ? h.wq[tid] : (tid == N3P ? h.wq[n3] : 0.f), wqt_a = tid < n3 ? h.wq_t[tid] : (tid == N3P ? h.wq_t[n3] : 0.f);
   float wov[2], wotv[2];                               // (n2a + 1) * A <= 2 * 256
@@ -184,6 +189,15 @@ __global__ __launch_bounds__(HEADS_THREADS) void ddpg_heads_kernel(const DdpgHea
       at[i] = tanhf(team_sum(st) + Wot[n2a * A + i]);
       ab[i] = abv[i];
     }
+  }
+  if (SMOOTH) {
+    // lanes >= A draw values nobody reads (a wave's instruction either way); the count is uniform, the row is the team's
+    const float e = tps_noise(h.tps, tps_n, (unsigned)row, (unsigned)t);
+    if (rv && t < A) h.tps.eps[(long)row * A + t] = e;
+    if (tid == 0 && blockIdx.x == 0) h.tps.n_out[0] = tps_n;
+#pragma unroll
+    for (int i = 0; i < AT; ++i)
+      if (i < A) at[i] = tps_apply(at[i], __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), i)));
   }
   HCK();
   // ---- concat layer of the critic: three evaluations sharing the state part; lane t owns unit t; q, q'; dQ/da
@@ -303,12 +317,12 @@ bool ddpg_heads_supported(const DdpgHeadsArgs& h) {
 int launch_ddpg_heads(cpp_ctx* ctx, const DdpgHeadsArgs& h) {
   const size_t lds = ddpg_heads_lds_bytes(h);
   typedef void (*kern_t)(const DdpgHeadsArgs);
-  static const kern_t kerns[12] = {ddpg_heads_kernel<1, true, false>, ddpg_heads_kernel<2, true, false>, ddpg_heads_kernel<4, true, false>,
-                                   ddpg_heads_kernel<8, true, false>, ddpg_heads_kernel<4, false, false>, ddpg_heads_kernel<8, false, false>,
-                                   ddpg_heads_kernel<1, true, true>, ddpg_heads_kernel<2, true, true>, ddpg_heads_kernel<4, true, true>,
-                                   ddpg_heads_kernel<8, true, true>, ddpg_heads_kernel<4, false, true>, ddpg_heads_kernel<8, false, true>};
-  const int ki = (h.A == 1 ? 0 : h.A == 2 ? 1 : h.A == 4 ? 2 : h.A == 8 ? 3 : h.A == 3 ? 4 : 5) + (h.w ? 6 : 0);
-  static size_t attr[CPP_MAX_DEVICES][12] = {};      // (kernel attributes are per device)
+#define HEADS_SIX(W, S) ddpg_heads_kernel<1, true, W, S>, ddpg_heads_kernel<2, true, W, S>, ddpg_heads_kernel<4, true, W, S>, \
+                        ddpg_heads_kernel<8, true, W, S>, ddpg_heads_kernel<4, false, W, S>, ddpg_heads_kernel<8, false, W, S>
+  static const kern_t kerns[24] = {HEADS_SIX(false, false), HEADS_SIX(true, false), HEADS_SIX(false, true), HEADS_SIX(true, true)};
+#undef HEADS_SIX
+  const int ki = (h.A == 1 ? 0 : h.A == 2 ? 1 : h.A == 4 ? 2 : h.A == 8 ? 3 : h.A == 3 ? 4 : 5) + (h.w ? 6 : 0) + (h.tps.n ? 12 : 0);
+  static size_t attr[CPP_MAX_DEVICES][24] = {};      // (kernel attributes are per device)
   size_t& have = attr[cpp_dev_slot(ctx)][ki];
   if (lds > have) {
     HIP_CHECK(hipFuncSetAttribute((const void*)kerns[ki], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -318,5 +332,26 @@ int launch_ddpg_heads(cpp_ctx* ctx, const DdpgHeadsArgs& h) {
   hipLaunchKernelGGL(kerns[ki], dim3((h.B + HEADS_ROWS - 1) / HEADS_ROWS), dim3(HEADS_THREADS), lds, ctx->stream, h);
   LAUNCH_CHECK();
   prof_end(ctx, K_HEADS);
+  return 0;
+}
+
+// ---- target policy smoothing where the heads kernel does not run (GEMM levels: A > 8, wide or low-dimensional stacks; the single
+// train ops): the same function over the B x A action columns the target critic is about to read
+__global__ __launch_bounds__(256) void tps_smooth_kernel(const TpsArgs s, const float* __restrict__ in, int ld_in, float* out, int ld_out, int B, int A) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i >= B * A) return;
+  const unsigned long long n = s.n[0];                 // (read only, as in the heads kernel)
+  const int b = i / A, c = i - b * A;
+  const float e = tps_noise(s, n, (unsigned)b, (unsigned)c);
+  s.eps[i] = e;
+  out[(long)b * ld_out + c] = tps_apply(in[(long)b * ld_in + c], e);
+  if (i == 0) s.n_out[0] = n;
+}
+
+int launch_tps_smooth(cpp_ctx* ctx, const TpsArgs& s, const float* in, int ld_in, float* out, int ld_out, int B, int A) {
+  prof_begin(ctx);
+  hipLaunchKernelGGL(tps_smooth_kernel, dim3((B * A + 255) / 256), dim3(256), 0, ctx->stream, s, in, ld_in, out, ld_out, B, A);
+  LAUNCH_CHECK();
+  prof_end(ctx, K_ELEMENTWISE);
   return 0;
 }

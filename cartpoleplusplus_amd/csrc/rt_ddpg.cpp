@@ -43,6 +43,11 @@ struct cpp_ddpg {
   float *opt_m, *opt_v; uint64_t* opt_step;
   bool bump_in_heads;      // step_body: the gradient pass in front of an apply() of both lists advances both counts in its heads kernel ...
   bool step_bumped;        // ... and has (the next apply must not)
+  // target policy smoothing (cpp_ddpg_set_target_smoothing; common.h: TpsArgs).  tps_n[0]: the count of target-forming gradient passes (a
+  // device word: captured graphs replay it), tps_n[1]: the count the last pass drew at; tps_eps: its clipped noise, maxB x A;
+  // tps_act: the smoothed action of the single train op (cpp_ddpg_train_critic), maxB x A
+  bool tps_on; float tps_sigma, tps_clip; uint64_t tps_seed; uint64_t* tps_n; float *tps_eps, *tps_act;
+  bool tps_pending;        // a pass has read tps_n[0] and its increment is still owed: the apply() behind it carries it, or tps_settle()
   Arena arena;
 };
 
@@ -71,6 +76,7 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   d->per_w = nullptr;
   d->opt_kind = OPT_SGD; d->opt_momentum = 0.f; d->opt_beta1 = 0.9f; d->opt_beta2 = 0.999f; d->opt_epsilon = 1e-8f;
   d->opt_m = d->opt_v = nullptr; d->opt_step = nullptr; d->bump_in_heads = d->step_bumped = false;
+  d->tps_on = d->tps_pending = false; d->tps_sigma = d->tps_clip = 0.f; d->tps_seed = 0; d->tps_n = nullptr; d->tps_eps = d->tps_act = nullptr;
   const int A = actor->spec.action_dim;
   int rc = dalloc(d->arena, &d->gradbuf, (size_t)(d->nA + d->nC));
   if (!rc) rc = dalloc(d->arena, &d->dq_da, (size_t)d->maxB * A);
@@ -135,6 +141,22 @@ static int check_batch(cpp_ddpg* d, cpp_batch* b, const char* who) {
   ARG_CHECK(b->B >= 1 && b->B <= d->maxB, "%s: batch size %d outside [1,%d]", who, b->B, d->maxB);
   ARG_CHECK(b->elems == d->actor->state_elems && b->A == d->actor->spec.action_dim, "%s: batch shape does not match the networks", who);
   return CPP_OK;
+}
+
+static TpsArgs tps_args(const cpp_ddpg* d) {
+  TpsArgs t; memset(&t, 0, sizeof(t));
+  if (!d->tps_on) return t;
+  t.n = (const unsigned long long*)d->tps_n; t.n_out = (unsigned long long*)(d->tps_n + 1); t.eps = d->tps_eps;
+  t.sigma = d->tps_sigma; t.clip = d->tps_clip; t.seed_lo = (unsigned)d->tps_seed; t.seed_hi = (unsigned)(d->tps_seed >> 32);
+  return t;
+}
+// the increment of a target-forming pass that no apply() follows (cpp_ddpg_compute_gradients, the half steps): a launch of its own
+// behind the pass -- only with smoothing on
+static int tps_settle(cpp_ddpg* d, int rc) {
+  const bool owed = d->tps_pending;
+  d->tps_pending = false;
+  if (rc) return rc;
+  return owed ? launch_counter_add(d->ctx, d->tps_n, 1) : CPP_OK;
 }
 
 const float* white_of(cpp_batch* b, int which, int C) { return b->white + (long)which * 2 * C; }
@@ -213,7 +235,14 @@ static int critic_gradients_impl(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_d
   RC(net_forward_trunk(ta, ta->ws[0], b->s[1], b->dtype, w2, B));
   RC(net_forward_fc(ta, ta->ws[0], 0, B, nullptr));
   RC(critic_prefix(tc, b->s[1], b->dtype, w2, B));
-  RC(critic_head(tc, 0, ta->ws[0].out, B));
+  const float* tact = ta->ws[0].out;
+  if (backward && d->tps_on) {      // (the train op only: check_loss is an evaluation and draws nothing)
+    const int A = ta->spec.action_dim;
+    RC(launch_tps_smooth(d->ctx, tps_args(d), tact, A, d->tps_act, A, B, A));
+    tact = d->tps_act;
+    d->tps_pending = true;
+  }
+  RC(critic_head(tc, 0, tact, B));
   if (!critic_prefix_done) RC(critic_prefix(c, b->s[0], b->dtype, w1, B));
   RC(critic_head(c, 0, b->a, B));
   const int last = (int)c->fc.size() - 1;
@@ -232,6 +261,7 @@ static int apply(cpp_ddpg* d, bool do_actor, bool do_critic, float grad_scale, u
                  const cpp_batch* next = nullptr, int next_B = 0, int next_C = 0, long elems = 0, bool tables_done = false) {
   OptSegs s; memset(&s, 0, sizeof(s));
   s.bump = bump;
+  if (d->tps_pending) { s.bump2 = d->tps_n; d->tps_pending = false; }      // (the pass in front read the count; nobody in this launch does)
   if (d->targets_in_apply && !next && do_actor && do_critic) {      // (the outer step's last launch: both target updates leave with it)
     s.tgt[0] = d->tactor->params; s.tgt[1] = d->tcritic->params; s.tgt_coeff = d->hp.target_update_rate;
     d->tactor->wimg_key = nullptr; d->tcritic->wimg_key = nullptr;
@@ -321,7 +351,8 @@ extern "C" int cpp_ddpg_train_critic(cpp_ddpg* d, cpp_batch* b) {
   RC(check_batch(d, b, "cpp_ddpg_train_critic"));
   HIP_CHECK(hipSetDevice(d->ctx->device));
   RC(prep_batch(d, b));
-  RC(critic_gradients(d, b, false, true));
+  const int rc = critic_gradients(d, b, false, true);
+  if (rc) { d->tps_pending = false; return rc; }
   RC(apply(d, false, true, 1.0f));
   return CPP_OK;
 }
@@ -446,6 +477,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     hd.loss_part = d->heads_part;
     hd.w = d->per_w;
     hd.step_bump = (d->bump_in_heads && d->opt_kind != OPT_SGD && phase == 0) ? (unsigned long long*)d->opt_step : nullptr;
+    hd.tps = tps_args(d);
     fused = ddpg_heads_supported(hd);
     // the actors are one layer deeper than the critics' prefix (100-100-50 against 200-50): their last hidden layer joins the
     // heads kernel so that both stacks reach it, and leave it, in the same number of GEMM levels.  CPP_HEADS_PRE=0: GEMMs.
@@ -531,11 +563,19 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   }
   if (cat == 0)     // low-dim critic: the "prefix" is the converted state itself
     cP = G.fn([=] { return launch_copy_cols(ctx, c->ws[1].fcin[0], ldcat, 0, c->ws[0].fcin[0], ldcat, 0, Lcat.n_in - A, B); }, {tC});
+  // target policy smoothing: the target actor's action in the target critic's splice columns, between the GEMM that wrote it and the
+  // concat GEMM that reads it (ta->ws[0].out keeps the unsmoothed action)
+  int taS = taF;
+  if (d->tps_on) {
+    const TpsArgs ts = tps_args(d);
+    float* col = tc->ws[0].fcin[cat] + (Lcat.n_in - A);
+    taS = G.fn([=] { return launch_tps_smooth(ctx, ts, col, (int)ldcat, col, (int)ldcat, B, A); }, {taF});
+  }
   int c1 = -1, c0 = -1, tcH = -1;
   for (int l = cat; l < nc; ++l) {
     c1 = G.gemm(fc_fwd_args(c, c->ws[1], l, B), {l == cat ? cP : c1, l == cat ? aF : -1});
     c0 = G.gemm(fc_fwd_args(c, c->ws[0], l, B), {l == cat ? cP : c0, l == cat ? cb : -1, l == cat ? tC : -1});
-    tcH = G.gemm(fc_fwd_args(tc, tc->ws[0], l, B), {l == cat ? tcP : tcH, l == cat ? taF : -1});
+    tcH = G.gemm(fc_fwd_args(tc, tc->ws[0], l, B), {l == cat ? tcP : tcH, l == cat ? taS : -1});
   }
 
   // ---- dQ/da at a = actor(s1): back through q_value .. splice on the second evaluation (dz of q is 1)
@@ -586,6 +626,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     conv_bwd = G.fn([=] { return nets_backward_conv(ctx, bn, 2, B, s1, dt, w1); }, {adz, cdz});
   }
   DwPendingGuard pending(ctx);      // (a failure below drops what was queued)
+  if (d->tps_on && phase != 2) d->tps_pending = true;      // (this pass reads the count: exactly one increment follows it)
   if (phase == 2) {
     if (conv_bwd >= 0) RC(G.ops[conv_bwd].fn());
     return flush_dw_reduce(ctx);
@@ -599,7 +640,7 @@ extern "C" int cpp_ddpg_compute_gradients(cpp_ddpg* d, cpp_batch* b) {
   RC(check_batch(d, b, "cpp_ddpg_compute_gradients"));
   HIP_CHECK(hipSetDevice(d->ctx->device));
   RC(prep_batch(d, b));
-  return compute_gradients(d, b);
+  return tps_settle(d, compute_gradients(d, b));
 }
 
 extern "C" int cpp_ddpg_grad_buffer(cpp_ddpg* d, void** p, int64_t* n) {
@@ -639,6 +680,43 @@ extern "C" int cpp_ddpg_set_optimiser(cpp_ddpg* d, int kind, float momentum, flo
   d->graph_ok = false; d->rgraph_ok = false; d->dgraph_ok = false;      // (the captured launches carry the old rule)
   drop_half_graphs(d);
   d->pre_variant = 0;
+  return CPP_OK;
+}
+
+// Target policy smoothing of the critic's target (an extension of ddpg_cartpole.py:199-209; include/cartpolepp_abi.h).  sigma, clip and
+// the seed are captured by value: the call drops the cached graphs, and it zeroes the count.
+extern "C" int cpp_ddpg_set_target_smoothing(cpp_ddpg* d, float sigma, float clip, uint64_t seed) {
+  ARG_CHECK(d, "cpp_ddpg_set_target_smoothing: NULL argument");
+  ARG_CHECK(sigma >= 0.f && sigma < 1e30f && clip >= 0.f && clip < 1e30f, "cpp_ddpg_set_target_smoothing: sigma %g, clip %g (both finite, >= 0)",
+            (double)sigma, (double)clip);
+  ARG_CHECK(!(sigma > 0.f && clip == 0.f), "cpp_ddpg_set_target_smoothing: sigma %g with clip 0 (the noise would be clipped away)", (double)sigma);
+  ARG_CHECK(!(sigma == 0.f && clip > 0.f), "cpp_ddpg_set_target_smoothing: clip %g without a noise (sigma 0, clip 0 switches smoothing off)", (double)clip);
+  cpp_ctx* ctx = d->ctx;
+  HIP_CHECK(hipSetDevice(ctx->device));
+  HIP_CHECK(ctx_sync_stream(ctx));
+  const size_t n = (size_t)d->maxB * d->actor->spec.action_dim;
+  if (sigma > 0.f && !d->tps_n) RC(dalloc(d->arena, &d->tps_n, (size_t)2));
+  if (sigma > 0.f && !d->tps_eps) RC(dalloc(d->arena, &d->tps_eps, n));
+  if (sigma > 0.f && !d->tps_act) RC(dalloc(d->arena, &d->tps_act, n));
+  if (d->tps_n) HIP_CHECK(hipMemsetAsync(d->tps_n, 0, 2 * sizeof(uint64_t), ctx->stream));
+  if (d->tps_eps) HIP_CHECK(hipMemsetAsync(d->tps_eps, 0, n * sizeof(float), ctx->stream));
+  HIP_CHECK(ctx_sync_stream(ctx));
+  d->tps_on = sigma > 0.f; d->tps_sigma = sigma; d->tps_clip = clip; d->tps_seed = seed; d->tps_pending = false;
+  d->graph_ok = false; d->rgraph_ok = false; d->dgraph_ok = false;      // (the captured launches carry the old values, or none)
+  drop_half_graphs(d);
+  d->pre_variant = 0;
+  return CPP_OK;
+}
+
+extern "C" int cpp_ddpg_last_target_noise(cpp_ddpg* d, int B, float* eps, uint64_t* n) {
+  ARG_CHECK(d, "cpp_ddpg_last_target_noise: NULL argument");
+  ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_target_noise: batch %d outside [1,%d]", B, d->maxB);
+  if (!d->tps_on) { cpp_set_error("cpp_ddpg_last_target_noise: target policy smoothing is off"); return CPP_ERR_STATE; }
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  hipStream_t st = d->ctx->stream;
+  if (eps) HIP_CHECK(hipMemcpyAsync(eps, d->tps_eps, (size_t)B * d->actor->spec.action_dim * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (n) HIP_CHECK(hipMemcpyAsync(n, d->tps_n + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(ctx_sync_stream(d->ctx));
   return CPP_OK;
 }
 
@@ -759,7 +837,7 @@ static int step_body(cpp_ddpg* d, cpp_replay* r, int B, int n_batches, const int
     d->bump_in_heads = true;      // (the apply() below takes both lists)
     const int rc = compute_gradients(d, d->step_batch);
     d->bump_in_heads = false;
-    if (rc) d->step_bumped = false;
+    if (rc) { d->step_bumped = false; d->tps_pending = false; }
     d->per_hook = nullptr;
     const bool rode = ctx->ride != nullptr && ctx->ride_done;
     const bool tables_done = ctx->st_ride != nullptr && ctx->st_ride_done && rode;
@@ -891,13 +969,13 @@ static int half_step_body(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed, int 
     RC(replay_sample_finish(r, B, Cg, C, b, r->counter, &bumped));
     if (!bumped) RC(launch_counter_add(ctx, r->counter, 1));
   }
-  if (phase == 1) return compute_gradients(d, b, 1);
+  if (phase == 1) return tps_settle(d, compute_gradients(d, b, 1));
   const bool ride_ok = !no_ride && direct && Cg > 0 && r->store_dtype == CPP_F16;
   if (ride_ok) {
     ga.out_slot[0] = b->slot_alt[0]; ga.out_slot[1] = b->slot_alt[1];
     ctx->ride = &ga; ctx->ride_done = false; ctx->ride_dtype = r->store_dtype; ctx->ride_at_dw = true;
   }
-  const int rc = compute_gradients(d, b, phase);
+  const int rc = tps_settle(d, compute_gradients(d, b, phase));      // (phase 2 reads no count and owes nothing)
   const bool rode = ctx->ride != nullptr && ctx->ride_done;
   ctx->ride = nullptr;
   *next = rode ? (cur == 0 ? 1 : 2) : 0;

@@ -139,6 +139,15 @@ def build_parser():
            "--critic-learning-rate")
     a('--ddpg-optimiser-args', type=str, default=argparse.SUPPRESS,
       help="json object with any of momentum (0.0), beta1 (0.9), beta2 (0.999), epsilon (1e-8) for --ddpg-optimiser")
+    # target policy smoothing of the critic's target (an extension beyond the reference, ddpg_cartpole.py:199-209: TD3, Fujimoto et al.
+    # 2018; DrQ-v2's critic target): a' = clip(mu'(s2) + clip(N(0, sigma^2), -c, c), -1, 1), drawn on the device per row and component
+    # (absent from the parsed options unless given, like --ddpg-optimiser; target_policy_smoothing() reads them with their defaults)
+    a('--target-policy-noise', type=float, default=argparse.SUPPRESS,
+      help="standard deviation sigma of the noise added to the target actor's action in the critic's target (default 0: none)")
+    a('--target-policy-noise-clip', type=float, default=argparse.SUPPRESS,
+      help="--target-policy-noise: the noise is clipped to +- this (default 0.5)")
+    a('--target-policy-noise-seed', type=int, default=argparse.SUPPRESS,
+      help="--target-policy-noise: seed of the device's noise stream (default 0)")
     return parser
 
 
@@ -169,6 +178,35 @@ def ddpg_optimiser(o):
     return (DDPG_OPTIMISERS[name], v["momentum"], v["beta1"], v["beta2"], v["epsilon"])
 
 
+_TARGET_SMOOTHING_DEFAULTS = (0.0, 0.5, 0)      # sigma, clip, seed
+
+
+def target_policy_smoothing(o):
+    """(sigma, clip, seed) of --target-policy-noise / -clip / -seed; refuses what cannot be meant.  sigma == 0: off."""
+    import math
+    given_clip, given_seed = hasattr(o, "target_policy_noise_clip"), hasattr(o, "target_policy_noise_seed")
+    try:
+        sigma = float(getattr(o, "target_policy_noise", _TARGET_SMOOTHING_DEFAULTS[0]))
+        clip = float(getattr(o, "target_policy_noise_clip", _TARGET_SMOOTHING_DEFAULTS[1]))
+        seed = int(getattr(o, "target_policy_noise_seed", _TARGET_SMOOTHING_DEFAULTS[2]))
+    except (TypeError, ValueError) as e:
+        raise SystemExit("--target-policy-noise: %s" % e)
+    if not math.isfinite(sigma) or sigma < 0.0:
+        raise SystemExit("--target-policy-noise %r is not a finite standard deviation >= 0" % sigma)
+    if not math.isfinite(clip) or clip < 0.0:
+        raise SystemExit("--target-policy-noise-clip %r is not a finite bound >= 0" % clip)
+    if not 0 <= seed < 2 ** 64:
+        raise SystemExit("--target-policy-noise-seed %r is not in [0, 2^64)" % seed)
+    if sigma == 0.0:
+        # (default_opts() fills the defaults in: a clip or seed that IS the default says nothing)
+        if (given_clip and clip != _TARGET_SMOOTHING_DEFAULTS[1]) or (given_seed and seed != _TARGET_SMOOTHING_DEFAULTS[2]):
+            raise SystemExit("--target-policy-noise-clip / --target-policy-noise-seed need a noise: give --target-policy-noise SIGMA")
+        return (0.0, clip, seed)
+    if clip == 0.0:
+        raise SystemExit("--target-policy-noise %g with --target-policy-noise-clip 0 would clip the noise away" % sigma)
+    return (sigma, clip, seed)
+
+
 def priority_beta(o, train_steps):
     """beta of the outer train step `train_steps` (linear from --priority-beta to --priority-beta-final)"""
     n = max(1, int(o.priority_beta_steps))
@@ -189,6 +227,7 @@ def check_prioritized_opts(o):
 def default_opts(**overrides):
     o = build_parser().parse_args([])
     o.ddpg_optimiser, o.ddpg_optimiser_args = "GradientDescent", "{}"
+    o.target_policy_noise, o.target_policy_noise_clip, o.target_policy_noise_seed = _TARGET_SMOOTHING_DEFAULTS
     for k, v in overrides.items():
         assert hasattr(o, k), k
         setattr(o, k, v)
@@ -322,6 +361,11 @@ class _Trainer(object):
         self._upload = {}
         self._pending = None         # (actor network, Batch) of a deferred actor.train(batch.state_1)
         self.fused_pairs = 0         # actor.train + critic.train pairs that ran as one fused sequence (tests, profiles)
+        # target policy smoothing, as parsed when the critic's train op was declared (off, the trainer's state as created, needs no call)
+        smoothing = getattr(critic, "_target_smoothing", None) or target_policy_smoothing(opts)
+        self.target_smoothing = (0.0, 0.0, 0)
+        if smoothing[0] > 0.0:
+            self.set_target_smoothing(*smoothing)
 
     @property
     def handle(self):
@@ -392,6 +436,18 @@ class _Trainer(object):
         check(lib.cpp_ddpg_last_values(self.handle, B, ptr(actions), ptr(dq_da), ptr(q), ptr(td)))
         return actions, dq_da, q, td
 
+    def set_target_smoothing(self, sigma, clip, seed):
+        """target policy smoothing of the critic's target (include/cartpolepp_abi.h, cpp_ddpg_set_target_smoothing): sigma > 0 switches
+        it on, (0, 0, seed) off; zeroes the count of target-forming passes and drops the captured graphs."""
+        check(lib.cpp_ddpg_set_target_smoothing(self.handle, float(sigma), float(clip), int(seed)))
+        self.target_smoothing = (float(sigma), float(clip), int(seed))
+
+    def last_target_noise(self, B):
+        """((B, action_dim) clipped noise of the last target-forming pass, the count n it was drawn at)"""
+        eps, n = np.empty((int(B), self.action_dim), np.float32), C.c_uint64()
+        check(lib.cpp_ddpg_last_target_noise(self.handle, int(B), ptr(eps), C.byref(n)))
+        return eps, int(n.value)
+
     def grad_buffer(self):
         p, n = C.c_void_p(), C.c_int64()
         check(lib.cpp_ddpg_grad_buffer(self.handle, C.byref(p), C.byref(n)))
@@ -461,6 +517,7 @@ class CriticNetwork(base_network.Network):
         # clip by global norm; SGD (ddpg_cartpole.py:186-218)
         self.target_critic = target_critic
         self._optimiser = ddpg_optimiser(opts)      # (kind, momentum, beta1, beta2, epsilon) of this train op and the actor's
+        self._target_smoothing = target_policy_smoothing(opts)      # (sigma, clip, seed) of this train op's target
         self.reward = base_network.Placeholder([None, 1], name="critic_reward")
         self.terminal_mask = base_network.Placeholder([None, 1], name="critic_terminal_mask")
         self.input_state_2 = target_critic.input_state

@@ -365,6 +365,11 @@ def learner_for_agent(agent, opts, batch_size):
         dev = torch.device("cuda", local_rank) if dist.get_backend() == "nccl" else None
         sync_replicas_from_rank0(agent, dist, device=dev)
         agent._replicas_synced = True
+    # target policy smoothing (DDPG): each rank's noise stream is seeded like its sampler, so that the shards do not share the draws
+    tps = getattr(getattr(agent, "critic", None), "_target_smoothing", None)
+    if tps is not None and tps[0] > 0.0 and rank > 0 and not getattr(agent, "_tps_rank_seeded", False):
+        agent.trainer.set_target_smoothing(tps[0], tps[1], (int(tps[2]) + rank) & (2 ** 64 - 1))
+        agent._tps_rank_seeded = True
     return make_learner(agent, batch_size, seed=int(opts.sample_seed) + rank, sync_every=int(opts.sync_every),
                         overlap=bool(opts.overlap_allreduce), always=True)
 

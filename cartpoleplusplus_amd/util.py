@@ -126,7 +126,7 @@ class SaverUtil(object):
     """checkpoint save / restore with the behaviour of the reference's util.SaverUtil (util.py:88-131): on start,
     restore the latest checkpoint named in `<dir>/checkpoint` or initialise the variables and save at once;
     `save_if_required()` saves every `save_freq` seconds; `force_save()` at exit.  The replay memory is not
-    checkpointed (util.py:91).  The reference hands a tf.Session to tf.train.Saver; here the first argument is
+    checkpointed (util.py:91); neither is the count of --target-policy-noise's stream: a resumed run restarts it.  The reference hands a tf.Session to tf.train.Saver; here the first argument is
     the agent (anything with `.networks()` -> [Network] and `.initialise_variables()`), and a checkpoint is one
     `.npz` with the flat f32 buffer of every namespace (variable names and shapes stored alongside and checked
     on restore) plus, for agents whose optimiser has slot variables (NAF with Momentum / Adam: `agent.naf`; DDPG with

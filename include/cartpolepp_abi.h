@@ -363,6 +363,23 @@ int cpp_ddpg_update_targets(cpp_ddpg* ddpg);
  * slots (actor + critic parameters, the gradient buffer's layout), zeroes both step counts and drops the captured graphs.  Bad kinds
  * and ranges (momentum < 0, a beta outside [0, 1), epsilon <= 0) are refused. */
 int cpp_ddpg_set_optimiser(cpp_ddpg* ddpg, int kind, float momentum, float beta1, float beta2, float epsilon);
+/* Target policy smoothing (TD3: Fujimoto et al. 2018, section 5.3), an extension of the critic's target ddpg_cartpole.py:199-209: with
+ * sigma > 0 every pass that forms a training target evaluates the target critic at
+ *     a' = clamp(mu'(s2) + clamp(sigma z, -clip, clip), -1, 1),   z ~ N(0, 1) per row b and action component i, fresh in every minibatch:
+ *     (x, y, _, _) = philox4x32_10({b, 0x100 + i, n_lo, n_hi}, key = (seed_lo, seed_hi))
+ *     u1 = ((x >> 8) + 1) 2^-24,  u2 = (y >> 8) 2^-24,  z = sqrtf(-2 logf(u1)) cos(2 pi u2)          (f32, the accurate logf / cosine)
+ * n is the trainer's count of such passes since this call: a 64-bit device word that the call zeroes and that every pass advances
+ * by exactly one -- cpp_ddpg_train_critic, cpp_ddpg_compute_gradients, cpp_ddpg_train_rows, cpp_ddpg_sample_and_compute and each
+ * minibatch of cpp_ddpg_train_step / cpp_ddpg_dp_train_step, graph replays included.  cpp_ddpg_check_loss is an evaluation: no
+ * noise, no count.  The actor's update, dQ/da and the fed-action Q are untouched.  sigma == 0 with clip == 0 switches the feature
+ * off (the state after cpp_ddpg_create: every path then launches exactly what it did before the feature existed).  Refused
+ * (CPP_ERR_ARG): a negative, NaN or infinite sigma or clip, sigma > 0 with clip == 0, clip > 0 with sigma == 0.  sigma, clip and
+ * seed are captured by value: the call drops the captured graphs.  n is not part of any checkpoint: a resumed run restarts the
+ * stream.  Data-parallel learners: distinct seeds per rank are the caller's business (distributed.py adds the rank). */
+int cpp_ddpg_set_target_smoothing(cpp_ddpg* ddpg, float sigma, float clip, uint64_t seed);
+/* the (B, action_dim) clipped noise clamp(sigma z, -clip, clip) of the last target-forming pass and the count n it was drawn at (written
+ * by the launch that applied it); either output may be NULL.  CPP_ERR_STATE when smoothing is off. */
+int cpp_ddpg_last_target_noise(cpp_ddpg* ddpg, int B, float* eps, uint64_t* n);
 /* The slot variables tf.train.Saver checkpoints besides the weights (util.py:88-90; the slots of ddpg_cartpole.py:118 and :218's
  * optimisers): m and v hold the actor's list, then the critic's (n = cpp_ddpg_opt_state_size values each; v only under Adam);
  * steps[0] is the actor's step count, steps[1] the critic's.  Refused under GradientDescent, which has no slots. */
