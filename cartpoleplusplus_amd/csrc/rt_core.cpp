@@ -207,6 +207,44 @@ extern "C" int cpp_sync(cpp_ctx* c) {
   return CPP_OK;
 }
 
+// ---- cached step graphs (rt_internal.h: StepGraph)
+void StepGraph::drop() {
+  if (e) { (void)hipGraphExecDestroy(e); e = nullptr; }
+  if (g) { (void)hipGraphDestroy(g); g = nullptr; }
+  ok = false;
+}
+int StepGraph::capture(cpp_ctx* ctx, const GraphKey& k, const std::function<int()>& body) {
+  drop();
+  HIP_CHECK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+  int rc = body();
+  const hipError_t err = hipStreamEndCapture(ctx->stream, &g);      // (also after a failed body: the stream must leave capture mode)
+  if (!rc && err != hipSuccess) { cpp_set_error("hipStreamEndCapture -> %s", hipGetErrorString(err)); rc = CPP_ERR_HIP; }
+  if (!rc) rc = [this]() -> int { HIP_CHECK(hipGraphInstantiate(&e, g, nullptr, nullptr, 0)); return CPP_OK; }();
+  if (rc) { drop(); return rc; }
+  key = k; ok = true;
+  return CPP_OK;
+}
+int StepGraph::launch(cpp_ctx* ctx) {
+  HIP_CHECK(hipGraphLaunch(e, ctx->stream));
+  return CPP_OK;
+}
+int StepGraph::rebuild(cpp_ctx* ctx, const GraphKey& k, const std::function<int()>& body, StepRan* ran) {
+  drop();
+  RC(body());
+  HIP_CHECK(ctx_sync_stream(ctx));
+  const int rc = capture(ctx, k, body);
+  *ran = rc ? STEP_CAPTURE_FAILED : STEP_CAPTURED;
+  return rc;
+}
+int dp_graph_refused(DpGraph& D, const char* learner) {
+  (void)hipGetLastError();
+  D.graph.drop();
+  D.refused = true;
+  snprintf(D.reason, sizeof(D.reason), "%s", cpp_last_error());
+  fprintf(stderr, "cartpolepp: the data-parallel %s step could not be captured as a hipGraph (%s); running it as stream launches\n", learner, D.reason);
+  return CPP_OK;
+}
+
 extern "C" int cpp_timer_begin(cpp_ctx* c) {
   ARG_CHECK(c, "ctx is NULL");
   HIP_CHECK(hipEventRecord(c->t0, c->stream));

@@ -13,22 +13,23 @@ struct cpp_ddpg {
   double* heads_part;                              // fused heads kernel: per-workgroup partial sums of td^2
   int heads_grid, heads_B;                         // ... of the last graph built by compute_gradients (0: GEMM levels + td_kernel)
   int loss_parts, loss_B;                          // how cpp_ddpg_last_stats finds the loss of the last call: partials to add, or loss_norms[0]
-  // graph replay of the full inner step
-  hipGraph_t graph; hipGraphExec_t gexec; bool graph_ok; int g_B, g_nb; uint64_t g_seed, g_replay_uid;   // (the sampler's range is read from the replay's device size word: one graph survives growth)
+  // graph replay of the full inner step (the sampler's range is read from the replay's device size word: one graph survives growth)
+  StepGraph graph;
   cpp_batch* step_batch;
   // graph replay of ONE minibatch on host-drawn rows, no target update (cpp_ddpg_train_rows: the reference's literal loop)
-  hipGraph_t rgraph; hipGraphExec_t rgexec; bool rgraph_ok; int rg_B; uint64_t rg_replay_uid;
+  StepGraph rgraph;
+  uint64_t graph_gen = 0;    // part of every graph's key: invalidate_graphs() moves it
   uint64_t epoch;            // cpp_ctx::kernel_epoch the cached graphs were captured under (route_check)
   bool publish_in_apply;     // the next apply() closes a training call: its launch publishes the call's whitening scale
   bool targets_in_apply, targets_applied;      // ... and an outer step: its launch carries both target updates (step_body)
-  hipGraph_t dgraph; hipGraphExec_t dgexec; bool dgraph_ok; int dg_B, dg_nb; uint64_t dg_seed, dg_replay_uid; uint64_t dg_comm_uid; bool dgraph_refused; char dg_reason[256];   // the data-parallel step (default mode)
+  DpGraph dgraph;            // the data-parallel step (default mode)
   // graph replay of the data-parallel half step (sample + both gradient sets)
   // three variants: 0 samples its own minibatch; 1 / 2 find it presampled (by the previous call's rider, conv1_dw_gather.hip)
-  // in the second / first set of slot arrays.  One key for all three.
+  // in the second / first set of slot arrays.  One key for all three and for both families (half_key).
   // hg[0]: the whole half step as one graph per variant; hg[1]: split at the conv backward (two graphs per variant) so that the
   // all-reduce of the fully-connected layers' gradients can run beside the conv backward (cpp_ddpg_dp_train_step, overlap)
-  struct HalfGraphs { hipGraph_t g[3][2]; hipGraphExec_t e[3][2]; bool ok[3]; int next[3]; } hg[2];   // next: variant of the following call
-  int h_B; uint64_t h_seed, h_replay_uid, h_write_gen;
+  struct HalfGraphs { StepGraph g[3][2]; int next[3] = {0, 0, 0}; } hg[2];   // next: variant of the following call
+  GraphKey half_key; uint64_t h_write_gen;
   uint64_t dp_local;       // minibatches applied locally since the last parameter averaging (periodic mode)
   int sq_cnt[2];           // norm partials the last gradient pass left per list in cpp_ctx::sq_part (<= 0: none, run the sumsq kernel)
   int pre_variant;         // variant of the next cpp_ddpg_sample_and_compute call if its key still matches (0: sample)
@@ -65,12 +66,10 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   d->ctx = ctx; d->actor = actor; d->critic = critic; d->tactor = tactor; d->tcritic = tcritic; d->hp = *hp;
   d->maxB = actor->maxB < critic->maxB ? actor->maxB : critic->maxB;
   d->nA = actor->nparams; d->nC = critic->nparams;
-  d->graph = nullptr; d->gexec = nullptr; d->graph_ok = false; d->step_batch = nullptr; d->g_replay_uid = 0;
-  d->rgraph = nullptr; d->rgexec = nullptr; d->rgraph_ok = false; d->rg_B = 0; d->rg_replay_uid = 0;
+  d->step_batch = nullptr;
   d->epoch = ctx->kernel_epoch;
-  d->dgraph = nullptr; d->dgexec = nullptr; d->dgraph_ok = false; d->dg_B = d->dg_nb = 0; d->dg_seed = d->dg_replay_uid = 0; d->dg_comm_uid = 0; d->dgraph_refused = false; d->dg_reason[0] = 0;
-  memset(d->hg, 0, sizeof(d->hg)); d->dp_local = 0; d->sq_cnt[0] = d->sq_cnt[1] = 0;
-  d->h_replay_uid = 0; d->h_write_gen = 0; d->pre_variant = 0; d->h_B = 0; d->h_seed = 0;
+  d->dp_local = 0; d->sq_cnt[0] = d->sq_cnt[1] = 0;
+  d->h_write_gen = 0; d->pre_variant = 0;
   memset(d->slot_set, 0, sizeof(d->slot_set));
   d->heads_grid = d->heads_B = d->loss_parts = d->loss_B = 0;
   d->per_w = nullptr;
@@ -95,15 +94,19 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   return CPP_OK;
 }
 
-static void drop_half_graphs(cpp_ddpg* d) {
-  for (auto& H : d->hg)
-    for (int v = 0; v < 3; ++v) {
-      for (int k = 0; k < 2; ++k) {
-        if (H.e[v][k]) { (void)hipGraphExecDestroy(H.e[v][k]); H.e[v][k] = nullptr; }
-        if (H.g[v][k]) { (void)hipGraphDestroy(H.g[v][k]); H.g[v][k] = nullptr; }
-      }
-      H.ok[v] = false; H.next[v] = 0;
-    }
+// Everything the captured launches hold by value has changed (the conv1 route, the optimiser's rule, target smoothing): every cached graph
+// of this trainer, the half steps' variants included, misses at its next use.  A new cache needs no line here: gen is part of its key.
+static void invalidate_graphs(cpp_ddpg* d) { ++d->graph_gen; }
+
+// What a replay must leave on the host as the eager body would have: how cpp_ddpg_last_stats finds the loss, and -- step: the body was
+// step_body -- no presampled minibatch for the half steps (it lived in the step_batch the step has just used).
+static void after_replay(cpp_ddpg* d, bool step) {
+  if (step) d->pre_variant = 0;
+  d->loss_parts = d->heads_grid; d->loss_B = d->heads_B;
+}
+static int step_ran(cpp_ddpg* d, int rc, StepRan how) {
+  if (!rc && how == STEP_REPLAYED) after_replay(d, true);
+  return rc;
 }
 
 // Every training entry point starts here: the context may have moved conv1 to the other kernel family since the last call (nearly
@@ -113,8 +116,7 @@ static void route_check(cpp_ddpg* d) {
   ctx_route_update(d->ctx);
   if (d->epoch == d->ctx->kernel_epoch) return;
   d->epoch = d->ctx->kernel_epoch;
-  d->graph_ok = false; d->rgraph_ok = false; d->dgraph_ok = false;
-  drop_half_graphs(d);
+  invalidate_graphs(d);
   d->pre_variant = 0;
   for (cpp_net* n : {d->actor, d->critic, d->tactor, d->tcritic}) n->wimg_key = nullptr;
 }
@@ -123,17 +125,10 @@ extern "C" int cpp_ddpg_destroy(cpp_ddpg* d) {
   if (!d) return CPP_OK;
   (void)hipSetDevice(d->ctx->device);
   (void)ctx_sync_stream(d->ctx);
-  if (d->gexec) (void)hipGraphExecDestroy(d->gexec);
-  if (d->graph) (void)hipGraphDestroy(d->graph);
-  if (d->dgexec) (void)hipGraphExecDestroy(d->dgexec);
-  if (d->dgraph) (void)hipGraphDestroy(d->dgraph);
-  if (d->rgexec) (void)hipGraphExecDestroy(d->rgexec);
-  if (d->rgraph) (void)hipGraphDestroy(d->rgraph);
-  drop_half_graphs(d);
   if (d->step_batch) cpp_batch_destroy(d->step_batch);
   d->actor->grads = nullptr; d->critic->grads = nullptr;
   d->ctx->n_trainers -= 1;
-  d->arena.release(); delete d; return CPP_OK;
+  d->arena.release(); delete d; return CPP_OK;      // (the cached graphs go with their StepGraph members)
 }
 
 static int check_batch(cpp_ddpg* d, cpp_batch* b, const char* who) {
@@ -677,8 +672,7 @@ extern "C" int cpp_ddpg_set_optimiser(cpp_ddpg* d, int kind, float momentum, flo
   HIP_CHECK(ctx_sync_stream(ctx));
   d->opt_kind = kind; d->opt_momentum = momentum; d->opt_beta1 = beta1; d->opt_beta2 = beta2; d->opt_epsilon = epsilon;
   d->step_bumped = false;
-  d->graph_ok = false; d->rgraph_ok = false; d->dgraph_ok = false;      // (the captured launches carry the old rule)
-  drop_half_graphs(d);
+  invalidate_graphs(d);      // (the captured launches carry the old rule)
   d->pre_variant = 0;
   return CPP_OK;
 }
@@ -702,8 +696,7 @@ extern "C" int cpp_ddpg_set_target_smoothing(cpp_ddpg* d, float sigma, float cli
   if (d->tps_eps) HIP_CHECK(hipMemsetAsync(d->tps_eps, 0, n * sizeof(float), ctx->stream));
   HIP_CHECK(ctx_sync_stream(ctx));
   d->tps_on = sigma > 0.f; d->tps_sigma = sigma; d->tps_clip = clip; d->tps_seed = seed; d->tps_pending = false;
-  d->graph_ok = false; d->rgraph_ok = false; d->dgraph_ok = false;      // (the captured launches carry the old values, or none)
-  drop_half_graphs(d);
+  invalidate_graphs(d);      // (the captured launches carry the old values, or none)
   d->pre_variant = 0;
   return CPP_OK;
 }
@@ -770,7 +763,6 @@ bool direct_replay_ok(cpp_net* a, cpp_replay* r, int B) {
   return conv1_f16_pipes_ok(a->ctx, C, a->conv[0].H, a->conv[0].W, B, a->spec.use_batch_norm != 0);
 }
 
-static int capture_into(cpp_ctx* ctx, hipGraph_t* g, hipGraphExec_t* e, const std::function<int()>& body);
 // dp: this rank's part of the data-parallel step (cpp_ddpg_dp_train_step): between a minibatch's gradients and its update the flat
 // gradient buffer is summed over the ranks (comm; NULL: a single learner on the same path) and the update takes the mean -- the
 // all-reduce is issued on the context's stream, i.e. it is PART OF THE CAPTURED GRAPH (RCCL's kernels capture like any other).
@@ -879,42 +871,21 @@ static int step_body(cpp_ddpg* d, cpp_replay* r, int B, int n_batches, const int
 // returns while the previous minibatch is still running.
 extern "C" int cpp_ddpg_train_rows(cpp_ddpg* d, cpp_replay* r, int B, const int32_t* idxs) {
   ARG_CHECK(d && r && idxs, "cpp_ddpg_train_rows: NULL argument");
-  ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_train_rows: batch %d outside [1,%d]", B, d->maxB);
-  ARG_CHECK(r->elems == d->actor->state_elems && r->A == d->actor->spec.action_dim, "cpp_ddpg_train_rows: replay shape does not match the networks");
-  RC(nstep_refuse(r, d->hp.discount, "cpp_ddpg_train_rows"));
-  if (r->size <= 0) { cpp_set_error("cpp_ddpg_train_rows: replay memory is empty"); return CPP_ERR_STATE; }
-  ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_ddpg_train_rows: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
+  RC(train_entry_checks("cpp_ddpg_train_rows", r, B, d->maxB, d->actor->state_elems, d->actor->spec.action_dim, d->hp.discount));
   route_check(d);
   cpp_ctx* ctx = d->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
   if (!d->step_batch) RC(cpp_batch_create(ctx, d->maxB, r->elems, r->A, &d->step_batch));
   RC(replay_stage_rows(r, idxs, B, "cpp_ddpg_train_rows"));
   static const bool no_graph = cpp_switch_set("CPP_NO_GRAPH");
-  if (ctx->prof || no_graph) return step_body(d, r, B, 1, r->rows_in, 0, false);
-  if (!d->rgraph_ok || d->rg_B != B || d->rg_replay_uid != r->uid) {
-    if (d->rgexec) { (void)hipGraphExecDestroy(d->rgexec); d->rgexec = nullptr; }
-    if (d->rgraph) { (void)hipGraphDestroy(d->rgraph); d->rgraph = nullptr; }
-    d->rgraph_ok = false;
-    RC(step_body(d, r, B, 1, r->rows_in, 0, false));          // eager pass: kernel attributes; it is also this call's minibatch
-    HIP_CHECK(ctx_sync_stream(ctx));
-    RC(capture_into(ctx, &d->rgraph, &d->rgexec, [&] { return step_body(d, r, B, 1, r->rows_in, 0, false); }));
-    d->rgraph_ok = true; d->rg_B = B; d->rg_replay_uid = r->uid;
-    return CPP_OK;
-  }
-  HIP_CHECK(hipGraphLaunch(d->rgexec, ctx->stream));
-  d->pre_variant = 0;
-  d->loss_parts = d->heads_grid; d->loss_B = d->heads_B;
-  return CPP_OK;
+  StepRan how;
+  const int rc = run_step_graph(ctx, d->rgraph, GraphKey{B, 1, 0, r->uid, 0, d->graph_gen}, [&] { return step_body(d, r, B, 1, r->rows_in, 0, false); }, &how, no_graph);
+  return step_ran(d, rc, how);
 }
 
 extern "C" int cpp_ddpg_train_step(cpp_ddpg* d, cpp_replay* r, int B, int n_batches, const int32_t* idxs, uint64_t seed) {
   ARG_CHECK(d && r, "cpp_ddpg_train_step: NULL argument");
-  ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_train_step: batch %d outside [1,%d]", B, d->maxB);
-  ARG_CHECK(n_batches >= 1 && (size_t)n_batches * B <= 65536, "cpp_ddpg_train_step: n_batches %d", n_batches);
-  ARG_CHECK(r->elems == d->actor->state_elems && r->A == d->actor->spec.action_dim, "cpp_ddpg_train_step: replay shape does not match the networks");
-  RC(nstep_refuse(r, d->hp.discount, "cpp_ddpg_train_step"));
-  if (r->size <= 0) { cpp_set_error("cpp_ddpg_train_step: replay memory is empty"); return CPP_ERR_STATE; }
-  ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_ddpg_train_step: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
+  RC(train_entry_checks("cpp_ddpg_train_step", r, B, d->maxB, d->actor->state_elems, d->actor->spec.action_dim, d->hp.discount, &n_batches));
   route_check(d);
   cpp_ctx* ctx = d->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
@@ -926,26 +897,9 @@ extern "C" int cpp_ddpg_train_step(cpp_ddpg* d, cpp_replay* r, int B, int n_batc
     return step_body(d, r, B, n_batches, r->rows_in, seed);
   }
   static const bool no_graph = cpp_switch_set("CPP_NO_GRAPH");   // plain in-order stream launches (A/B measurements)
-  if (ctx->prof || no_graph) return step_body(d, r, B, n_batches, nullptr, seed);
-  if (!d->graph_ok || d->g_B != B || d->g_nb != n_batches || d->g_seed != seed || d->g_replay_uid != r->uid) {
-    if (d->gexec) { (void)hipGraphExecDestroy(d->gexec); d->gexec = nullptr; }
-    if (d->graph) { (void)hipGraphDestroy(d->graph); d->graph = nullptr; }
-    d->graph_ok = false;
-    // one eager pass first: it sets every kernel's LDS attribute (not allowed during capture)
-    RC(step_body(d, r, B, n_batches, nullptr, seed));
-    HIP_CHECK(ctx_sync_stream(ctx));
-    HIP_CHECK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    int rc = step_body(d, r, B, n_batches, nullptr, seed);
-    hipError_t e = hipStreamEndCapture(ctx->stream, &d->graph);
-    if (rc) return rc;
-    if (e != hipSuccess) { cpp_set_error("hipStreamEndCapture -> %s", hipGetErrorString(e)); return CPP_ERR_HIP; }
-    HIP_CHECK(hipGraphInstantiate(&d->gexec, d->graph, nullptr, nullptr, 0));
-    d->graph_ok = true; d->g_B = B; d->g_nb = n_batches; d->g_seed = seed; d->g_replay_uid = r->uid;
-    return CPP_OK;   // the eager pass above was this call's step
-  }
-  HIP_CHECK(hipGraphLaunch(d->gexec, ctx->stream));
-  d->loss_parts = d->heads_grid; d->loss_B = d->heads_B;
-  return CPP_OK;
+  StepRan how;
+  const int rc = run_step_graph(ctx, d->graph, GraphKey{B, n_batches, seed, r->uid, 0, d->graph_gen}, [&] { return step_body(d, r, B, n_batches, nullptr, seed); }, &how, no_graph);
+  return step_ran(d, rc, how);
 }
 
 // variant 0: sample + gather + statistics of this call's minibatch; 1 / 2: it was presampled by the previous call's rider into
@@ -983,16 +937,6 @@ static int half_step_body(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed, int 
   return ctx_route_publish(ctx);
 }
 
-static int capture_into(cpp_ctx* ctx, hipGraph_t* g, hipGraphExec_t* e, const std::function<int()>& body) {
-  HIP_CHECK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-  const int rc = body();
-  const hipError_t err = hipStreamEndCapture(ctx->stream, g);
-  if (rc) return rc;
-  if (err != hipSuccess) { cpp_set_error("hipStreamEndCapture -> %s", hipGetErrorString(err)); return CPP_ERR_HIP; }
-  HIP_CHECK(hipGraphInstantiate(e, *g, nullptr, nullptr, 0));
-  return CPP_OK;
-}
-
 // One half step: sample (or find presampled) a minibatch and leave both gradient sets in the flat buffer.  hipGraph replay after
 // the first call per (variant, B, seed, replay).  split: two graphs per variant, `between` is called on the host between their
 // launches (the data-parallel step starts the all-reduce of the fully connected layers' gradients there).
@@ -1001,11 +945,11 @@ static int half_step(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed, bool spli
   if (!d->step_batch) RC(cpp_batch_create(ctx, d->maxB, r->elems, r->A, &d->step_batch));
   if (d->slot_set[0][0] == nullptr)
     for (int k = 0; k < 2; ++k) { d->slot_set[0][k] = d->step_batch->slot[k]; d->slot_set[1][k] = d->step_batch->slot_alt[k]; }
-  const bool key_ok = d->h_B == B && d->h_seed == seed && d->h_replay_uid == r->uid;
-  if (!key_ok) {                                     // another batch size / seed / memory: start over
-    drop_half_graphs(d);
+  const GraphKey key{B, 0, seed, r->uid, 0, d->graph_gen};
+  if (!(d->half_key == key)) {                       // another batch size / seed / memory, or invalidated: start over
+    for (auto& F : d->hg) for (auto& variant : F.g) for (StepGraph& g : variant) g.drop();
     d->pre_variant = 0;
-    d->h_B = B; d->h_seed = seed; d->h_replay_uid = r->uid;
+    d->half_key = key;
   }
   // a minibatch the previous call's rider presampled is only good while the memory is as it was: an episode added since may have
   // overwritten its rows or recycled their state slots (the slots are read at step time).  Draw again (same counter, new contents).
@@ -1019,14 +963,15 @@ static int half_step(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed, bool spli
     if (between) RC(between());
     return half_step_body(d, r, B, seed, variant, nx, 2);
   };
+  const int parts = split ? 2 : 1;
   auto capture = [&](int variant, int* nx) -> int {
-    if (!split) return capture_into(ctx, &H.g[variant][0], &H.e[variant][0], [&] { return half_step_body(d, r, B, seed, variant, nx, 0); });
-    RC(capture_into(ctx, &H.g[variant][0], &H.e[variant][0], [&] { return half_step_body(d, r, B, seed, variant, nx, 1); }));
-    return capture_into(ctx, &H.g[variant][1], &H.e[variant][1], [&] { return half_step_body(d, r, B, seed, variant, nx, 2); });
+    for (int k = 0; k < parts; ++k)
+      RC(H.g[variant][k].capture(ctx, key, [&] { return half_step_body(d, r, B, seed, variant, nx, split ? k + 1 : 0); }));
+    return CPP_OK;
   };
   int next = 0;
   if (ctx->prof) { RC(eager(v, &next)); d->pre_variant = next; return CPP_OK; }
-  if (!H.ok[v]) {
+  if (!H.g[v][parts - 1].hit(key)) {                 // (the last part is captured last: a variant is there whole or not at all)
     // Variants 1 / 2 consume a presampled minibatch: their work must be done by the captured graph's first launch (an eager
     // pass would consume it and leave another one behind).  Kernel attributes (LDS sizes: not allowed during capture) are set
     // by variant 0's eager pass, which is also that call's work.
@@ -1035,30 +980,27 @@ static int half_step(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed, bool spli
       RC(eager(0, &next));
       HIP_CHECK(ctx_sync_stream(ctx));
       RC(capture(0, &nx));
-      H.ok[0] = true; H.next[0] = nx;
+      H.next[0] = nx;
       d->pre_variant = next;
       return CPP_OK;
     }
     HIP_CHECK(ctx_sync_stream(ctx));
     RC(capture(v, &nx));
-    H.ok[v] = true; H.next[v] = nx;
+    H.next[v] = nx;
   }
-  HIP_CHECK(hipGraphLaunch(H.e[v][0], ctx->stream));
+  RC(H.g[v][0].launch(ctx));
   if (split) {
     if (between) RC(between());
-    HIP_CHECK(hipGraphLaunch(H.e[v][1], ctx->stream));
+    RC(H.g[v][1].launch(ctx));
   }
+  after_replay(d, false);
   d->pre_variant = H.next[v];
-  d->loss_parts = d->heads_grid; d->loss_B = d->heads_B;
   return CPP_OK;
 }
 
 static int half_step_checks(cpp_ddpg* d, cpp_replay* r, int B, const char* who) {
   ARG_CHECK(d && r, "%s: NULL argument", who);
-  ARG_CHECK(B >= 1 && B <= d->maxB, "%s: batch %d outside [1,%d]", who, B, d->maxB);
-  ARG_CHECK(r->elems == d->actor->state_elems && r->A == d->actor->spec.action_dim, "%s: replay shape does not match the networks", who);
-  if (r->size <= 0) { cpp_set_error("%s: replay memory is empty", who); return CPP_ERR_STATE; }
-  return CPP_OK;
+  return train_entry_checks(who, r, B, d->maxB, d->actor->state_elems, d->actor->spec.action_dim, d->hp.discount, nullptr, false);
 }
 
 extern "C" int cpp_ddpg_sample_and_compute(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed) {
@@ -1126,35 +1068,11 @@ extern "C" int cpp_ddpg_dp_train_step(cpp_ddpg* d, cpp_replay* r, cpp_comm* c, i
     // i's conv1 dW as in the fused step.  (Rounds 2-3: one graph per half step, the all-reduce, sumsq and the optimiser as host
     // launches per minibatch: 0.946 of the fused step at world size 1.)
     if (!d->step_batch) RC(cpp_batch_create(ctx, d->maxB, r->elems, r->A, &d->step_batch));
-    if (ctx->prof) return step_body(d, r, B, n_batches, nullptr, seed, true, true, c);
-    if (d->dgraph_refused) return step_body(d, r, B, n_batches, nullptr, seed, true, true, c);
-    if (!d->dgraph_ok || d->dg_B != B || d->dg_nb != n_batches || d->dg_seed != seed || d->dg_replay_uid != r->uid || d->dg_comm_uid != (c ? c->uid : 0)) {
-      if (d->dgexec) { (void)hipGraphExecDestroy(d->dgexec); d->dgexec = nullptr; }
-      if (d->dgraph) { (void)hipGraphDestroy(d->dgraph); d->dgraph = nullptr; }
-      d->dgraph_ok = false;
-      RC(step_body(d, r, B, n_batches, nullptr, seed, true, true, c));      // eager pass: kernel attributes; it is also this call's step
-      HIP_CHECK(ctx_sync_stream(ctx));
-      if (d->dgraph_refused) return CPP_OK;           // (capture failed once on this trainer: every step takes the eager sequence above)
-      // No N > 1 box has run this yet: if the runtime or RCCL refuses to capture / instantiate the step with the collective inside,
-      // the trainer keeps the SAME sequence as plain stream launches (identical arithmetic on every rank, no graph) instead of failing.
-      if (capture_into(ctx, &d->dgraph, &d->dgexec, [&] { return step_body(d, r, B, n_batches, nullptr, seed, true, true, c); }) != CPP_OK) {
-        (void)hipGetLastError();
-        if (d->dgexec) { (void)hipGraphExecDestroy(d->dgexec); d->dgexec = nullptr; }
-        if (d->dgraph) { (void)hipGraphDestroy(d->dgraph); d->dgraph = nullptr; }
-        // (the very same calls have just run eagerly and returned CPP_OK: whatever fails here fails BECAUSE of the capture -- the
-        // runtime's or RCCL's refusal.  The reason is kept for cpp_ddpg_dp_status; a failure of the eager pass above is returned.)
-        d->dgraph_refused = true;
-        snprintf(d->dg_reason, sizeof(d->dg_reason), "%s", cpp_last_error());
-        fprintf(stderr, "cartpolepp: the data-parallel step could not be captured as a hipGraph (%s); running it as stream launches\n", d->dg_reason);
-        return CPP_OK;
-      }
-      d->dgraph_ok = true; d->dg_B = B; d->dg_nb = n_batches; d->dg_seed = seed; d->dg_replay_uid = r->uid; d->dg_comm_uid = c ? c->uid : 0;
-      return CPP_OK;
-    }
-    HIP_CHECK(hipGraphLaunch(d->dgexec, ctx->stream));
-    d->pre_variant = 0;
-    d->loss_parts = d->heads_grid; d->loss_B = d->heads_B;
-    return CPP_OK;
+    // (No N > 1 box has run this yet: a refused capture leaves the same sequence as stream launches -- rt_internal.h, DpGraph)
+    StepRan how;
+    const int rc = run_dp_graph(ctx, d->dgraph, GraphKey{B, n_batches, seed, r->uid, c ? c->uid : 0, d->graph_gen}, "DDPG",
+                                [&] { return step_body(d, r, B, n_batches, nullptr, seed, true, true, c); }, &how);
+    return step_ran(d, rc, how);
   }
   for (int i = 0; i < n_batches; ++i) {
     if (sync_every > 1) {                           // local update; every k-th one is followed by the parameter averaging
@@ -1195,8 +1113,8 @@ extern "C" int cpp_ddpg_dp_train_step(cpp_ddpg* d, cpp_replay* r, cpp_comm* c, i
 // collective inside), 2 = the same sequence as stream launches (the capture was refused; `reason` says by what)
 extern "C" int cpp_ddpg_dp_status(const cpp_ddpg* d, int* mode, char* reason, int cap) {
   ARG_CHECK(d && mode, "cpp_ddpg_dp_status: NULL argument");
-  *mode = d->dgraph_refused ? 2 : (d->dgraph_ok ? 1 : 0);
-  if (reason && cap > 0) snprintf(reason, (size_t)cap, "%s", d->dg_reason);
+  *mode = d->dgraph.mode(d->graph_gen);
+  if (reason && cap > 0) snprintf(reason, (size_t)cap, "%s", d->dgraph.reason);
   return CPP_OK;
 }
 

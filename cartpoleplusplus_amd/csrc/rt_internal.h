@@ -203,6 +203,62 @@ struct OpGraph {
   }
 };
 
+// ---------------------------------------------------------------------------------------------
+// Cached step graphs (definitions: rt_core.cpp).  A training entry point replays its launch sequence as ONE hipGraph while everything
+// the captured launches hold by value stays what it was: that is the key.  gen is the owning trainer's generation number: its
+// invalidate_graphs() bumps it, and every graph of that trainer is captured again at its next use.
+// ---------------------------------------------------------------------------------------------
+struct GraphKey {
+  int B = 0, nb = 0; uint64_t seed = 0, replay_uid = 0, comm_uid = 0, gen = 0;
+  bool operator==(const GraphKey& o) const {
+    return B == o.B && nb == o.nb && seed == o.seed && replay_uid == o.replay_uid && comm_uid == o.comm_uid && gen == o.gen;
+  }
+};
+enum StepRan { STEP_EAGER, STEP_CAPTURED, STEP_REPLAYED, STEP_CAPTURE_FAILED };
+struct StepGraph {
+  hipGraph_t g = nullptr; hipGraphExec_t e = nullptr; bool ok = false; GraphKey key;
+  StepGraph() = default;
+  StepGraph(const StepGraph&) = delete;
+  StepGraph& operator=(const StepGraph&) = delete;
+  ~StepGraph() { drop(); }
+  bool hit(const GraphKey& k) const { return ok && key == k; }
+  void drop();
+  // body's launches, captured (thread-local mode) and instantiated under key k; any failure leaves the StepGraph empty
+  int capture(cpp_ctx* ctx, const GraphKey& k, const std::function<int()>& body);
+  int launch(cpp_ctx* ctx);
+  // a miss: the eager pass is this call's work and sets the kernels' LDS attributes (not allowed during capture); the stream drains;
+  // then the capture, for the next call
+  int rebuild(cpp_ctx* ctx, const GraphKey& k, const std::function<int()>& body, StepRan* ran);
+};
+// One call of a cached entry point: on a miss the eager pass, sync and capture; on a hit one hipGraphLaunch.  The profiler (cpp_ctx::prof)
+// and `eager` keep the call on plain stream launches.  (A template, so that a hit builds no std::function.)
+template <class Body>
+int run_step_graph(cpp_ctx* ctx, StepGraph& G, const GraphKey& key, Body&& body, StepRan* ran = nullptr, bool eager = false) {
+  StepRan how_;
+  StepRan& how = ran ? *ran : how_;
+  how = STEP_EAGER;
+  if (ctx->prof || eager) return body();
+  if (!G.hit(key)) return G.rebuild(ctx, key, body, &how);
+  how = STEP_REPLAYED;
+  return G.launch(ctx);
+}
+// The data-parallel step's graph has the collective inside.  If the runtime or RCCL refuses to capture or instantiate it, the trainer
+// keeps the SAME sequence as plain stream launches (identical arithmetic on every rank) instead of failing: the very same calls have
+// just run eagerly and returned CPP_OK, so whatever fails in the capture fails BECAUSE of the capture.  A failure of the eager pass is
+// returned.
+struct DpGraph {
+  StepGraph graph; bool refused = false; char reason[256] = "";
+  // cpp_*_dp_status: 0 = no graph (none run yet, or invalidated since), 1 = one hipGraph replay per outer step, 2 = stream launches (refused)
+  int mode(uint64_t gen) const { return refused ? 2 : (graph.ok && graph.key.gen == gen ? 1 : 0); }
+};
+int dp_graph_refused(DpGraph& D, const char* learner);
+template <class Body>
+int run_dp_graph(cpp_ctx* ctx, DpGraph& D, const GraphKey& key, const char* learner, Body&& body, StepRan* ran = nullptr) {
+  StepRan how_;
+  StepRan& how = ran ? *ran : how_;
+  const int rc = run_step_graph(ctx, D.graph, key, body, &how, D.refused);
+  return (rc && how == STEP_CAPTURE_FAILED) ? dp_graph_refused(D, learner) : rc;
+}
 
 // kernel ids of conv layer i's forward / dW / dX launches (profile rows)
 static const int kFwdKid[3] = {K_CONV1_FWD, K_CONV2_FWD, K_CONV3_FWD};
@@ -237,6 +293,8 @@ int batch_stats(cpp_ctx* ctx, const void* s0, const void* s1, int dtype, long el
 int batch_ensure_stats(cpp_batch* b, int C);
 uint64_t replay_next_uid();      // graph keys: a fresh uid per cpp_replay_create and per change of a sampled memory's statistics setting
 int nstep_refuse(const cpp_replay* r, float discount, const char* who);      // CPP_ERR_ARG: an n-step memory folded with another discount
+int train_entry_checks(const char* who, const cpp_replay* r, int B, int maxB, long state_elems, int A, float discount, const int* n_batches = nullptr,
+                       bool nstep = true);      // batch range, replay shape, n-step discount, empty memory, prioritized batch limit
 GatherArgs replay_gather_args(cpp_replay* r, int B, const int32_t* rows_dev, uint64_t seed, const uint64_t* counter_dev, int channels, cpp_batch* out, bool direct, int* C_out,
                               bool augment = true);      // augment: a memory with random shift on gathers shifted (false: cpp_replay_sample, the stored pixels)
 int replay_sample_finish(cpp_replay* r, int B, int C, int channels, cpp_batch* out, uint64_t* bump = nullptr, bool* bumped = nullptr);

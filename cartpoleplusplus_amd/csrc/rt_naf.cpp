@@ -14,14 +14,12 @@ struct cpp_naf {
   double* heads_part; unsigned* heads_ticket;      // fused heads kernel (naf_heads_kernel): per-workgroup td^2 sums + bad flags, arrival counter
   int sq_cnt;              // norm partials the last folded gradient pass left in cpp_ctx::sq_part (<= 0: none, run the sumsq kernel)
   bool step_bumped;        // the last gradient pass advanced opt_step in its heads kernel (the next apply must not)
-  hipGraph_t graph; hipGraphExec_t gexec; bool graph_ok; int g_B, g_nb; uint64_t g_seed, g_replay_uid;
-  // the data-parallel half step (sample + gradients) as a graph of its own
-  hipGraph_t hgraph; hipGraphExec_t hexec; bool hgraph_ok; int h_B; uint64_t h_seed, h_replay_uid;
-  // ONE minibatch on host-drawn rows up to (not including) the optimiser (cpp_naf_train_rows)
-  hipGraph_t rgraph; hipGraphExec_t rgexec; bool rgraph_ok; int rg_B; uint64_t rg_replay_uid;
-  hipGraph_t dgraph; hipGraphExec_t dgexec; bool dgraph_ok; int dg_B, dg_nb; uint64_t dg_seed, dg_replay_uid; uint64_t dg_comm_uid; bool dgraph_refused; char dg_reason[256];   // the data-parallel step
-  // ... and including it, the loss coming back later (cpp_naf_train_rows_async / cpp_naf_loss_wait): pinned (loss, flag) slots
-  hipGraph_t agraph; hipGraphExec_t agexec; bool agraph_ok; int ag_B; uint64_t ag_replay_uid;
+  StepGraph graph;           // the full inner step (cpp_naf_train_step)
+  StepGraph hgraph;          // the data-parallel half step (sample + gradients) as a graph of its own
+  StepGraph rgraph;          // ONE minibatch on host-drawn rows up to (not including) the optimiser (cpp_naf_train_rows)
+  DpGraph dgraph;            // the data-parallel step
+  StepGraph agraph;          // ... and including it, the loss coming back later (cpp_naf_train_rows_async / cpp_naf_loss_wait): pinned (loss, flag) slots
+  uint64_t graph_gen = 0;    // part of every graph's key: moved by naf_route_check, every graph is then captured again
   uint64_t epoch;            // cpp_ctx::kernel_epoch the cached graphs were captured under (naf_route_check)
   bool targets_in_apply, targets_applied;      // the next naf_apply closes an outer step: its launch carries the target update (rt_ddpg.cpp's twin)
   float* res_pin; hipEvent_t res_ev[CPP_NAF_TICKETS]; uint64_t next_ticket;
@@ -67,14 +65,11 @@ extern "C" int cpp_naf_create(cpp_ctx* ctx, cpp_net* value, cpp_net* tvalue, cpp
   f->maxB = value->maxB; f->A = A; f->NL = A * (A + 1) / 2;
   for (cpp_net* n : {tvalue, mu, lv}) if (n->maxB < f->maxB) f->maxB = n->maxB;
   f->nV = value->nparams; f->nM = mu->nparams; f->nL = lv->nparams;
-  f->graph = nullptr; f->gexec = nullptr; f->graph_ok = false; f->step_batch = nullptr; f->g_replay_uid = 0;
+  f->step_batch = nullptr;
   f->sq_cnt = 0; f->step_bumped = false;
-  f->rgraph = nullptr; f->rgexec = nullptr; f->rgraph_ok = false; f->rg_B = 0; f->rg_replay_uid = 0;
-  f->dgraph = nullptr; f->dgexec = nullptr; f->dgraph_ok = false; f->dg_B = f->dg_nb = 0; f->dg_seed = f->dg_replay_uid = 0; f->dg_comm_uid = 0; f->dgraph_refused = false; f->dg_reason[0] = 0;
-  f->agraph = nullptr; f->agexec = nullptr; f->agraph_ok = false; f->ag_B = 0; f->ag_replay_uid = 0;
   f->epoch = ctx->kernel_epoch;
   f->res_pin = nullptr; f->next_ticket = 0; memset(f->res_ev, 0, sizeof(f->res_ev));
-  f->hgraph = nullptr; f->hexec = nullptr; f->hgraph_ok = false; f->h_B = 0; f->h_seed = 0; f->h_replay_uid = 0; f->dp_local = 0;
+  f->dp_local = 0;
   f->per_w = nullptr;
   const size_t nall = (size_t)(f->nV + f->nM + f->nL);
   int rc = dalloc(f->arena, &f->gradbuf, nall);
@@ -105,22 +100,12 @@ extern "C" int cpp_naf_destroy(cpp_naf* f) {
   if (!f) return CPP_OK;
   (void)hipSetDevice(f->ctx->device);
   (void)ctx_sync_stream(f->ctx);
-  if (f->hexec) (void)hipGraphExecDestroy(f->hexec);
-  if (f->hgraph) (void)hipGraphDestroy(f->hgraph);
-  if (f->dgexec) (void)hipGraphExecDestroy(f->dgexec);
-  if (f->dgraph) (void)hipGraphDestroy(f->dgraph);
-  if (f->rgexec) (void)hipGraphExecDestroy(f->rgexec);
-  if (f->rgraph) (void)hipGraphDestroy(f->rgraph);
-  if (f->agexec) (void)hipGraphExecDestroy(f->agexec);
-  if (f->agraph) (void)hipGraphDestroy(f->agraph);
   if (f->res_pin) (void)hipHostFree(f->res_pin);
   for (hipEvent_t e : f->res_ev) if (e) (void)hipEventDestroy(e);
-  if (f->gexec) (void)hipGraphExecDestroy(f->gexec);
-  if (f->graph) (void)hipGraphDestroy(f->graph);
   if (f->step_batch) cpp_batch_destroy(f->step_batch);
   f->value->grads = nullptr; f->mu->grads = nullptr; f->lv->grads = nullptr;
   f->ctx->n_trainers -= 1;
-  f->arena.release(); delete f; return CPP_OK;
+  f->arena.release(); delete f; return CPP_OK;      // (the cached graphs go with their StepGraph members)
 }
 
 static int naf_check_batch(cpp_naf* f, cpp_batch* b, const char* who) {
@@ -484,12 +469,14 @@ extern "C" int cpp_naf_debug_values(cpp_naf* f, cpp_batch* b, float* l_values, f
   return CPP_OK;
 }
 
+static void invalidate_graphs(cpp_naf* f) { ++f->graph_gen; }      // (every cached graph misses at its next use: gen is part of every key)
+
 // (as rt_ddpg.cpp's route_check: the context may have moved conv1 to the other kernel family -- every cached graph is rebuilt)
 static void naf_route_check(cpp_naf* f) {
   ctx_route_update(f->ctx);
   if (f->epoch == f->ctx->kernel_epoch) return;
   f->epoch = f->ctx->kernel_epoch;
-  f->graph_ok = false; f->hgraph_ok = false; f->rgraph_ok = false; f->dgraph_ok = false; f->agraph_ok = false;
+  invalidate_graphs(f);
   f->value->wimg_key = nullptr; f->tvalue->wimg_key = nullptr; f->mu->wimg_key = nullptr;
 }
 
@@ -579,12 +566,7 @@ static int naf_step_body(cpp_naf* f, cpp_replay* r, int B, int n_batches, const 
 extern "C" int cpp_naf_train_step(cpp_naf* f, cpp_replay* r, int B, int n_batches, const int32_t* idxs, uint64_t seed) {
   if (f) naf_route_check(f);
   ARG_CHECK(f && r, "cpp_naf_train_step: NULL %s", r && r->per_tree ? "NAF learner for a prioritized memory" : "argument");
-  ARG_CHECK(B >= 1 && B <= f->maxB, "cpp_naf_train_step: batch %d outside [1,%d]", B, f->maxB);
-  ARG_CHECK(n_batches >= 1 && (size_t)n_batches * B <= 65536, "cpp_naf_train_step: n_batches %d", n_batches);
-  ARG_CHECK(r->elems == f->value->state_elems && r->A == f->A, "cpp_naf_train_step: replay shape does not match the networks");
-  RC(nstep_refuse(r, f->hp.discount, "cpp_naf_train_step"));
-  if (r->size <= 0) { cpp_set_error("cpp_naf_train_step: replay memory is empty"); return CPP_ERR_STATE; }
-  ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_naf_train_step: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
+  RC(train_entry_checks("cpp_naf_train_step", r, B, f->maxB, f->value->state_elems, f->A, f->hp.discount, &n_batches));
   cpp_ctx* ctx = f->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
   if (!f->step_batch) RC(cpp_batch_create(ctx, f->maxB, r->elems, r->A, &f->step_batch));
@@ -594,24 +576,7 @@ extern "C" int cpp_naf_train_step(cpp_naf* f, cpp_replay* r, int B, int n_batche
     HIP_CHECK(hipMemcpyAsync(r->rows_in, idxs, (size_t)n_batches * B * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     return naf_step_body(f, r, B, n_batches, r->rows_in, seed);
   }
-  if (ctx->prof) return naf_step_body(f, r, B, n_batches, nullptr, seed);
-  if (!f->graph_ok || f->g_B != B || f->g_nb != n_batches || f->g_seed != seed || f->g_replay_uid != r->uid) {
-    if (f->gexec) { (void)hipGraphExecDestroy(f->gexec); f->gexec = nullptr; }
-    if (f->graph) { (void)hipGraphDestroy(f->graph); f->graph = nullptr; }
-    f->graph_ok = false;
-    RC(naf_step_body(f, r, B, n_batches, nullptr, seed));
-    HIP_CHECK(ctx_sync_stream(ctx));
-    HIP_CHECK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    int rc = naf_step_body(f, r, B, n_batches, nullptr, seed);
-    hipError_t e = hipStreamEndCapture(ctx->stream, &f->graph);
-    if (rc) return rc;
-    if (e != hipSuccess) { cpp_set_error("hipStreamEndCapture -> %s", hipGetErrorString(e)); return CPP_ERR_HIP; }
-    HIP_CHECK(hipGraphInstantiate(&f->gexec, f->graph, nullptr, nullptr, 0));
-    f->graph_ok = true; f->g_B = B; f->g_nb = n_batches; f->g_seed = seed; f->g_replay_uid = r->uid;
-    return CPP_OK;
-  }
-  HIP_CHECK(hipGraphLaunch(f->gexec, ctx->stream));
-  return CPP_OK;
+  return run_step_graph(ctx, f->graph, GraphKey{B, n_batches, seed, r->uid, 0, f->graph_gen}, [&] { return naf_step_body(f, r, B, n_batches, nullptr, seed); });
 }
 
 // naf_cartpole.py:367-371 for ONE minibatch whose rows the HOST drew: `batch = replay_memory.batch(B); loss = naf.train(batch)` without a
@@ -644,33 +609,12 @@ static int naf_rows_body(cpp_naf* f, cpp_replay* r, int B, bool fold = false, bo
 extern "C" int cpp_naf_train_rows(cpp_naf* f, cpp_replay* r, int B, const int32_t* idxs, float* loss) {
   if (f) naf_route_check(f);
   ARG_CHECK(f && r && idxs, "cpp_naf_train_rows: NULL %s", r && r->per_tree ? "argument (NAF learner or rows) for a prioritized memory" : "argument");
-  ARG_CHECK(B >= 1 && B <= f->maxB, "cpp_naf_train_rows: batch %d outside [1,%d]", B, f->maxB);
-  ARG_CHECK(r->elems == f->value->state_elems && r->A == f->A, "cpp_naf_train_rows: replay shape does not match the networks");
-  RC(nstep_refuse(r, f->hp.discount, "cpp_naf_train_rows"));
-  if (r->size <= 0) { cpp_set_error("cpp_naf_train_rows: replay memory is empty"); return CPP_ERR_STATE; }
-  ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_naf_train_rows: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
+  RC(train_entry_checks("cpp_naf_train_rows", r, B, f->maxB, f->value->state_elems, f->A, f->hp.discount));
   cpp_ctx* ctx = f->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
   if (!f->step_batch) RC(cpp_batch_create(ctx, f->maxB, r->elems, r->A, &f->step_batch));
   RC(replay_stage_rows(r, idxs, B, "cpp_naf_train_rows"));
-  if (ctx->prof) {
-    RC(naf_rows_body(f, r, B));
-  } else if (!f->rgraph_ok || f->rg_B != B || f->rg_replay_uid != r->uid) {
-    if (f->rgexec) { (void)hipGraphExecDestroy(f->rgexec); f->rgexec = nullptr; }
-    if (f->rgraph) { (void)hipGraphDestroy(f->rgraph); f->rgraph = nullptr; }
-    f->rgraph_ok = false;
-    RC(naf_rows_body(f, r, B));                      // eager pass: sets kernel attributes, is this call's work
-    HIP_CHECK(ctx_sync_stream(ctx));
-    HIP_CHECK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = naf_rows_body(f, r, B);
-    const hipError_t e = hipStreamEndCapture(ctx->stream, &f->rgraph);
-    if (rc) return rc;
-    if (e != hipSuccess) { cpp_set_error("hipStreamEndCapture -> %s", hipGetErrorString(e)); return CPP_ERR_HIP; }
-    HIP_CHECK(hipGraphInstantiate(&f->rgexec, f->rgraph, nullptr, nullptr, 0));
-    f->rgraph_ok = true; f->rg_B = B; f->rg_replay_uid = r->uid;
-  } else {
-    HIP_CHECK(hipGraphLaunch(f->rgexec, ctx->stream));
-  }
+  RC(run_step_graph(ctx, f->rgraph, GraphKey{B, 1, 0, r->uid, 0, f->graph_gen}, [&] { return naf_rows_body(f, r, B); }));
   int bad = 0; float l = 0.f;
   HIP_CHECK(hipMemcpyAsync(&bad, f->nonfinite, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(hipMemcpyAsync(&l, f->stats, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -692,11 +636,7 @@ static int naf_rows_apply_body(cpp_naf* f, cpp_replay* r, int B) {
 extern "C" int cpp_naf_train_rows_async(cpp_naf* f, cpp_replay* r, int B, const int32_t* idxs, uint64_t* ticket) {
   if (f) naf_route_check(f);
   ARG_CHECK(f && r && idxs && ticket, "cpp_naf_train_rows_async: NULL %s", r && r->per_tree ? "argument for a prioritized memory" : "argument");
-  ARG_CHECK(B >= 1 && B <= f->maxB, "cpp_naf_train_rows_async: batch %d outside [1,%d]", B, f->maxB);
-  ARG_CHECK(r->elems == f->value->state_elems && r->A == f->A, "cpp_naf_train_rows_async: replay shape does not match the networks");
-  RC(nstep_refuse(r, f->hp.discount, "cpp_naf_train_rows_async"));
-  if (r->size <= 0) { cpp_set_error("cpp_naf_train_rows_async: replay memory is empty"); return CPP_ERR_STATE; }
-  ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "cpp_naf_train_rows_async: a prioritized memory takes batches of at most %d rows", PER_MAX_ROWS);
+  RC(train_entry_checks("cpp_naf_train_rows_async", r, B, f->maxB, f->value->state_elems, f->A, f->hp.discount));
   cpp_ctx* ctx = f->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
   if (!f->step_batch) RC(cpp_batch_create(ctx, f->maxB, r->elems, r->A, &f->step_batch));
@@ -705,24 +645,7 @@ extern "C" int cpp_naf_train_rows_async(cpp_naf* f, cpp_replay* r, int B, const 
     for (hipEvent_t& e : f->res_ev) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
   RC(replay_stage_rows(r, idxs, B, "cpp_naf_train_rows_async"));
-  if (ctx->prof) {
-    RC(naf_rows_apply_body(f, r, B));
-  } else if (!f->agraph_ok || f->ag_B != B || f->ag_replay_uid != r->uid) {
-    if (f->agexec) { (void)hipGraphExecDestroy(f->agexec); f->agexec = nullptr; }
-    if (f->agraph) { (void)hipGraphDestroy(f->agraph); f->agraph = nullptr; }
-    f->agraph_ok = false;
-    RC(naf_rows_apply_body(f, r, B));                // eager pass: sets kernel attributes, is this call's work
-    HIP_CHECK(ctx_sync_stream(ctx));
-    HIP_CHECK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = naf_rows_apply_body(f, r, B);
-    const hipError_t e = hipStreamEndCapture(ctx->stream, &f->agraph);
-    if (rc) return rc;
-    if (e != hipSuccess) { cpp_set_error("hipStreamEndCapture -> %s", hipGetErrorString(e)); return CPP_ERR_HIP; }
-    HIP_CHECK(hipGraphInstantiate(&f->agexec, f->agraph, nullptr, nullptr, 0));
-    f->agraph_ok = true; f->ag_B = B; f->ag_replay_uid = r->uid;
-  } else {
-    HIP_CHECK(hipGraphLaunch(f->agexec, ctx->stream));
-  }
+  RC(run_step_graph(ctx, f->agraph, GraphKey{B, 1, 0, r->uid, 0, f->graph_gen}, [&] { return naf_rows_apply_body(f, r, B); }));
   const uint64_t t = f->next_ticket++;
   float* slot = f->res_pin + (t % CPP_NAF_TICKETS) * 2;
   HIP_CHECK(hipMemcpyAsync(slot, f->stats, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -755,10 +678,7 @@ static int naf_half_body(cpp_naf* f, cpp_replay* r, int B, uint64_t seed) {
 
 static int naf_half_checks(cpp_naf* f, cpp_replay* r, int B, const char* who) {
   ARG_CHECK(f && r, "%s: NULL argument", who);
-  ARG_CHECK(B >= 1 && B <= f->maxB, "%s: batch %d outside [1,%d]", who, B, f->maxB);
-  ARG_CHECK(r->elems == f->value->state_elems && r->A == f->A, "%s: replay shape does not match the networks", who);
-  if (r->size <= 0) { cpp_set_error("%s: replay memory is empty", who); return CPP_ERR_STATE; }
-  return CPP_OK;
+  return train_entry_checks(who, r, B, f->maxB, f->value->state_elems, f->A, f->hp.discount, nullptr, false);
 }
 
 // sample B rows on the device (Philox; the counter advances by one) and leave the gradients of the three networks in the flat
@@ -771,24 +691,7 @@ extern "C" int cpp_naf_sample_and_compute(cpp_naf* f, cpp_replay* r, int B, uint
   cpp_ctx* ctx = f->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
   if (!f->step_batch) RC(cpp_batch_create(ctx, f->maxB, r->elems, r->A, &f->step_batch));
-  if (ctx->prof) return naf_half_body(f, r, B, seed);
-  if (!f->hgraph_ok || f->h_B != B || f->h_seed != seed || f->h_replay_uid != r->uid) {
-    if (f->hexec) { (void)hipGraphExecDestroy(f->hexec); f->hexec = nullptr; }
-    if (f->hgraph) { (void)hipGraphDestroy(f->hgraph); f->hgraph = nullptr; }
-    f->hgraph_ok = false;
-    RC(naf_half_body(f, r, B, seed));                // eager pass: sets kernel attributes, is this call's work
-    HIP_CHECK(ctx_sync_stream(ctx));
-    HIP_CHECK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = naf_half_body(f, r, B, seed);
-    const hipError_t e = hipStreamEndCapture(ctx->stream, &f->hgraph);
-    if (rc) return rc;
-    if (e != hipSuccess) { cpp_set_error("hipStreamEndCapture -> %s", hipGetErrorString(e)); return CPP_ERR_HIP; }
-    HIP_CHECK(hipGraphInstantiate(&f->hexec, f->hgraph, nullptr, nullptr, 0));
-    f->hgraph_ok = true; f->h_B = B; f->h_seed = seed; f->h_replay_uid = r->uid;
-    return CPP_OK;
-  }
-  HIP_CHECK(hipGraphLaunch(f->hexec, ctx->stream));
-  return CPP_OK;
+  return run_step_graph(ctx, f->hgraph, GraphKey{B, 1, seed, r->uid, 0, f->graph_gen}, [&] { return naf_half_body(f, r, B, seed); });
 }
 
 extern "C" int cpp_naf_allreduce_grads(cpp_naf* f, cpp_comm* c) {
@@ -820,8 +723,8 @@ extern "C" int cpp_naf_average_params(cpp_naf* f, cpp_comm* c) {
 // the inner step naf_cartpole.py:367-373 for N synchronous learners (this rank's part); see cpp_ddpg_dp_train_step
 extern "C" int cpp_naf_dp_status(const cpp_naf* f, int* mode, char* reason, int cap) {      // (see cpp_ddpg_dp_status)
   ARG_CHECK(f && mode, "cpp_naf_dp_status: NULL argument");
-  *mode = f->dgraph_refused ? 2 : (f->dgraph_ok ? 1 : 0);
-  if (reason && cap > 0) snprintf(reason, (size_t)cap, "%s", f->dg_reason);
+  *mode = f->dgraph.mode(f->graph_gen);
+  if (reason && cap > 0) snprintf(reason, (size_t)cap, "%s", f->dgraph.reason);
   return CPP_OK;
 }
 
@@ -838,35 +741,8 @@ extern "C" int cpp_naf_dp_train_step(cpp_naf* f, cpp_replay* r, cpp_comm* c, int
     cpp_ctx* ctx = f->ctx;
     HIP_CHECK(hipSetDevice(ctx->device));
     if (!f->step_batch) RC(cpp_batch_create(ctx, f->maxB, r->elems, r->A, &f->step_batch));
-    if (ctx->prof) return naf_step_body(f, r, B, n_batches, nullptr, seed, true, c);
-    if (f->dgraph_refused) return naf_step_body(f, r, B, n_batches, nullptr, seed, true, c);
-    if (!f->dgraph_ok || f->dg_B != B || f->dg_nb != n_batches || f->dg_seed != seed || f->dg_replay_uid != r->uid || f->dg_comm_uid != (c ? c->uid : 0)) {
-      if (f->dgexec) { (void)hipGraphExecDestroy(f->dgexec); f->dgexec = nullptr; }
-      if (f->dgraph) { (void)hipGraphDestroy(f->dgraph); f->dgraph = nullptr; }
-      f->dgraph_ok = false;
-      RC(naf_step_body(f, r, B, n_batches, nullptr, seed, true, c));
-      HIP_CHECK(ctx_sync_stream(ctx));
-      if (f->dgraph_refused) return CPP_OK;
-      // (as cpp_ddpg_dp_train_step: a runtime / RCCL that refuses the capture leaves the same sequence as plain stream launches)
-      HIP_CHECK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-      const int rc = naf_step_body(f, r, B, n_batches, nullptr, seed, true, c);
-      const hipError_t e = hipStreamEndCapture(ctx->stream, &f->dgraph);
-      hipError_t ei = hipSuccess;
-      if (!rc && e == hipSuccess) ei = hipGraphInstantiate(&f->dgexec, f->dgraph, nullptr, nullptr, 0);
-      if (rc || e != hipSuccess || ei != hipSuccess) {
-        (void)hipGetLastError();
-        if (f->dgexec) { (void)hipGraphExecDestroy(f->dgexec); f->dgexec = nullptr; }
-        if (f->dgraph) { (void)hipGraphDestroy(f->dgraph); f->dgraph = nullptr; }
-        f->dgraph_refused = true;
-        snprintf(f->dg_reason, sizeof(f->dg_reason), "%s", rc ? cpp_last_error() : hipGetErrorString(e != hipSuccess ? e : ei));
-        fprintf(stderr, "cartpolepp: the data-parallel NAF step could not be captured as a hipGraph (%s); running it as stream launches\n", f->dg_reason);
-        return CPP_OK;
-      }
-      f->dgraph_ok = true; f->dg_B = B; f->dg_nb = n_batches; f->dg_seed = seed; f->dg_replay_uid = r->uid; f->dg_comm_uid = c ? c->uid : 0;
-      return CPP_OK;
-    }
-    HIP_CHECK(hipGraphLaunch(f->dgexec, ctx->stream));
-    return CPP_OK;
+    return run_dp_graph(ctx, f->dgraph, GraphKey{B, n_batches, seed, r->uid, c ? c->uid : 0, f->graph_gen}, "NAF",
+                        [&] { return naf_step_body(f, r, B, n_batches, nullptr, seed, true, c); });
   }
   for (int i = 0; i < n_batches; ++i) {
     RC(cpp_naf_sample_and_compute(f, r, B, seed));

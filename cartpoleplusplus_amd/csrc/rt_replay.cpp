@@ -664,6 +664,18 @@ int nstep_refuse(const cpp_replay* r, float discount, const char* who) {
   return CPP_OK;
 }
 
+// What every training entry point that draws from a replay memory checks behind its NULL arguments.  n_batches: the entry points that
+// take several minibatches.  nstep = false: the half steps, which check the memory's discount themselves, behind this.
+int train_entry_checks(const char* who, const cpp_replay* r, int B, int maxB, long state_elems, int A, float discount, const int* n_batches, bool nstep) {
+  ARG_CHECK(B >= 1 && B <= maxB, "%s: batch %d outside [1,%d]", who, B, maxB);
+  ARG_CHECK(!n_batches || (*n_batches >= 1 && (size_t)*n_batches * B <= 65536), "%s: n_batches %d", who, n_batches ? *n_batches : 0);
+  ARG_CHECK(r->elems == state_elems && r->A == A, "%s: replay shape does not match the networks", who);
+  if (nstep) RC(nstep_refuse(r, discount, who));
+  if (r->size <= 0) { cpp_set_error("%s: replay memory is empty", who); return CPP_ERR_STATE; }
+  ARG_CHECK(!r->per_tree || B <= PER_MAX_ROWS, "%s: a prioritized memory takes batches of at most %d rows", who, PER_MAX_ROWS);
+  return CPP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // random shift (gather_body.h: ShiftVec, shift_draw): extension, no reference counterpart
 // ---------------------------------------------------------------------------------------------
