@@ -294,17 +294,42 @@ def naf_path(agent, B, hidden, share):
     return fit[0]
 
 
+# ---- which kernels ran the conv trunk: the profiler families that are alternatives of each other (rt_core.cpp's names; conv.hip books
+# ---- conv1 under *_f16 when conv_k16.h / conv_rs16.h / conv_dw16.h took the launch, the pair launches under conv<i>_bwd)
+CONV_ROUTE_FAMILIES = (("conv1_fwd", ("conv1_fwd_f16", "conv1_fwd")),
+                       ("conv1_dw", ("conv1_dw_f16", "conv1_dw_gather", "conv1_dw")),
+                       ("conv2_bwd", ("conv2_bwd", "conv2_dx", "conv2_dw")),
+                       ("conv3_bwd", ("conv3_bwd", "conv3_dx", "conv3_dw")),
+                       ("stats", ("stats_generic", "gather_stats", "reduce_gather")))
+
+
+def conv_routes_of(calls):
+    """launch counts per family -> {part of the trunk: the families that launched for it, joined with '+' in CONV_ROUTE_FAMILIES' order}
+    and 'conv3_fwd': whether conv3's forward had a launch of its own (False: the tail of conv2's, conv23_fuse_ok)."""
+    out = {part: "+".join(f for f in fams if calls.get(f, 0) > 0) for part, fams in CONV_ROUTE_FAMILIES}
+    out["conv3_fwd"] = calls.get("conv3_fwd", 0) > 0
+    return out
+
+
+def conv_routes(agent, B):
+    """one eager minibatch on the replay memory's rows, profiled: which kernel families ran conv1's forward ('conv1_fwd_f16': the f16
+    pipes, 'conv1_fwd': the f32-input kernels), conv1's dW ('conv1_dw_f16' / 'conv1_dw_gather', or 'conv1_dw'), conv2's and conv3's
+    backward ('conv<i>_bwd': one launch, or 'conv<i>_dx+conv<i>_dw'), the sample pass's statistics, and whether conv3's forward launched
+    on its own.  A part that nothing launched for is ''; conv1 on two routes at once would read 'conv1_fwd_f16+conv1_fwd'."""
+    return conv_routes_of(_profiled_step(agent, agent.actor.ctx, B))
+
+
 def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_size=None, seed=0, graph=True,
                                   atol=1e-5, grad_rel=2e-5, param_rel=2e-6, warm="philox", report_only=False,
                                   fill="noise", f32_twin=False, flip_tol=1e-5, probe=False, before_step=None, pixel=True, hyper=None,
-                                  prepare=None, host_seed=None, **pair_kw):
+                                  prepare=None, host_seed=None, probe_conv=False, **pair_kw):
     """ONE minibatch of the fused inner step (cpp_ddpg_train_step, default kernels: f16-pipe conv1 reading the replay store
     through the sampled slots, bf16-pipe conv2, fused heads, paired launches) -- with graph=True the hipGraph REPLAY of it,
     on rows drawn by the device's Philox sampler -- against oracle.DDPG(float64) on the same rows and the same starting
     parameters: actions / Q / TD / dQ/da at `atol` (north_star: 1e-5), both pre-clip gradient lists per variable at
     `grad_rel` (pool routes: the device's, accepted only at near ties), the clipped SGD result and the target updates.
     pair_kw: make_pair's widths, action size and options (--use-dropout: the oracle draws the device's masks).  probe: one
-    profiled minibatch first, report["path"] = ddpg_path().  before_step(): called right before the minibatch that is checked.
+    profiled minibatch first, report["path"] = ddpg_path().  probe_conv: the same, report["conv"] = conv_routes().  before_step(): called right before the minibatch that is checked.
     pixel=False: a low-dimensional state of `shape` (no trunk: the pool and ReLU routes are not compared).  hyper: an O.Hyper the
     device agent and the oracle are both built with (None: the reference's defaults).  prepare(agent): called on the fresh agent, before
     anything runs (edge-case parameters).  host_seed: parameters, episodes and (graph=False) rows are host_case(shape, B, 1, host_seed,
@@ -343,6 +368,9 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
                                         glint=0.02 if fill == "render-glint" else 0.0)
         if probe:
             report["path"] = ddpg_path(agent, B, aspec.hidden, cspec.hidden, pixel)
+            steps += 1
+        if probe_conv:
+            report["conv"] = conv_routes(agent, B)
             steps += 1
         if graph or warm == "philox-eager":
             agent.train_step(B, 1)                        # eager pass + capture
