@@ -130,6 +130,8 @@ SIGNATURES = {
     "cpp_ddpg_set_optimiser": (_I, [_P, _I, _F, _F, _F, _F]),
     "cpp_ddpg_set_target_smoothing": (_I, [_P, _F, _F, _U64]),
     "cpp_ddpg_last_target_noise": (_I, [_P, _I, _P, C.POINTER(_U64)]),
+    "cpp_ddpg_set_policy_delay": (_I, [_P, _I]),
+    "cpp_ddpg_policy_delay_status": (_I, [_P, C.POINTER(_I), C.POINTER(_U64), C.POINTER(_I)]),
     "cpp_ddpg_opt_state_size": (_L, [_P]),
     "cpp_ddpg_get_opt_state": (_I, [_P, _P, _P, _L, _P]),
     "cpp_ddpg_set_opt_state": (_I, [_P, _P, _P, _L, _P]),

@@ -409,6 +409,11 @@ struct OptSegs {
   // optional, appended (every argument above keeps its offset): a second counter this launch advances by one -- target policy
   // smoothing's count of gradient passes, which the pass in front has read and nobody in this launch does
   uint64_t* bump2;
+  // optional, appended likewise (hold[seg] != nullptr): a device word this launch only reads; non-zero = the segment is HELD -- its
+  // parameters, slots and conv1 image rider's weights stay as they are, to the bit, while the norm, the counters, the publish, the
+  // segment's target update (from the unchanged values) and the next minibatch's operand image still leave with this launch.  DDPG's
+  // delayed policy updates (rt_ddpg.cpp: cpp_ddpg_set_policy_delay); the word is written by the launch in front (heads.hip)
+  const uint64_t* hold[OPT_MAX_SEGS];
 };
 // the SGD update of one parameter, p - lr * (g * scale), with its roundings pinned (one product, one fused multiply-add): opt_apply_kernel
 // writes it, the conv1 image rider of the same launch recomputes it, and both must hold the same bits whatever the compiler contracts
@@ -491,7 +496,17 @@ struct DdpgHeadsArgs {
   // optional (tps.n != nullptr: the SMOOTH instances, which alone read it): target policy smoothing of the target actor's action.
   // Appended: every argument above keeps its offset, the instances without it their instructions.
   TpsArgs tps;
+  // optional, appended likewise (pd != nullptr): delayed policy updates (TD3: Fujimoto et al. 2018, Algorithm 1; rt_ddpg.cpp).  The thread
+  // that bumps the step counts also counts this minibatch -- pd[PD_N] += 1, pd[PD_PHASE] = n mod pd_d kept without a division -- and
+  // leaves in pd[PD_HOLD] whether the actor's list is held (n' % pd_d != 0) for the optimiser's launch behind this one, which only reads
+  // it; the actor's step count then moves only when its list is applied.  Nobody else in this launch touches the three words.
+  unsigned long long* pd; unsigned pd_d;
 };
+enum { PD_N = 0, PD_HOLD = 1, PD_PHASE = 2, PD_WORDS = 3 };
+// the same count where the heads kernel does not carry it (GEMM-level paths, the stand-alone ops, cpp_ddpg_apply_gradients): one thread, in
+// front of the optimiser's launch.  step: the two optimisers' step counts or nullptr (GradientDescent).  peek (cpp_ddpg_train_actor: the
+// actor half of the minibatch whose critic half follows): n stays, the hold word is that of n + 1.
+int launch_pd_tick(cpp_ctx* ctx, uint64_t* pd, unsigned pd_d, uint64_t* step, bool do_actor, bool do_critic, bool peek);
 #define DDPG_HEADS_MAX_WGS 256
 size_t ddpg_heads_lds_bytes(const DdpgHeadsArgs& h);
 bool ddpg_heads_supported(const DdpgHeadsArgs& h);

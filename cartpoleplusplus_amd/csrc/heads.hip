@@ -290,7 +290,15 @@ __global__ __launch_bounds__(HEADS_THREADS) void ddpg_heads_kernel(const DdpgHea
     double s = 0.0;
     for (int i = 0; i < HEADS_ROWS; ++i) s += lred[i];
     h.loss_part[blockIdx.x] = s;
-    if (blockIdx.x == 0 && h.step_bump) { h.step_bump[0] += 1ull; h.step_bump[1] += 1ull; }
+    if (blockIdx.x == 0) {
+      unsigned long long act = 1ull;                     // the actor's list is applied behind this pass (always, without a policy delay)
+      if (h.pd) {                                        // (uniform: one scalar branch; common.h, DdpgHeadsArgs::pd)
+        const unsigned long long ph = h.pd[PD_PHASE] + 1ull;
+        act = ph == (unsigned long long)h.pd_d ? 1ull : 0ull;
+        h.pd[PD_N] += 1ull; h.pd[PD_PHASE] = act ? 0ull : ph; h.pd[PD_HOLD] = 1ull - act;
+      }
+      if (h.step_bump) { h.step_bump[0] += act; h.step_bump[1] += 1ull; }
+    }
   }
 #ifdef HEADS_CLOCK
   HCK();
@@ -351,6 +359,24 @@ __global__ __launch_bounds__(256) void tps_smooth_kernel(const TpsArgs s, const 
 int launch_tps_smooth(cpp_ctx* ctx, const TpsArgs& s, const float* in, int ld_in, float* out, int ld_out, int B, int A) {
   prof_begin(ctx);
   hipLaunchKernelGGL(tps_smooth_kernel, dim3((B * A + 255) / 256), dim3(256), 0, ctx->stream, s, in, ld_in, out, ld_out, B, A);
+  LAUNCH_CHECK();
+  prof_end(ctx, K_ELEMENTWISE);
+  return 0;
+}
+
+// ---- delayed policy updates where the heads kernel does not count the minibatch (common.h: launch_pd_tick): the same arithmetic, one thread
+__global__ void pd_tick_kernel(unsigned long long* pd, unsigned pd_d, unsigned long long* step, int do_actor, int do_critic, int peek) {
+  const unsigned long long ph = pd[PD_PHASE] + 1ull;
+  const unsigned long long act = ph == (unsigned long long)pd_d ? 1ull : 0ull;
+  pd[PD_HOLD] = 1ull - act;
+  if (!peek) { pd[PD_N] += 1ull; pd[PD_PHASE] = act ? 0ull : ph; }
+  if (step && do_actor) step[0] += act;
+  if (step && do_critic) step[1] += 1ull;
+}
+
+int launch_pd_tick(cpp_ctx* ctx, uint64_t* pd, unsigned pd_d, uint64_t* step, bool do_actor, bool do_critic, bool peek) {
+  prof_begin(ctx);
+  hipLaunchKernelGGL(pd_tick_kernel, dim3(1), dim3(1), 0, ctx->stream, (unsigned long long*)pd, pd_d, (unsigned long long*)step, do_actor ? 1 : 0, do_critic ? 1 : 0, peek ? 1 : 0);
   LAUNCH_CHECK();
   prof_end(ctx, K_ELEMENTWISE);
   return 0;

@@ -80,10 +80,12 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(const OptSegs s,
     extern __shared__ __attribute__((aligned(16))) unsigned char img_lds[];
     __shared__ float wh[2 * CPP_MAX_CHANNELS];
     const int j = blockIdx.x, ws = s.img[j].seg;
+    // a held segment's workgroup takes the path a target network's takes: the image from the weights as they are, nothing written back
+    const float* const gwj = (s.hold[ws] && *s.hold[ws]) ? nullptr : s.img[j].gw;      // (uniform: a scalar load and select)
     // (run by conv1_image_body once its weight / gradient loads are in flight)
     auto pre = [&](float, float& lr_io) __attribute__((always_inline)) -> float {
     // the update's scale, as the workgroups of segment ws compute it below (same partials, same order)
-      if (s.img[j].gw) {
+      if (gwj) {
         double tot = 0.0;
         if (threadIdx.x < 64) {
           if (s.sq) {
@@ -142,14 +144,14 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(const OptSegs s,
         }
       }
       __syncthreads();
-      if (ADAM && s.img[j].gw) lr_io = sh_lr;
-      return s.img[j].gw ? sh_scale : 0.f;
+      if (ADAM && gwj) lr_io = sh_lr;
+      return gwj ? sh_scale : 0.f;
     };
     Conv1ImageArgs ia;
     ia.w = s.img[j].w; ia.bias = s.img[j].bias; ia.scale = wh; ia.shift = wh + s.img_cin; ia.wscale = 0.f; ia.nout = s.img[j].nout; ia.rec = s.img[j].rec;
-    ia.gw = s.img[j].gw; ia.gb = s.img[j].gb; ia.lr = s.img[j].gw ? s.lr[ws] : 0.f; ia.gscale = 0.f;      // (the scale: pre's return value)
-    ia.w_out = s.img[j].gw ? s.img[j].w : nullptr; ia.b_out = s.img[j].gw ? s.img[j].bias : nullptr;
-    const bool slots = s.img[j].gw && (ADAM || s.kind == OPT_MOMENTUM), adam = ADAM && s.img[j].gw;
+    ia.gw = gwj; ia.gb = s.img[j].gb; ia.lr = gwj ? s.lr[ws] : 0.f; ia.gscale = 0.f;      // (the scale: pre's return value)
+    ia.w_out = gwj ? s.img[j].w : nullptr; ia.b_out = gwj ? s.img[j].bias : nullptr;
+    const bool slots = gwj && (ADAM || s.kind == OPT_MOMENTUM), adam = ADAM && gwj;
     ia.mw = slots ? s.img[j].mw : nullptr; ia.mb = slots ? s.img[j].mb : nullptr; ia.momentum = s.momentum;
     ia.vw = adam ? s.img[j].vw : nullptr; ia.vb = adam ? s.img[j].vb : nullptr; ia.beta1 = s.beta1; ia.beta2 = s.beta2; ia.epsilon = s.epsilon;
     switch (s.img_cin) {                                // (uniform: one of conv_fwd_rs16.hip's instances)
@@ -205,6 +207,11 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(const OptSegs s,
   const long stride = (long)gridDim.x * OPT_THREADS;
   float* tp = s.tgt[seg] ? s.tgt[seg] + skip : nullptr;      // (uniform) the segment's target network: updated from the new values
   const float tc = s.tgt_coeff;
+  if (s.hold[seg] && *s.hold[seg]) {                 // (uniform) a held segment: p, m, v keep their bits; its target follows the values as they are
+    if (tp)
+      for (long i = (long)blockIdx.x * OPT_THREADS + threadIdx.x; i < n; i += stride) tp[i] = soft_update_value(tp[i], p[i], tc);
+    return;
+  }
   if (!ADAM && s.kind == OPT_SGD) {
     long i = (long)blockIdx.x * OPT_THREADS + threadIdx.x;
     for (; i + 3 * stride < n; i += 4 * stride) {

@@ -49,6 +49,10 @@ struct cpp_ddpg {
   // tps_act: the smoothed action of the single train op (cpp_ddpg_train_critic), maxB x A
   bool tps_on; float tps_sigma, tps_clip; uint64_t tps_seed; uint64_t* tps_n; float *tps_eps, *tps_act;
   bool tps_pending;        // a pass has read tps_n[0] and its increment is still owed: the apply() behind it carries it, or tps_settle()
+  // delayed policy updates (cpp_ddpg_set_policy_delay; common.h: DdpgHeadsArgs::pd, OptSegs::hold).  pd_d: the delay (1: off, and pd is
+  // never passed to a launch); pd: three device words (captured graphs replay them) -- the critic updates applied since the configuring
+  // call, whether the last minibatch held the actor, the count modulo pd_d
+  int pd_d; uint64_t* pd;
   Arena arena;
 };
 
@@ -75,6 +79,7 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   d->per_w = nullptr;
   d->opt_kind = OPT_SGD; d->opt_momentum = 0.f; d->opt_beta1 = 0.9f; d->opt_beta2 = 0.999f; d->opt_epsilon = 1e-8f;
   d->opt_m = d->opt_v = nullptr; d->opt_step = nullptr; d->bump_in_heads = d->step_bumped = false;
+  d->pd_d = 1; d->pd = nullptr;
   d->tps_on = d->tps_pending = false; d->tps_sigma = d->tps_clip = 0.f; d->tps_seed = 0; d->tps_n = nullptr; d->tps_eps = d->tps_act = nullptr;
   const int A = actor->spec.action_dim;
   int rc = dalloc(d->arena, &d->gradbuf, (size_t)(d->nA + d->nC));
@@ -275,13 +280,20 @@ static int apply(cpp_ddpg* d, bool do_actor, bool do_critic, float grad_scale, u
   s.nseg = 2; s.kind = d->opt_kind;
   const bool bumped = d->step_bumped;
   d->step_bumped = false;
+  // delayed policy updates: the launch in front has counted this minibatch and left the actor's hold word -- the heads kernel of the
+  // gradient pass (step_body), or one tick launch here, which then moves the step counts as well.  The critic's half alone counts the
+  // minibatch; the actor's half alone looks one ahead (it belongs to the minibatch whose critic half follows) and counts nothing.
+  const bool pd_on = d->pd_d > 1;
+  if (pd_on && do_actor) s.hold[0] = d->pd + PD_HOLD;
+  if (pd_on && !bumped)
+    RC(launch_pd_tick(d->ctx, d->pd, (unsigned)d->pd_d, s.kind != OPT_SGD ? d->opt_step : nullptr, do_actor, do_critic, do_actor && !do_critic));
   if (s.kind != OPT_SGD) {
     s.momentum = d->opt_momentum; s.beta1 = d->opt_beta1; s.beta2 = d->opt_beta2; s.epsilon = d->opt_epsilon;
     s.m[0] = d->opt_m; s.m[1] = d->opt_m + d->nA; s.v[0] = d->opt_v; s.v[1] = d->opt_v ? d->opt_v + d->nA : nullptr;
     s.step_seg[0] = d->opt_step; s.step_seg[1] = d->opt_step + 1;
     // a list's count moves with its own applies only (actor.train / critic.train: two optimisers).  Not in the optimiser's launch, whose
     // other workgroups read the counts: in the heads kernel of the gradient pass (step_body) or, on the other paths, a launch in front
-    if (!bumped) {
+    if (!bumped && !pd_on) {
       if (do_actor) RC(launch_counter_add(d->ctx, d->opt_step, 1));
       if (do_critic) RC(launch_counter_add(d->ctx, d->opt_step + 1, 1));
     }
@@ -473,6 +485,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     hd.w = d->per_w;
     hd.step_bump = (d->bump_in_heads && d->opt_kind != OPT_SGD && phase == 0) ? (unsigned long long*)d->opt_step : nullptr;
     hd.tps = tps_args(d);
+    if (d->bump_in_heads && d->pd_d > 1 && phase == 0) { hd.pd = (unsigned long long*)d->pd; hd.pd_d = (unsigned)d->pd_d; }
     fused = ddpg_heads_supported(hd);
     // the actors are one layer deeper than the critics' prefix (100-100-50 against 200-50): their last hidden layer joins the
     // heads kernel so that both stacks reach it, and leave it, in the same number of GEMM levels.  CPP_HEADS_PRE=0: GEMMs.
@@ -487,7 +500,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     }
   }
   const int pre = (fused && hd.n1a > 0) ? 1 : 0;
-  d->step_bumped = fused && hd.step_bump != nullptr;
+  d->step_bumped = fused && (hd.step_bump != nullptr || hd.pd != nullptr);
   d->heads_grid = fused ? (B + 3) / 4 : 0; d->heads_B = B;
   d->loss_parts = d->heads_grid; d->loss_B = B;
   int adz, cdz;
@@ -698,6 +711,38 @@ extern "C" int cpp_ddpg_set_target_smoothing(cpp_ddpg* d, float sigma, float cli
   d->tps_on = sigma > 0.f; d->tps_sigma = sigma; d->tps_clip = clip; d->tps_seed = seed; d->tps_pending = false;
   invalidate_graphs(d);      // (the captured launches carry the old values, or none)
   d->pre_variant = 0;
+  return CPP_OK;
+}
+
+// Delayed policy updates (TD3: Fujimoto et al. 2018, Algorithm 1; an extension of ddpg_cartpole.py:332-337; include/cartpolepp_abi.h).  The
+// delay is captured by value: the call drops the cached graphs, and it zeroes the count.  delay 1 is off: no launch carries the words.
+extern "C" int cpp_ddpg_set_policy_delay(cpp_ddpg* d, int delay) {
+  ARG_CHECK(d, "cpp_ddpg_set_policy_delay: NULL argument");
+  ARG_CHECK(delay >= 1 && delay <= 65536, "cpp_ddpg_set_policy_delay: delay %d outside [1, 65536]", delay);
+  cpp_ctx* ctx = d->ctx;
+  HIP_CHECK(hipSetDevice(ctx->device));
+  HIP_CHECK(ctx_sync_stream(ctx));
+  if (delay > 1 && !d->pd) RC(dalloc(d->arena, &d->pd, (size_t)PD_WORDS));
+  if (d->pd) HIP_CHECK(hipMemsetAsync(d->pd, 0, PD_WORDS * sizeof(uint64_t), ctx->stream));
+  HIP_CHECK(ctx_sync_stream(ctx));
+  d->pd_d = delay;
+  d->step_bumped = false;
+  invalidate_graphs(d);      // (the captured launches carry the old delay, or none)
+  d->pre_variant = 0;
+  return CPP_OK;
+}
+
+extern "C" int cpp_ddpg_policy_delay_status(cpp_ddpg* d, int* delay, uint64_t* n, int* held) {
+  ARG_CHECK(d, "cpp_ddpg_policy_delay_status: NULL argument");
+  uint64_t w[PD_WORDS] = {0, 0, 0};
+  if (d->pd) {
+    HIP_CHECK(hipSetDevice(d->ctx->device));
+    HIP_CHECK(hipMemcpyAsync(w, d->pd, sizeof(w), hipMemcpyDeviceToHost, d->ctx->stream));
+    HIP_CHECK(ctx_sync_stream(d->ctx));
+  }
+  if (delay) *delay = d->pd_d;
+  if (n) *n = w[PD_N];
+  if (held) *held = (d->pd_d > 1 && w[PD_HOLD]) ? 1 : 0;
   return CPP_OK;
 }
 

@@ -148,6 +148,12 @@ def build_parser():
       help="--target-policy-noise: the noise is clipped to +- this (default 0.5)")
     a('--target-policy-noise-seed', type=int, default=argparse.SUPPRESS,
       help="--target-policy-noise: seed of the device's noise stream (default 0)")
+    # delayed policy updates (an extension beyond the reference, ddpg_cartpole.py:332-337: TD3, Fujimoto et al. 2018, Algorithm 1): the
+    # actor's list is applied with every D-th critic update only, decided on the device (absent from the parsed options unless given,
+    # like --ddpg-optimiser; policy_delay() reads it with its default)
+    a('--policy-delay', type=int, default=argparse.SUPPRESS,
+      help="apply the actor's update with every D-th critic update only (default 1: every minibatch); with --batches-per-step D the "
+           "actor moves in the outer step's last minibatch and the targets follow it: TD3's schedule")
     return parser
 
 
@@ -207,6 +213,23 @@ def target_policy_smoothing(o):
     return (sigma, clip, seed)
 
 
+_POLICY_DELAY_DEFAULT, POLICY_DELAY_MAX = 1, 65536
+
+
+def policy_delay(o):
+    """D of --policy-delay; refuses what cannot be meant.  1: off."""
+    d = getattr(o, "policy_delay", _POLICY_DELAY_DEFAULT)
+    if isinstance(d, bool) or not isinstance(d, (int, np.integer)):
+        if isinstance(d, float) and d == int(d):
+            d = int(d)
+        else:
+            raise SystemExit("--policy-delay %r is not a whole number of critic updates" % (d,))
+    d = int(d)
+    if not 1 <= d <= POLICY_DELAY_MAX:
+        raise SystemExit("--policy-delay %d is outside [1, %d] (1: the actor is updated in every minibatch)" % (d, POLICY_DELAY_MAX))
+    return d
+
+
 def priority_beta(o, train_steps):
     """beta of the outer train step `train_steps` (linear from --priority-beta to --priority-beta-final)"""
     n = max(1, int(o.priority_beta_steps))
@@ -228,6 +251,7 @@ def default_opts(**overrides):
     o = build_parser().parse_args([])
     o.ddpg_optimiser, o.ddpg_optimiser_args = "GradientDescent", "{}"
     o.target_policy_noise, o.target_policy_noise_clip, o.target_policy_noise_seed = _TARGET_SMOOTHING_DEFAULTS
+    o.policy_delay = _POLICY_DELAY_DEFAULT
     for k, v in overrides.items():
         assert hasattr(o, k), k
         setattr(o, k, v)
@@ -366,6 +390,11 @@ class _Trainer(object):
         self.target_smoothing = (0.0, 0.0, 0)
         if smoothing[0] > 0.0:
             self.set_target_smoothing(*smoothing)
+        # delayed policy updates, as parsed when the critic's train op was declared (1: off, the trainer's state as created, needs no call)
+        delay = getattr(critic, "_policy_delay", None) or policy_delay(opts)
+        self.policy_delay = 1
+        if delay > 1:
+            self.set_policy_delay(delay)
 
     @property
     def handle(self):
@@ -448,6 +477,18 @@ class _Trainer(object):
         check(lib.cpp_ddpg_last_target_noise(self.handle, int(B), ptr(eps), C.byref(n)))
         return eps, int(n.value)
 
+    def set_policy_delay(self, delay):
+        """delayed policy updates (include/cartpolepp_abi.h, cpp_ddpg_set_policy_delay): the actor's list is applied with every
+        delay-th critic update; 1 switches it off; zeroes the count of critic updates and drops the captured graphs."""
+        check(lib.cpp_ddpg_set_policy_delay(self.handle, int(delay)))
+        self.policy_delay = int(delay)
+
+    def policy_delay_status(self):
+        """(delay, critic updates counted since it was set, whether the last minibatch held the actor)"""
+        d, n, held = C.c_int(), C.c_uint64(), C.c_int()
+        check(lib.cpp_ddpg_policy_delay_status(self.handle, C.byref(d), C.byref(n), C.byref(held)))
+        return int(d.value), int(n.value), bool(held.value)
+
     def grad_buffer(self):
         p, n = C.c_void_p(), C.c_int64()
         check(lib.cpp_ddpg_grad_buffer(self.handle, C.byref(p), C.byref(n)))
@@ -518,6 +559,7 @@ class CriticNetwork(base_network.Network):
         self.target_critic = target_critic
         self._optimiser = ddpg_optimiser(opts)      # (kind, momentum, beta1, beta2, epsilon) of this train op and the actor's
         self._target_smoothing = target_policy_smoothing(opts)      # (sigma, clip, seed) of this train op's target
+        self._policy_delay = policy_delay(opts)      # critic updates per actor update (the actor's train op is bound to this one)
         self.reward = base_network.Placeholder([None, 1], name="critic_reward")
         self.terminal_mask = base_network.Placeholder([None, 1], name="critic_terminal_mask")
         self.input_state_2 = target_critic.input_state

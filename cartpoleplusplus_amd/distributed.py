@@ -370,6 +370,11 @@ def learner_for_agent(agent, opts, batch_size):
     if tps is not None and tps[0] > 0.0 and rank > 0 and not getattr(agent, "_tps_rank_seeded", False):
         agent.trainer.set_target_smoothing(tps[0], tps[1], (int(tps[2]) + rank) & (2 ** 64 - 1))
         agent._tps_rank_seeded = True
+    # delayed policy updates (DDPG): the learner trains through the agent's trainer, which carries the delay parsed with the critic's train
+    # op; every rank counts its own minibatches, so the schedule is the same everywhere and the all-reduced update keeps the replicas equal
+    delay = getattr(getattr(agent, "critic", None), "_policy_delay", 1)
+    if delay > 1 and getattr(agent.trainer, "policy_delay", delay) != delay:
+        agent.trainer.set_policy_delay(delay)
     return make_learner(agent, batch_size, seed=int(opts.sample_seed) + rank, sync_every=int(opts.sync_every),
                         overlap=bool(opts.overlap_allreduce), always=True)
 

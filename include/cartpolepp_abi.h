@@ -380,6 +380,27 @@ int cpp_ddpg_set_target_smoothing(cpp_ddpg* ddpg, float sigma, float clip, uint6
 /* the (B, action_dim) clipped noise clamp(sigma z, -clip, clip) of the last target-forming pass and the count n it was drawn at (written
  * by the launch that applied it); either output may be NULL.  CPP_ERR_STATE when smoothing is off. */
 int cpp_ddpg_last_target_noise(cpp_ddpg* ddpg, int B, float* eps, uint64_t* n);
+/* Delayed policy updates (TD3: Fujimoto et al. 2018, Algorithm 1: `total_it += 1; if total_it % policy_freq == 0`), an extension of the
+ * loop body ddpg_cartpole.py:332-337.  delay is d, 1 <= d <= 65536; d = 1 is off, the trainer's state after cpp_ddpg_create (every path
+ * then launches exactly what it did before the feature existed).  n is a 64-bit word in device memory: the critic updates this trainer
+ * has applied since this call.  A minibatch that applies the critic's list advances n by one, to n'; the actor's list is applied iff
+ * n' % d == 0 and is otherwise HELD: its parameters, its Momentum / Adam slots and its own step count do not move, and no bit of them
+ * is rewritten to a different value.  On a held minibatch the actor's gradient is still computed and its pre-clip norm still reported
+ * (cpp_ddpg_last_stats); the critic's list, the sampler's counter, the smoothing count, the priorities and the whitening tables are
+ * what they would have been.  The decision is taken on the device, so one captured graph serves every phase of the schedule.
+ * Target updates keep :336-337's cadence: both targets take their soft update at the end of every outer step, whether or not the
+ * actor was held in its last minibatch (the target actor then takes it from the held, unchanged actor); with n_batches == d the
+ * actor moves in the outer step's last minibatch and the targets follow: TD3's schedule exactly.
+ * Who counts: cpp_ddpg_train_step, cpp_ddpg_train_rows and cpp_ddpg_dp_train_step per minibatch; cpp_ddpg_train_critic;
+ * cpp_ddpg_apply_gradients (both lists, under the predicate).  cpp_ddpg_train_actor does not advance n and applies iff
+ * (n + 1) % d == 0: it is the actor half of the minibatch whose critic half follows (:333-334).  cpp_ddpg_compute_gradients and
+ * cpp_ddpg_sample_and_compute alone, cpp_ddpg_check_loss and cpp_ddpg_q_gradients_wrt_actions count nothing; neither does a gradient
+ * pass that fails.  The call zeroes n and drops the captured graphs (d is captured by value).  Refused (CPP_ERR_ARG, the call's name in
+ * cpp_last_error): d outside [1, 65536], a NULL handle.  n is not part of any checkpoint: a resumed run restarts the phase.
+ * Data-parallel learners each count their own minibatches: the schedule is the same on every rank. */
+int cpp_ddpg_set_policy_delay(cpp_ddpg* ddpg, int delay);
+/* d, n and whether the last counted minibatch (or the last cpp_ddpg_train_actor) held the actor; any output may be NULL. */
+int cpp_ddpg_policy_delay_status(cpp_ddpg* ddpg, int* delay, uint64_t* n, int* held);
 /* The slot variables tf.train.Saver checkpoints besides the weights (util.py:88-90; the slots of ddpg_cartpole.py:118 and :218's
  * optimisers): m and v hold the actor's list, then the critic's (n = cpp_ddpg_opt_state_size values each; v only under Adam);
  * steps[0] is the actor's step count, steps[1] the critic's.  Refused under GradientDescent, which has no slots. */
