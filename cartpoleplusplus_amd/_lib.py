@@ -75,6 +75,8 @@ SIGNATURES = {
     "cpp_prof_kernel_name": (C.c_char_p, [_I]),
     "cpp_prof_read": (_I, [_P, _I, C.POINTER(C.c_double), C.POINTER(_L)]),
     "cpp_net_create": (_I, [_P, C.POINTER(NetSpec), _I, _PP]),
+    "cpp_net_create_twin_q": (_I, [_P, C.POINTER(NetSpec), _I, _PP]),
+    "cpp_net_is_twin_q": (_I, [_P]),
     "cpp_net_destroy": (_I, [_P]),
     "cpp_net_num_params": (_L, [_P]),
     "cpp_net_num_vars": (_I, [_P]),
@@ -140,6 +142,7 @@ SIGNATURES = {
     "cpp_ddpg_sample_and_compute": (_I, [_P, _P, _I, _U64]),
     "cpp_ddpg_last_stats": (_I, [_P, _P]),
     "cpp_ddpg_last_values": (_I, [_P, _I, _P, _P, _P, _P]),
+    "cpp_ddpg_last_twin_values": (_I, [_P, _I, _P, _P, _P, _P]),
     "cpp_comm_unique_id": (_I, [_P, _I]),
     "cpp_comm_create": (_I, [_P, _P, _I, _I, _PP]),
     "cpp_comm_destroy": (_I, [_P]),

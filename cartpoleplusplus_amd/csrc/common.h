@@ -277,6 +277,9 @@ int launch_state_to_f32(cpp_ctx* ctx, float* dst, long ldd, const void* src, int
 int launch_actor_head_grad(cpp_ctx* ctx, float* dz, const float* dq_da, const float* act, int n);
 int launch_td(cpp_ctx* ctx, const float* q, const float* tq, const float* r, const float* mask,
               float discount, int B, float* td, float* dq, float* loss, const float* w = nullptr);   // w: importance weights (per.hip)
+// twin Q heads: one target from min(tq1, tq2), both TDs, both dq (nullptr: none, check_loss), loss = mean(w (td1^2 + td2^2))
+int launch_td_twin(cpp_ctx* ctx, const float* q1, const float* q2, const float* tq1, const float* tq2, const float* r, const float* mask, float discount,
+                   int B, float* td1, float* td2, float* dq1, float* dq2, float* loss, const float* w = nullptr);
 
 // ---------------------------------------------------------------------------------------------
 // replay + whitening statistics (replay.hip)
@@ -501,6 +504,13 @@ struct DdpgHeadsArgs {
   // leaves in pd[PD_HOLD] whether the actor's list is held (n' % pd_d != 0) for the optimiser's launch behind this one, which only reads
   // it; the actor's step count then moves only when its list is applied.  Nobody else in this launch touches the three words.
   unsigned long long* pd; unsigned pd_d;
+  // optional, appended likewise (W3b != nullptr: the TWIN instances, which alone read them): twin Q heads (rt_net.cpp, cpp_net_create_twin_q).
+  // [W3b; b3b] / wqb are head 2's copies of [W3; b3] / wq, of the same shapes; head 2 reads the same concat input and the same (smoothed)
+  // target action.  y = r + mask discount min(Q1', Q2'); td2 = Q2 - y; dzq2 = (td2 w) 2 / B; dz2c takes (head 1's term) + (head 2's), then
+  // the mask; loss_part becomes the sum of w (td^2 + td2^2).  tq_out stays head 1's target value.
+  const float *W3b, *W3b_t, *wqb, *wqb_t;
+  float *h3b_out;                                  // input buffer of head 2's q layer (row stride ld_h3)
+  float *q2_out, *tq2_out, *td2, *dzq2, *dz3b;
 };
 enum { PD_N = 0, PD_HOLD = 1, PD_PHASE = 2, PD_WORDS = 3 };
 // the same count where the heads kernel does not carry it (GEMM-level paths, the stand-alone ops, cpp_ddpg_apply_gradients): one thread, in

@@ -396,6 +396,57 @@ int launch_td(cpp_ctx* ctx, const float* q, const float* tq, const float* r, con
   return 0;
 }
 
+// Twin Q heads (TD3's clipped double-Q, Fujimoto et al. 2018, Algorithm 1; an extension of ddpg_cartpole.py:199-209): both online heads
+// regress onto ONE target, y = r + (mask*discount)*min(Q1', Q2'); td_k = Q_k - y; loss = mean(w (td_1^2 + td_2^2)), td_1^2 first;
+// dq_k = (td_k w) 2 / B.  w == nullptr: uniform.
+template <bool WEIGHTED>
+__device__ __forceinline__ void td_twin_body(const float* q1, const float* q2, const float* tq1, const float* tq2, const float* r, const float* mask,
+                                             float discount, int B, float* td1, float* td2, float* dq1, float* dq2, float* loss, const float* w) {
+  __shared__ double red[256];
+  double s = 0.0;
+  const float inv_b = 2.f / (float)B;
+  for (int i = threadIdx.x; i < B; i += 256) {
+    const float y = r[i] + (mask[i] * discount) * fminf(tq1[i], tq2[i]);
+    const float t1 = q1[i] - y, t2 = q2[i] - y;
+    td1[i] = t1; td2[i] = t2;
+    const double sq = (double)t1 * (double)t1 + (double)t2 * (double)t2;
+    if (WEIGHTED) {
+      if (dq1) { dq1[i] = (t1 * w[i]) * inv_b; dq2[i] = (t2 * w[i]) * inv_b; }
+      s += (double)w[i] * sq;
+    } else {
+      if (dq1) { dq1[i] = t1 * inv_b; dq2[i] = t2 * inv_b; }
+      s += sq;
+    }
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)B);
+}
+
+__global__ __launch_bounds__(256) void td_twin_kernel(const float* q1, const float* q2, const float* tq1, const float* tq2, const float* r, const float* mask,
+                                                      float discount, int B, float* td1, float* td2, float* dq1, float* dq2, float* loss) {
+  td_twin_body<false>(q1, q2, tq1, tq2, r, mask, discount, B, td1, td2, dq1, dq2, loss, nullptr);
+}
+
+__global__ __launch_bounds__(256) void td_twin_weighted_kernel(const float* q1, const float* q2, const float* tq1, const float* tq2, const float* r,
+                                                               const float* mask, float discount, int B, float* td1, float* td2, float* dq1, float* dq2,
+                                                               float* loss, const float* w) {
+  td_twin_body<true>(q1, q2, tq1, tq2, r, mask, discount, B, td1, td2, dq1, dq2, loss, w);
+}
+
+int launch_td_twin(cpp_ctx* ctx, const float* q1, const float* q2, const float* tq1, const float* tq2, const float* r, const float* mask, float discount,
+                   int B, float* td1, float* td2, float* dq1, float* dq2, float* loss, const float* w) {
+  prof_begin(ctx);
+  if (w) hipLaunchKernelGGL(td_twin_weighted_kernel, dim3(1), dim3(256), 0, ctx->stream, q1, q2, tq1, tq2, r, mask, discount, B, td1, td2, dq1, dq2, loss, w);
+  else hipLaunchKernelGGL(td_twin_kernel, dim3(1), dim3(256), 0, ctx->stream, q1, q2, tq1, tq2, r, mask, discount, B, td1, td2, dq1, dq2, loss);
+  LAUNCH_CHECK();
+  prof_end(ctx, K_TD);
+  return 0;
+}
 
 // NAF head (naf_cartpole.py:186-230) forward + backward, one row per thread iteration:
 //   L = [lower | exp(diag) | 0] from l_values; d = u - mu; z = L^T d; A = -1/2 |z|^2; Q = V + A;

@@ -54,6 +54,9 @@ struct cpp_ddpg {
   // call, whether the last minibatch held the actor, the count modulo pd_d
   int pd_d; uint64_t* pd;
   Arena arena;
+  // twin Q heads (cpp_net_create_twin_q: both critics are twin critics, or neither): head 2's temporal difference, maxB.  The trainer
+  // has no switch of its own -- what the critics are decides every path
+  bool twin = false; float* td2 = nullptr;
 };
 
 extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cpp_net* tactor, cpp_net* tcritic,
@@ -61,6 +64,8 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   ARG_CHECK(ctx && actor && critic && tactor && tcritic && hp && out, "cpp_ddpg_create: NULL argument");
   ARG_CHECK(actor->spec.kind == CPP_ACTOR && tactor->spec.kind == CPP_ACTOR, "cpp_ddpg_create: actor kinds");
   ARG_CHECK(critic->spec.kind == CPP_CRITIC && tcritic->spec.kind == CPP_CRITIC, "cpp_ddpg_create: critic kinds");
+  ARG_CHECK(!actor->twin && !tactor->twin, "cpp_ddpg_create: a twin actor");
+  ARG_CHECK(critic->twin == tcritic->twin, "cpp_ddpg_create: a twin critic needs a twin target critic (and a plain one a plain one)");
   ARG_CHECK(actor->nparams == tactor->nparams && critic->nparams == tcritic->nparams, "cpp_ddpg_create: target shapes differ");
   ARG_CHECK(actor->state_elems == critic->state_elems && actor->spec.action_dim == critic->spec.action_dim,
             "cpp_ddpg_create: actor/critic input shapes differ");
@@ -90,6 +95,8 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   if (!rc) rc = dalloc(d->arena, &d->loss_norms, (size_t)4);
   if (!rc) rc = dalloc(d->arena, &d->norm_part, (size_t)OPT_MAX_SEGS * NORM_PARTS);
   if (!rc) rc = dalloc(d->arena, &d->heads_part, (size_t)DDPG_HEADS_MAX_WGS);
+  d->twin = critic->twin;
+  if (!rc && d->twin) rc = dalloc(d->arena, &d->td2, (size_t)d->maxB);
   if (!rc) rc = launch_fill(ctx, d->ones, 1, 0, 1, d->maxB, 1.0f);
   if (rc) { d->arena.release(); delete d; return rc; }
   actor->grads = d->gradbuf; critic->grads = d->gradbuf + d->nA;
@@ -182,7 +189,8 @@ static int critic_head(cpp_net* c, int wi, const float* action, int B) {
     const FcL& L = c->fc[cl];
     RC(launch_copy_cols(c->ctx, c->ws[1].fcin[cl], L.n_in + 1, 0, c->ws[0].fcin[cl], L.n_in + 1, 0, L.n_in - A, B));
   }
-  return net_forward_fc(c, c->ws[wi], cl, B, action);
+  RC(net_forward_fc(c, c->ws[wi], cl, B, action));
+  return (c->twin && wi == 0) ? twin_forward_fc(c, c->ws[0], B) : CPP_OK;      // (head 2 reads the same concat input)
 }
 
 // ddpg_cartpole.py:111-113 + :220-222.  critic_prefix_done: the critic prefix for batch.state_1 is
@@ -246,6 +254,10 @@ static int critic_gradients_impl(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_d
   if (!critic_prefix_done) RC(critic_prefix(c, b->s[0], b->dtype, w1, B));
   RC(critic_head(c, 0, b->a, B));
   const int last = (int)c->fc.size() - 1;
+  if (d->twin)
+    RC(launch_td_twin(d->ctx, c->ws[0].out, c->ws[0].out2, tc->ws[0].out, tc->ws[0].out2, b->r, b->m, d->hp.discount, B, d->td, d->td2,
+                      backward ? c->ws[0].dz[last] : nullptr, backward ? c->ws[0].dz2[last] : nullptr, d->loss_norms));
+  else
   RC(launch_td(d->ctx, c->ws[0].out, tc->ws[0].out, b->r, b->m, d->hp.discount, B, d->td,
                backward ? c->ws[0].dz[last] : nullptr, d->loss_norms));
   d->loss_parts = 0;
@@ -464,6 +476,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   // CPP_FUSED_HEADS=0 keeps the GEMM levels.
   static const bool no_heads = cpp_switch_off("CPP_FUSED_HEADS");
   DdpgHeadsArgs hd; memset(&hd, 0, sizeof(hd));
+  const bool twin = d->twin;
   bool fused = !no_heads && na >= 2 && cat >= 1 && nc - cat == 2 && a->fc[na - 1].act == GE_TANH && Lcat.act == GE_RELU &&
                c->fc[nc - 1].n_out == 1 && c->fc[nc - 1].act == GE_NONE && a->fc[na - 1].n_out == A;
   if (fused) {
@@ -486,6 +499,12 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     hd.step_bump = (d->bump_in_heads && d->opt_kind != OPT_SGD && phase == 0) ? (unsigned long long*)d->opt_step : nullptr;
     hd.tps = tps_args(d);
     if (d->bump_in_heads && d->pd_d > 1 && phase == 0) { hd.pd = (unsigned long long*)d->pd; hd.pd_d = (unsigned)d->pd_d; }
+    if (twin) {      // twin Q heads: head 2's two layers of both critics (nc - cat == 2), its buffers of the first workspace
+      const FcL &L3b = c->fc2[cat], &Lqb = c->fc2[nc - 1];
+      hd.W3b = c->params + L3b.w_off; hd.W3b_t = tc->params + L3b.w_off; hd.wqb = c->params + Lqb.w_off; hd.wqb_t = tc->params + Lqb.w_off;
+      hd.h3b_out = c->ws[0].fcin2[nc - 1]; hd.q2_out = c->ws[0].out2; hd.tq2_out = tc->ws[0].out2; hd.td2 = d->td2;
+      hd.dzq2 = c->ws[0].dz2[nc - 1]; hd.dz3b = c->ws[0].dz2[cat];
+    }
     fused = ddpg_heads_supported(hd);
     // the actors are one layer deeper than the critics' prefix (100-100-50 against 200-50): their last hidden layer joins the
     // heads kernel so that both stacks reach it, and leave it, in the same number of GEMM levels.  CPP_HEADS_PRE=0: GEMMs.
@@ -537,6 +556,10 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     // ---- critic backward below its concat layer
     G.gemm(sqg(1, fc_dw_args(c, c->ws[0], nc - 1, B, c->ws[0].dz[nc - 1])), {hk});
     G.gemm(sqg(1, fc_dw_args(c, c->ws[0], cat, B, c->ws[0].dz[cat])), {hk});
+    if (twin) {      // head 2's two dW GEMMs depend on the heads launch alone: they ride in this level
+      G.gemm(sqg(1, twin_dw_args(c, c->ws[0], nc - 1, B)), {hk});
+      G.gemm(sqg(1, twin_dw_args(c, c->ws[0], cat, B)), {hk});
+    }
     cdz = hk;
     for (int l = cat - 1; l >= 0; --l) {
       const FcL& L = c->fc[l];
@@ -579,11 +602,15 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     float* col = tc->ws[0].fcin[cat] + (Lcat.n_in - A);
     taS = G.fn([=] { return launch_tps_smooth(ctx, ts, col, (int)ldcat, col, (int)ldcat, B, A); }, {taF});
   }
-  int c1 = -1, c0 = -1, tcH = -1;
+  int c1 = -1, c0 = -1, tcH = -1, c0b = -1, tcHb = -1;
   for (int l = cat; l < nc; ++l) {
     c1 = G.gemm(fc_fwd_args(c, c->ws[1], l, B), {l == cat ? cP : c1, l == cat ? aF : -1});
     c0 = G.gemm(fc_fwd_args(c, c->ws[0], l, B), {l == cat ? cP : c0, l == cat ? cb : -1, l == cat ? tC : -1});
     tcH = G.gemm(fc_fwd_args(tc, tc->ws[0], l, B), {l == cat ? tcP : tcH, l == cat ? taS : -1});
+    if (twin) {      // head 2 of both critics on the same concat inputs (one smoothed action for both target heads), in head 1's levels
+      c0b = G.gemm(twin_fwd_args(c, c->ws[0], l, B), {l == cat ? cP : c0b, l == cat ? cb : -1, l == cat ? tC : -1});
+      tcHb = G.gemm(twin_fwd_args(tc, tc->ws[0], l, B), {l == cat ? tcP : tcHb, l == cat ? taS : -1});
+    }
   }
 
   // ---- dQ/da at a = actor(s1): back through q_value .. splice on the second evaluation (dz of q is 1)
@@ -614,14 +641,26 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
 
   // ---- TD target + critic backward on the first evaluation (fed actions)
   const float* per_w = d->per_w;
+  if (twin)
+    cdz = G.fn([=] { return launch_td_twin(ctx, c->ws[0].out, c->ws[0].out2, tc->ws[0].out, tc->ws[0].out2, b->r, b->m, d->hp.discount, B, d->td, d->td2,
+                                           c->ws[0].dz[nc - 1], c->ws[0].dz2[nc - 1], d->loss_norms, per_w); }, {c0, tcH, c0b, tcHb});
+  else
   cdz = G.fn([=] { return launch_td(ctx, c->ws[0].out, tc->ws[0].out, b->r, b->m, d->hp.discount, B, d->td,
                                         c->ws[0].dz[nc - 1], d->loss_norms, per_w); }, {c0, tcH});
   if (d->per_hook) G.fn(d->per_hook, {cdz});
+  int cdz2 = cdz;      // head 2's chain down to the concat layer, level by level beside head 1's
   for (int l = nc - 1; l >= 0; --l) {
     const FcL& L = c->fc[l];
     G.gemm(sqg(1, fc_dw_args(c, c->ws[0], l, B, c->ws[0].dz[l])), {cdz});
     const int ncols = L.cat ? L.n_in - A : L.n_in;
-    if (l > 0)
+    if (twin && l >= cat) {
+      G.gemm(sqg(1, twin_dw_args(c, c->ws[0], l, B)), {cdz2});
+      if (l > cat) cdz2 = G.gemm(twin_dx_args(c, c->ws[0], l, B), {cdz2});
+    }
+    if (twin && l == cat && l > 0) {      // the shared layer's dz: (head 1) + (head 2), then the mask
+      const int h1 = G.gemm(fc_dx_args(c, l, B, c->ws[0].dz[l], L.n_out, 0, ncols, c->ws[0].dz[l - 1], ncols, GE_NONE, nullptr, 0), {cdz});
+      cdz = G.gemm(twin_dx_args(c, c->ws[0], l, B), {h1, cdz2});
+    } else if (l > 0)
       cdz = G.gemm(fc_dx_args(c, l, B, c->ws[0].dz[l], L.n_out, 0, ncols, c->ws[0].dz[l - 1], ncols, GE_MUL_RELU_GRAD,
                               c->ws[0].fcin[l], L.n_in + 1), {cdz});
     else if (c->spec.pixel)
@@ -1192,3 +1231,20 @@ extern "C" int cpp_ddpg_last_values(cpp_ddpg* d, int B, float* actions, float* d
   return CPP_OK;
 }
 
+
+// Twin Q heads: what head 2 and the two target heads left in the last minibatch's gradient pass (cpp_ddpg_last_values keeps reporting
+// head 1's q and td): Q2(state_1, fed action), Q1'(state_2, a'), Q2'(state_2, a') and td_2 = Q2 - y, each (B).  NULL pointers are skipped.
+extern "C" int cpp_ddpg_last_twin_values(cpp_ddpg* d, int B, float* q2, float* target_q1, float* target_q2, float* td2) {
+  ARG_CHECK(d, "cpp_ddpg_last_twin_values: NULL argument");
+  ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_twin_values: batch %d outside [1,%d]", B, d->maxB);
+  if (!d->twin) { cpp_set_error("cpp_ddpg_last_twin_values: the trainer's critics are not twin critics"); return CPP_ERR_STATE; }
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  hipStream_t st = d->ctx->stream;
+  const size_t n = (size_t)B * sizeof(float);
+  if (q2) HIP_CHECK(hipMemcpyAsync(q2, d->critic->ws[0].out2, n, hipMemcpyDeviceToHost, st));
+  if (target_q1) HIP_CHECK(hipMemcpyAsync(target_q1, d->tcritic->ws[0].out, n, hipMemcpyDeviceToHost, st));
+  if (target_q2) HIP_CHECK(hipMemcpyAsync(target_q2, d->tcritic->ws[0].out2, n, hipMemcpyDeviceToHost, st));
+  if (td2) HIP_CHECK(hipMemcpyAsync(td2, d->td2, n, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  return CPP_OK;
+}

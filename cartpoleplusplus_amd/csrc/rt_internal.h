@@ -76,6 +76,10 @@ struct Workspace {
   float* bn_stat[3] = {nullptr, nullptr, nullptr};
   std::vector<float*> fcin, dz;
   float* out = nullptr;
+  // twin Q heads (cpp_net_create_twin_q): the second copy of the layers [cat, nfc) on the fed action (ws[0] only).  fcin2[cat] is
+  // fcin[cat] itself -- both heads read one concat input, and with it one smoothed target action --, the others are its own
+  std::vector<float*> fcin2, dz2;
+  float* out2 = nullptr;
 };
 
 struct cpp_net {
@@ -98,6 +102,9 @@ struct cpp_net {
   double* bn_part; float* bn_means; float* bn_scratch;   // batch norm: reduction partials, (mean dy, mean dy*zhat), dW bias-slot dump
   void* stage_state; float* stage_action; float* stage_out;
   Arena arena;
+  // twin Q heads (TD3's clipped double-Q with a shared representation): fc2[l], l in [cat_layer, nfc), is the second copy of fc[l];
+  // its variables follow the plain critic's nparams in the flat buffer.  Empty for every other network.
+  bool twin = false; std::vector<FcL> fc2;
 };
 
 struct cpp_batch {
@@ -289,6 +296,12 @@ int net_backward(cpp_net* n, Workspace& w, int B, bool want_params, float* d_act
 GemmArgs fc_fwd_args(cpp_net* n, Workspace& w, int l, int B);
 GemmArgs fc_dw_args(cpp_net* n, Workspace& w, int l, int B, const float* dz);
 GemmArgs fc_dx_args(cpp_net* n, int l, int B, const float* dz, long dz_ld, int col0, int ncols, float* C, long ldc, int epi, const float* Y, long ldy);
+// the same three for head 2 of a twin critic (layers [cat, nfc) of ws[0]); twin_dx_args at the concat layer adds into C (head 1's
+// term is there already) before the epilogue: "(head 1) + (head 2), then the mask"
+GemmArgs twin_fwd_args(cpp_net* n, Workspace& w, int l, int B);
+GemmArgs twin_dw_args(cpp_net* n, Workspace& w, int l, int B);
+GemmArgs twin_dx_args(cpp_net* n, Workspace& w, int l, int B);
+int twin_forward_fc(cpp_net* n, Workspace& w, int B);
 int batch_stats(cpp_ctx* ctx, const void* s0, const void* s1, int dtype, long elems, int B, int C, double* part, float* white);
 int batch_ensure_stats(cpp_batch* b, int C);
 uint64_t replay_next_uid();      // graph keys: a fresh uid per cpp_replay_create and per change of a sampled memory's statistics setting

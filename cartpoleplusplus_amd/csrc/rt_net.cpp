@@ -55,6 +55,18 @@ static int net_build(cpp_net* n) {
     n->cat_layer = 0;
     add_fc("q_value", n_in, 1, GE_NONE, 0);
   }
+  // twin Q heads: a second copy of the layers from the concat layer upward, behind the plain critic's variables (whose names, shapes
+  // and offsets stay what they are): 'hidden3b', 'q_valueb' (pixel), 'h<i>b', 'q_valueb' (low-dimensional: the whole stack)
+  if (n->twin) {
+    const std::vector<FcL> head1 = n->fc;
+    n->fc2 = head1;
+    for (int l = n->cat_layer; l < (int)head1.size(); ++l) {
+      const FcL L = head1[l];
+      add_fc(L.name + "b", L.n_in, L.n_out, L.act, L.cat);
+      n->fc2[l] = n->fc.back();
+      n->fc.pop_back();
+    }
+  }
   n->nparams = off;
   return CPP_OK;
 }
@@ -71,6 +83,20 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
     RC(dalloc(n->arena, &w.dz[l], (size_t)mb * L.n_out));
   }
   RC(dalloc(n->arena, &w.out, (size_t)mb * n->fc.back().n_out));
+  if (n->twin && trunk) {      // (head 2 runs on the fed action only: the first workspace)
+    w.fcin2.assign(nfc, nullptr);
+    w.dz2.assign(nfc, nullptr);
+    for (int l = n->cat_layer; l < nfc; ++l) {
+      const FcL& L = n->fc2[l];
+      if (l == n->cat_layer) w.fcin2[l] = w.fcin[l];
+      else {
+        RC(dalloc(n->arena, &w.fcin2[l], (size_t)mb * (L.n_in + 1)));
+        RC(launch_fill(n->ctx, w.fcin2[l], L.n_in + 1, L.n_in, 1, mb, 1.0f));
+      }
+      RC(dalloc(n->arena, &w.dz2[l], (size_t)mb * L.n_out));
+    }
+    RC(dalloc(n->arena, &w.out2, (size_t)mb * n->fc2.back().n_out));
+  }
   if (trunk && n->spec.pixel) {
     for (int i = 0; i < 3; ++i) {
       const ConvL& L = n->conv[i];
@@ -89,7 +115,20 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
   return CPP_OK;
 }
 
+static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out);
 extern "C" int cpp_net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, cpp_net** out) {
+  return net_create(ctx, spec, max_batch, false, out);
+}
+// A critic whose layers from the concat layer upward exist twice (TD3's clipped double-Q on a shared representation; an extension of
+// ddpg_cartpole.py:166-171): see include/cartpolepp_abi.h
+extern "C" int cpp_net_create_twin_q(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, cpp_net** out) {
+  ARG_CHECK(ctx && spec && out, "cpp_net_create_twin_q: NULL argument");
+  ARG_CHECK(spec->kind == CPP_CRITIC, "cpp_net_create_twin_q: kind %d (twin Q heads belong to a critic)", spec->kind);
+  return net_create(ctx, spec, max_batch, true, out);
+}
+extern "C" int cpp_net_is_twin_q(const cpp_net* n) { return (n && n->twin) ? 1 : 0; }
+
+static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out) {
   ARG_CHECK(ctx && spec && out, "cpp_net_create: NULL argument");
   ARG_CHECK(max_batch >= 1, "cpp_net_create: max_batch %d", max_batch);
   ARG_CHECK(spec->kind == CPP_ACTOR || spec->kind == CPP_CRITIC || spec->kind == CPP_HEAD, "cpp_net_create: kind %d", spec->kind);
@@ -113,6 +152,7 @@ extern "C" int cpp_net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_ba
   n->stage_out = nullptr; n->dw_partial[0] = n->dw_partial[1] = n->dw_partial[2] = nullptr; n->white = nullptr; n->white_rows = nullptr; n->stats_part = nullptr;
   n->img_slot = nullptr; n->use_b16 = false; n->wimg = nullptr; n->wimg_key = nullptr;
   n->is_training = true; n->drop_counter = nullptr; n->bn_part = nullptr; n->bn_means = nullptr; n->bn_scratch = nullptr;
+  n->twin = twin;
   int rc = net_build(n);
   if (rc) { delete n; return rc; }
   auto fail = [&](int r) { n->arena.release(); delete n; return r; };
@@ -121,6 +161,7 @@ extern "C" int cpp_net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_ba
   if ((rc = ws_alloc(n, n->ws[0], 0, true))) return fail(rc);
   if (spec->kind == CPP_CRITIC) {
     n->ws[1] = n->ws[0];
+    n->ws[1].fcin2.clear(); n->ws[1].dz2.clear(); n->ws[1].out2 = nullptr;
     if ((rc = ws_alloc(n, n->ws[1], n->cat_layer, false))) return fail(rc);
     for (int l = 0; l < n->cat_layer; ++l) { n->ws[1].fcin[l] = n->ws[0].fcin[l]; n->ws[1].dz[l] = n->ws[0].dz[l]; }
     for (int i = 0; i < 3; ++i) { n->ws[1].pool[i] = n->ws[0].pool[i]; n->ws[1].amax[i] = n->ws[0].amax[i]; n->ws[1].dpool[i] = n->ws[0].dpool[i]; n->ws[1].dpool_imax = n->ws[0].dpool_imax;
@@ -495,6 +536,13 @@ int net_backward(cpp_net* n, Workspace& w, int B, bool want_params, float* d_act
   const int nfc = (int)n->fc.size(), A = n->spec.action_dim;
   if (want_params && !n->grads) { cpp_set_error("network has no gradient buffer"); return CPP_ERR_STATE; }
   if (start_layer == -2) start_layer = nfc - 1;       // -1: only the conv trunk (w.dpool[2] already holds d flat)
+  // twin Q heads (the critic's train op): head 2's chain down to the concat layer first; its term joins the shared layer's dz below
+  const bool twin = n->twin && want_params && start_layer == nfc - 1 && !w.dz2.empty();
+  if (twin)
+    for (int l = nfc - 1; l >= n->cat_layer; --l) {
+      RC(launch_gemm(ctx, twin_dw_args(n, w, l, B)));
+      if (l > n->cat_layer) RC(launch_gemm(ctx, twin_dx_args(n, w, l, B)));
+    }
   for (int l = start_layer; l >= 0; --l) {
     const FcL& L = n->fc[l];
     const float* dz = w.dz[l];
@@ -505,7 +553,10 @@ int net_backward(cpp_net* n, Workspace& w, int B, bool want_params, float* d_act
       if (d_action)     // dQ/da: the action columns of dz W^T (ddpg_cartpole.py:222)
         RC(gemm(ctx, dz, L.n_out, 1, W + (long)(L.n_in - A) * L.n_out, 1, L.n_out, d_action, A, B, A, L.n_out, GE_NONE));
       if (!want_params) return CPP_OK;
-      if (l > 0)
+      if (l > 0 && twin) {      // (head 1) + (head 2), then the mask
+        RC(gemm(ctx, dz, L.n_out, 1, W, 1, L.n_out, w.dz[l - 1], L.n_in - A, B, L.n_in - A, L.n_out, GE_NONE));
+        RC(launch_gemm(ctx, twin_dx_args(n, w, l, B)));
+      } else if (l > 0)
         RC(gemm(ctx, dz, L.n_out, 1, W, 1, L.n_out, w.dz[l - 1], L.n_in - A, B, L.n_in - A, L.n_out,
                 relu_grad_epi(n, l - 1), w.fcin[l], L.n_in + 1));
     } else if (l > 0) {
@@ -563,6 +614,34 @@ GemmArgs fc_dx_args(cpp_net* n, int l, int B, const float* dz, long dz_ld, int c
                            int epi, const float* Y, long ldy) {
   const FcL& L = n->fc[l];
   return mk_gemm(dz, dz_ld, 1, n->params + L.w_off + (long)col0 * L.n_out, 1, L.n_out, C, ldc, B, ncols, L.n_out, epi, Y, ldy);
+}
+
+// ---- head 2 of a twin critic: layers [cat, nfc) of the first workspace
+GemmArgs twin_fwd_args(cpp_net* n, Workspace& w, int l, int B) {
+  const FcL& L = n->fc2[l];
+  const int nfc = (int)n->fc2.size();
+  float* C = (l + 1 < nfc) ? w.fcin2[l + 1] : w.out2;
+  const long ldc = (l + 1 < nfc) ? n->fc2[l + 1].n_in + 1 : L.n_out;
+  return mk_gemm(w.fcin2[l], L.n_in + 1, 1, n->params + L.w_off, L.n_out, 1, C, ldc, B, L.n_out, L.n_in + 1, L.act);
+}
+GemmArgs twin_dw_args(cpp_net* n, Workspace& w, int l, int B) {
+  const FcL& L = n->fc2[l];
+  return mk_gemm(w.fcin2[l], 1, L.n_in + 1, w.dz2[l], L.n_out, 1, n->grads + L.w_off, L.n_out, L.n_in + 1, L.n_out, B, GE_NONE);
+}
+// l > cat: dz2[l - 1] = (dz2[l] W2^T) relu'(fcin2[l]); l == cat (> 0): the shared layer's dz += dz2[cat] W2^T (state columns), then its mask
+GemmArgs twin_dx_args(cpp_net* n, Workspace& w, int l, int B) {
+  const FcL& L = n->fc2[l];
+  if (l > n->cat_layer)
+    return mk_gemm(w.dz2[l], L.n_out, 1, n->params + L.w_off, 1, L.n_out, w.dz2[l - 1], L.n_in, B, L.n_in, L.n_out, GE_MUL_RELU_GRAD, w.fcin2[l], L.n_in + 1);
+  const int ncols = L.n_in - n->spec.action_dim;
+  GemmArgs g = mk_gemm(w.dz2[l], L.n_out, 1, n->params + L.w_off, 1, L.n_out, w.dz[l - 1], ncols, B, ncols, L.n_out, relu_grad_epi(n, l - 1), w.fcin[l], L.n_in + 1);
+  g.accumulate = 1;
+  return g;
+}
+// head 2's forward behind head 1's on the same concat input (the single train ops, check_loss)
+int twin_forward_fc(cpp_net* n, Workspace& w, int B) {
+  for (int l = n->cat_layer; l < (int)n->fc2.size(); ++l) RC(launch_gemm(n->ctx, twin_fwd_args(n, w, l, B)));
+  return CPP_OK;
 }
 
 // whitening statistics of a device-resident (B, H*W*C) batch -> white[2][C]

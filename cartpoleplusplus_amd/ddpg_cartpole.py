@@ -154,6 +154,11 @@ def build_parser():
     a('--policy-delay', type=int, default=argparse.SUPPRESS,
       help="apply the actor's update with every D-th critic update only (default 1: every minibatch); with --batches-per-step D the "
            "actor moves in the outer step's last minibatch and the targets follow it: TD3's schedule")
+    # twin Q heads (an extension beyond the reference, ddpg_cartpole.py:166-171, :199-209: TD3's clipped double-Q, Fujimoto et al. 2018,
+    # on a shared representation as in DrQ-v2): the critic's layers from the concat layer upward exist twice, the target takes the smaller
+    # of the two target heads (absent from the parsed options unless given, like --ddpg-optimiser; twin_q() reads it with its default)
+    a('--twin-q', action='store_true', default=argparse.SUPPRESS,
+      help="critics with two Q heads on one representation; both regress onto r + discount * min(Q1', Q2'), the actor follows Q1")
     return parser
 
 
@@ -230,6 +235,11 @@ def policy_delay(o):
     return d
 
 
+def twin_q(o):
+    """--twin-q; off unless given"""
+    return bool(getattr(o, "twin_q", False))
+
+
 def priority_beta(o, train_steps):
     """beta of the outer train step `train_steps` (linear from --priority-beta to --priority-beta-final)"""
     n = max(1, int(o.priority_beta_steps))
@@ -252,6 +262,7 @@ def default_opts(**overrides):
     o.ddpg_optimiser, o.ddpg_optimiser_args = "GradientDescent", "{}"
     o.target_policy_noise, o.target_policy_noise_clip, o.target_policy_noise_seed = _TARGET_SMOOTHING_DEFAULTS
     o.policy_delay = _POLICY_DELAY_DEFAULT
+    o.twin_q = False
     for k, v in overrides.items():
         assert hasattr(o, k), k
         setattr(o, k, v)
@@ -465,6 +476,14 @@ class _Trainer(object):
         check(lib.cpp_ddpg_last_values(self.handle, B, ptr(actions), ptr(dq_da), ptr(q), ptr(td)))
         return actions, dq_da, q, td
 
+    def last_twin_values(self, B):
+        """(q2, target_q1, target_q2, td2) of the last minibatch's gradient pass of a --twin-q trainer, each (B, 1): head 2 on the fed
+        action, the two target heads at the (smoothed) target action, head 2's temporal difference (last_values has head 1's)"""
+        B = int(B)
+        out = [np.empty((B, 1), np.float32) for _ in range(4)]
+        check(lib.cpp_ddpg_last_twin_values(self.handle, B, *[ptr(x) for x in out]))
+        return tuple(out)
+
     def set_target_smoothing(self, sigma, clip, seed):
         """target policy smoothing of the critic's target (include/cartpolepp_abi.h, cpp_ddpg_set_target_smoothing): sigma > 0 switches
         it on, (0, 0, seed) off; zeroes the count of target-forming passes and drops the captured graphs."""
@@ -543,7 +562,9 @@ class CriticNetwork(base_network.Network):
         else:
             # flatten(state) | action -> hidden stack (:172-177; B1: opts=None means no dropout)
             self.hidden_layers_starting_at(self.input_state, opts.critic_hidden_layers)
-        self._build_native(_lib.CPP_CRITIC, self.action_dim, max(int(opts.batch_size), 1))
+        # --twin-q: hidden3 / q_value (low-dimensional: the whole stack) twice; q_value, forward and dQ/da stay head 1's
+        self.twin_q = twin_q(opts)
+        self._build_native(_lib.CPP_CRITIC, self.action_dim, max(int(opts.batch_size), 1), twin_q=self.twin_q)
         self.q_value = _OpHandle(namespace + "/q_value")
         self.target_critic = None
         self._ddpg = None

@@ -136,6 +136,22 @@ typedef struct cpp_net_spec {
 } cpp_net_spec;
 
 int cpp_net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, cpp_net** out);
+/* Twin Q heads (TD3's clipped double-Q, Fujimoto et al. 2018, Algorithm 1, on a shared representation as in DrQ-v2), an extension of
+ * the critic ddpg_cartpole.py:166-171 (pixel) / :172-177 (low-dimensional): a critic whose layers from the concat layer upward exist
+ * twice.  The first cpp_net_num_params(plain critic) floats of the flat buffer are laid out exactly as cpp_net_create's critic --
+ * names, shapes, offsets --; the twin variables follow in creation order: 'hidden3b/weights', 'hidden3b/biases', 'q_valueb/weights',
+ * 'q_valueb/biases' (pixel); 'h<i>b/...' for every hidden layer, then 'q_valueb/...' (low-dimensional: the whole stack is twinned,
+ * which is TD3 exactly).  spec->kind must be CPP_CRITIC (CPP_ERR_ARG otherwise).  Head 1 is the plain critic's: cpp_net_forward*
+ * evaluate it and never read head 2.  A trainer built on twin critics (cpp_ddpg_create: both critics, or neither) is a twin trainer:
+ *     y = r + mask discount min(Q1'(s2, a'), Q2'(s2, a')),  td_k = Q_k(s1, a) - y,  loss = mean_b(w_b (td_1^2 + td_2^2))
+ * with ONE a' for both target heads (target policy smoothing: one noise draw).  The gradient into the shared layer below the concat
+ * layer is head 1's term plus head 2's, added in that order, then the ReLU mask.  The actor follows dQ1/da only; priorities,
+ * cpp_ddpg_last_values, cpp_ddpg_check_loss's td and q and q_gradients_wrt_actions stay head 1's; the loss they report is the twin
+ * loss.  The clip's norm, the optimiser slots, the soft update and the collectives cover the longer buffer.  cpp_naf_create refuses
+ * twin networks. */
+int cpp_net_create_twin_q(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, cpp_net** out);
+/* 1 for a network made by cpp_net_create_twin_q, 0 for any other (NULL included) */
+int cpp_net_is_twin_q(const cpp_net* net);
 int cpp_net_destroy(cpp_net* net);
 /* Network.trainable_model_vars (base_network.py:51-56): variables in creation order. */
 int64_t cpp_net_num_params(const cpp_net* net);
@@ -432,6 +448,10 @@ int cpp_ddpg_last_stats(cpp_ddpg* ddpg, float out[3]);
  * what the reference prints under VERBOSE_DEBUG (ddpg_cartpole.py:339-349).  NULL pointers are skipped.  Parity tests read
  * the fused step's values through this call. */
 int cpp_ddpg_last_values(cpp_ddpg* ddpg, int B, float* actions, float* dq_da, float* q, float* td);
+/* Twin trainers (cpp_net_create_twin_q; an extension of the target ddpg_cartpole.py:199-214): what head 2 and the two target heads left
+ * in the last minibatch's gradient pass -- Q2(state_1, fed action), Q1'(state_2, a'), Q2'(state_2, a') and td_2 = Q2 - y, each (B).
+ * NULL pointers are skipped.  CPP_ERR_STATE on a trainer of plain critics. */
+int cpp_ddpg_last_twin_values(cpp_ddpg* ddpg, int B, float* q2, float* target_q1, float* target_q2, float* td2);
 
 /* ---- data-parallel actor-learners (the reference's TODO "switch back to async training with multiple replicas",
  * ddpg_cartpole.py:259, naf_cartpole.py:294; its exps only launch independent processes, exps/run_87.sh:12-36) ------------
