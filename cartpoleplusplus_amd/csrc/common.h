@@ -59,6 +59,7 @@ enum KernelId {
   K_ALLREDUCE,            // the data-parallel step's gradient all-reduce (RCCL), as the stream sees it between the gradient kernels and the update
   K_CONV1_IMAGE,          // conv1's operand images as a launch of their own (conv_rs16.h; in the fused step they ride in the optimiser's launch)
   K_PER,                  // prioritized replay: sum-tree updates, draws and importance weights (per.hip)
+  K_DIST,                 // distributional critic: softmax / expectation, projected target and cross-entropy (dist.hip)
   K_NUM_KERNELS
 };
 
@@ -513,6 +514,15 @@ struct DdpgHeadsArgs {
   float *q2_out, *tq2_out, *td2, *dzq2, *dz3b;
 };
 enum { PD_N = 0, PD_HOLD = 1, PD_PHASE = 2, PD_WORDS = 3 };
+// ---- distributional (categorical) critic (dist.hip; include/cartpolepp_abi.h, cpp_net_create_distributional).  logits: (B, N), N in [2, 64].
+// job (a): q_out[b] = Q = sum_i p_i z_i and, dz != nullptr, dz[b][i] = p_i (z_i - Q)
+int launch_dist_expect(cpp_ctx* ctx, const float* logits, int B, int N, float v_min, float v_max, float* q_out, float* dz);
+// job (b): Q, Q', p, p', the projected target m (each (B, N)), td = Q - sum_i m_i z_i, dz = (w_b / B) (p - m) (nullptr: none, check_loss) and
+// the per-workgroup sums of w_b L_b in loss_part[dist_td_grid(B)] (f64, finalised on the host like the heads kernel's).  w == nullptr: uniform.
+int dist_td_grid(int B);
+int launch_dist_td(cpp_ctx* ctx, const float* logits, const float* tlogits, const float* r, const float* mask, float discount, int B, int N,
+                   float v_min, float v_max, float* q_out, float* tq_out, float* p_out, float* tp_out, float* m_out, float* td, float* dz,
+                   double* loss_part, const float* w = nullptr);
 // the same count where the heads kernel does not carry it (GEMM-level paths, the stand-alone ops, cpp_ddpg_apply_gradients): one thread, in
 // front of the optimiser's launch.  step: the two optimisers' step counts or nullptr (GradientDescent).  peek (cpp_ddpg_train_actor: the
 // actor half of the minibatch whose critic half follows): n stays, the hold word is that of n + 1.

@@ -11,7 +11,7 @@ struct cpp_ddpg {
   float* gradbuf; float *dq_da, *td, *dq, *loss_norms /* [0] loss [1] actor norm [2] critic norm */, *ones;
   double* norm_part;
   double* heads_part;                              // fused heads kernel: per-workgroup partial sums of td^2
-  int heads_grid, heads_B;                         // ... of the last graph built by compute_gradients (0: GEMM levels + td_kernel)
+  int heads_grid, heads_B;                         // ... of the last graph built by compute_gradients (0: GEMM levels + td_kernel; a distributional trainer's GEMM levels: dist_td_kernel's grid, its partials live in heads_part too)
   int loss_parts, loss_B;                          // how cpp_ddpg_last_stats finds the loss of the last call: partials to add, or loss_norms[0]
   // graph replay of the full inner step (the sampler's range is read from the replay's device size word: one graph survives growth)
   StepGraph graph;
@@ -57,7 +57,26 @@ struct cpp_ddpg {
   // twin Q heads (cpp_net_create_twin_q: both critics are twin critics, or neither): head 2's temporal difference, maxB.  The trainer
   // has no switch of its own -- what the critics are decides every path
   bool twin = false; float* td2 = nullptr;
+  // distributional critic (cpp_net_create_distributional: both critics with one (N, v_min, v_max), or neither): what the last gradient
+  // pass left for cpp_ddpg_last_distribution -- p of the fed evaluation, p' of the target evaluation, the projected target m, each
+  // maxB x N.  Such a trainer always takes the GEMM levels of compute_gradients; dist.hip stands where td_kernel and `ones` stand
+  int dist_n = 0; float *dist_p = nullptr, *dist_tp = nullptr, *dist_m = nullptr;
 };
+
+// the minibatch's loss from the per-workgroup partials of the heads kernel or of dist.hip's job (b), added in a fixed order
+static float loss_of_parts(const double* parts, int n, int B) {
+  double s = 0.0;
+  for (int i = 0; i < n; ++i) s += parts[i];
+  return (float)(s / (double)B);
+}
+
+// job (b) of dist.hip on the fed and the target evaluation the forward passes left in the first workspaces
+static int dist_td(cpp_ddpg* d, const cpp_batch* b, int B, bool backward, const float* w) {
+  cpp_net *c = d->critic, *tc = d->tcritic;
+  return launch_dist_td(d->ctx, c->ws[0].logits, tc->ws[0].logits, b->r, b->m, d->hp.discount, B, d->dist_n, c->dist_vmin, c->dist_vmax,
+                        c->ws[0].out, tc->ws[0].out, d->dist_p, d->dist_tp, d->dist_m, d->td, backward ? c->ws[0].dz[c->fc.size() - 1] : nullptr,
+                        d->heads_part, w);
+}
 
 extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cpp_net* tactor, cpp_net* tcritic,
                                const cpp_ddpg_hyper* hp, cpp_ddpg** out) {
@@ -66,6 +85,10 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   ARG_CHECK(critic->spec.kind == CPP_CRITIC && tcritic->spec.kind == CPP_CRITIC, "cpp_ddpg_create: critic kinds");
   ARG_CHECK(!actor->twin && !tactor->twin, "cpp_ddpg_create: a twin actor");
   ARG_CHECK(critic->twin == tcritic->twin, "cpp_ddpg_create: a twin critic needs a twin target critic (and a plain one a plain one)");
+  ARG_CHECK(!actor->dist_n && !tactor->dist_n, "cpp_ddpg_create: a distributional actor");
+  ARG_CHECK(critic->dist_n == tcritic->dist_n && critic->dist_vmin == tcritic->dist_vmin && critic->dist_vmax == tcritic->dist_vmax,
+            "cpp_ddpg_create: critic and target critic must carry one value distribution (N, v_min, v_max), or none");
+  ARG_CHECK(!(critic->dist_n && critic->twin), "cpp_ddpg_create: a distributional critic with twin Q heads");
   ARG_CHECK(actor->nparams == tactor->nparams && critic->nparams == tcritic->nparams, "cpp_ddpg_create: target shapes differ");
   ARG_CHECK(actor->state_elems == critic->state_elems && actor->spec.action_dim == critic->spec.action_dim,
             "cpp_ddpg_create: actor/critic input shapes differ");
@@ -97,6 +120,13 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   if (!rc) rc = dalloc(d->arena, &d->heads_part, (size_t)DDPG_HEADS_MAX_WGS);
   d->twin = critic->twin;
   if (!rc && d->twin) rc = dalloc(d->arena, &d->td2, (size_t)d->maxB);
+  d->dist_n = critic->dist_n;
+  if (d->dist_n && dist_td_grid(d->maxB) > DDPG_HEADS_MAX_WGS) {
+    cpp_set_error("cpp_ddpg_create: a distributional trainer takes batches up to %d (got %d)", 4 * DDPG_HEADS_MAX_WGS, d->maxB);
+    rc = CPP_ERR_ARG;
+  }
+  for (float** p : {&d->dist_p, &d->dist_tp, &d->dist_m})
+    if (!rc && d->dist_n) rc = dalloc(d->arena, p, (size_t)d->maxB * d->dist_n);
   if (!rc) rc = launch_fill(ctx, d->ones, 1, 0, 1, d->maxB, 1.0f);
   if (rc) { d->arena.release(); delete d; return rc; }
   actor->grads = d->gradbuf; critic->grads = d->gradbuf + d->nA;
@@ -190,6 +220,8 @@ static int critic_head(cpp_net* c, int wi, const float* action, int B) {
     RC(launch_copy_cols(c->ctx, c->ws[1].fcin[cl], L.n_in + 1, 0, c->ws[0].fcin[cl], L.n_in + 1, 0, L.n_in - A, B));
   }
   RC(net_forward_fc(c, c->ws[wi], cl, B, action));
+  // (a distributional critic's second evaluation: Q, and p (z - Q) where the scalar critic's q layer is fed ones)
+  if (c->dist_n && wi == 1) return dist_expect(c, c->ws[1], B, c->ws[1].dz[c->fc.size() - 1]);
   return (c->twin && wi == 0) ? twin_forward_fc(c, c->ws[0], B) : CPP_OK;      // (head 2 reads the same concat input)
 }
 
@@ -205,7 +237,7 @@ static int actor_gradients(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done) {
   RC(critic_head(c, 1, a->ws[0].out, B));
   // d(sum_b Q)/da: dz of the linear q layer is 1
   const int last = (int)c->fc.size() - 1;
-  RC(launch_copy_cols(d->ctx, c->ws[1].dz[last], 1, 0, d->ones, 1, 0, 1, B));
+  if (!c->dist_n) RC(launch_copy_cols(d->ctx, c->ws[1].dz[last], 1, 0, d->ones, 1, 0, 1, B));
   // walk back to the splice (hidden layers after the splice are ReLU)
   for (int l = last; l > c->cat_layer; --l) {
     const FcL& L = c->fc[l];
@@ -254,6 +286,12 @@ static int critic_gradients_impl(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_d
   if (!critic_prefix_done) RC(critic_prefix(c, b->s[0], b->dtype, w1, B));
   RC(critic_head(c, 0, b->a, B));
   const int last = (int)c->fc.size() - 1;
+  if (d->dist_n) {
+    RC(dist_td(d, b, B, backward, nullptr));
+    d->loss_parts = dist_td_grid(B); d->loss_B = B;
+    if (backward) RC(net_backward(c, c->ws[0], B, true, nullptr, b->s[0], b->dtype, w1));
+    return CPP_OK;
+  }
   if (d->twin)
     RC(launch_td_twin(d->ctx, c->ws[0].out, c->ws[0].out2, tc->ws[0].out, tc->ws[0].out2, b->r, b->m, d->hp.discount, B, d->td, d->td2,
                       backward ? c->ws[0].dz[last] : nullptr, backward ? c->ws[0].dz2[last] : nullptr, d->loss_norms));
@@ -382,10 +420,14 @@ extern "C" int cpp_ddpg_check_loss(cpp_ddpg* d, cpp_batch* b, float* loss, float
   RC(prep_batch(d, b));
   RC(critic_gradients(d, b, false, false));
   hipStream_t st = d->ctx->stream;
-  if (loss) HIP_CHECK(hipMemcpyAsync(loss, d->loss_norms, sizeof(float), hipMemcpyDeviceToHost, st));
+  double parts[DDPG_HEADS_MAX_WGS];      // (a distributional trainer: the cross-entropy from its per-workgroup partials, as cpp_ddpg_last_stats)
+  const int nparts = d->dist_n ? d->loss_parts : 0;
+  if (loss && nparts) HIP_CHECK(hipMemcpyAsync(parts, d->heads_part, (size_t)nparts * sizeof(double), hipMemcpyDeviceToHost, st));
+  else if (loss) HIP_CHECK(hipMemcpyAsync(loss, d->loss_norms, sizeof(float), hipMemcpyDeviceToHost, st));
   if (td) HIP_CHECK(hipMemcpyAsync(td, d->td, (size_t)b->B * sizeof(float), hipMemcpyDeviceToHost, st));
   if (q) HIP_CHECK(hipMemcpyAsync(q, d->critic->ws[0].out, (size_t)b->B * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
+  if (loss && nparts) *loss = loss_of_parts(parts, nparts, d->loss_B);
   return CPP_OK;
 }
 
@@ -477,7 +519,8 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   static const bool no_heads = cpp_switch_off("CPP_FUSED_HEADS");
   DdpgHeadsArgs hd; memset(&hd, 0, sizeof(hd));
   const bool twin = d->twin;
-  bool fused = !no_heads && na >= 2 && cat >= 1 && nc - cat == 2 && a->fc[na - 1].act == GE_TANH && Lcat.act == GE_RELU &&
+  const int dist = d->dist_n;      // (its q layer has N outputs: never the fused heads)
+  bool fused = !dist && !no_heads && na >= 2 && cat >= 1 && nc - cat == 2 && a->fc[na - 1].act == GE_TANH && Lcat.act == GE_RELU &&
                c->fc[nc - 1].n_out == 1 && c->fc[nc - 1].act == GE_NONE && a->fc[na - 1].n_out == A;
   if (fused) {
     const FcL& Lo = a->fc[na - 1];
@@ -520,7 +563,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   }
   const int pre = (fused && hd.n1a > 0) ? 1 : 0;
   d->step_bumped = fused && (hd.step_bump != nullptr || hd.pd != nullptr);
-  d->heads_grid = fused ? (B + 3) / 4 : 0; d->heads_B = B;
+  d->heads_grid = fused ? (B + 3) / 4 : (dist ? dist_td_grid(B) : 0); d->heads_B = B;
   d->loss_parts = d->heads_grid; d->loss_B = B;
   int adz, cdz;
   if (fused) {
@@ -615,14 +658,17 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
 
   // ---- dQ/da at a = actor(s1): back through q_value .. splice on the second evaluation (dz of q is 1)
   int g = c1;
+  // (a distributional critic: the gradient of the expectation, p (z - Q), stands where the scalar critic's q layer is fed ones)
+  if (dist) g = G.fn([=] { return dist_expect(c, c->ws[1], B, c->ws[1].dz[nc - 1]); }, {c1});
+  const float* top = dist ? c->ws[1].dz[nc - 1] : d->ones;
   for (int l = nc - 1; l > cat; --l) {
     const FcL& L = c->fc[l];
-    const float* dz = (l == nc - 1) ? d->ones : c->ws[1].dz[l];
+    const float* dz = (l == nc - 1) ? top : c->ws[1].dz[l];
     g = G.gemm(fc_dx_args(c, l, B, dz, L.n_out, 0, L.n_in, c->ws[1].dz[l - 1], L.n_in, GE_MUL_RELU_GRAD,
                           c->ws[1].fcin[l], L.n_in + 1), {g});
   }
   {   // dQ/da (kept for cpp_ddpg_q_gradients_wrt_actions) and, in the same epilogue, the actor's head gradient
-    const float* dz = (cat == nc - 1) ? d->ones : c->ws[1].dz[cat];
+    const float* dz = (cat == nc - 1) ? top : c->ws[1].dz[cat];
     GemmArgs ga = fc_dx_args(c, cat, B, dz, Lcat.n_out, Lcat.n_in - A, A, d->dq_da, A, GE_ACTOR_HEAD, a->ws[0].out, A);
     ga.C2 = a->ws[0].dz[na - 1]; ga.ldc2 = A;
     adz = G.gemm(ga, {g, aF});
@@ -641,7 +687,9 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
 
   // ---- TD target + critic backward on the first evaluation (fed actions)
   const float* per_w = d->per_w;
-  if (twin)
+  if (dist)
+    cdz = G.fn([=] { return dist_td(d, b, B, true, per_w); }, {c0, tcH});
+  else if (twin)
     cdz = G.fn([=] { return launch_td_twin(ctx, c->ws[0].out, c->ws[0].out2, tc->ws[0].out, tc->ws[0].out2, b->r, b->m, d->hp.discount, B, d->td, d->td2,
                                            c->ws[0].dz[nc - 1], c->ws[0].dz2[nc - 1], d->loss_norms, per_w); }, {c0, tcH, c0b, tcHb});
   else
@@ -1209,11 +1257,7 @@ extern "C" int cpp_ddpg_last_stats(cpp_ddpg* d, float out[3]) {
   if (d->loss_parts > 0)
     HIP_CHECK(hipMemcpyAsync(parts, d->heads_part, (size_t)d->loss_parts * sizeof(double), hipMemcpyDeviceToHost, d->ctx->stream));
   HIP_CHECK(ctx_sync_stream(d->ctx));
-  if (d->loss_parts > 0) {                          // fused heads kernel: mean(td^2) from its per-workgroup partials, fixed order
-    double s = 0.0;
-    for (int i = 0; i < d->loss_parts; ++i) s += parts[i];
-    out[0] = (float)(s / (double)d->loss_B);
-  }
+  if (d->loss_parts > 0) out[0] = loss_of_parts(parts, d->loss_parts, d->loss_B);      // fused heads kernel: mean(td^2); dist.hip: mean(w L)
   return CPP_OK;
 }
 
@@ -1245,6 +1289,22 @@ extern "C" int cpp_ddpg_last_twin_values(cpp_ddpg* d, int B, float* q2, float* t
   if (target_q1) HIP_CHECK(hipMemcpyAsync(target_q1, d->tcritic->ws[0].out, n, hipMemcpyDeviceToHost, st));
   if (target_q2) HIP_CHECK(hipMemcpyAsync(target_q2, d->tcritic->ws[0].out2, n, hipMemcpyDeviceToHost, st));
   if (td2) HIP_CHECK(hipMemcpyAsync(td2, d->td2, n, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  return CPP_OK;
+}
+
+// Distributional trainers: what the last minibatch's gradient pass left -- p of the fed evaluation, p' of the target evaluation at the
+// (smoothed) target action and the projected target m, each (B, N).  NULL pointers are skipped.
+extern "C" int cpp_ddpg_last_distribution(cpp_ddpg* d, int B, float* p, float* target_p, float* m) {
+  ARG_CHECK(d, "cpp_ddpg_last_distribution: NULL argument");
+  ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_distribution: batch %d outside [1,%d]", B, d->maxB);
+  if (!d->dist_n) { cpp_set_error("cpp_ddpg_last_distribution: the trainer's critics are not distributional"); return CPP_ERR_STATE; }
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  hipStream_t st = d->ctx->stream;
+  const size_t n = (size_t)B * d->dist_n * sizeof(float);
+  if (p) HIP_CHECK(hipMemcpyAsync(p, d->dist_p, n, hipMemcpyDeviceToHost, st));
+  if (target_p) HIP_CHECK(hipMemcpyAsync(target_p, d->dist_tp, n, hipMemcpyDeviceToHost, st));
+  if (m) HIP_CHECK(hipMemcpyAsync(m, d->dist_m, n, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
   return CPP_OK;
 }

@@ -5,6 +5,7 @@
 #include "../../include/cartpolepp_abi.h"
 #include "common.h"
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -80,6 +81,9 @@ struct Workspace {
   // fcin[cat] itself -- both heads read one concat input, and with it one smoothed target action --, the others are its own
   std::vector<float*> fcin2, dz2;
   float* out2 = nullptr;
+  // distributional critic (cpp_net_create_distributional): the last layer's N logits land here, (maxB, N), and `out` holds Q = sum_i p_i z_i,
+  // (maxB), which dist.hip writes -- every reader of `out` keeps its width of one.  nullptr for every other network.
+  float* logits = nullptr;
 };
 
 struct cpp_net {
@@ -105,6 +109,8 @@ struct cpp_net {
   // twin Q heads (TD3's clipped double-Q with a shared representation): fc2[l], l in [cat_layer, nfc), is the second copy of fc[l];
   // its variables follow the plain critic's nparams in the flat buffer.  Empty for every other network.
   bool twin = false; std::vector<FcL> fc2;
+  // distributional critic: N atoms on the support [v_min, v_max] (dist_n == 0: every other network); q_value is (n_in, N)
+  int dist_n = 0; float dist_vmin = 0.f, dist_vmax = 0.f;
 };
 
 struct cpp_batch {
@@ -302,6 +308,10 @@ GemmArgs twin_fwd_args(cpp_net* n, Workspace& w, int l, int B);
 GemmArgs twin_dw_args(cpp_net* n, Workspace& w, int l, int B);
 GemmArgs twin_dx_args(cpp_net* n, Workspace& w, int l, int B);
 int twin_forward_fc(cpp_net* n, Workspace& w, int B);
+// where the last layer's GEMM writes: the logits of a distributional critic, `out` otherwise
+inline float* fc_last_out(const Workspace& w) { return w.logits ? w.logits : w.out; }
+// Q (and, dz != nullptr, p (z - Q)) from the logits the forward left in w: a no-op for every other network
+int dist_expect(cpp_net* n, Workspace& w, int B, float* dz);
 int batch_stats(cpp_ctx* ctx, const void* s0, const void* s1, int dtype, long elems, int B, int C, double* part, float* white);
 int batch_ensure_stats(cpp_batch* b, int C);
 uint64_t replay_next_uid();      // graph keys: a fresh uid per cpp_replay_create and per change of a sampled memory's statistics setting

@@ -48,12 +48,12 @@ static int net_build(cpp_net* n) {
     add_fc("hidden1", n_in, 200, GE_RELU, 0);
     add_fc("hidden2", 200, 50, GE_RELU, 0);
     add_fc("hidden3", 50 + A, 50, GE_RELU, 1); n->cat_layer = 2;
-    add_fc("q_value", 50, 1, GE_NONE, 0);
+    add_fc("q_value", 50, n->dist_n ? n->dist_n : 1, GE_NONE, 0);      // (a distributional critic: N logits)
   } else {                                                              // ddpg_cartpole.py:174-177
     n_in += A;
     for (int i = 0; i < s.n_hidden; ++i) { add_fc("h" + std::to_string(i), n_in, s.hidden[i], GE_RELU, i == 0); n_in = s.hidden[i]; }
     n->cat_layer = 0;
-    add_fc("q_value", n_in, 1, GE_NONE, 0);
+    add_fc("q_value", n_in, n->dist_n ? n->dist_n : 1, GE_NONE, 0);
   }
   // twin Q heads: a second copy of the layers from the concat layer upward, behind the plain critic's variables (whose names, shapes
   // and offsets stay what they are): 'hidden3b', 'q_valueb' (pixel), 'h<i>b', 'q_valueb' (low-dimensional: the whole stack)
@@ -82,6 +82,10 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
     RC(launch_fill(n->ctx, w.fcin[l], L.n_in + 1, L.n_in, 1, mb, 1.0f));   // the bias "ones" column
     RC(dalloc(n->arena, &w.dz[l], (size_t)mb * L.n_out));
   }
+  if (n->dist_n) {      // distributional critic: the logits beside a Q of width one
+    RC(dalloc(n->arena, &w.logits, (size_t)mb * n->dist_n));
+    RC(dalloc(n->arena, &w.out, (size_t)mb));
+  } else
   RC(dalloc(n->arena, &w.out, (size_t)mb * n->fc.back().n_out));
   if (n->twin && trunk) {      // (head 2 runs on the fed action only: the first workspace)
     w.fcin2.assign(nfc, nullptr);
@@ -115,7 +119,7 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
   return CPP_OK;
 }
 
-static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out);
+static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out, int dist_n = 0, float v_min = 0.f, float v_max = 0.f);
 extern "C" int cpp_net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, cpp_net** out) {
   return net_create(ctx, spec, max_batch, false, out);
 }
@@ -128,7 +132,29 @@ extern "C" int cpp_net_create_twin_q(cpp_ctx* ctx, const cpp_net_spec* spec, int
 }
 extern "C" int cpp_net_is_twin_q(const cpp_net* n) { return (n && n->twin) ? 1 : 0; }
 
-static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out) {
+// A critic whose last layer emits N logits over a fixed support (Bellemare et al. 2017; D4PG, Barth-Maron et al. 2018; an extension of
+// ddpg_cartpole.py:166-177): see include/cartpolepp_abi.h
+extern "C" int cpp_net_create_distributional(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, int n_atoms, float v_min, float v_max, cpp_net** out) {
+  ARG_CHECK(ctx && spec && out, "cpp_net_create_distributional: NULL argument");
+  ARG_CHECK(spec->kind == CPP_CRITIC, "cpp_net_create_distributional: kind %d (a value distribution belongs to a critic)", spec->kind);
+  ARG_CHECK(n_atoms >= 2 && n_atoms <= 64, "cpp_net_create_distributional: %d atoms outside [2, 64]", n_atoms);
+  ARG_CHECK(std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max, "cpp_net_create_distributional: support [%g, %g] (finite, v_min < v_max)",
+            (double)v_min, (double)v_max);
+  return net_create(ctx, spec, max_batch, false, out, n_atoms, v_min, v_max);
+}
+extern "C" int cpp_net_distribution_info(const cpp_net* n, int* n_atoms, float* v_min, float* v_max) {
+  ARG_CHECK(n, "cpp_net_distribution_info: NULL argument");
+  if (n_atoms) *n_atoms = n->dist_n;
+  if (v_min) *v_min = n->dist_vmin;
+  if (v_max) *v_max = n->dist_vmax;
+  return CPP_OK;
+}
+int dist_expect(cpp_net* n, Workspace& w, int B, float* dz) {
+  if (!n->dist_n) return CPP_OK;
+  return launch_dist_expect(n->ctx, w.logits, B, n->dist_n, n->dist_vmin, n->dist_vmax, w.out, dz);
+}
+
+static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out, int dist_n, float v_min, float v_max) {
   ARG_CHECK(ctx && spec && out, "cpp_net_create: NULL argument");
   ARG_CHECK(max_batch >= 1, "cpp_net_create: max_batch %d", max_batch);
   ARG_CHECK(spec->kind == CPP_ACTOR || spec->kind == CPP_CRITIC || spec->kind == CPP_HEAD, "cpp_net_create: kind %d", spec->kind);
@@ -153,6 +179,7 @@ static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, boo
   n->img_slot = nullptr; n->use_b16 = false; n->wimg = nullptr; n->wimg_key = nullptr;
   n->is_training = true; n->drop_counter = nullptr; n->bn_part = nullptr; n->bn_means = nullptr; n->bn_scratch = nullptr;
   n->twin = twin;
+  n->dist_n = dist_n; n->dist_vmin = v_min; n->dist_vmax = v_max;
   int rc = net_build(n);
   if (rc) { delete n; return rc; }
   auto fail = [&](int r) { n->arena.release(); delete n; return r; };
@@ -389,7 +416,7 @@ int net_forward_fc(cpp_net* n, Workspace& w, int from, int B, const float* actio
       if (!action) { cpp_set_error("critic forward needs an action batch"); return CPP_ERR_ARG; }
       RC(launch_copy_cols(ctx, w.fcin[l], L.n_in + 1, L.n_in - A, action, A, 0, A, B));
     }
-    float* C = (l + 1 < nfc) ? w.fcin[l + 1] : w.out;
+    float* C = (l + 1 < nfc) ? w.fcin[l + 1] : fc_last_out(w);
     const long ldc = (l + 1 < nfc) ? n->fc[l + 1].n_in + 1 : L.n_out;
     GemmArgs g = mk_gemm(w.fcin[l], L.n_in + 1, 1, n->params + L.w_off, L.n_out, 1, C, ldc, B, L.n_out, L.n_in + 1, L.act, nullptr, 0);
     set_dropout(g, n, l);
@@ -598,7 +625,7 @@ int bump_dropout(cpp_net* n) {      // after every training-mode forward of the 
 GemmArgs fc_fwd_args(cpp_net* n, Workspace& w, int l, int B) {
   const FcL& L = n->fc[l];
   const int nfc = (int)n->fc.size();
-  float* C = (l + 1 < nfc) ? w.fcin[l + 1] : w.out;
+  float* C = (l + 1 < nfc) ? w.fcin[l + 1] : fc_last_out(w);
   const long ldc = (l + 1 < nfc) ? n->fc[l + 1].n_in + 1 : L.n_out;
   GemmArgs g = mk_gemm(w.fcin[l], L.n_in + 1, 1, n->params + L.w_off, L.n_out, 1, C, ldc, B, L.n_out, L.n_in + 1, L.act);
   set_dropout(g, n, l);
@@ -669,7 +696,7 @@ extern "C" int cpp_net_forward(cpp_net* n, const void* state, int state_dtype, i
   ARG_CHECK(n->spec.kind != CPP_CRITIC || action, "cpp_net_forward: critic needs an action batch");
   cpp_ctx* ctx = n->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
-  const int A = n->spec.action_dim, no = n->fc.back().n_out;
+  const int A = n->spec.action_dim, no = n->dist_n ? 1 : n->fc.back().n_out;      // (a distributional critic returns Q)
   if (!n->stage_state) {
     RC(n->arena.alloc(&n->stage_state, (size_t)n->maxB * n->state_elems * sizeof(float), false));
     RC(dalloc(n->arena, &n->stage_action, (size_t)n->maxB * A));
@@ -682,6 +709,7 @@ extern "C" int cpp_net_forward(cpp_net* n, const void* state, int state_dtype, i
   n->is_training = false;                              // IS_TRAINING: False (ddpg_cartpole.py:125)
   int frc = net_forward_trunk(n, n->ws[0], n->stage_state, state_dtype, n->white, B);
   if (!frc) frc = net_forward_fc(n, n->ws[0], 0, B, action ? n->stage_action : nullptr);
+  if (!frc) frc = dist_expect(n, n->ws[0], B, nullptr);
   n->is_training = true;
   if (frc) return frc;
   HIP_CHECK(hipMemcpyAsync(out, n->ws[0].out, (size_t)B * no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -699,7 +727,7 @@ extern "C" int cpp_net_forward_each(cpp_net* n, const void* state, int state_dty
   ARG_CHECK(n->spec.kind != CPP_CRITIC || action, "cpp_net_forward_each: critic needs an action batch");
   cpp_ctx* ctx = n->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
-  const int A = n->spec.action_dim, no = n->fc.back().n_out, C = n->spec.C;
+  const int A = n->spec.action_dim, no = n->dist_n ? 1 : n->fc.back().n_out, C = n->spec.C;
   if (!n->stage_state) {
     RC(n->arena.alloc(&n->stage_state, (size_t)n->maxB * n->state_elems * sizeof(float), false));
     RC(dalloc(n->arena, &n->stage_action, (size_t)n->maxB * A));
@@ -726,6 +754,7 @@ extern "C" int cpp_net_forward_each(cpp_net* n, const void* state, int state_dty
   n->is_training = false;
   int frc = net_forward_trunk(n, n->ws[0], n->stage_state, state_dtype, n->white_rows, B, wbs);
   if (!frc) frc = net_forward_fc(n, n->ws[0], 0, B, action ? n->stage_action : nullptr);
+  if (!frc) frc = dist_expect(n, n->ws[0], B, nullptr);
   n->is_training = true;
   if (frc) return frc;
   HIP_CHECK(hipMemcpyAsync(out, n->ws[0].out, (size_t)B * no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));

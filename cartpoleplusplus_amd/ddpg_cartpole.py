@@ -159,6 +159,19 @@ def build_parser():
     # of the two target heads (absent from the parsed options unless given, like --ddpg-optimiser; twin_q() reads it with its default)
     a('--twin-q', action='store_true', default=argparse.SUPPRESS,
       help="critics with two Q heads on one representation; both regress onto r + discount * min(Q1', Q2'), the actor follows Q1")
+    # distributional critic (an extension beyond the reference, ddpg_cartpole.py:166-177, :199-214: the categorical value distribution of
+    # Bellemare et al. 2017 as D4PG uses it, Barth-Maron et al. 2018): the critic's last layer emits logits over a fixed support, trained
+    # with the projected Bellman target and cross-entropy; the actor ascends the distribution's mean (absent from the parsed options
+    # unless given, like --twin-q; distributional_critic() reads them)
+    a('--distributional-critic', action='store_true', default=argparse.SUPPRESS,
+      help="critics that emit a categorical value distribution over --num-atoms atoms on [--v-min, --v-max] (both required)")
+    a('--num-atoms', type=int, default=argparse.SUPPRESS, help="--distributional-critic: atoms of the support (default 51; 2 .. 64)")
+    a('--v-min', type=float, default=argparse.SUPPRESS, help="--distributional-critic: the support's lower end (no default fits every reward scale)")
+    a('--v-max', type=float, default=argparse.SUPPRESS, help="--distributional-critic: the support's upper end")
+    # n-step returns for this learner (ReplayMemory.enable_n_step; absent unless given): with --prioritized-replay, --data-parallel and
+    # --distributional-critic this is D4PG from the command line
+    a('--n-step', type=int, default=argparse.SUPPRESS,
+      help="train on n-step returns: reward = sum_k discount^k r_k, bootstrap with discount^n (default 1: one-step transitions)")
     return parser
 
 
@@ -240,6 +253,43 @@ def twin_q(o):
     return bool(getattr(o, "twin_q", False))
 
 
+_NUM_ATOMS_DEFAULT, NUM_ATOMS_MAX = 51, 64
+
+
+def distributional_critic(o):
+    """(n_atoms, v_min, v_max) of --distributional-critic / --num-atoms / --v-min / --v-max, or None (off); refuses what cannot be meant."""
+    import math
+    on = bool(getattr(o, "distributional_critic", False))
+    given = [k for k in ("num_atoms", "v_min", "v_max") if getattr(o, k, None) is not None]
+    if not on:
+        if given:
+            raise SystemExit("--%s needs --distributional-critic" % given[0].replace("_", "-"))
+        return None
+    if twin_q(o):
+        raise SystemExit("--distributional-critic cannot be combined with --twin-q (one value distribution, one head)")
+    if "v_min" not in given or "v_max" not in given:
+        raise SystemExit("--distributional-critic needs --v-min and --v-max: no default support fits every reward scale")
+    n = getattr(o, "num_atoms", None)
+    n = _NUM_ATOMS_DEFAULT if n is None else n
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= int(n) <= NUM_ATOMS_MAX:
+        raise SystemExit("--num-atoms %r is not a whole number in [2, %d]" % (n, NUM_ATOMS_MAX))
+    try:
+        v_min, v_max = float(np.float32(o.v_min)), float(np.float32(o.v_max))
+    except (TypeError, ValueError) as e:
+        raise SystemExit("--v-min / --v-max: %s" % e)
+    if not (math.isfinite(v_min) and math.isfinite(v_max) and v_min < v_max):
+        raise SystemExit("--v-min %r, --v-max %r: both finite, --v-min below --v-max" % (o.v_min, o.v_max))
+    return (int(n), v_min, v_max)
+
+
+def n_step(o):
+    """n of --n-step; 1 (off) unless given"""
+    n = getattr(o, "n_step", 1)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= 64:
+        raise SystemExit("--n-step %r is not a whole number in [1, 64]" % (n,))
+    return int(n)
+
+
 def priority_beta(o, train_steps):
     """beta of the outer train step `train_steps` (linear from --priority-beta to --priority-beta-final)"""
     n = max(1, int(o.priority_beta_steps))
@@ -263,6 +313,8 @@ def default_opts(**overrides):
     o.target_policy_noise, o.target_policy_noise_clip, o.target_policy_noise_seed = _TARGET_SMOOTHING_DEFAULTS
     o.policy_delay = _POLICY_DELAY_DEFAULT
     o.twin_q = False
+    o.distributional_critic, o.num_atoms, o.v_min, o.v_max = False, None, None, None
+    o.n_step = 1
     for k, v in overrides.items():
         assert hasattr(o, k), k
         setattr(o, k, v)
@@ -484,6 +536,16 @@ class _Trainer(object):
         check(lib.cpp_ddpg_last_twin_values(self.handle, B, *[ptr(x) for x in out]))
         return tuple(out)
 
+    def last_distribution(self, B):
+        """(p, target_p, m) of the last minibatch's gradient pass of a --distributional-critic trainer, each (B, num_atoms): the fed
+        evaluation's distribution, the target critic's at the (smoothed) target action, the projected Bellman target"""
+        B = int(B)
+        dist = getattr(self.nets[1], "distribution", None)
+        n = dist[0] if dist else 1
+        out = [np.empty((B, n), np.float32) for _ in range(3)]
+        check(lib.cpp_ddpg_last_distribution(self.handle, B, *[ptr(x) for x in out]))
+        return tuple(out)
+
     def set_target_smoothing(self, sigma, clip, seed):
         """target policy smoothing of the critic's target (include/cartpolepp_abi.h, cpp_ddpg_set_target_smoothing): sigma > 0 switches
         it on, (0, 0, seed) off; zeroes the count of target-forming passes and drops the captured graphs."""
@@ -564,7 +626,9 @@ class CriticNetwork(base_network.Network):
             self.hidden_layers_starting_at(self.input_state, opts.critic_hidden_layers)
         # --twin-q: hidden3 / q_value (low-dimensional: the whole stack) twice; q_value, forward and dQ/da stay head 1's
         self.twin_q = twin_q(opts)
-        self._build_native(_lib.CPP_CRITIC, self.action_dim, max(int(opts.batch_size), 1), twin_q=self.twin_q)
+        # --distributional-critic: q_value emits num_atoms logits; q_value, forward and dQ/da are the distribution's mean
+        self.distribution = distributional_critic(opts)
+        self._build_native(_lib.CPP_CRITIC, self.action_dim, max(int(opts.batch_size), 1), twin_q=self.twin_q, distribution=self.distribution)
         self.q_value = _OpHandle(namespace + "/q_value")
         self.target_critic = None
         self._ddpg = None
@@ -649,6 +713,9 @@ class DeepDeterministicPolicyGradientAgent(object):
         self.env = env
         state_shape = self.env.observation_space.shape
         action_dim = self.env.action_space.shape[1]
+        # (the refusals of --distributional-critic and --n-step come before anything exists on the device, as check_prioritized_opts')
+        distributional_critic(opts)
+        n_step(opts)
         # (--exact-products asks for the exact arithmetic contract; without the flag the context keeps whatever mode its owner chose --
         # an explicit Context.set_precision("exact") is not undone, and a second agent on the shared context does not fight the first)
         if getattr(opts, "exact_products", False) and _lib.default_context().precision != "exact":
@@ -660,6 +727,8 @@ class DeepDeterministicPolicyGradientAgent(object):
             check_prioritized_opts(opts)
             self.replay_memory.enable_priorities(opts.priority_alpha, opts.priority_eps, seed=opts.sample_seed)
             self.replay_memory.set_priority_beta(priority_beta(opts, 0))
+        if n_step(opts) > 1:
+            self.replay_memory.enable_n_step(n_step(opts), opts.discount)
         # s1 and s2 placeholders
         batched_state_shape = [None] + list(state_shape)
         s1 = base_network.Placeholder(batched_state_shape)

@@ -152,6 +152,29 @@ int cpp_net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, cpp_ne
 int cpp_net_create_twin_q(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, cpp_net** out);
 /* 1 for a network made by cpp_net_create_twin_q, 0 for any other (NULL included) */
 int cpp_net_is_twin_q(const cpp_net* net);
+/* Distributional (categorical) critic: Bellemare et al. 2017 ("C51") as the critic of D4PG (Barth-Maron et al. 2018), an extension of the
+ * critic ddpg_cartpole.py:166-171 (pixel) / :172-177 (low-dimensional) and of its target :199-214.  The layout is cpp_net_create's critic
+ * except that 'q_value/weights' is (n_in, N) and 'q_value/biases' is (N): the last layer emits N logits.  spec->kind must be CPP_CRITIC,
+ * 2 <= N <= 64, v_min < v_max, both finite (CPP_ERR_ARG otherwise).  All arithmetic below is float32.
+ *   support   z_i = v_min + i * delta,  delta = (v_max - v_min) / (N - 1),  i = 0 .. N-1
+ *   p = softmax(logits), the row maximum subtracted first;  Q = sum_i p_i z_i
+ * cpp_net_forward* return Q (width 1).  A trainer built on such critics (cpp_ddpg_create: both critics with equal (N, v_min, v_max), or
+ * neither; never together with twin Q heads) trains, per row b of the minibatch,
+ *   g    = mask_b * discount              (an n-step memory has folded its powers into mask, as for the scalar target)
+ *   a'   = mu'(s2), smoothed if target policy smoothing is on;   p' = softmax(target critic's logits at (s2, a'))
+ *   Tz_j = clamp(r_b + g * z_j, v_min, v_max),   b_j = (Tz_j - v_min) / delta
+ *   m_i  = sum_j p'_j * max(0, 1 - |b_j - i|),   summed in the order j = 0 .. N-1
+ *   L_b  = -sum_i m_i log p_i(s1, a_fed),   loss = mean_b(w_b L_b)   (w: importance weights, 1 without prioritized replay)
+ * The triangular kernel is the usual floor / ceil scatter of the projection, puts the whole mass on atom b_j when b_j is an integer, needs
+ * no atomics and has one summation order.  The gradient into the fed evaluation's logits is (w_b / B) (p_i - m_i).  The actor follows
+ * dQ/da at a = mu(s1): the gradient entering the critic's last layer on that evaluation is p_i (z_i - Q) where the scalar critic feeds ones.
+ *   y_b  = sum_i m_i z_i  (= r + g Q' whenever no clamp binds),   td_b = Q(s1, a_fed) - y_b
+ * is what priorities, cpp_ddpg_last_values and cpp_ddpg_check_loss's td read; their q is Q; the loss they report is the cross-entropy.
+ * Such a trainer always takes the GEMM levels of the gradient pass; batches up to 1024.  cpp_naf_create refuses such networks.  The support
+ * is not part of a checkpoint: a mismatch in N fails the layout check, (v_min, v_max) are the creator's to keep. */
+int cpp_net_create_distributional(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, int n_atoms, float v_min, float v_max, cpp_net** out);
+/* (N, v_min, v_max) of a network made by cpp_net_create_distributional; n_atoms 0 for any other.  NULL pointers are skipped. */
+int cpp_net_distribution_info(const cpp_net* net, int* n_atoms, float* v_min, float* v_max);
 int cpp_net_destroy(cpp_net* net);
 /* Network.trainable_model_vars (base_network.py:51-56): variables in creation order. */
 int64_t cpp_net_num_params(const cpp_net* net);
@@ -452,6 +475,9 @@ int cpp_ddpg_last_values(cpp_ddpg* ddpg, int B, float* actions, float* dq_da, fl
  * in the last minibatch's gradient pass -- Q2(state_1, fed action), Q1'(state_2, a'), Q2'(state_2, a') and td_2 = Q2 - y, each (B).
  * NULL pointers are skipped.  CPP_ERR_STATE on a trainer of plain critics. */
 int cpp_ddpg_last_twin_values(cpp_ddpg* ddpg, int B, float* q2, float* target_q1, float* target_q2, float* td2);
+/* Distributional trainers (cpp_net_create_distributional): p of the fed evaluation, p' of the target evaluation and the projected target m
+ * of the last minibatch's gradient pass, each (B, N).  NULL pointers are skipped.  CPP_ERR_STATE on any other trainer. */
+int cpp_ddpg_last_distribution(cpp_ddpg* ddpg, int B, float* p, float* target_p, float* m);
 
 /* ---- data-parallel actor-learners (the reference's TODO "switch back to async training with multiple replicas",
  * ddpg_cartpole.py:259, naf_cartpole.py:294; its exps only launch independent processes, exps/run_87.sh:12-36) ------------

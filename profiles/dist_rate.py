@@ -1,0 +1,91 @@
+#!/usr/bin/env python
+"""The distributional critic's cost in the fused DDPG step: cfg3 (64x64x18, B = 256, 5 minibatches per outer step, 22 000 synthetic rows),
+a trainer of plain critics against one of distributional critics (--distributional-critic --num-atoms 51 --v-min -10 --v-max 10: the
+GEMM levels of the gradient pass with csrc/dist.hip's two launches per minibatch), ONE process, two agents, alternating timed blocks of
+hipGraph-replayed outer steps.  Then the launches alone, event-timed both ways (the library's profiling mode: the eager launch sequence
+with an event pair around every launch), alternating as well.  Two runs say two things:
+    dist_rate.py                                             the plain trainer on its default route (the fused heads launch): what a user pays
+    CARTPOLEPP_ABLATION=1 CPP_FUSED_HEADS=0 dist_rate.py     the plain trainer on the SAME GEMM levels (td_kernel): the kernel's own price
+Prints one JSON line: steps/s of each and their ratio, microseconds per launch of the dist / td / heads / gemm families (medians over
+the block pairs), and both launch censuses of an outer step.
+Usage: dist_rate.py [blocks] [steps per block]"""
+import json, os, sys, time
+import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cartpoleplusplus_amd import ddpg_cartpole as D
+
+shape, B, NB, ROWS = (64, 64, 3, 2, 3), 256, 5, 22000
+DIST = (51, -10.0, 10.0)
+blocks = int(sys.argv[1]) if len(sys.argv) > 1 else 8
+steps = int(sys.argv[2]) if len(sys.argv) > 2 else 40
+FAMILIES = ("dist", "td", "heads", "gemm", "clip_sgd")
+
+
+class Env(object):
+    class S(object):
+        def __init__(self, s): self.shape = tuple(s)
+    observation_space, action_space = S(shape), S((1, 2))
+
+
+def agent(dist):
+    kw = dict(distributional_critic=True, num_atoms=dist[0], v_min=dist[1], v_max=dist[2]) if dist else {}
+    D.set_opts(D.default_opts(use_raw_pixels=True, render_height=64, render_width=64, num_cameras=2, action_repeats=3, batch_size=B,
+                              replay_memory_size=ROWS, **kw))
+    a = D.DeepDeterministicPolicyGradientAgent(Env())
+    a.initialise_variables(seed=42)
+    a.post_var_init_setup()
+    a.replay_memory.fill_synthetic(ROWS, seed=1234)
+    return a
+
+
+agents = {"plain": agent(None), "dist": agent(DIST)}
+assert agents["plain"].critic.distribution is None and agents["dist"].critic.distribution == DIST
+assert agents["dist"].critic.num_params - agents["plain"].critic.num_params == 51 * (DIST[0] - 1)
+ctx = agents["plain"].actor.ctx
+for a in agents.values():
+    for _ in range(4):
+        a.train_step(B, NB)
+ctx.sync()
+rates = {k: [] for k in agents}
+for _ in range(blocks):
+    for k, a in agents.items():
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            a.train_step(B, NB)
+        ctx.sync()
+        rates[k].append(steps / (time.perf_counter() - t0))
+us = {k: {f: [] for f in FAMILIES} for k in agents}
+launches = {}
+for _ in range(blocks):
+    for k, a in agents.items():
+        ctx.sync()
+        ctx.prof_reset()
+        ctx.prof_enable(True)
+        try:
+            for _ in range(4):
+                a.train_step(B, NB)
+            ctx.sync()
+        finally:
+            ctx.prof_enable(False)
+        prof = ctx.prof_read()
+        for f in FAMILIES:
+            ms, n = prof.get(f, (0.0, 0))
+            if n:
+                us[k][f].append(1e3 * ms / n)
+        launches[k] = {name: cnt for name, (_ms, cnt) in prof.items()}
+ctx.prof_reset()
+assert launches["dist"]["dist"] == 2 * 4 * NB and launches["dist"].get("heads", 0) == 0 and launches["dist"].get("td", 0) == 0, launches["dist"]
+assert launches["plain"].get("dist", 0) == 0, launches["plain"]
+out = {"workload": "cfg3", "B": B, "batches_per_step": NB, "blocks": blocks, "steps_per_block": steps, "atoms": DIST[0],
+       "plain_route": "fused heads" if launches["plain"].get("heads", 0) else "gemm levels",
+       "plain_steps_per_s": float(np.median(rates["plain"])), "dist_steps_per_s": float(np.median(rates["dist"])),
+       "dist_over_plain": float(np.median(np.array(rates["dist"]) / np.array(rates["plain"])))}
+for k in agents:
+    for f in FAMILIES:
+        if us[k][f]:
+            out["%s_%s_us" % (k, f)] = float(np.median(us[k][f]))
+for k in agents:
+    out["%s_launches_per_outer_step" % k] = {name: int(v // 4) for name, v in sorted(launches[k].items()) if v}
+print(json.dumps(out))
+for a in agents.values():
+    a.close()
