@@ -60,6 +60,7 @@ enum KernelId {
   K_CONV1_IMAGE,          // conv1's operand images as a launch of their own (conv_rs16.h; in the fused step they ride in the optimiser's launch)
   K_PER,                  // prioritized replay: sum-tree updates, draws and importance weights (per.hip)
   K_DIST,                 // distributional critic: softmax / expectation, projected target and cross-entropy (dist.hip)
+  K_QUANT,                // quantile critic: expectation, sorted and truncated targets, quantile Huber loss (quant.hip)
   K_NUM_KERNELS
 };
 
@@ -523,6 +524,16 @@ int dist_td_grid(int B);
 int launch_dist_td(cpp_ctx* ctx, const float* logits, const float* tlogits, const float* r, const float* mask, float discount, int B, int N,
                    float v_min, float v_max, float* q_out, float* tq_out, float* p_out, float* tp_out, float* m_out, float* td, float* dz,
                    double* loss_part, const float* w = nullptr);
+// ---- quantile critic (quant.hip; include/cartpolepp_abi.h, cpp_net_create_quantile).  theta: (B, N), N in [2, 64].
+// job (a): q_out[b] = Q = (sum_i theta_i) / N and, dz != nullptr, dz[b][i] = 1 / N
+int launch_quant_expect(cpp_ctx* ctx, const float* theta, int B, int N, float* q_out, float* dz);
+// job (b): Q, Q', theta, the target atoms sorted ascending, y_j = r + g s_j for j < N - drop_top (0 beyond; each (B, N)), td = Q - mean_j y_j,
+// dz = the quantile Huber gradient (nullptr: none, check_loss) and the per-workgroup sums of w_b L_b in loss_part[quant_td_grid(B)] (f64,
+// dist.hip's region and finalisation).  w == nullptr: uniform.
+int quant_td_grid(int B);
+int launch_quant_td(cpp_ctx* ctx, const float* theta, const float* ttheta, const float* r, const float* mask, float discount, int B, int N,
+                    float kappa, int drop_top, float* q_out, float* tq_out, float* theta_out, float* sorted_out, float* y_out, float* td,
+                    float* dz, double* loss_part, const float* w = nullptr);
 // the same count where the heads kernel does not carry it (GEMM-level paths, the stand-alone ops, cpp_ddpg_apply_gradients): one thread, in
 // front of the optimiser's launch.  step: the two optimisers' step counts or nullptr (GradientDescent).  peek (cpp_ddpg_train_actor: the
 // actor half of the minibatch whose critic half follows): n stays, the hold word is that of n + 1.

@@ -61,6 +61,10 @@ struct cpp_ddpg {
   // pass left for cpp_ddpg_last_distribution -- p of the fed evaluation, p' of the target evaluation, the projected target m, each
   // maxB x N.  Such a trainer always takes the GEMM levels of compute_gradients; dist.hip stands where td_kernel and `ones` stand
   int dist_n = 0; float *dist_p = nullptr, *dist_tp = nullptr, *dist_m = nullptr;
+  // quantile critic (cpp_net_create_quantile: both critics with one N, or neither): dist_n is N, the three buffers hold theta, the sorted
+  // target atoms and y for cpp_ddpg_last_quantiles, quant.hip stands where dist.hip stands.  kappa and the dropped top atoms
+  // (cpp_ddpg_set_quantile_target) are captured by value
+  bool quant = false; float quant_kappa = 1.f; int quant_drop = 0;
 };
 
 // the minibatch's loss from the per-workgroup partials of the heads kernel or of dist.hip's job (b), added in a fixed order
@@ -73,6 +77,10 @@ static float loss_of_parts(const double* parts, int n, int B) {
 // job (b) of dist.hip on the fed and the target evaluation the forward passes left in the first workspaces
 static int dist_td(cpp_ddpg* d, const cpp_batch* b, int B, bool backward, const float* w) {
   cpp_net *c = d->critic, *tc = d->tcritic;
+  if (d->quant)
+    return launch_quant_td(d->ctx, c->ws[0].logits, tc->ws[0].logits, b->r, b->m, d->hp.discount, B, d->dist_n, d->quant_kappa, d->quant_drop,
+                           c->ws[0].out, tc->ws[0].out, d->dist_p, d->dist_tp, d->dist_m, d->td, backward ? c->ws[0].dz[c->fc.size() - 1] : nullptr,
+                           d->heads_part, w);
   return launch_dist_td(d->ctx, c->ws[0].logits, tc->ws[0].logits, b->r, b->m, d->hp.discount, B, d->dist_n, c->dist_vmin, c->dist_vmax,
                         c->ws[0].out, tc->ws[0].out, d->dist_p, d->dist_tp, d->dist_m, d->td, backward ? c->ws[0].dz[c->fc.size() - 1] : nullptr,
                         d->heads_part, w);
@@ -89,6 +97,7 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   ARG_CHECK(critic->dist_n == tcritic->dist_n && critic->dist_vmin == tcritic->dist_vmin && critic->dist_vmax == tcritic->dist_vmax,
             "cpp_ddpg_create: critic and target critic must carry one value distribution (N, v_min, v_max), or none");
   ARG_CHECK(!(critic->dist_n && critic->twin), "cpp_ddpg_create: a distributional critic with twin Q heads");
+  ARG_CHECK(critic->quant == tcritic->quant, "cpp_ddpg_create: a quantile critic needs a quantile target critic with the same N (never a categorical or a plain one)");
   ARG_CHECK(actor->nparams == tactor->nparams && critic->nparams == tcritic->nparams, "cpp_ddpg_create: target shapes differ");
   ARG_CHECK(actor->state_elems == critic->state_elems && actor->spec.action_dim == critic->spec.action_dim,
             "cpp_ddpg_create: actor/critic input shapes differ");
@@ -120,7 +129,7 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   if (!rc) rc = dalloc(d->arena, &d->heads_part, (size_t)DDPG_HEADS_MAX_WGS);
   d->twin = critic->twin;
   if (!rc && d->twin) rc = dalloc(d->arena, &d->td2, (size_t)d->maxB);
-  d->dist_n = critic->dist_n;
+  d->dist_n = critic->dist_n; d->quant = critic->quant;
   if (d->dist_n && dist_td_grid(d->maxB) > DDPG_HEADS_MAX_WGS) {
     cpp_set_error("cpp_ddpg_create: a distributional trainer takes batches up to %d (got %d)", 4 * DDPG_HEADS_MAX_WGS, d->maxB);
     rc = CPP_ERR_ARG;
@@ -1293,12 +1302,44 @@ extern "C" int cpp_ddpg_last_twin_values(cpp_ddpg* d, int B, float* q2, float* t
   return CPP_OK;
 }
 
+// Quantile trainers (Dabney et al. 2018; Kuznetsov et al. 2020; an extension of the target ddpg_cartpole.py:199-214): the Huber threshold
+// and the number of top target atoms dropped.  Both are captured by value: the call drops the cached graphs.
+extern "C" int cpp_ddpg_set_quantile_target(cpp_ddpg* d, float kappa, int drop_top) {
+  ARG_CHECK(d, "cpp_ddpg_set_quantile_target: NULL argument");
+  if (!d->quant) { cpp_set_error("cpp_ddpg_set_quantile_target: the trainer's critics are not quantile critics"); return CPP_ERR_STATE; }
+  ARG_CHECK(std::isfinite(kappa) && kappa > 0.f, "cpp_ddpg_set_quantile_target: kappa %g (finite, positive)", (double)kappa);
+  ARG_CHECK(drop_top >= 0 && drop_top <= d->dist_n - 1, "cpp_ddpg_set_quantile_target: %d dropped atoms outside [0, %d]", drop_top, d->dist_n - 1);
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  HIP_CHECK(ctx_sync_stream(d->ctx));
+  d->quant_kappa = kappa; d->quant_drop = drop_top;
+  invalidate_graphs(d);      // (the captured launches carry the old values)
+  d->pre_variant = 0;
+  return CPP_OK;
+}
+
+// Quantile trainers: what the last minibatch's gradient pass left (the critic of ddpg_cartpole.py:166-177 at the fed action, the target
+// :199-214) -- theta of the fed evaluation, the target critic's atoms at the (smoothed) target action sorted ascending, and
+// y_j = r + g s_j (columns j >= M zero), each (B, N).  NULL pointers are skipped.
+extern "C" int cpp_ddpg_last_quantiles(cpp_ddpg* d, int B, float* theta, float* sorted_target_theta, float* y) {
+  ARG_CHECK(d, "cpp_ddpg_last_quantiles: NULL argument");
+  ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_quantiles: batch %d outside [1,%d]", B, d->maxB);
+  if (!d->quant) { cpp_set_error("cpp_ddpg_last_quantiles: the trainer's critics are not quantile critics"); return CPP_ERR_STATE; }
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  hipStream_t st = d->ctx->stream;
+  const size_t n = (size_t)B * d->dist_n * sizeof(float);
+  if (theta) HIP_CHECK(hipMemcpyAsync(theta, d->dist_p, n, hipMemcpyDeviceToHost, st));
+  if (sorted_target_theta) HIP_CHECK(hipMemcpyAsync(sorted_target_theta, d->dist_tp, n, hipMemcpyDeviceToHost, st));
+  if (y) HIP_CHECK(hipMemcpyAsync(y, d->dist_m, n, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  return CPP_OK;
+}
+
 // Distributional trainers: what the last minibatch's gradient pass left -- p of the fed evaluation, p' of the target evaluation at the
 // (smoothed) target action and the projected target m, each (B, N).  NULL pointers are skipped.
 extern "C" int cpp_ddpg_last_distribution(cpp_ddpg* d, int B, float* p, float* target_p, float* m) {
   ARG_CHECK(d, "cpp_ddpg_last_distribution: NULL argument");
   ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_distribution: batch %d outside [1,%d]", B, d->maxB);
-  if (!d->dist_n) { cpp_set_error("cpp_ddpg_last_distribution: the trainer's critics are not distributional"); return CPP_ERR_STATE; }
+  if (!d->dist_n || d->quant) { cpp_set_error("cpp_ddpg_last_distribution: the trainer's critics are not distributional"); return CPP_ERR_STATE; }
   HIP_CHECK(hipSetDevice(d->ctx->device));
   hipStream_t st = d->ctx->stream;
   const size_t n = (size_t)B * d->dist_n * sizeof(float);

@@ -111,6 +111,9 @@ struct cpp_net {
   bool twin = false; std::vector<FcL> fc2;
   // distributional critic: N atoms on the support [v_min, v_max] (dist_n == 0: every other network); q_value is (n_in, N)
   int dist_n = 0; float dist_vmin = 0.f, dist_vmax = 0.f;
+  // quantile critic (cpp_net_create_quantile): the same N-wide q_value and `logits` workspace, dist_n = N, read as N quantile atoms
+  // theta_i at tau_i = (2 i + 1) / (2 N) -- there is no support, and cpp_net_distribution_info keeps answering 0 atoms
+  bool quant = false;
 };
 
 struct cpp_batch {
@@ -310,7 +313,7 @@ GemmArgs twin_dx_args(cpp_net* n, Workspace& w, int l, int B);
 int twin_forward_fc(cpp_net* n, Workspace& w, int B);
 // where the last layer's GEMM writes: the logits of a distributional critic, `out` otherwise
 inline float* fc_last_out(const Workspace& w) { return w.logits ? w.logits : w.out; }
-// Q (and, dz != nullptr, p (z - Q)) from the logits the forward left in w: a no-op for every other network
+// Q (and, dz != nullptr, p (z - Q); a quantile critic: 1 / N) from the logits the forward left in w: a no-op for every other network
 int dist_expect(cpp_net* n, Workspace& w, int B, float* dz);
 int batch_stats(cpp_ctx* ctx, const void* s0, const void* s1, int dtype, long elems, int B, int C, double* part, float* white);
 int batch_ensure_stats(cpp_batch* b, int C);

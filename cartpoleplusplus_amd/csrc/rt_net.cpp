@@ -119,7 +119,8 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
   return CPP_OK;
 }
 
-static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out, int dist_n = 0, float v_min = 0.f, float v_max = 0.f);
+static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out, int dist_n = 0, float v_min = 0.f, float v_max = 0.f,
+                      bool quant = false);
 extern "C" int cpp_net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, cpp_net** out) {
   return net_create(ctx, spec, max_batch, false, out);
 }
@@ -144,17 +145,33 @@ extern "C" int cpp_net_create_distributional(cpp_ctx* ctx, const cpp_net_spec* s
 }
 extern "C" int cpp_net_distribution_info(const cpp_net* n, int* n_atoms, float* v_min, float* v_max) {
   ARG_CHECK(n, "cpp_net_distribution_info: NULL argument");
-  if (n_atoms) *n_atoms = n->dist_n;
+  if (n_atoms) *n_atoms = n->quant ? 0 : n->dist_n;      // (a quantile critic has no support)
   if (v_min) *v_min = n->dist_vmin;
   if (v_max) *v_max = n->dist_vmax;
   return CPP_OK;
 }
+// A critic whose last layer emits N quantile atoms (Dabney et al. 2018, QR-DQN; truncated targets: Kuznetsov et al. 2020, TQC; an
+// extension of ddpg_cartpole.py:166-177 and :199-214): see include/cartpolepp_abi.h.  The layout, the N-wide q_value and the `logits`
+// workspace are the distributional critic's; what reads them differs (quant.hip)
+extern "C" int cpp_net_create_quantile(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, int n_quantiles, cpp_net** out) {
+  ARG_CHECK(ctx && spec && out, "cpp_net_create_quantile: NULL argument");
+  ARG_CHECK(spec->kind == CPP_CRITIC, "cpp_net_create_quantile: kind %d (quantiles belong to a critic)", spec->kind);
+  ARG_CHECK(n_quantiles >= 2 && n_quantiles <= 64, "cpp_net_create_quantile: %d quantiles outside [2, 64]", n_quantiles);
+  return net_create(ctx, spec, max_batch, false, out, n_quantiles, 0.f, 0.f, true);
+}
+// the critic of ddpg_cartpole.py:166-177 widened: N of a network made by cpp_net_create_quantile, 0 for any other
+extern "C" int cpp_net_quantile_info(const cpp_net* n, int* n_quantiles) {
+  ARG_CHECK(n, "cpp_net_quantile_info: NULL argument");
+  if (n_quantiles) *n_quantiles = n->quant ? n->dist_n : 0;
+  return CPP_OK;
+}
 int dist_expect(cpp_net* n, Workspace& w, int B, float* dz) {
   if (!n->dist_n) return CPP_OK;
+  if (n->quant) return launch_quant_expect(n->ctx, w.logits, B, n->dist_n, w.out, dz);
   return launch_dist_expect(n->ctx, w.logits, B, n->dist_n, n->dist_vmin, n->dist_vmax, w.out, dz);
 }
 
-static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out, int dist_n, float v_min, float v_max) {
+static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out, int dist_n, float v_min, float v_max, bool quant) {
   ARG_CHECK(ctx && spec && out, "cpp_net_create: NULL argument");
   ARG_CHECK(max_batch >= 1, "cpp_net_create: max_batch %d", max_batch);
   ARG_CHECK(spec->kind == CPP_ACTOR || spec->kind == CPP_CRITIC || spec->kind == CPP_HEAD, "cpp_net_create: kind %d", spec->kind);
@@ -179,7 +196,7 @@ static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, boo
   n->img_slot = nullptr; n->use_b16 = false; n->wimg = nullptr; n->wimg_key = nullptr;
   n->is_training = true; n->drop_counter = nullptr; n->bn_part = nullptr; n->bn_means = nullptr; n->bn_scratch = nullptr;
   n->twin = twin;
-  n->dist_n = dist_n; n->dist_vmin = v_min; n->dist_vmax = v_max;
+  n->dist_n = dist_n; n->dist_vmin = v_min; n->dist_vmax = v_max; n->quant = quant;
   int rc = net_build(n);
   if (rc) { delete n; return rc; }
   auto fail = [&](int r) { n->arena.release(); delete n; return r; };

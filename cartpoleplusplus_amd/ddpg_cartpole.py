@@ -168,6 +168,16 @@ def build_parser():
     a('--num-atoms', type=int, default=argparse.SUPPRESS, help="--distributional-critic: atoms of the support (default 51; 2 .. 64)")
     a('--v-min', type=float, default=argparse.SUPPRESS, help="--distributional-critic: the support's lower end (no default fits every reward scale)")
     a('--v-max', type=float, default=argparse.SUPPRESS, help="--distributional-critic: the support's upper end")
+    # quantile critic (an extension beyond the reference, ddpg_cartpole.py:166-177, :199-214: quantile regression, Dabney et al. 2018, with
+    # the truncated targets of Kuznetsov et al. 2020 inside one network): the critic's last layer emits N quantile atoms, trained with the
+    # quantile Huber loss against the sorted target atoms without their largest D; the actor ascends their mean (absent from the parsed
+    # options unless given, like --twin-q; quantile_critic() reads them)
+    a('--quantile-critic', action='store_true', default=argparse.SUPPRESS,
+      help="critics that emit --num-quantiles quantiles of the return (no support to configure), trained by quantile regression")
+    a('--num-quantiles', type=int, default=argparse.SUPPRESS, help="--quantile-critic: quantiles per critic (default 25; 2 .. 64)")
+    a('--quantile-huber-kappa', type=float, default=argparse.SUPPRESS, help="--quantile-critic: the Huber threshold of the quantile loss (default 1.0)")
+    a('--drop-top-quantiles', type=int, default=argparse.SUPPRESS,
+      help="--quantile-critic: drop the D largest target quantiles before the regression (overestimation control; default 0; 0 .. N - 1)")
     # n-step returns for this learner (ReplayMemory.enable_n_step; absent unless given): with --prioritized-replay, --data-parallel and
     # --distributional-critic this is D4PG from the command line
     a('--n-step', type=int, default=argparse.SUPPRESS,
@@ -282,6 +292,41 @@ def distributional_critic(o):
     return (int(n), v_min, v_max)
 
 
+_NUM_QUANTILES_DEFAULT, NUM_QUANTILES_MAX, _QUANTILE_KAPPA_DEFAULT = 25, 64, 1.0
+
+
+def quantile_critic(o):
+    """(n_quantiles, kappa, drop_top) of --quantile-critic / --num-quantiles / --quantile-huber-kappa / --drop-top-quantiles, or None
+    (off); refuses what cannot be meant."""
+    import math
+    on = bool(getattr(o, "quantile_critic", False))
+    given = [k for k in ("num_quantiles", "quantile_huber_kappa", "drop_top_quantiles") if getattr(o, k, None) is not None]
+    if not on:
+        if given:
+            raise SystemExit("--%s needs --quantile-critic" % given[0].replace("_", "-"))
+        return None
+    if twin_q(o):
+        raise SystemExit("--quantile-critic cannot be combined with --twin-q (--drop-top-quantiles is its overestimation control)")
+    if bool(getattr(o, "distributional_critic", False)):
+        raise SystemExit("--quantile-critic cannot be combined with --distributional-critic (one value distribution per critic)")
+    n = getattr(o, "num_quantiles", None)
+    n = _NUM_QUANTILES_DEFAULT if n is None else n
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= int(n) <= NUM_QUANTILES_MAX:
+        raise SystemExit("--num-quantiles %r is not a whole number in [2, %d]" % (n, NUM_QUANTILES_MAX))
+    d = getattr(o, "drop_top_quantiles", None)
+    d = 0 if d is None else d
+    if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or not 0 <= int(d) <= int(n) - 1:
+        raise SystemExit("--drop-top-quantiles %r is not a whole number in [0, %d] (at least one target quantile stays)" % (d, int(n) - 1))
+    k = getattr(o, "quantile_huber_kappa", None)
+    try:
+        k = _QUANTILE_KAPPA_DEFAULT if k is None else float(np.float32(k))
+    except (TypeError, ValueError) as e:
+        raise SystemExit("--quantile-huber-kappa: %s" % e)
+    if not (math.isfinite(k) and k > 0.0):
+        raise SystemExit("--quantile-huber-kappa %r is not finite and positive" % (getattr(o, "quantile_huber_kappa", None),))
+    return (int(n), k, int(d))
+
+
 def n_step(o):
     """n of --n-step; 1 (off) unless given"""
     n = getattr(o, "n_step", 1)
@@ -314,6 +359,7 @@ def default_opts(**overrides):
     o.policy_delay = _POLICY_DELAY_DEFAULT
     o.twin_q = False
     o.distributional_critic, o.num_atoms, o.v_min, o.v_max = False, None, None, None
+    o.quantile_critic, o.num_quantiles, o.quantile_huber_kappa, o.drop_top_quantiles = False, None, None, None
     o.n_step = 1
     for k, v in overrides.items():
         assert hasattr(o, k), k
@@ -458,6 +504,10 @@ class _Trainer(object):
         self.policy_delay = 1
         if delay > 1:
             self.set_policy_delay(delay)
+        # --quantile-critic: the Huber threshold and the dropped top target quantiles, as parsed when the critic was built
+        quantiles = getattr(critic, "quantiles", None)
+        if quantiles:
+            self.set_quantile_target(quantiles[1], quantiles[2])
 
     @property
     def handle(self):
@@ -546,6 +596,23 @@ class _Trainer(object):
         check(lib.cpp_ddpg_last_distribution(self.handle, B, *[ptr(x) for x in out]))
         return tuple(out)
 
+    def last_quantiles(self, B):
+        """(theta, sorted_target_theta, y) of the last minibatch's gradient pass of a --quantile-critic trainer, each (B, num_quantiles):
+        the fed evaluation's quantiles, the target critic's at the (smoothed) target action sorted ascending, and y_j = r + g s_j with
+        the columns of the dropped quantiles zero"""
+        B = int(B)
+        q = getattr(self.nets[1], "quantiles", None)
+        n = q[0] if q else 1
+        out = [np.empty((B, n), np.float32) for _ in range(3)]
+        check(lib.cpp_ddpg_last_quantiles(self.handle, B, *[ptr(x) for x in out]))
+        return tuple(out)
+
+    def set_quantile_target(self, kappa, drop_top):
+        """the quantile Huber threshold and the number of largest target quantiles dropped (include/cartpolepp_abi.h,
+        cpp_ddpg_set_quantile_target); drops the captured graphs."""
+        check(lib.cpp_ddpg_set_quantile_target(self.handle, float(kappa), int(drop_top)))
+        self.quantile_target = (float(kappa), int(drop_top))
+
     def set_target_smoothing(self, sigma, clip, seed):
         """target policy smoothing of the critic's target (include/cartpolepp_abi.h, cpp_ddpg_set_target_smoothing): sigma > 0 switches
         it on, (0, 0, seed) off; zeroes the count of target-forming passes and drops the captured graphs."""
@@ -628,7 +695,10 @@ class CriticNetwork(base_network.Network):
         self.twin_q = twin_q(opts)
         # --distributional-critic: q_value emits num_atoms logits; q_value, forward and dQ/da are the distribution's mean
         self.distribution = distributional_critic(opts)
-        self._build_native(_lib.CPP_CRITIC, self.action_dim, max(int(opts.batch_size), 1), twin_q=self.twin_q, distribution=self.distribution)
+        # --quantile-critic: q_value emits num_quantiles quantile atoms; q_value, forward and dQ/da are their mean
+        self.quantiles = quantile_critic(opts)
+        self._build_native(_lib.CPP_CRITIC, self.action_dim, max(int(opts.batch_size), 1), twin_q=self.twin_q, distribution=self.distribution,
+                           quantiles=self.quantiles[0] if self.quantiles else None)
         self.q_value = _OpHandle(namespace + "/q_value")
         self.target_critic = None
         self._ddpg = None
@@ -715,6 +785,7 @@ class DeepDeterministicPolicyGradientAgent(object):
         action_dim = self.env.action_space.shape[1]
         # (the refusals of --distributional-critic and --n-step come before anything exists on the device, as check_prioritized_opts')
         distributional_critic(opts)
+        quantile_critic(opts)
         n_step(opts)
         # (--exact-products asks for the exact arithmetic contract; without the flag the context keeps whatever mode its owner chose --
         # an explicit Context.set_precision("exact") is not undone, and a second agent on the shared context does not fight the first)

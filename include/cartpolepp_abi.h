@@ -175,6 +175,32 @@ int cpp_net_is_twin_q(const cpp_net* net);
 int cpp_net_create_distributional(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, int n_atoms, float v_min, float v_max, cpp_net** out);
 /* (N, v_min, v_max) of a network made by cpp_net_create_distributional; n_atoms 0 for any other.  NULL pointers are skipped. */
 int cpp_net_distribution_info(const cpp_net* net, int* n_atoms, float* v_min, float* v_max);
+/* Quantile critic: quantile regression (Dabney et al. 2018, QR-DQN) with truncated targets (Kuznetsov et al. 2020, TQC, within one network),
+ * an extension of the critic ddpg_cartpole.py:166-171 (pixel) / :172-177 (low-dimensional) and of its target :199-214.  The layout is
+ * cpp_net_create_distributional's: 'q_value/weights' is (n_in, N), 'q_value/biases' is (N).  Output i, theta_i(s, a), estimates the
+ * quantile at tau_i = (2 i + 1) / (2 N); there is no support to configure.  spec->kind must be CPP_CRITIC, 2 <= N <= 64 (CPP_ERR_ARG
+ * otherwise).  All arithmetic below is float32 except the loss, whose terms are formed and added in float64.
+ *   Q(s, a) = (sum_i theta_i) / N
+ * cpp_net_forward* return Q (width 1).  A trainer built on such critics (cpp_ddpg_create: both critics with one N, or neither; never with
+ * twin Q heads, never mixed with categorical ones) trains, per row b of the minibatch, with kappa and d of cpp_ddpg_set_quantile_target,
+ *   g      = mask_b * discount              (an n-step memory has folded its powers into mask, as for the scalar target)
+ *   a'     = mu'(s2), smoothed if target policy smoothing is on;   theta' = the target critic's N outputs at (s2, a')
+ *   s_0 <= s_1 <= .. <= s_{N-1}             theta' sorted ascending (always, also with d = 0: one summation order)
+ *   M      = N - d;   y_j = r_b + g * s_j,  j = 0 .. M-1          the d largest target atoms are dropped
+ *   u_ij   = y_j - theta_i(s1, a_fed)
+ *   H(u)   = u^2 / 2 if |u| <= kappa, else kappa (|u| - kappa / 2)
+ *   rho_ij = |tau_i - [u_ij < 0]| * H(u_ij) / kappa
+ *   L_b    = (1 / (N M)) sum_i sum_j rho_ij   (j ascending inside i),   loss = mean_b(w_b L_b)   (w: importance weights, 1 without them)
+ *   d theta_i = -(w_b / B) (1 / (N M)) sum_j |tau_i - [u_ij < 0]| * clip(u_ij, -kappa, kappa) / kappa
+ *   td_b   = Q(s1, a_fed) - (sum_{j<M} y_j) / M
+ * td is what priorities, cpp_ddpg_last_values and cpp_ddpg_check_loss's td read; their q is Q; the loss they report is the quantile Huber
+ * loss.  Truncation works on values: ties among the theta' cannot change any result.  The actor follows dQ/da at a = mu(s1): the gradient
+ * entering the critic's last layer on that evaluation is the constant 1 / N where the scalar critic feeds ones.  Such a trainer always
+ * takes the GEMM levels of the gradient pass; batches up to 1024.  cpp_naf_create refuses such networks.  A checkpoint carries the N-wide
+ * q_value by name: a mismatch in N fails the layout check.  cpp_net_distribution_info answers n_atoms = 0 for such a network. */
+int cpp_net_create_quantile(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, int n_quantiles, cpp_net** out);
+/* N of a network made by cpp_net_create_quantile (the critic of ddpg_cartpole.py:166-177 widened); 0 for any other.  NULL is skipped. */
+int cpp_net_quantile_info(const cpp_net* net, int* n_quantiles);
 int cpp_net_destroy(cpp_net* net);
 /* Network.trainable_model_vars (base_network.py:51-56): variables in creation order. */
 int64_t cpp_net_num_params(const cpp_net* net);
@@ -478,6 +504,15 @@ int cpp_ddpg_last_twin_values(cpp_ddpg* ddpg, int B, float* q2, float* target_q1
 /* Distributional trainers (cpp_net_create_distributional): p of the fed evaluation, p' of the target evaluation and the projected target m
  * of the last minibatch's gradient pass, each (B, N).  NULL pointers are skipped.  CPP_ERR_STATE on any other trainer. */
 int cpp_ddpg_last_distribution(cpp_ddpg* ddpg, int B, float* p, float* target_p, float* m);
+/* Quantile trainers (cpp_net_create_quantile; an extension of the target ddpg_cartpole.py:199-214): the Huber threshold kappa and the
+ * number d of largest target atoms dropped before the regression.  After cpp_ddpg_create: kappa 1, d 0 (plain quantile regression).
+ * CPP_ERR_ARG for a kappa that is not finite and positive or a d outside [0, N - 1]; CPP_ERR_STATE on any other trainer.  Both values are
+ * captured by value: the call drops the captured graphs, as cpp_ddpg_set_policy_delay does. */
+int cpp_ddpg_set_quantile_target(cpp_ddpg* ddpg, float kappa, int drop_top);
+/* Quantile trainers (an extension of ddpg_cartpole.py:166-177, :199-214): theta of the fed evaluation, the target evaluation's atoms
+ * sorted ascending and y_j = r + g s_j of the last minibatch's gradient pass, each (B, N); columns j >= M of y are zero.  NULL pointers are
+ * skipped.  CPP_ERR_STATE on any other trainer. */
+int cpp_ddpg_last_quantiles(cpp_ddpg* ddpg, int B, float* theta, float* sorted_target_theta, float* y);
 
 /* ---- data-parallel actor-learners (the reference's TODO "switch back to async training with multiple replicas",
  * ddpg_cartpole.py:259, naf_cartpole.py:294; its exps only launch independent processes, exps/run_87.sh:12-36) ------------
