@@ -143,7 +143,7 @@ class Network(object):
         return self.hidden_layers_starting_at(input_state, opts.hidden_layers, opts)
 
     # ------------------------------------------------------------------ native instantiation
-    def _build_native(self, kind, action_dim, max_batch, ctx=None, head_out=0, head_act=0, twin_q=False, distribution=None, quantiles=None):
+    def _build_native(self, kind, action_dim, max_batch, ctx=None, head_out=0, head_act=0, twin_q=False, distribution=None, quantiles=None, gaussian=None):
         self.ctx = ctx or _lib.default_context()
         spec = _lib.NetSpec()
         spec.kind, spec.action_dim = kind, int(action_dim)
@@ -163,7 +163,9 @@ class Network(object):
         handle = C.c_void_p()
         # (twin_q: a critic with twin Q heads, include/cartpolepp_abi.h cpp_net_create_twin_q; without it the call is what it always was)
         create = lib.cpp_net_create_twin_q if twin_q else lib.cpp_net_create
-        if quantiles is not None:         # N: a quantile critic, cpp_net_create_quantile
+        if gaussian is not None:          # (log_std_min, log_std_max): a Gaussian actor, cpp_net_create_gaussian
+            check(lib.cpp_net_create_gaussian(self.ctx.handle, C.byref(spec), int(max_batch), float(gaussian[0]), float(gaussian[1]), C.byref(handle)))
+        elif quantiles is not None:       # N: a quantile critic, cpp_net_create_quantile
             check(lib.cpp_net_create_quantile(self.ctx.handle, C.byref(spec), int(max_batch), int(quantiles), C.byref(handle)))
         elif distribution is not None:    # (n_atoms, v_min, v_max): a distributional critic, cpp_net_create_distributional
             n_atoms, v_min, v_max = distribution

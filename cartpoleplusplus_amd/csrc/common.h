@@ -61,6 +61,7 @@ enum KernelId {
   K_PER,                  // prioritized replay: sum-tree updates, draws and importance weights (per.hip)
   K_DIST,                 // distributional critic: softmax / expectation, projected target and cross-entropy (dist.hip)
   K_QUANT,                // quantile critic: expectation, sorted and truncated targets, quantile Huber loss (quant.hip)
+  K_SAC,                  // soft actor-critic: policy sample / mean, soft reward, actor head gradient, temperature (sac.hip)
   K_NUM_KERNELS
 };
 
@@ -534,6 +535,32 @@ int quant_td_grid(int B);
 int launch_quant_td(cpp_ctx* ctx, const float* theta, const float* ttheta, const float* r, const float* mask, float discount, int B, int N,
                     float kappa, int drop_top, float* q_out, float* tq_out, float* theta_out, float* sorted_out, float* y_out, float* td,
                     float* dz, double* loss_part, const float* w = nullptr);
+// ---- soft actor-critic (sac.hip; include/cartpolepp_abi.h, cpp_net_create_gaussian / cpp_ddpg_set_sac).  logits: (B, 2A), A in [1, 64]:
+// m in columns [0, A), x in [A, 2A).
+struct SacSampleArgs {
+  const float* logits; int B, A; float lo, hi;
+  const unsigned long long* n;                     // the count of target-forming passes (a device word); nullptr: the mean, eps = 0
+  unsigned stream, seed_lo, seed_hi;               // 0x200: the draw at state_1, 0x300: the draw at state_2
+  unsigned long long* n_out;                       // optional: the count the noise was drawn at
+  float *eps, *a_out, *splice; long ld_splice;     // eps, splice optional; splice: the critic's concat columns (row stride ld_splice)
+  float *logp, *m_out, *ls_out;                    // each optional
+  // job 2 (r_soft != nullptr): r_soft = r - ((mask discount) alpha) logp, alpha = exp(*log_alpha)
+  const float *log_alpha, *r, *mask; float discount; float* r_soft;
+};
+struct SacGradArgs {
+  const float *logits, *a, *eps, *dq_da, *logp, *log_alpha; int B, A; float lo, hi, target_entropy;
+  float* dz;                                       // (B, 2A): d m | d x
+  double* part;                                    // [sac_grid(B)] per-workgroup sums of (logp_b + Hbar), rows in order; nullptr: none
+  float* alpha_out;                                // the temperature this pass read; nullptr: not recorded
+};
+// the trainer's temperature words (floats, device): log_alpha, Adam's m and v, log_alpha as the target-forming pass reads it (the copy
+// that closes a minibatch refreshes it), the alpha of the last actor pass
+enum { SAC_W_LOG_ALPHA = 0, SAC_W_M = 1, SAC_W_V = 2, SAC_W_TARGET = 3, SAC_W_ALPHA = 4, SAC_WORDS = 8 };
+int sac_grid(int B);
+int launch_sac_sample(cpp_ctx* ctx, const SacSampleArgs& s);
+int launch_sac_actor_grad(cpp_ctx* ctx, const SacGradArgs& s);
+// g_alpha = -(1 / B) (the partials added in order), Adam's element on w[SAC_W_LOG_ALPHA] with its count *step (+= 1)
+int launch_sac_temperature(cpp_ctx* ctx, const double* part, int B, float lr, float* w, uint64_t* step);
 // the same count where the heads kernel does not carry it (GEMM-level paths, the stand-alone ops, cpp_ddpg_apply_gradients): one thread, in
 // front of the optimiser's launch.  step: the two optimisers' step counts or nullptr (GradientDescent).  peek (cpp_ddpg_train_actor: the
 // actor half of the minibatch whose critic half follows): n stays, the hold word is that of n + 1.

@@ -65,7 +65,63 @@ struct cpp_ddpg {
   // target atoms and y for cpp_ddpg_last_quantiles, quant.hip stands where dist.hip stands.  kappa and the dropped top atoms
   // (cpp_ddpg_set_quantile_target) are captured by value
   bool quant = false; float quant_kappa = 1.f; int quant_drop = 0;
+  // soft actor-critic (cpp_net_create_gaussian: both actors Gaussian with one (lo, hi), or neither; cpp_ddpg_set_sac).  sac_w: the
+  // temperature words (common.h: SAC_W_*), sac_step: Adam's count, sac_part: the partials of g_alpha the last actor pass left for a batch
+  // of sac_B rows (0: none yet); [0] / [1]: the draw at state_1 / state_2 -- eps (maxB x A), logp (maxB); sac_rsoft: the soft reward the
+  // TD kernels read where they read the batch's reward.  The noise count is tps_n (smoothing is refused with SAC), its increment tps_pending's.
+  // Target entropy, rate and seed are captured by value.
+  bool sac = false; float sac_hbar = 0.f, sac_lr = 0.f; uint64_t sac_seed = 0;
+  float* sac_w = nullptr; uint64_t* sac_step = nullptr; double* sac_part = nullptr; int sac_B = 0;
+  float *sac_eps[2] = {nullptr, nullptr}, *sac_logp[2] = {nullptr, nullptr}, *sac_rsoft = nullptr;
 };
+
+// jobs 1 / 2 of sac.hip on the head the (target) actor's forward left in its first workspace: a sample (draw) or the mean
+static SacSampleArgs sac_sample_args(const cpp_ddpg* d, bool target, bool draw, const cpp_batch* b = nullptr) {
+  const cpp_net* n = target ? d->tactor : d->actor;
+  SacSampleArgs s; memset(&s, 0, sizeof(s));
+  s.logits = n->ws[0].logits; s.A = n->spec.action_dim; s.lo = n->ls_lo; s.hi = n->ls_hi;
+  s.n = draw ? (const unsigned long long*)d->tps_n : nullptr;
+  s.stream = target ? 0x300u : 0x200u; s.seed_lo = (unsigned)d->sac_seed; s.seed_hi = (unsigned)(d->sac_seed >> 32);
+  s.eps = d->sac_eps[target ? 1 : 0]; s.a_out = n->ws[0].out; s.logp = d->sac_logp[target ? 1 : 0];
+  if (target) {
+    s.n_out = draw ? (unsigned long long*)(d->tps_n + 1) : nullptr;
+    s.log_alpha = d->sac_w + SAC_W_TARGET; s.r = b->r; s.mask = b->m; s.discount = d->hp.discount; s.r_soft = d->sac_rsoft;
+  }
+  return s;
+}
+static SacGradArgs sac_grad_args(const cpp_ddpg* d, int B) {
+  const cpp_net* a = d->actor;
+  SacGradArgs g; memset(&g, 0, sizeof(g));
+  g.logits = a->ws[0].logits; g.a = a->ws[0].out; g.eps = d->sac_eps[0]; g.dq_da = d->dq_da; g.logp = d->sac_logp[0];
+  g.log_alpha = d->sac_w + SAC_W_LOG_ALPHA; g.B = B; g.A = a->spec.action_dim; g.lo = a->ls_lo; g.hi = a->ls_hi; g.target_entropy = d->sac_hbar;
+  g.dz = a->ws[0].dz[a->fc.size() - 1]; g.part = d->sac_part; g.alpha_out = d->sac_w + SAC_W_ALPHA;
+  return g;
+}
+// SAC has no target actor: its parameters are a bit copy of the actor's (and the target-forming pass's temperature word of log_alpha)
+static int sac_sync_target(cpp_ddpg* d) {
+  hipStream_t st = d->ctx->stream;
+  if (d->tactor != d->actor)      // (actor-only training binds the live networks as stand-ins)
+    HIP_CHECK(hipMemcpyAsync(d->tactor->params, d->actor->params, (size_t)d->nA * sizeof(float), hipMemcpyDeviceToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(d->sac_w + SAC_W_TARGET, d->sac_w + SAC_W_LOG_ALPHA, sizeof(float), hipMemcpyDeviceToDevice, st));
+  d->tactor->wimg_key = nullptr;      // (the image the rider built is of the parameters before the copy)
+  return CPP_OK;
+}
+static void invalidate_graphs(cpp_ddpg* d);
+static int sac_configure(cpp_ddpg* d, float init_temperature, float target_entropy, float lr, uint64_t seed) {
+  cpp_ctx* ctx = d->ctx;
+  HIP_CHECK(ctx_sync_stream(ctx));
+  float w[SAC_WORDS]; memset(w, 0, sizeof(w));
+  w[SAC_W_LOG_ALPHA] = w[SAC_W_TARGET] = logf(init_temperature); w[SAC_W_ALPHA] = init_temperature;
+  HIP_CHECK(hipMemcpyAsync(d->sac_w, w, sizeof(w), hipMemcpyHostToDevice, ctx->stream));
+  HIP_CHECK(hipMemsetAsync(d->sac_step, 0, sizeof(uint64_t), ctx->stream));
+  HIP_CHECK(hipMemsetAsync(d->tps_n, 0, 2 * sizeof(uint64_t), ctx->stream));
+  RC(sac_sync_target(d));
+  HIP_CHECK(ctx_sync_stream(ctx));
+  d->sac_hbar = target_entropy; d->sac_lr = lr; d->sac_seed = seed; d->sac_B = 0; d->tps_pending = false;
+  invalidate_graphs(d);
+  d->pre_variant = 0;
+  return CPP_OK;
+}
 
 // the minibatch's loss from the per-workgroup partials of the heads kernel or of dist.hip's job (b), added in a fixed order
 static float loss_of_parts(const double* parts, int n, int B) {
@@ -98,6 +154,11 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
             "cpp_ddpg_create: critic and target critic must carry one value distribution (N, v_min, v_max), or none");
   ARG_CHECK(!(critic->dist_n && critic->twin), "cpp_ddpg_create: a distributional critic with twin Q heads");
   ARG_CHECK(critic->quant == tcritic->quant, "cpp_ddpg_create: a quantile critic needs a quantile target critic with the same N (never a categorical or a plain one)");
+  ARG_CHECK(actor->gauss == tactor->gauss && actor->ls_lo == tactor->ls_lo && actor->ls_hi == tactor->ls_hi,
+            "cpp_ddpg_create: a Gaussian actor needs a Gaussian target actor with the same log std bounds (and a plain one a plain one)");
+  ARG_CHECK(!(actor->gauss && critic->dist_n), "cpp_ddpg_create: a Gaussian actor with a distributional or quantile critic");
+  for (cpp_net* n : {actor, critic, tactor, tcritic})
+    ARG_CHECK(!(actor->gauss && (n->spec.use_batch_norm || n->spec.use_dropout)), "cpp_ddpg_create: a Gaussian actor with batch norm or dropout");
   ARG_CHECK(actor->nparams == tactor->nparams && critic->nparams == tcritic->nparams, "cpp_ddpg_create: target shapes differ");
   ARG_CHECK(actor->state_elems == critic->state_elems && actor->spec.action_dim == critic->spec.action_dim,
             "cpp_ddpg_create: actor/critic input shapes differ");
@@ -136,6 +197,24 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   }
   for (float** p : {&d->dist_p, &d->dist_tp, &d->dist_m})
     if (!rc && d->dist_n) rc = dalloc(d->arena, p, (size_t)d->maxB * d->dist_n);
+  d->sac = actor->gauss;
+  if (d->sac && sac_grid(d->maxB) > DDPG_HEADS_MAX_WGS) {
+    cpp_set_error("cpp_ddpg_create: a soft actor-critic trainer takes batches up to %d (got %d)", 4 * DDPG_HEADS_MAX_WGS, d->maxB);
+    rc = CPP_ERR_ARG;
+  }
+  if (d->sac) {
+    if (!rc) rc = dalloc(d->arena, &d->sac_w, (size_t)SAC_WORDS);
+    if (!rc) rc = dalloc(d->arena, &d->sac_step, (size_t)1);
+    if (!rc) rc = dalloc(d->arena, &d->tps_n, (size_t)2);
+    if (!rc) rc = dalloc(d->arena, &d->sac_part, (size_t)DDPG_HEADS_MAX_WGS);
+    if (!rc) rc = dalloc(d->arena, &d->sac_rsoft, (size_t)d->maxB);
+    for (int k = 0; k < 2; ++k) {
+      if (!rc) rc = dalloc(d->arena, &d->sac_eps[k], (size_t)d->maxB * A);
+      if (!rc) rc = dalloc(d->arena, &d->sac_logp[k], (size_t)d->maxB);
+    }
+    // (until cpp_ddpg_set_sac: temperature 0.1, target entropy -A, rate 1e-4, seed 0)
+    if (!rc) rc = sac_configure(d, 0.1f, -(float)A, 1e-4f, 0);
+  }
   if (!rc) rc = launch_fill(ctx, d->ones, 1, 0, 1, d->maxB, 1.0f);
   if (rc) { d->arena.release(); delete d; return rc; }
   actor->grads = d->gradbuf; critic->grads = d->gradbuf + d->nA;
@@ -236,12 +315,16 @@ static int critic_head(cpp_net* c, int wi, const float* action, int B) {
 
 // ddpg_cartpole.py:111-113 + :220-222.  critic_prefix_done: the critic prefix for batch.state_1 is
 // already in critic->ws[0] (fused step computes it once for both updates).
-static int actor_gradients(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done) {
+static int actor_gradients(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, bool draw = true) {
   cpp_net *a = d->actor, *c = d->critic;
   const int B = b->B, C = a->spec.pixel ? a->spec.C : 0;
   const float* w1 = white_of(b, 0, C);
   RC(net_forward_trunk(a, a->ws[0], b->s[0], b->dtype, w1, B));
   RC(net_forward_fc(a, a->ws[0], 0, B, nullptr));
+  if (d->sac) {      // (draw == false: an evaluation, eps = 0 and the count unread)
+    SacSampleArgs sa = sac_sample_args(d, false, draw); sa.B = B;
+    RC(launch_sac_sample(d->ctx, sa));
+  }
   if (!critic_prefix_done) RC(critic_prefix(c, b->s[0], b->dtype, w1, B));
   RC(critic_head(c, 1, a->ws[0].out, B));
   // d(sum_b Q)/da: dz of the linear q layer is 1
@@ -261,6 +344,13 @@ static int actor_gradients(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done) {
   }
   // grad_ys = -dQ/da through the tanh head, then the whole actor backward
   const int alast = (int)a->fc.size() - 1;
+  if (d->sac) {      // (an evaluation, draw == false, leaves the partials, their batch size and the recorded temperature to the last gradient pass)
+    SacGradArgs sg = sac_grad_args(d, B);
+    if (!draw) { sg.part = nullptr; sg.alpha_out = nullptr; }
+    RC(launch_sac_actor_grad(d->ctx, sg));
+    if (draw) d->sac_B = B;
+  }
+  else
   RC(launch_actor_head_grad(d->ctx, a->ws[0].dz[alast], d->dq_da, a->ws[0].out, B * a->spec.action_dim));
   RC(net_backward(a, a->ws[0], B, true, nullptr, b->s[0], b->dtype, w1));
   return CPP_OK;
@@ -285,6 +375,12 @@ static int critic_gradients_impl(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_d
   RC(net_forward_fc(ta, ta->ws[0], 0, B, nullptr));
   RC(critic_prefix(tc, b->s[1], b->dtype, w2, B));
   const float* tact = ta->ws[0].out;
+  if (d->sac) {      // a' and logp' from the target actor's head (the actor's, to the bit); check_loss: eps = 0, nothing drawn
+    SacSampleArgs st = sac_sample_args(d, true, backward, b); st.B = B;
+    RC(launch_sac_sample(d->ctx, st));
+    if (backward) d->tps_pending = true;
+  }
+  const float* rw = d->sac ? d->sac_rsoft : b->r;
   if (backward && d->tps_on) {      // (the train op only: check_loss is an evaluation and draws nothing)
     const int A = ta->spec.action_dim;
     RC(launch_tps_smooth(d->ctx, tps_args(d), tact, A, d->tps_act, A, B, A));
@@ -302,10 +398,10 @@ static int critic_gradients_impl(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_d
     return CPP_OK;
   }
   if (d->twin)
-    RC(launch_td_twin(d->ctx, c->ws[0].out, c->ws[0].out2, tc->ws[0].out, tc->ws[0].out2, b->r, b->m, d->hp.discount, B, d->td, d->td2,
+    RC(launch_td_twin(d->ctx, c->ws[0].out, c->ws[0].out2, tc->ws[0].out, tc->ws[0].out2, rw, b->m, d->hp.discount, B, d->td, d->td2,
                       backward ? c->ws[0].dz[last] : nullptr, backward ? c->ws[0].dz2[last] : nullptr, d->loss_norms));
   else
-  RC(launch_td(d->ctx, c->ws[0].out, tc->ws[0].out, b->r, b->m, d->hp.discount, B, d->td,
+  RC(launch_td(d->ctx, c->ws[0].out, tc->ws[0].out, rw, b->m, d->hp.discount, B, d->td,
                backward ? c->ws[0].dz[last] : nullptr, d->loss_norms));
   d->loss_parts = 0;
   if (backward) RC(net_backward(c, c->ws[0], B, true, nullptr, b->s[0], b->dtype, w1));
@@ -393,9 +489,13 @@ static int apply(cpp_ddpg* d, bool do_actor, bool do_critic, float grad_scale, u
       s.img[j].white = tables_done ? next->white + (long)s.img[j].col * 2 * next_C : nullptr;
     }
   }
+  // soft actor-critic: the temperature's update leaves with the actor's list, a launch of its own (rate 0: a fixed temperature, none)
+  if (d->sac && do_actor && d->sac_lr > 0.f && d->sac_B > 0) RC(launch_sac_temperature(d->ctx, d->sac_part, d->sac_B, d->sac_lr, d->sac_w, d->sac_step));
   // norms_out[group] is only written for lists that were applied (n > 0)
   RC(launch_opt_apply(d->ctx, s, grad_scale, d->hp.gradient_clip, d->norm_part, NORM_PARTS, d->loss_norms + 1));
   if (img && s.img_n) for (int j = 0; j < 4; ++j) inets[j]->wimg_key = next->white + (long)(j < 2 ? 0 : 1) * 2 * next_C;
+  // ... and the critic's list closes a minibatch: the target actor becomes the actor as this launch left it (behind the soft update)
+  if (d->sac && do_critic) RC(sac_sync_target(d));
   return CPP_OK;
 }
 
@@ -444,7 +544,7 @@ extern "C" int cpp_ddpg_q_gradients_wrt_actions(cpp_ddpg* d, cpp_batch* b, float
   RC(check_batch(d, b, "cpp_ddpg_q_gradients_wrt_actions"));
   HIP_CHECK(hipSetDevice(d->ctx->device));
   RC(prep_batch(d, b));
-  RC(actor_gradients(d, b, false));
+  RC(actor_gradients(d, b, false, false));
   hipStream_t st = d->ctx->stream;
   const int A = d->actor->spec.action_dim;
   if (dq_da) HIP_CHECK(hipMemcpyAsync(dq_da, d->dq_da, (size_t)b->B * A * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -528,6 +628,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   static const bool no_heads = cpp_switch_off("CPP_FUSED_HEADS");
   DdpgHeadsArgs hd; memset(&hd, 0, sizeof(hd));
   const bool twin = d->twin;
+  const bool sac = d->sac;         // (its actor's head is 2A wide and linear: never the fused heads)
   const int dist = d->dist_n;      // (its q layer has N outputs: never the fused heads)
   bool fused = !dist && !no_heads && na >= 2 && cat >= 1 && nc - cat == 2 && a->fc[na - 1].act == GE_TANH && Lcat.act == GE_RELU &&
                c->fc[nc - 1].n_out == 1 && c->fc[nc - 1].act == GE_NONE && a->fc[na - 1].n_out == A;
@@ -627,7 +728,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   int aF = tA, taF = tTA;
   for (int l = 0; l < na; ++l) {
     GemmArgs g = fc_fwd_args(a, a->ws[0], l, B), t = fc_fwd_args(ta, ta->ws[0], l, B);
-    if (l == na - 1) {      // actions land directly in the critics' splice columns as well
+    if (l == na - 1 && !sac) {      // actions land directly in the critics' splice columns as well
       g.C2 = c->ws[1].fcin[cat] + (Lcat.n_in - A); g.ldc2 = ldcat;
       t.C2 = tc->ws[0].fcin[cat] + (Lcat.n_in - A); t.ldc2 = ldcat;
     }
@@ -636,6 +737,13 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   if (a->drop_counter) {     // --use-dropout: this forward is counted once its layers have read the counter
     G.fn([=] { return bump_dropout(a); }, {aF});
     G.fn([=] { return bump_dropout(ta); }, {taF});
+  }
+  if (sac) {      // sac.hip's jobs 1 and 2 stand where the tanh epilogue stood: sample, log-density, splice columns, the soft reward
+    SacSampleArgs sa = sac_sample_args(d, false, true), st = sac_sample_args(d, true, true, b);
+    sa.B = st.B = B; sa.ld_splice = st.ld_splice = ldcat;
+    sa.splice = c->ws[1].fcin[cat] + (Lcat.n_in - A); st.splice = tc->ws[0].fcin[cat] + (Lcat.n_in - A);
+    aF = G.fn([=] { return launch_sac_sample(ctx, sa); }, {aF});
+    taF = G.fn([=] { return launch_sac_sample(ctx, st); }, {taF});
   }
   int cP = tC, tcP = tTC;
   for (int l = 0; l < cat; ++l) {
@@ -678,9 +786,14 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   }
   {   // dQ/da (kept for cpp_ddpg_q_gradients_wrt_actions) and, in the same epilogue, the actor's head gradient
     const float* dz = (cat == nc - 1) ? top : c->ws[1].dz[cat];
-    GemmArgs ga = fc_dx_args(c, cat, B, dz, Lcat.n_out, Lcat.n_in - A, A, d->dq_da, A, GE_ACTOR_HEAD, a->ws[0].out, A);
-    ga.C2 = a->ws[0].dz[na - 1]; ga.ldc2 = A;
+    GemmArgs ga = fc_dx_args(c, cat, B, dz, Lcat.n_out, Lcat.n_in - A, A, d->dq_da, A, sac ? GE_NONE : GE_ACTOR_HEAD, sac ? nullptr : a->ws[0].out, sac ? 0 : A);
+    if (!sac) { ga.C2 = a->ws[0].dz[na - 1]; ga.ldc2 = A; }
     adz = G.gemm(ga, {g, aF});
+    if (sac) {      // job 3: the (B, 2A) head gradient and the temperature gradient's partials
+      const SacGradArgs sg = sac_grad_args(d, B);
+      adz = G.fn([=] { return launch_sac_actor_grad(ctx, sg); }, {adz});
+      d->sac_B = B;
+    }
   }
 
   // ---- actor backward
@@ -696,13 +809,14 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
 
   // ---- TD target + critic backward on the first evaluation (fed actions)
   const float* per_w = d->per_w;
+  const float* rw = sac ? d->sac_rsoft : b->r;      // (r_soft: written by job 2, which tcH follows)
   if (dist)
     cdz = G.fn([=] { return dist_td(d, b, B, true, per_w); }, {c0, tcH});
   else if (twin)
-    cdz = G.fn([=] { return launch_td_twin(ctx, c->ws[0].out, c->ws[0].out2, tc->ws[0].out, tc->ws[0].out2, b->r, b->m, d->hp.discount, B, d->td, d->td2,
+    cdz = G.fn([=] { return launch_td_twin(ctx, c->ws[0].out, c->ws[0].out2, tc->ws[0].out, tc->ws[0].out2, rw, b->m, d->hp.discount, B, d->td, d->td2,
                                            c->ws[0].dz[nc - 1], c->ws[0].dz2[nc - 1], d->loss_norms, per_w); }, {c0, tcH, c0b, tcHb});
   else
-  cdz = G.fn([=] { return launch_td(ctx, c->ws[0].out, tc->ws[0].out, b->r, b->m, d->hp.discount, B, d->td,
+  cdz = G.fn([=] { return launch_td(ctx, c->ws[0].out, tc->ws[0].out, rw, b->m, d->hp.discount, B, d->td,
                                         c->ws[0].dz[nc - 1], d->loss_norms, per_w); }, {c0, tcH});
   if (d->per_hook) G.fn(d->per_hook, {cdz});
   int cdz2 = cdz;      // head 2's chain down to the concat layer, level by level beside head 1's
@@ -730,7 +844,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     conv_bwd = G.fn([=] { return nets_backward_conv(ctx, bn, 2, B, s1, dt, w1); }, {adz, cdz});
   }
   DwPendingGuard pending(ctx);      // (a failure below drops what was queued)
-  if (d->tps_on && phase != 2) d->tps_pending = true;      // (this pass reads the count: exactly one increment follows it)
+  if ((d->tps_on || sac) && phase != 2) d->tps_pending = true;      // (this pass reads the count: exactly one increment follows it)
   if (phase == 2) {
     if (conv_bwd >= 0) RC(G.ops[conv_bwd].fn());
     return flush_dw_reduce(ctx);
@@ -794,6 +908,8 @@ extern "C" int cpp_ddpg_set_target_smoothing(cpp_ddpg* d, float sigma, float cli
             (double)sigma, (double)clip);
   ARG_CHECK(!(sigma > 0.f && clip == 0.f), "cpp_ddpg_set_target_smoothing: sigma %g with clip 0 (the noise would be clipped away)", (double)sigma);
   ARG_CHECK(!(sigma == 0.f && clip > 0.f), "cpp_ddpg_set_target_smoothing: clip %g without a noise (sigma 0, clip 0 switches smoothing off)", (double)clip);
+  ARG_CHECK(!(d->sac && sigma > 0.f), "cpp_ddpg_set_target_smoothing: a soft actor-critic trainer (its target action is a sample already)");
+  if (d->sac) return CPP_OK;      // ("off" on a soft actor-critic trainer: the count word is its noise stream's and stays as it is)
   cpp_ctx* ctx = d->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
   HIP_CHECK(ctx_sync_stream(ctx));
@@ -815,6 +931,7 @@ extern "C" int cpp_ddpg_set_target_smoothing(cpp_ddpg* d, float sigma, float cli
 extern "C" int cpp_ddpg_set_policy_delay(cpp_ddpg* d, int delay) {
   ARG_CHECK(d, "cpp_ddpg_set_policy_delay: NULL argument");
   ARG_CHECK(delay >= 1 && delay <= 65536, "cpp_ddpg_set_policy_delay: delay %d outside [1, 65536]", delay);
+  ARG_CHECK(!(d->sac && delay > 1), "cpp_ddpg_set_policy_delay: a soft actor-critic trainer updates its policy in every minibatch");
   cpp_ctx* ctx = d->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
   HIP_CHECK(ctx_sync_stream(ctx));
@@ -1139,12 +1256,18 @@ static int half_step(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed, bool spli
   return CPP_OK;
 }
 
+// the data-parallel entry points: g_alpha is not in the flat gradient buffer the ranks reduce
+static int sac_refuse(const cpp_ddpg* d, const char* who) {
+  ARG_CHECK(!(d && d->sac), "%s: a soft actor-critic trainer has no data-parallel step (the temperature's gradient is not in the reduced buffer)", who);
+  return CPP_OK;
+}
 static int half_step_checks(cpp_ddpg* d, cpp_replay* r, int B, const char* who) {
   ARG_CHECK(d && r, "%s: NULL argument", who);
   return train_entry_checks(who, r, B, d->maxB, d->actor->state_elems, d->actor->spec.action_dim, d->hp.discount, nullptr, false);
 }
 
 extern "C" int cpp_ddpg_sample_and_compute(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed) {
+  RC(sac_refuse(d, "cpp_ddpg_sample_and_compute"));
   RC(per_refuse(r, "cpp_ddpg_sample_and_compute"));
   if (d) route_check(d);
   RC(half_step_checks(d, r, B, "cpp_ddpg_sample_and_compute"));
@@ -1159,6 +1282,7 @@ static long fc_start(const cpp_net* n) { return n->fc[0].w_off; }
 
 extern "C" int cpp_ddpg_allreduce_grads(cpp_ddpg* d, cpp_comm* c) {
   ARG_CHECK(d && c, "cpp_ddpg_allreduce_grads: NULL argument");
+  RC(sac_refuse(d, "cpp_ddpg_allreduce_grads"));
   ARG_CHECK(c->ctx == d->ctx, "cpp_ddpg_allreduce_grads: communicator and networks live on different contexts");
   HIP_CHECK(hipSetDevice(d->ctx->device));
   NCCL_CHECK(ncclAllReduce(d->gradbuf, d->gradbuf, (size_t)(d->nA + d->nC), ncclFloat, ncclSum, c->comm, d->ctx->stream));
@@ -1169,6 +1293,7 @@ extern "C" int cpp_ddpg_allreduce_grads(cpp_ddpg* d, cpp_comm* c) {
 // functions of the parameter history and would otherwise drift apart)
 extern "C" int cpp_ddpg_average_params(cpp_ddpg* d, cpp_comm* c) {
   ARG_CHECK(d && c, "cpp_ddpg_average_params: NULL argument");
+  RC(sac_refuse(d, "cpp_ddpg_average_params"));
   ARG_CHECK(c->ctx == d->ctx, "cpp_ddpg_average_params: communicator and networks live on different contexts");
   HIP_CHECK(hipSetDevice(d->ctx->device));
   cpp_net* nets[4] = {d->actor, d->critic, d->tactor, d->tcritic};
@@ -1191,6 +1316,7 @@ extern "C" int cpp_ddpg_average_params(cpp_ddpg* d, cpp_comm* c) {
 // comm == NULL: a single learner taking the same path (tests).  Whitening statistics and target updates are local.
 extern "C" int cpp_ddpg_dp_train_step(cpp_ddpg* d, cpp_replay* r, cpp_comm* c, int B, int n_batches, uint64_t seed,
                                       int sync_every, int overlap) {
+  RC(sac_refuse(d, "cpp_ddpg_dp_train_step"));
   RC(per_refuse(r, "cpp_ddpg_dp_train_step"));
   RC(half_step_checks(d, r, B, "cpp_ddpg_dp_train_step"));
   RC(nstep_refuse(r, d->hp.discount, "cpp_ddpg_dp_train_step"));
@@ -1346,6 +1472,80 @@ extern "C" int cpp_ddpg_last_distribution(cpp_ddpg* d, int B, float* p, float* t
   if (p) HIP_CHECK(hipMemcpyAsync(p, d->dist_p, n, hipMemcpyDeviceToHost, st));
   if (target_p) HIP_CHECK(hipMemcpyAsync(target_p, d->dist_tp, n, hipMemcpyDeviceToHost, st));
   if (m) HIP_CHECK(hipMemcpyAsync(m, d->dist_m, n, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  return CPP_OK;
+}
+
+// Soft actor-critic (Haarnoja et al. 2018; an extension of the actor's train op ddpg_cartpole.py:102-119 and of the critic's target
+// :199-214; include/cartpolepp_abi.h).  Temperature, target entropy, rate and seed are captured by value: the call zeroes the noise count,
+// Adam's slots and count, copies the actor into the target actor and drops the cached graphs.
+extern "C" int cpp_ddpg_set_sac(cpp_ddpg* d, float init_temperature, float target_entropy, float temperature_lr, uint64_t seed) {
+  ARG_CHECK(d, "cpp_ddpg_set_sac: NULL argument");
+  if (!d->sac) { cpp_set_error("cpp_ddpg_set_sac: the trainer's actors are not Gaussian actors (cpp_net_create_gaussian)"); return CPP_ERR_STATE; }
+  ARG_CHECK(std::isfinite(init_temperature) && init_temperature > 0.f, "cpp_ddpg_set_sac: temperature %g (finite, positive)", (double)init_temperature);
+  ARG_CHECK(std::isfinite(target_entropy), "cpp_ddpg_set_sac: target entropy %g (finite)", (double)target_entropy);
+  ARG_CHECK(std::isfinite(temperature_lr) && temperature_lr >= 0.f, "cpp_ddpg_set_sac: temperature learning rate %g (finite, >= 0; 0: fixed)", (double)temperature_lr);
+  ARG_CHECK(d->tps_on == false && d->pd_d == 1, "cpp_ddpg_set_sac: target policy smoothing or a policy delay is on");
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  return sac_configure(d, init_temperature, target_entropy, temperature_lr, seed);
+}
+
+// What the last gradient pass of a soft actor-critic trainer left (the sample that stands where ddpg_cartpole.py:95-100's tanh stood, the
+// target :199-214): eps, a (B, A) and logp (B) of the draw at state_1 and of the draw at state_2, r_soft (B), the temperature the actor
+// pass read, g_alpha of its rows and the count the target draw was made at; dz: the head gradient (d m | d x), (B, 2A).  NULL pointers are skipped.
+extern "C" int cpp_ddpg_last_sac(cpp_ddpg* d, int B, float* eps, float* a, float* logp, float* eps2, float* a2, float* logp2, float* r_soft,
+                                 float* alpha, float* g_alpha, uint64_t* n, float* dz) {
+  ARG_CHECK(d, "cpp_ddpg_last_sac: NULL argument");
+  ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_sac: batch %d outside [1,%d]", B, d->maxB);
+  if (!d->sac) { cpp_set_error("cpp_ddpg_last_sac: the trainer's actors are not Gaussian actors"); return CPP_ERR_STATE; }
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  hipStream_t st = d->ctx->stream;
+  const size_t nA = (size_t)B * d->actor->spec.action_dim * sizeof(float), nB = (size_t)B * sizeof(float);
+  if (eps) HIP_CHECK(hipMemcpyAsync(eps, d->sac_eps[0], nA, hipMemcpyDeviceToHost, st));
+  if (a) HIP_CHECK(hipMemcpyAsync(a, d->actor->ws[0].out, nA, hipMemcpyDeviceToHost, st));
+  if (logp) HIP_CHECK(hipMemcpyAsync(logp, d->sac_logp[0], nB, hipMemcpyDeviceToHost, st));
+  if (eps2) HIP_CHECK(hipMemcpyAsync(eps2, d->sac_eps[1], nA, hipMemcpyDeviceToHost, st));
+  if (a2) HIP_CHECK(hipMemcpyAsync(a2, d->tactor->ws[0].out, nA, hipMemcpyDeviceToHost, st));
+  if (logp2) HIP_CHECK(hipMemcpyAsync(logp2, d->sac_logp[1], nB, hipMemcpyDeviceToHost, st));
+  if (r_soft) HIP_CHECK(hipMemcpyAsync(r_soft, d->sac_rsoft, nB, hipMemcpyDeviceToHost, st));
+  if (dz) HIP_CHECK(hipMemcpyAsync(dz, d->actor->ws[0].dz[d->actor->fc.size() - 1], 2 * nA, hipMemcpyDeviceToHost, st));
+  if (alpha) HIP_CHECK(hipMemcpyAsync(alpha, d->sac_w + SAC_W_ALPHA, sizeof(float), hipMemcpyDeviceToHost, st));
+  if (n) HIP_CHECK(hipMemcpyAsync(n, d->tps_n + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  double parts[DDPG_HEADS_MAX_WGS];
+  const int np = d->sac_B > 0 ? sac_grid(d->sac_B) : 0;
+  if (g_alpha && np) HIP_CHECK(hipMemcpyAsync(parts, d->sac_part, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  if (g_alpha) {      // (the fixed-order finalisation of sac.hip's job 4)
+    double s = 0.0;
+    for (int i = 0; i < np; ++i) s += parts[i];
+    *g_alpha = np ? (float)(-(s / (double)d->sac_B)) : 0.f;
+  }
+  return CPP_OK;
+}
+
+// log_alpha, Adam's slots and its count for checkpoints (util.py:88-90: tf.train.Saver saves every variable of the graph).  set == 0: read
+// into the pointers; otherwise written from them (all four needed).  The noise count is not part of it: a resumed run restarts the stream.
+extern "C" int cpp_ddpg_sac_temperature(cpp_ddpg* d, int set, float* log_alpha, float* m, float* v, uint64_t* step) {
+  ARG_CHECK(d, "cpp_ddpg_sac_temperature: NULL argument");
+  if (!d->sac) { cpp_set_error("cpp_ddpg_sac_temperature: the trainer's actors are not Gaussian actors"); return CPP_ERR_STATE; }
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  hipStream_t st = d->ctx->stream;
+  float w[SAC_WORDS];
+  HIP_CHECK(hipMemcpyAsync(w, d->sac_w, sizeof(w), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  if (!set) {
+    if (log_alpha) *log_alpha = w[SAC_W_LOG_ALPHA];
+    if (m) *m = w[SAC_W_M];
+    if (v) *v = w[SAC_W_V];
+    if (step) { HIP_CHECK(hipMemcpyAsync(step, d->sac_step, sizeof(uint64_t), hipMemcpyDeviceToHost, st)); HIP_CHECK(hipStreamSynchronize(st)); }
+    return CPP_OK;
+  }
+  ARG_CHECK(log_alpha && m && v && step, "cpp_ddpg_sac_temperature: NULL argument");
+  ARG_CHECK(std::isfinite(*log_alpha) && std::isfinite(*m) && std::isfinite(*v) && *v >= 0.f, "cpp_ddpg_sac_temperature: log_alpha %g, m %g, v %g",
+            (double)*log_alpha, (double)*m, (double)*v);
+  w[SAC_W_LOG_ALPHA] = w[SAC_W_TARGET] = *log_alpha; w[SAC_W_M] = *m; w[SAC_W_V] = *v;
+  HIP_CHECK(hipMemcpyAsync(d->sac_w, w, sizeof(w), hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(d->sac_step, step, sizeof(uint64_t), hipMemcpyHostToDevice, st));
   HIP_CHECK(hipStreamSynchronize(st));
   return CPP_OK;
 }

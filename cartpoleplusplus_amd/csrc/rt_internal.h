@@ -114,6 +114,9 @@ struct cpp_net {
   // quantile critic (cpp_net_create_quantile): the same N-wide q_value and `logits` workspace, dist_n = N, read as N quantile atoms
   // theta_i at tau_i = (2 i + 1) / (2 N) -- there is no support, and cpp_net_distribution_info keeps answering 0 atoms
   bool quant = false;
+  // Gaussian actor (cpp_net_create_gaussian): output_action is 2A wide, (m | x), and lands in `logits`; `out` stays (maxB, A) and holds
+  // the action sac.hip forms from it.  ls = lo + 0.5 (hi - lo) (tanh(x) + 1).  gauss_stage: (2, maxB, A) for cpp_net_forward_gaussian
+  bool gauss = false; float ls_lo = 0.f, ls_hi = 0.f; float* gauss_stage = nullptr;
 };
 
 struct cpp_batch {
@@ -315,6 +318,8 @@ int twin_forward_fc(cpp_net* n, Workspace& w, int B);
 inline float* fc_last_out(const Workspace& w) { return w.logits ? w.logits : w.out; }
 // Q (and, dz != nullptr, p (z - Q); a quantile critic: 1 / N) from the logits the forward left in w: a no-op for every other network
 int dist_expect(cpp_net* n, Workspace& w, int B, float* dz);
+// a = tanh(m) (eps = 0) of a Gaussian actor from the head the forward left in w, into w.out: a no-op for every other network
+int gauss_mean(cpp_net* n, Workspace& w, int B, float* m_out = nullptr, float* ls_out = nullptr);
 int batch_stats(cpp_ctx* ctx, const void* s0, const void* s1, int dtype, long elems, int B, int C, double* part, float* white);
 int batch_ensure_stats(cpp_batch* b, int C);
 uint64_t replay_next_uid();      // graph keys: a fresh uid per cpp_replay_create and per change of a sampled memory's statistics setting

@@ -40,7 +40,7 @@ static int net_build(cpp_net* n) {
   const int hid_act = s.use_dropout ? GE_RELU_DROPOUT : GE_RELU;       // hidden_layers_starting_at with opts (base_network.py:69-70)
   if (s.kind == CPP_ACTOR) {
     for (int i = 0; i < s.n_hidden; ++i) { add_fc("h" + std::to_string(i), n_in, s.hidden[i], hid_act, 0); n_in = s.hidden[i]; }
-    add_fc("output_action", n_in, A, GE_TANH, 0);                       // ddpg_cartpole.py:95-100
+    add_fc("output_action", n_in, n->gauss ? 2 * A : A, n->gauss ? GE_NONE : GE_TANH, 0);      // ddpg_cartpole.py:95-100 (a Gaussian actor: (m | x))
   } else if (s.kind == CPP_HEAD) {                                      // naf_cartpole.py:104-109,156-161,180-184
     for (int i = 0; i < s.n_hidden; ++i) { add_fc("h" + std::to_string(i), n_in, s.hidden[i], hid_act, 0); n_in = s.hidden[i]; }
     add_fc("fc", n_in, s.head_out, s.head_act == 2 ? GE_TANH : GE_NONE, 0);
@@ -85,6 +85,9 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
   if (n->dist_n) {      // distributional critic: the logits beside a Q of width one
     RC(dalloc(n->arena, &w.logits, (size_t)mb * n->dist_n));
     RC(dalloc(n->arena, &w.out, (size_t)mb));
+  } else if (n->gauss) {      // Gaussian actor: the 2A-wide head beside an action of width A
+    RC(dalloc(n->arena, &w.logits, (size_t)mb * n->fc.back().n_out));
+    RC(dalloc(n->arena, &w.out, (size_t)mb * n->spec.action_dim));
   } else
   RC(dalloc(n->arena, &w.out, (size_t)mb * n->fc.back().n_out));
   if (n->twin && trunk) {      // (head 2 runs on the fed action only: the first workspace)
@@ -120,7 +123,7 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
 }
 
 static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out, int dist_n = 0, float v_min = 0.f, float v_max = 0.f,
-                      bool quant = false);
+                      bool quant = false, bool gauss = false, float ls_lo = 0.f, float ls_hi = 0.f);
 extern "C" int cpp_net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, cpp_net** out) {
   return net_create(ctx, spec, max_batch, false, out);
 }
@@ -165,22 +168,48 @@ extern "C" int cpp_net_quantile_info(const cpp_net* n, int* n_quantiles) {
   if (n_quantiles) *n_quantiles = n->quant ? n->dist_n : 0;
   return CPP_OK;
 }
+// An actor whose last layer emits the mean and the bounded log standard deviation of a Gaussian under a tanh (Haarnoja et al. 2018; an
+// extension of ddpg_cartpole.py:95-100): see include/cartpolepp_abi.h
+extern "C" int cpp_net_create_gaussian(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, float log_std_min, float log_std_max, cpp_net** out) {
+  ARG_CHECK(ctx && spec && out, "cpp_net_create_gaussian: NULL argument");
+  ARG_CHECK(spec->kind == CPP_ACTOR, "cpp_net_create_gaussian: kind %d (a Gaussian policy belongs to an actor)", spec->kind);
+  ARG_CHECK(std::isfinite(log_std_min) && std::isfinite(log_std_max) && log_std_min < log_std_max,
+            "cpp_net_create_gaussian: log std bounds [%g, %g] (finite, min < max)", (double)log_std_min, (double)log_std_max);
+  ARG_CHECK(spec->action_dim >= 1 && spec->action_dim <= 64, "cpp_net_create_gaussian: action_dim %d outside [1, 64]", spec->action_dim);
+  return net_create(ctx, spec, max_batch, false, out, 0, 0.f, 0.f, false, true, log_std_min, log_std_max);
+}
+// the actor of ddpg_cartpole.py:95-100 widened: 1 and the bounds for a network made by cpp_net_create_gaussian, 0 for any other
+extern "C" int cpp_net_gaussian_info(const cpp_net* n, int* gaussian, float* log_std_min, float* log_std_max) {
+  ARG_CHECK(n, "cpp_net_gaussian_info: NULL argument");
+  if (gaussian) *gaussian = n->gauss ? 1 : 0;
+  if (log_std_min) *log_std_min = n->ls_lo;
+  if (log_std_max) *log_std_max = n->ls_hi;
+  return CPP_OK;
+}
+int gauss_mean(cpp_net* n, Workspace& w, int B, float* m_out, float* ls_out) {
+  if (!n->gauss) return CPP_OK;
+  SacSampleArgs s; memset(&s, 0, sizeof(s));
+  s.logits = w.logits; s.B = B; s.A = n->spec.action_dim; s.lo = n->ls_lo; s.hi = n->ls_hi;
+  s.a_out = w.out; s.m_out = m_out; s.ls_out = ls_out;
+  return launch_sac_sample(n->ctx, s);
+}
 int dist_expect(cpp_net* n, Workspace& w, int B, float* dz) {
   if (!n->dist_n) return CPP_OK;
   if (n->quant) return launch_quant_expect(n->ctx, w.logits, B, n->dist_n, w.out, dz);
   return launch_dist_expect(n->ctx, w.logits, B, n->dist_n, n->dist_vmin, n->dist_vmax, w.out, dz);
 }
 
-static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out, int dist_n, float v_min, float v_max, bool quant) {
+static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out, int dist_n, float v_min, float v_max, bool quant,
+                      bool gauss, float ls_lo, float ls_hi) {
   ARG_CHECK(ctx && spec && out, "cpp_net_create: NULL argument");
   ARG_CHECK(max_batch >= 1, "cpp_net_create: max_batch %d", max_batch);
   ARG_CHECK(spec->kind == CPP_ACTOR || spec->kind == CPP_CRITIC || spec->kind == CPP_HEAD, "cpp_net_create: kind %d", spec->kind);
   if (spec->kind == CPP_HEAD) ARG_CHECK(spec->head_out >= 1 && spec->head_out <= 64 && (spec->head_act == 0 || spec->head_act == 2),
                                         "cpp_net_create: head_out %d head_act %d", spec->head_out, spec->head_act);
   // (a head network's action_dim is its output width -- NAF's l_values head has A (A + 1) / 2 outputs, up to 36 -- and shapes nothing)
-  if (spec->kind != CPP_HEAD)
+  if (spec->kind != CPP_HEAD && !gauss)      // (cpp_net_create_gaussian has checked its own range)
     ARG_CHECK(spec->action_dim >= 1 && spec->action_dim <= 16, "cpp_net_create: action_dim %d outside [1, 16]", spec->action_dim);
-  else ARG_CHECK(spec->action_dim >= 1, "cpp_net_create: action_dim %d", spec->action_dim);
+  else if (spec->kind == CPP_HEAD) ARG_CHECK(spec->action_dim >= 1, "cpp_net_create: action_dim %d", spec->action_dim);
   ARG_CHECK(spec->n_hidden >= 0 && spec->n_hidden <= 8, "cpp_net_create: n_hidden %d outside [0, 8]", spec->n_hidden);
   for (int i = 0; i < spec->n_hidden; ++i)
     ARG_CHECK(spec->hidden[i] >= 1, "cpp_net_create: hidden layer %d has width %d (at least 1)", i, spec->hidden[i]);
@@ -197,6 +226,7 @@ static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, boo
   n->is_training = true; n->drop_counter = nullptr; n->bn_part = nullptr; n->bn_means = nullptr; n->bn_scratch = nullptr;
   n->twin = twin;
   n->dist_n = dist_n; n->dist_vmin = v_min; n->dist_vmax = v_max; n->quant = quant;
+  n->gauss = gauss; n->ls_lo = ls_lo; n->ls_hi = ls_hi;
   int rc = net_build(n);
   if (rc) { delete n; return rc; }
   auto fail = [&](int r) { n->arena.release(); delete n; return r; };
@@ -706,14 +736,15 @@ int batch_stats(cpp_ctx* ctx, const void* s0, const void* s1, int dtype, long el
   return CPP_OK;
 }
 
-extern "C" int cpp_net_forward(cpp_net* n, const void* state, int state_dtype, int B, const float* action, float* out) {
-  ARG_CHECK(n && state && out, "cpp_net_forward: NULL argument");
+// (m_out / ls_out: device buffers a Gaussian actor's mean kernel also fills -- cpp_net_forward_gaussian; out == nullptr: nothing is copied back)
+static int forward_batch(cpp_net* n, const void* state, int state_dtype, int B, const float* action, float* out, float* m_out, float* ls_out) {
+  ARG_CHECK(n && state, "cpp_net_forward / cpp_net_forward_gaussian: NULL argument");
   ARG_CHECK(B >= 1 && B <= n->maxB, "cpp_net_forward: batch %d outside [1,%d]", B, n->maxB);
   ARG_CHECK(state_dtype == CPP_F32 || state_dtype == CPP_F16, "cpp_net_forward: dtype %d", state_dtype);
   ARG_CHECK(n->spec.kind != CPP_CRITIC || action, "cpp_net_forward: critic needs an action batch");
   cpp_ctx* ctx = n->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
-  const int A = n->spec.action_dim, no = n->dist_n ? 1 : n->fc.back().n_out;      // (a distributional critic returns Q)
+  const int A = n->spec.action_dim, no = n->dist_n ? 1 : n->gauss ? A : n->fc.back().n_out;      // (a distributional critic returns Q, a Gaussian actor tanh(m))
   if (!n->stage_state) {
     RC(n->arena.alloc(&n->stage_state, (size_t)n->maxB * n->state_elems * sizeof(float), false));
     RC(dalloc(n->arena, &n->stage_action, (size_t)n->maxB * A));
@@ -727,8 +758,10 @@ extern "C" int cpp_net_forward(cpp_net* n, const void* state, int state_dtype, i
   int frc = net_forward_trunk(n, n->ws[0], n->stage_state, state_dtype, n->white, B);
   if (!frc) frc = net_forward_fc(n, n->ws[0], 0, B, action ? n->stage_action : nullptr);
   if (!frc) frc = dist_expect(n, n->ws[0], B, nullptr);
+  if (!frc) frc = gauss_mean(n, n->ws[0], B, m_out, ls_out);
   n->is_training = true;
   if (frc) return frc;
+  if (!out) return CPP_OK;
   HIP_CHECK(hipMemcpyAsync(out, n->ws[0].out, (size_t)B * no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(ctx_sync_stream(ctx));
   return CPP_OK;
@@ -737,14 +770,14 @@ extern "C" int cpp_net_forward(cpp_net* n, const void* state, int state_dtype, i
 // B independent action_given calls in one pass (rollout-side inference for many env workers): every
 // image is whitened with ITS OWN statistics, exactly as B separate batches of one would be (base_network.py:95-99
 // at B = 1); everything after the whitening is row-local anyway.
-extern "C" int cpp_net_forward_each(cpp_net* n, const void* state, int state_dtype, int B, const float* action, float* out) {
-  ARG_CHECK(n && state && out, "cpp_net_forward_each: NULL argument");
+static int forward_each(cpp_net* n, const void* state, int state_dtype, int B, const float* action, float* out, float* m_out, float* ls_out) {
+  ARG_CHECK(n && state, "cpp_net_forward_each: NULL argument");
   ARG_CHECK(B >= 1 && B <= n->maxB, "cpp_net_forward_each: batch %d outside [1,%d]", B, n->maxB);
   ARG_CHECK(state_dtype == CPP_F32 || state_dtype == CPP_F16, "cpp_net_forward_each: dtype %d", state_dtype);
   ARG_CHECK(n->spec.kind != CPP_CRITIC || action, "cpp_net_forward_each: critic needs an action batch");
   cpp_ctx* ctx = n->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
-  const int A = n->spec.action_dim, no = n->dist_n ? 1 : n->fc.back().n_out, C = n->spec.C;
+  const int A = n->spec.action_dim, no = n->dist_n ? 1 : n->gauss ? A : n->fc.back().n_out, C = n->spec.C;
   if (!n->stage_state) {
     RC(n->arena.alloc(&n->stage_state, (size_t)n->maxB * n->state_elems * sizeof(float), false));
     RC(dalloc(n->arena, &n->stage_action, (size_t)n->maxB * A));
@@ -772,10 +805,38 @@ extern "C" int cpp_net_forward_each(cpp_net* n, const void* state, int state_dty
   int frc = net_forward_trunk(n, n->ws[0], n->stage_state, state_dtype, n->white_rows, B, wbs);
   if (!frc) frc = net_forward_fc(n, n->ws[0], 0, B, action ? n->stage_action : nullptr);
   if (!frc) frc = dist_expect(n, n->ws[0], B, nullptr);
+  if (!frc) frc = gauss_mean(n, n->ws[0], B, m_out, ls_out);
   n->is_training = true;
   if (frc) return frc;
+  if (!out) return CPP_OK;
   HIP_CHECK(hipMemcpyAsync(out, n->ws[0].out, (size_t)B * no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(ctx_sync_stream(ctx));
+  return CPP_OK;
+}
+
+extern "C" int cpp_net_forward(cpp_net* n, const void* state, int state_dtype, int B, const float* action, float* out) {
+  ARG_CHECK(out, "cpp_net_forward: NULL argument");
+  return forward_batch(n, state, state_dtype, B, action, out, nullptr, nullptr);
+}
+extern "C" int cpp_net_forward_each(cpp_net* n, const void* state, int state_dtype, int B, const float* action, float* out) {
+  ARG_CHECK(out, "cpp_net_forward_each: NULL argument");
+  return forward_each(n, state, state_dtype, B, action, out, nullptr, nullptr);
+}
+
+// The head of a Gaussian actor for host-side sampling (the exploration of ddpg_cartpole.py:127-134, whose noise stays outside the device
+// graph): m and ls, each (B, A), of cpp_net_forward (each == 0) or cpp_net_forward_each (each != 0) on the same states
+extern "C" int cpp_net_forward_gaussian(cpp_net* n, const void* state, int state_dtype, int B, int each, float* m, float* ls) {
+  ARG_CHECK(n && state && m && ls, "cpp_net_forward_gaussian: NULL argument");
+  if (!n->gauss) { cpp_set_error("cpp_net_forward_gaussian: not a Gaussian actor"); return CPP_ERR_STATE; }
+  ARG_CHECK(B >= 1 && B <= n->maxB, "cpp_net_forward_gaussian: batch %d outside [1,%d]", B, n->maxB);
+  const int A = n->spec.action_dim;
+  HIP_CHECK(hipSetDevice(n->ctx->device));
+  if (!n->gauss_stage) RC(dalloc(n->arena, &n->gauss_stage, (size_t)2 * n->maxB * A));
+  float *dm = n->gauss_stage, *dls = n->gauss_stage + (size_t)n->maxB * A;
+  RC(each ? forward_each(n, state, state_dtype, B, nullptr, nullptr, dm, dls) : forward_batch(n, state, state_dtype, B, nullptr, nullptr, dm, dls));
+  HIP_CHECK(hipMemcpyAsync(m, dm, (size_t)B * A * sizeof(float), hipMemcpyDeviceToHost, n->ctx->stream));
+  HIP_CHECK(hipMemcpyAsync(ls, dls, (size_t)B * A * sizeof(float), hipMemcpyDeviceToHost, n->ctx->stream));
+  HIP_CHECK(ctx_sync_stream(n->ctx));
   return CPP_OK;
 }
 

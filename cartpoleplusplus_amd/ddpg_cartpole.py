@@ -178,6 +178,18 @@ def build_parser():
     a('--quantile-huber-kappa', type=float, default=argparse.SUPPRESS, help="--quantile-critic: the Huber threshold of the quantile loss (default 1.0)")
     a('--drop-top-quantiles', type=int, default=argparse.SUPPRESS,
       help="--quantile-critic: drop the D largest target quantiles before the regression (overestimation control; default 0; 0 .. N - 1)")
+    # soft actor-critic (an extension beyond the reference, ddpg_cartpole.py:95-119, :199-214: Haarnoja et al. 2018): a stochastic
+    # tanh-Gaussian actor, an entropy term in the critic's target and a learned temperature; with --twin-q and random shift this is DrQ
+    # (absent from the parsed options unless given, like --twin-q; soft_actor_critic() reads them)
+    a('--soft-actor-critic', action='store_true', default=argparse.SUPPRESS,
+      help="maximum-entropy learner: the actor emits a tanh-Gaussian policy, the target carries -alpha log pi, alpha is learned")
+    a('--sac-init-temperature', type=float, default=argparse.SUPPRESS, help="--soft-actor-critic: the initial temperature alpha (default 0.1)")
+    a('--sac-target-entropy', type=float, default=argparse.SUPPRESS, help="--soft-actor-critic: the target entropy (default: -action_dim)")
+    a('--sac-temperature-learning-rate', type=float, default=argparse.SUPPRESS,
+      help="--soft-actor-critic: Adam's rate for log alpha (default 1e-4; 0: a fixed temperature)")
+    a('--sac-log-std-min', type=float, default=argparse.SUPPRESS, help="--soft-actor-critic: lower bound of the policy's log std (default -10)")
+    a('--sac-log-std-max', type=float, default=argparse.SUPPRESS, help="--soft-actor-critic: upper bound of the policy's log std (default 2)")
+    a('--sac-seed', type=int, default=argparse.SUPPRESS, help="--soft-actor-critic: seed of the policy noise on the device (default 0)")
     # n-step returns for this learner (ReplayMemory.enable_n_step; absent unless given): with --prioritized-replay, --data-parallel and
     # --distributional-critic this is D4PG from the command line
     a('--n-step', type=int, default=argparse.SUPPRESS,
@@ -327,6 +339,68 @@ def quantile_critic(o):
     return (int(n), k, int(d))
 
 
+_SAC_DEFAULTS = {"sac_init_temperature": 0.1, "sac_target_entropy": None, "sac_temperature_learning_rate": 1e-4,
+                 "sac_log_std_min": -10.0, "sac_log_std_max": 2.0, "sac_seed": 0}
+SAC_ACTION_DIM_MAX = 64
+
+
+def soft_actor_critic(o, action_dim=None):
+    """{init_temperature, target_entropy (None: -action_dim, filled in when action_dim is given), temperature_learning_rate, log_std_min,
+    log_std_max, seed} of --soft-actor-critic and its --sac-* flags, or None (off); refuses what cannot be meant."""
+    import math
+    on = bool(getattr(o, "soft_actor_critic", False))
+    given = [k for k in _SAC_DEFAULTS if getattr(o, k, None) is not None]
+    if not on:
+        if given:
+            raise SystemExit("--%s needs --soft-actor-critic" % given[0].replace("_", "-"))
+        return None
+    if float(getattr(o, "target_policy_noise", 0.0) or 0.0) > 0.0:
+        raise SystemExit("--soft-actor-critic cannot be combined with --target-policy-noise (its target action is a sample already)")
+    if policy_delay(o) > 1:
+        raise SystemExit("--soft-actor-critic cannot be combined with --policy-delay above 1")
+    if bool(getattr(o, "distributional_critic", False)):
+        raise SystemExit("--soft-actor-critic cannot be combined with --distributional-critic")
+    if bool(getattr(o, "quantile_critic", False)):
+        raise SystemExit("--soft-actor-critic cannot be combined with --quantile-critic")
+    if bool(getattr(o, "use_batch_norm", False)):
+        raise SystemExit("--soft-actor-critic cannot be combined with --use-batch-norm")
+    if bool(getattr(o, "use_dropout", False)):
+        raise SystemExit("--soft-actor-critic cannot be combined with --use-dropout")
+    if bool(getattr(o, "data_parallel", False)):
+        raise SystemExit("--soft-actor-critic is not supported by the data-parallel step (the temperature's gradient is not reduced): drop --data-parallel")
+    v = {}
+    for k, dflt in _SAC_DEFAULTS.items():
+        x = getattr(o, k, None)
+        x = dflt if x is None else x
+        if k == "sac_seed":
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 <= int(x) < 2 ** 64:
+                raise SystemExit("--sac-seed %r is not in [0, 2^64)" % (x,))
+            v[k[4:]] = int(x)
+            continue
+        if x is None:
+            v[k[4:]] = None
+            continue
+        try:
+            x = float(np.float32(x))
+        except (TypeError, ValueError) as e:
+            raise SystemExit("--%s: %s" % (k.replace("_", "-"), e))
+        if not math.isfinite(x):
+            raise SystemExit("--%s %r is not finite" % (k.replace("_", "-"), getattr(o, k, None)))
+        v[k[4:]] = x
+    if not v["init_temperature"] > 0.0:
+        raise SystemExit("--sac-init-temperature %r is not positive" % v["init_temperature"])
+    if v["temperature_learning_rate"] < 0.0:
+        raise SystemExit("--sac-temperature-learning-rate %r is negative (0: a fixed temperature)" % v["temperature_learning_rate"])
+    if not v["log_std_min"] < v["log_std_max"]:
+        raise SystemExit("--sac-log-std-min %r is not below --sac-log-std-max %r" % (v["log_std_min"], v["log_std_max"]))
+    if action_dim is not None:
+        if not 1 <= int(action_dim) <= SAC_ACTION_DIM_MAX:
+            raise SystemExit("--soft-actor-critic takes action dimensions up to %d (got %d)" % (SAC_ACTION_DIM_MAX, int(action_dim)))
+        if v["target_entropy"] is None:
+            v["target_entropy"] = -float(action_dim)
+    return v
+
+
 def n_step(o):
     """n of --n-step; 1 (off) unless given"""
     n = getattr(o, "n_step", 1)
@@ -361,6 +435,9 @@ def default_opts(**overrides):
     o.distributional_critic, o.num_atoms, o.v_min, o.v_max = False, None, None, None
     o.quantile_critic, o.num_quantiles, o.quantile_huber_kappa, o.drop_top_quantiles = False, None, None, None
     o.n_step = 1
+    o.soft_actor_critic = False
+    for k in _SAC_DEFAULTS:
+        setattr(o, k, None)
     for k, v in overrides.items():
         assert hasattr(o, k), k
         setattr(o, k, v)
@@ -400,7 +477,11 @@ class ActorNetwork(base_network.Network):
                                                              opts.action_noise_sigma)
         opts.hidden_layers = opts.actor_hidden_layers                 # ddpg_cartpole.py:91
         self.input_state_network(self.input_state, opts)
-        self._build_native(_lib.CPP_ACTOR, action_dim, max(int(opts.batch_size), 1))
+        # --soft-actor-critic: output_action emits (m | x), 2A wide; forward returns tanh(m), exploration samples on the host
+        self.sac = soft_actor_critic(opts, action_dim)
+        self._build_native(_lib.CPP_ACTOR, action_dim, max(int(opts.batch_size), 1),
+                           gaussian=(self.sac["log_std_min"], self.sac["log_std_max"]) if self.sac else None)
+        self._sac_rng = np.random.default_rng(self.sac["seed"]) if self.sac else None
         self.output_action = _OpHandle(namespace + "/output_action")
         self.train_op = None
         self.critic = None
@@ -426,6 +507,8 @@ class ActorNetwork(base_network.Network):
         add_noise each row gets its own Ornstein-Uhlenbeck process (one per worker, created on first use)."""
         s, dt = _lib.as_state_array(states)
         B = s.shape[0]
+        if self.sac and add_noise:
+            return self._sample_gaussian(s, dt, B, each=True)
         actions = np.empty((B, self.action_dim), np.float32)
         check(lib.cpp_net_forward_each(self.handle, ptr(s), dt, B, None, ptr(actions)))
         if add_noise:
@@ -437,8 +520,26 @@ class ActorNetwork(base_network.Network):
             actions = np.minimum(1, actions)     # the reference's clip quirk, per row (:134)
         return actions
 
+    def forward_gaussian(self, states, each=False):
+        """(m, ls), each (B, action_dim): the head of a --soft-actor-critic actor on a host batch of states (cpp_net_forward_gaussian)"""
+        s, dt = _lib.as_state_array(states)
+        B = s.shape[0]
+        m, ls = np.empty((B, self.action_dim), np.float32), np.empty((B, self.action_dim), np.float32)
+        check(lib.cpp_net_forward_gaussian(self.handle, ptr(s), dt, B, 1 if each else 0, ptr(m), ptr(ls)))
+        return m, ls
+
+    def _sample_gaussian(self, s, dt, B, each):
+        # tanh(m + exp(ls) z), z from numpy's generator: the policy's own exploration replaces the Ornstein-Uhlenbeck process; like it,
+        # the noise stays outside the device graph (:127-134)
+        m, ls = self.forward_gaussian(s, each)
+        z = self._sac_rng.standard_normal((B, self.action_dim)).astype(np.float32)
+        return np.tanh(m + np.exp(ls) * z).astype(np.float32)
+
     def action_given(self, state, add_noise=False):
         # feed explicitly provided state (batch of one; whitening uses this image's own statistics)
+        if self.sac and add_noise:
+            s, dt = _lib.as_state_array(np.asarray(state)[None])
+            return self._sample_gaussian(s, dt, 1, each=False)
         actions = self.forward(np.asarray(state)[None])
         # NOTE: noise is added outside the device graph, as in the reference (:127-134)
         if add_noise:
@@ -508,6 +609,10 @@ class _Trainer(object):
         quantiles = getattr(critic, "quantiles", None)
         if quantiles:
             self.set_quantile_target(quantiles[1], quantiles[2])
+        # --soft-actor-critic: temperature, target entropy, rate and seed, as parsed when the actor was built
+        self.sac = getattr(actor, "sac", None)
+        if self.sac:
+            self.set_sac(self.sac["init_temperature"], self.sac["target_entropy"], self.sac["temperature_learning_rate"], self.sac["seed"])
 
     @property
     def handle(self):
@@ -606,6 +711,35 @@ class _Trainer(object):
         out = [np.empty((B, n), np.float32) for _ in range(3)]
         check(lib.cpp_ddpg_last_quantiles(self.handle, B, *[ptr(x) for x in out]))
         return tuple(out)
+
+    def set_sac(self, init_temperature, target_entropy, temperature_lr, seed):
+        """soft actor-critic's temperature, target entropy, temperature rate (0: fixed) and noise seed (include/cartpolepp_abi.h,
+        cpp_ddpg_set_sac); zeroes the noise count and the temperature's Adam state, drops the captured graphs."""
+        check(lib.cpp_ddpg_set_sac(self.handle, float(init_temperature), float(target_entropy), float(temperature_lr), int(seed)))
+
+    def last_sac(self, B):
+        """what the last gradient pass of a --soft-actor-critic trainer left: dict of eps, a (B, A), logp (B) of the draw at state_1,
+        eps2, a2, logp2 of the draw at state_2, r_soft (B), alpha, g_alpha, the noise count n and dz, the head gradient (d m | d x), (B, 2A)"""
+        B, A = int(B), self.action_dim
+        o = {k: np.empty((B, A), np.float32) for k in ("eps", "a", "eps2", "a2")}
+        o.update({k: np.empty(B, np.float32) for k in ("logp", "logp2", "r_soft")})
+        o["dz"] = np.empty((B, 2 * A), np.float32)
+        alpha, g, n = C.c_float(), C.c_float(), C.c_uint64()
+        check(lib.cpp_ddpg_last_sac(self.handle, B, ptr(o["eps"]), ptr(o["a"]), ptr(o["logp"]), ptr(o["eps2"]), ptr(o["a2"]), ptr(o["logp2"]),
+                                    ptr(o["r_soft"]), C.byref(alpha), C.byref(g), C.byref(n), ptr(o["dz"])))
+        o.update(alpha=float(alpha.value), g_alpha=float(g.value), n=int(n.value))
+        return o
+
+    def get_sac_state(self):
+        """{log_alpha, m, v, step}: the temperature and its Adam state (checkpoints; the noise count is not part of it)"""
+        la, m, v, t = C.c_float(), C.c_float(), C.c_float(), C.c_uint64()
+        check(lib.cpp_ddpg_sac_temperature(self.handle, 0, C.byref(la), C.byref(m), C.byref(v), C.byref(t)))
+        return {"log_alpha": np.float32(la.value), "m": np.float32(m.value), "v": np.float32(v.value), "step": np.uint64(t.value)}
+
+    def set_sac_state(self, state):
+        la, m, v = (C.c_float(float(np.asarray(state[k]).reshape(()))) for k in ("log_alpha", "m", "v"))
+        t = C.c_uint64(int(np.asarray(state["step"]).reshape(())))
+        check(lib.cpp_ddpg_sac_temperature(self.handle, 1, C.byref(la), C.byref(m), C.byref(v), C.byref(t)))
 
     def set_quantile_target(self, kappa, drop_top):
         """the quantile Huber threshold and the number of largest target quantiles dropped (include/cartpolepp_abi.h,
@@ -786,6 +920,7 @@ class DeepDeterministicPolicyGradientAgent(object):
         # (the refusals of --distributional-critic and --n-step come before anything exists on the device, as check_prioritized_opts')
         distributional_critic(opts)
         quantile_critic(opts)
+        soft_actor_critic(opts, action_dim)
         n_step(opts)
         # (--exact-products asks for the exact arithmetic contract; without the flag the context keeps whatever mode its owner chose --
         # an explicit Context.set_precision("exact") is not undone, and a second agent on the shared context does not fight the first)
@@ -823,6 +958,13 @@ class DeepDeterministicPolicyGradientAgent(object):
 
     def networks(self):
         return [self.actor, self.critic, self.target_actor, self.target_critic]
+
+    def checkpoint_extras(self):
+        """(prefix, get, set) of state a checkpoint carries by name besides the networks and the optimiser slots: the temperature of a
+        --soft-actor-critic agent ('sac::log_alpha', 'sac::m', 'sac::v', 'sac::step'); nothing for any other agent"""
+        if not self.actor.sac:
+            return []
+        return [("sac::", lambda: self.trainer.get_sac_state(), lambda st: self.trainer.set_sac_state(st))]
 
     def post_var_init_setup(self):
         if opts.event_log_in:

@@ -163,6 +163,10 @@ class SaverUtil(object):
                 opt.set_optimiser_state({"m": data["optimiser::m"], "v": data["optimiser::v"], "step": data["optimiser::step"]})
             elif opt is not None:
                 sys.stderr.write("checkpoint %s holds no optimiser slots: Momentum / Adam restart from zero\n" % most_recent_ckpt)
+            for prefix, _get, put in getattr(self.agent, "checkpoint_extras", lambda: [])():      # (state an agent names itself)
+                keys = [k for k in data.files if k.startswith(prefix)]
+                assert keys, "checkpoint holds no %s* entries" % prefix
+                put({k[len(prefix):]: data[k] for k in keys})
             self.next_scheduled_save_time = time.time() + self.save_freq
         else:
             sys.stderr.write("no latest ckpt in %s, just initing vars...\n" % self.ckpt_dir)
@@ -183,6 +187,9 @@ class SaverUtil(object):
         if opt is not None:
             for k, v in opt.get_optimiser_state().items():
                 blob["optimiser::" + k] = v
+        for prefix, get, _put in getattr(self.agent, "checkpoint_extras", lambda: [])():
+            for k, v in get().items():
+                blob[prefix + k] = v
         final = "%s/%s.npz" % (self.ckpt_dir, name)
         with open(final + ".tmp", "wb") as f:          # (a file object: np.savez would append ".npz" to a temporary NAME)
             np.savez(f, **blob)

@@ -201,6 +201,44 @@ int cpp_net_distribution_info(const cpp_net* net, int* n_atoms, float* v_min, fl
 int cpp_net_create_quantile(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, int n_quantiles, cpp_net** out);
 /* N of a network made by cpp_net_create_quantile (the critic of ddpg_cartpole.py:166-177 widened); 0 for any other.  NULL is skipped. */
 int cpp_net_quantile_info(const cpp_net* net, int* n_quantiles);
+/* Gaussian actor: the stochastic tanh-Gaussian policy of soft actor-critic (Haarnoja et al. 2018), an extension of the actor
+ * ddpg_cartpole.py:95-100.  The layout is cpp_net_create's actor except that 'output_action/weights' is (n_in, 2A) and
+ * 'output_action/biases' is (2A): the last layer is linear and emits (m_k, x_k), k < A -- m in columns [0, A), x in [A, 2A).  spec->kind
+ * must be CPP_ACTOR, lo < hi both finite, 1 <= A <= 64 (CPP_ERR_ARG otherwise; a trainer needs a critic, whose A is at most 16).  All
+ * arithmetic below is float32, every operation rounded on its own, sums over k ascending from 0.
+ *   ls_k = lo + (0.5 (hi - lo)) (tanh(x_k) + 1)                 smooth bounds, no kinks
+ *   u_k  = m_k + exp(ls_k) eps_k ;   a_k = tanh(u_k)
+ *   logp = sum_k [ ((-0.5 eps_k^2 - ls_k) - 0.5 log(2 pi)) - 2 ((log 2 - u_k) - softplus(-2 u_k)) ]
+ *   softplus(y) = max(y, 0) + log1p(exp(-|y|))                  the stable form, never log(1 - a^2 + 1e-6)
+ * cpp_net_forward* return tanh(m) (eps = 0, width A); cpp_net_forward_gaussian returns m and ls for host-side sampling.
+ * A trainer built on such actors (cpp_ddpg_create: both actors Gaussian with one (lo, hi), or neither; never with distributional or
+ * quantile critics, batch norm or dropout; batches up to 1024) is a soft actor-critic trainer.  With alpha = exp(log_alpha), log_alpha
+ * one f32 in device memory, per row b of minibatch t:
+ *   eps    the unclipped Box-Muller z = sqrt(-2 log u1) cospi(2 u2) on two 24-bit uniforms of
+ *          philox4x32_10({row, S + k, n_lo, n_hi}, seed), S = 0x200 for the draw at state_1, 0x300 for the draw at state_2; n counts the
+ *          target-forming gradient passes since cpp_ddpg_set_sac (a device word: a replayed graph draws fresh noise; the pass that reads
+ *          it never writes it, the optimiser's launch behind it or a launch of its own does)
+ *   a', logp'  a sample of the policy as it stood before t's actor update, at state_2 (SAC has no target actor: the target actor's
+ *          parameters are a bit copy of the actor's, made behind every launch that applies the critic's list and when SAC is configured;
+ *          the soft update no longer decides them)
+ *   r_soft = r - ((mask discount) alpha) logp' ;   td = Q(s1, a_fed) - (r_soft + mask discount Q'(s2, a'))
+ *          (twin heads: min(Q1', Q2'); an n-step memory has folded its powers into mask) -- priorities, cpp_ddpg_last_values and
+ *          cpp_ddpg_check_loss read this td; check_loss keeps the entropy term at eps = 0 and draws nothing
+ *   actor  minimises sum_b (alpha logp - Q(s1, a)) at a sample a at state_1 (twin heads: head 1).  With dq = dQ/da_k:
+ *          g_u = 2 alpha a_k - dq (1 - a_k^2);   d m_k = g_u;   d x_k = ((g_u exp(ls_k)) eps_k - alpha) * ((0.5 (hi - lo)) (1 - tanh(x_k)^2))
+ *   temperature  g_alpha = -(1/B) sum_b (logp_b + Hbar), the gradient of -log_alpha (logp + Hbar), from per-workgroup f64 partials (four
+ *          rows each, in order) added in order; applied by Adam (TensorFlow's semantics, betas 0.9 / 0.999, epsilon 1e-8) at the
+ *          temperature's rate, in a launch of its own when the actor's list is applied; rate 0: a fixed temperature, no launch.
+ *          Both passes of minibatch t read the temperature as it stood before t's update.
+ * cpp_ddpg_q_gradients_wrt_actions evaluates at eps = 0.  Such a trainer always takes the GEMM levels of the gradient pass, refuses
+ * target policy smoothing, a policy delay above 1 and the data-parallel entry points.  cpp_naf_create refuses such networks.  A
+ * checkpoint carries the 2A-wide head by name: a plain checkpoint fails the layout check, in both directions. */
+int cpp_net_create_gaussian(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, float log_std_min, float log_std_max, cpp_net** out);
+/* gaussian = 1 and (lo, hi) of a network made by cpp_net_create_gaussian (the actor of ddpg_cartpole.py:95-100 widened); 0 for any other. */
+int cpp_net_gaussian_info(const cpp_net* net, int* gaussian, float* log_std_min, float* log_std_max);
+/* The head of a Gaussian actor on a fed state batch (ddpg_cartpole.py:123-125 widened; the exploration noise of :127-134 stays on the
+ * host): m and ls, each (B, A); each != 0: every row whitened with its own statistics, as cpp_net_forward_each. */
+int cpp_net_forward_gaussian(cpp_net* net, const void* state, int state_dtype, int B, int each, float* m, float* ls);
 int cpp_net_destroy(cpp_net* net);
 /* Network.trainable_model_vars (base_network.py:51-56): variables in creation order. */
 int64_t cpp_net_num_params(const cpp_net* net);
@@ -513,6 +551,20 @@ int cpp_ddpg_set_quantile_target(cpp_ddpg* ddpg, float kappa, int drop_top);
  * sorted ascending and y_j = r + g s_j of the last minibatch's gradient pass, each (B, N); columns j >= M of y are zero.  NULL pointers are
  * skipped.  CPP_ERR_STATE on any other trainer. */
 int cpp_ddpg_last_quantiles(cpp_ddpg* ddpg, int B, float* theta, float* sorted_target_theta, float* y);
+/* Soft actor-critic trainers (cpp_net_create_gaussian; an extension of the actor's train op ddpg_cartpole.py:102-119 and of the target
+ * :199-214): the initial temperature alpha (> 0), the target entropy Hbar, the temperature's Adam rate (0: fixed) and the noise seed, all
+ * captured by value.  Zeroes the noise count, Adam's slots and count, copies the actor into the target actor, drops the cached graphs.  A
+ * trainer that was never told has alpha 0.1, Hbar = -A, rate 1e-4, seed 0.  CPP_ERR_STATE on a trainer whose actors are not Gaussian. */
+int cpp_ddpg_set_sac(cpp_ddpg* ddpg, float init_temperature, float target_entropy, float temperature_lr, uint64_t seed);
+/* What the last gradient pass of such a trainer left (the sample standing where ddpg_cartpole.py:95-100's tanh stood): eps, a (B, A) and
+ * logp (B) of the draw at state_1, the same three of the draw at state_2, r_soft (B), the alpha the actor pass read, g_alpha of its rows
+ * and the count n the target draw was made at; dz: the actor's head gradient (d m | d x), (B, 2A), as the actor's backward read it.
+ * NULL pointers are skipped. */
+int cpp_ddpg_last_sac(cpp_ddpg* ddpg, int B, float* eps, float* a, float* logp, float* eps2, float* a2, float* logp2, float* r_soft,
+                      float* alpha, float* g_alpha, uint64_t* n, float* dz);
+/* log_alpha, its Adam slots m, v and its count for checkpoints (util.py:88-90).  set == 0: read into the pointers (NULL: skipped); else
+ * written from them (all needed).  The noise count is not checkpointed. */
+int cpp_ddpg_sac_temperature(cpp_ddpg* ddpg, int set, float* log_alpha, float* m, float* v, uint64_t* step);
 
 /* ---- data-parallel actor-learners (the reference's TODO "switch back to async training with multiple replicas",
  * ddpg_cartpole.py:259, naf_cartpole.py:294; its exps only launch independent processes, exps/run_87.sh:12-36) ------------
