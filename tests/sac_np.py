@@ -1,7 +1,8 @@
 """Soft actor-critic (Haarnoja et al. 2018) restated in numpy, in float64 and float32: the tanh-Gaussian policy, its log-density, the
 soft reward, the actor's head gradient, the temperature's gradient and Adam element, and the noise the device draws
-(include/cartpolepp_abi.h, cpp_net_create_gaussian / cpp_ddpg_set_sac).  No tests here: tests/test_sac_host.py and
-tests/test_gpu_sac.py share these.
+(include/cartpolepp_abi.h, cpp_net_create_gaussian / cpp_ddpg_set_sac); below, ComposedSac: the learner with twin critics, the optimisers'
+rules, importance weights and n-step memories, and its cases.  No tests here: tests/test_sac_host.py, tests/test_gpu_sac.py and
+tests/test_gpu_sac_composed.py share these.
 
     ls_k = lo + 0.5 (hi - lo) (tanh(x_k) + 1);   u_k = m_k + exp(ls_k) eps_k;   a_k = tanh(u_k)
     logp = sum_k [ -0.5 eps_k^2 - ls_k - 0.5 log(2 pi) - 2 (log 2 - u_k - softplus(-2 u_k)) ]          k ascending
@@ -14,6 +15,9 @@ FAULTS: the planted faults of the sensitivity test."""
 import numpy as np
 
 from oracle import ddpg_np as O
+from tests import ddpg_opt_np as R
+from tests import td3_np as T3
+from tests import twin_np as W
 from tests.helpers import philox4x32_10_np
 
 LO, HI = -10.0, 2.0
@@ -21,6 +25,19 @@ STREAM_S1, STREAM_S2 = 0x200, 0x300
 FAULTS = ("correction_1e-6", "correction_missing", "entropy_sign", "entropy_unmasked", "one_eps_for_both_draws", "eps_not_refreshed",
           "target_actor_soft_updated", "copy_before_update", "bounds_swapped", "no_2_alpha_a", "no_minus_alpha_in_dx", "no_std_eps_in_dx",
           "gradient_wrt_alpha", "adam_bias_one_step_off", "g_alpha_summed", "temperature_updated_first")
+# the faults of the composed learner (ComposedSac below: twin critics, the optimisers' rules, importance weights, n-step memories)
+COMPOSED_FAULTS = ("target_q1_only",                  # the target from Q1' alone, not the minimum
+                   "actor_follows_q2",
+                   "actor_follows_min",               # the actor ascends min(Q1, Q2) of the online heads
+                   "weights_missing",                 # a uniform loss on a prioritized draw
+                   "weights_on_actor",                # the importance weights on the actor's list as well
+                   "actor_norm_mean_columns_only",    # the actor's clip norm without the head's last A columns (the x half of (m | x))
+                   "g_alpha_in_actor_norm",           # the temperature's gradient counted into the actor's clip norm
+                   "temperature_scaled_by_clip",      # the actor's clip scale on the temperature's step
+                   "temperature_count_tied",          # the temperature's bias correction from the actor's count (none under gradient descent)
+                   "entropy_discount_only",           # the entropy term times discount, not mask discount, on an n-step row
+                   "slots_shared")                    # one set of m and v for both lists
+FAULTS = FAULTS + COMPOSED_FAULTS
 
 
 def _sum_k(t, dt):
@@ -120,7 +137,10 @@ def adam(p, g, m, v, t, lr, beta1=0.9, beta2=0.999, epsilon=1e-8, dt=np.float32,
     """TensorFlow's Adam element on one parameter; t: the count INCLUDING this apply.  Returns (p, m, v)"""
     p, g, m, v = dt(p), dt(g), dt(m), dt(v)
     tt = float(t - 1 if fault == "adam_bias_one_step_off" and t > 1 else (t + 1 if fault == "adam_bias_one_step_off" else t))
-    lr_t = dt(float(np.float32(lr)) * np.sqrt(1.0 - float(np.float32(beta2)) ** tt) / (1.0 - float(np.float32(beta1)) ** tt))
+    if tt <= 0:      # (a count that never advanced -- COMPOSED_FAULTS' "temperature_count_tied": no bias correction)
+        lr_t = dt(np.float32(lr))
+    else:
+        lr_t = dt(float(np.float32(lr)) * np.sqrt(1.0 - float(np.float32(beta2)) ** tt) / (1.0 - float(np.float32(beta1)) ** tt))
     b1, b2 = dt(np.float32(beta1)), dt(np.float32(beta2))
     m = dt(b1 * m + dt((dt(1) - b1) * g))
     v = dt(b2 * v + dt(dt((dt(1) - b2) * g) * g))
@@ -170,7 +190,11 @@ class SacDDPG(O.DDPG):
         _c, m, _x = self._head(self.actor, np.asarray(state)[None], None, training=False)
         return np.tanh(m)
 
-    def actor_gradients(self, s1, eps1=None, fault=None):
+    def _dq_da(self, cc):
+        return self.critic.backward(cc, np.ones_like(cc["out"]), params=False)[1]
+
+    def actor_gradients(self, s1, eps1=None, fault=None, row_scale=None):
+        """row_scale: (B, 1) factors on the head gradient's rows (a fault of the composed learner's)"""
         dt = self.dt
         alpha = dt(np.exp(np.float64(self.sac.log_alpha)))
         w1 = self._white(self.actor, s1)
@@ -178,12 +202,14 @@ class SacDDPG(O.DDPG):
         eps = np.zeros_like(m) if eps1 is None else np.asarray(eps1, dt)
         pol = policy(m, x, eps, self.lo, self.hi, dt, fault)
         cc = self.critic.forward(s1, action=pol["a"], white=w1)
-        _, dq = self.critic.backward(cc, np.ones_like(cc["out"]), params=False)
+        dq = self._dq_da(cc)
         dm, dx = head_gradient(x, pol["a"], eps, dq, alpha, self.lo, self.hi, dt, fault)
+        if row_scale is not None:
+            dm, dx = (dm * np.asarray(row_scale, dt)).astype(dt), (dx * np.asarray(row_scale, dt)).astype(dt)
         grads, _ = self.actor.backward(ca, np.concatenate([dm, dx], axis=1))
         g_alpha = temperature_gradient(pol["logp"], self.sac.hbar, alpha, fault=fault)
         return {"actions": pol["a"], "logp": pol["logp"], "q": cc["out"], "dq_da": dq, "dm": dm, "dx": dx, "alpha": alpha, "g_alpha": g_alpha,
-                "grads": O.flatten(self.actor.spec, grads, dt), "m": m, "x": x, "eps": eps}
+                "grads": O.flatten(self.actor.spec, grads, dt), "m": m, "x": x, "eps": eps, "cache_actor": ca, "q2": cc.get("out2")}
 
     def critic_gradients(self, batch, eps2=None, training=True, fault=None, weights=None):
         s1, a, r, mask, s2 = batch
@@ -203,7 +229,7 @@ class SacDDPG(O.DDPG):
         loss = (w * td * td).mean(dtype=dt)
         grads, _ = self.critic.backward(cb, (dt(2.0) * w * td / dt(B)).astype(dt))
         return {"q": cb["out"], "td": td, "loss": loss, "target_q": tq["out"], "target_actions": pol["a"], "logp2": pol["logp"], "r_soft": rs[:, 0],
-                "m2": m, "x2": x, "grads": O.flatten(self.critic.spec, grads, dt)}
+                "m2": m, "x2": x, "grads": O.flatten(self.critic.spec, grads, dt), "cache_critic": cb}
 
     def update_temperature(self, g_alpha, fault=None):
         s = self.sac
@@ -213,8 +239,8 @@ class SacDDPG(O.DDPG):
         s.log_alpha, s.m, s.v = adam(s.log_alpha, g_alpha, s.m, s.v, s.step, s.lr, fault=fault)
 
     def train_minibatch(self, batch, eps1=None, eps2=None, fault=None, weights=None):
-        """actor.train(s1) then critic.train(batch) on one snapshot; gradient descent on both lists (the other rules: the device's own
-        tests); then the temperature, then the copy that makes the target actor the updated actor"""
+        """actor.train(s1) then critic.train(batch) on one snapshot; gradient descent on both lists (the other rules: ComposedSac
+        below); then the temperature, then the copy that makes the target actor the updated actor"""
         dt, hp = self.dt, self.hp
         if fault == "temperature_updated_first":      # both passes then read the temperature this minibatch's update left
             self.update_temperature(self.actor_gradients(batch[0], eps1)["g_alpha"])
@@ -322,3 +348,456 @@ def eps_bar():
             worst = max(worst, float(np.max(np.abs(noise(7, 0, B, A, s, np.float64) - noise(7, 0, B, A, s, np.float32).astype(np.float64)))))
     b = 8.0 * worst
     return P_BAR if b < P_BAR / 4 else b
+
+
+# ---- the composed learner: twin critics, the optimisers' rules, importance weights, n-step memories -----------------------------------
+class ComposedSac(SacDDPG):
+    """SacDDPG as the trainer composes it (include/cartpolepp_abi.h, cpp_ddpg_set_sac): tests.twin_np.TwinCritic behind both critics
+    (both heads regress onto r_soft + mask discount min(Q1', Q2') at ONE sampled a'; loss = mean(w (td_1^2 + td_2^2)); the actor and
+    dQ/da follow head 1), tests.ddpg_opt_np.apply_rule on each list with its own slots and count (the clip before the moments), the
+    importance weights on the critic's loss alone, the temperature's own Adam element and count, which neither list's clip nor norm
+    touches.  On an n-step memory the mask column carries discount^(n-1): the entropy term is discounted by mask discount as every
+    other part of the target.  critic_flat: [plain critic | twin variables] (tests.twin_np.full_layout) if twin.  fault: one of
+    COMPOSED_FAULTS."""
+
+    def __init__(self, actor_spec, critic_spec, actor_flat, critic_flat, dt=np.float64, hyper=O.DEFAULT_HYPER, state=None,
+                 optimiser="GradientDescent", optimiser_args=None, twin=True, fault=None, lo=LO, hi=HI):
+        from oracle import naf_np as N
+        assert fault is None or fault in COMPOSED_FAULTS, fault
+        n1 = critic_spec.num_params()
+        SacDDPG.__init__(self, actor_spec, critic_spec, actor_flat, critic_flat[:n1], dt, hyper, lo, hi, state)
+        self.twin, self.cfault = bool(twin), fault
+        assert len(critic_flat) == (W.num_params(critic_spec) if twin else n1)
+        self.critic = self._critic(critic_flat)
+        self.target_critic = self._critic(O.soft_update(np.zeros_like(critic_flat), critic_flat, 1.0, dt))
+        args = dict(optimiser_args or {})
+        self.opt = {"actor": N.make_optimiser(optimiser, dict(args, learning_rate=hyper.actor_lr)),
+                    "critic": N.make_optimiser(optimiser, dict(args, learning_rate=hyper.critic_lr))}
+        self.slots = {"actor": R.Slots(len(actor_flat), dt), "critic": R.Slots(len(critic_flat), dt)}
+        self._shared = R.Slots(max(len(actor_flat), len(critic_flat)), dt)      # (the fault "slots_shared")
+        self.min_share = []                 # per target-forming pass: the share of rows whose minimum is head 1's
+        self.clip_scale = {}                # per list: the scale its last apply clipped with
+
+    def _critic(self, flat):
+        return W.TwinCritic(self.critic.spec, flat, self.dt) if self.twin else O.Net(self.critic.spec, flat, self.dt)
+
+    def set_target_critic(self, flat):
+        self.target_critic = self._critic(np.asarray(flat))
+
+    def _dq_da(self, cc):
+        if not self.twin:
+            return SacDDPG._dq_da(self, cc)
+        dq = self.critic.d_action(cc, 1)
+        if self.cfault == "actor_follows_q2":
+            dq = self.critic.d_action(cc, 2)
+        elif self.cfault == "actor_follows_min":
+            dq = np.where(cc["out"] <= cc["out2"], dq, self.critic.d_action(cc, 2))
+        return dq
+
+    def critic_gradients(self, batch, eps2=None, training=True, fault=None, weights=None):
+        s1, a, r, mask, s2 = batch
+        dt, cf = self.dt, self.cfault
+        alpha = dt(np.exp(np.float64(self.target_log_alpha)))
+        w2 = self._white(self.target_actor, s2)
+        _c, m, x = self._head(self.target_actor, s2, w2, training)
+        eps = np.zeros_like(m) if eps2 is None else np.asarray(eps2, dt)
+        pol = policy(m, x, eps, self.lo, self.hi, dt, fault)
+        tq = self.target_critic.forward(s2, action=pol["a"], white=w2, training=training)
+        tq1 = tq["out"]
+        tq2 = tq["out2"] if self.twin else tq1
+        tmin = tq1 if cf == "target_q1_only" else np.minimum(tq1, tq2)
+        if self.twin:
+            self.min_share.append(float((tq1 <= tq2).mean()))
+        mk = np.asarray(mask, dt).reshape(-1)
+        rs = soft_reward(r, (mk != 0).astype(dt) if cf == "entropy_discount_only" else mk, self.hp.discount, alpha, pol["logp"], dt,
+                         fault).reshape(-1, 1)
+        y = rs + mk.reshape(-1, 1) * dt(self.hp.discount) * tmin
+        cb = self.critic.forward(s1, action=np.asarray(a, dt), training=training)
+        td1 = cb["out"] - y
+        B = td1.shape[0]
+        w = np.ones_like(td1) if weights is None or cf == "weights_missing" else np.asarray(weights, dt).reshape(td1.shape)
+        if self.twin:
+            td2 = cb["out2"] - y
+            loss = (w * (td1 * td1) + w * (td2 * td2)).mean(dtype=dt)
+            grads, _ = self.critic.backward(cb, (dt(2.0) * td1 * w / dt(B)).astype(dt), (dt(2.0) * td2 * w / dt(B)).astype(dt))
+            flat = W.flatten_grads(self.critic.spec, grads, dt)
+        else:
+            td2 = td1
+            loss = (w * td1 * td1).mean(dtype=dt)
+            grads, _ = self.critic.backward(cb, (dt(2.0) * w * td1 / dt(B)).astype(dt))
+            flat = O.flatten(self.critic.spec, grads, dt)
+        return {"q": cb["out"], "q2": cb.get("out2"), "td": td1, "td2": td2, "loss": loss, "target_q": tq1, "target_q2": tq2,
+                "target_actions": pol["a"], "logp2": pol["logp"], "r_soft": rs[:, 0], "m2": m, "x2": x, "grads": flat, "cache_critic": cb}
+
+    # ---- the two applies
+    def _actor_norm(self, grads, g_alpha):
+        """the norm the actor's clip is taken with (the list's own; the faults' otherwise)"""
+        g = np.asarray(grads, self.dt)
+        sq = (g * g).sum(dtype=self.dt)
+        if self.cfault == "actor_norm_mean_columns_only":
+            A, off = self._A(), 0
+            for name, shape in self.actor.spec.layout():
+                n = int(np.prod(shape))
+                if name.startswith("output_action/"):
+                    part = g[off:off + n].reshape(shape)[..., A:]
+                    sq = sq - (part * part).sum(dtype=self.dt)
+                off += n
+        elif self.cfault == "g_alpha_in_actor_norm":
+            sq = sq + self.dt(g_alpha) * self.dt(g_alpha)
+        else:
+            return None
+        return np.sqrt(sq)
+
+    def _apply(self, which, grads, norm=None):
+        """tests.ddpg_opt_np.apply_rule on one list; norm: a norm to clip with in place of the list's own.  Returns the pre-clip norm"""
+        dt, clip = self.dt, self.hp.gradient_clip
+        net = getattr(self, which)
+        slots = self.slots[which]
+        if self.cfault == "slots_shared":
+            n = len(slots.m)
+            slots.m, slots.v = self._shared.m[:n].copy(), self._shared.v[:n].copy()
+        if norm is None:
+            new, norm = R.apply_rule(self.opt[which], net.flat(), grads, clip, slots, dt)
+            scale = dt(1.0) if clip is None or norm == 0 else dt(clip) * min(dt(1.0) / norm, dt(1.0) / dt(clip))
+        else:
+            scale = dt(1.0) if clip is None or norm == 0 else dt(clip) * min(dt(1.0) / norm, dt(1.0) / dt(clip))
+            new, _n = R.apply_rule(self.opt[which], net.flat(), (np.asarray(grads, dt) * scale).astype(dt), None, slots, dt)
+        if self.cfault == "slots_shared":
+            self._shared.m[:len(slots.m)], self._shared.v[:len(slots.v)] = slots.m, slots.v
+        self.clip_scale[which] = float(scale)
+        setattr(self, which, O.Net(net.spec, new, dt) if which == "actor" else self._critic(new))
+        return norm
+
+    def update_temperature(self, g_alpha, fault=None):
+        s = self.sac
+        if self.cfault == "temperature_scaled_by_clip":
+            g_alpha = np.float32(float(g_alpha) * self.clip_scale["actor"])
+        if self.cfault != "temperature_count_tied" or s.lr <= 0.0:
+            return SacDDPG.update_temperature(self, g_alpha, fault)
+        s.step += 1      # a list under gradient descent keeps no count: the tied correction reads zero there
+        t = 0 if self.opt["actor"].kind == "sgd" else self.slots["actor"].t
+        s.log_alpha, s.m, s.v = adam(s.log_alpha, g_alpha, s.m, s.v, t, s.lr)
+
+    # ---- the entry points: actor.train(s1), critic.train(batch); the fused minibatch is the two in that order on one snapshot (the
+    # critic's pass reads neither the live actor nor the temperature the actor's op just moved)
+    def train_actor(self, s1, eps1, weights=None):
+        ag = self.actor_gradients(s1, eps1, row_scale=weights if self.cfault == "weights_on_actor" else None)
+        ag["norm"] = self._apply("actor", ag["grads"], self._actor_norm(ag["grads"], ag["g_alpha"]))
+        self.update_temperature(ag["g_alpha"])
+        return ag
+
+    def train_critic(self, batch, eps2, weights=None):
+        cg = self.critic_gradients(batch, eps2, weights=weights)
+        cg["norm"] = self._apply("critic", cg["grads"])
+        self.target_actor = O.Net(self.actor.spec, self.actor.flat(), self.dt)
+        self.target_log_alpha = self.sac.log_alpha
+        self.sac.n += 1
+        return cg
+
+    def train_minibatch(self, batch, eps1=None, eps2=None, fault=None, weights=None, routes=None):
+        """routes: (actor's pool codes, critic's, actor's ReLU decisions, critic's) of the device, to route the trunks' gradients with"""
+        assert fault is None
+        if routes is not None:
+            self.actor.amax_override, self.critic.amax_override, self.actor.relu_override, self.critic.relu_override = routes
+        w = None if weights is None else np.asarray(weights, self.dt).reshape(-1, 1)
+        critic = self.critic                 # (the critic's pass runs on the snapshot: the actor's op does not write it)
+        ag = self.train_actor(batch[0], eps1, w)
+        assert self.critic is critic
+        cg = self.train_critic(batch, eps2, w)
+        out = {"actor_grads": ag["grads"], "critic_grads": cg["grads"], "actor_norm": float(ag["norm"]), "critic_norm": float(cg["norm"]),
+               "log_alpha": self.sac.log_alpha, "cache_actor": ag["cache_actor"], "cache_critic": cg["cache_critic"]}
+        out.update({k: ag[k] for k in ("actions", "logp", "dq_da", "dm", "dx", "alpha", "g_alpha", "m", "x")})
+        out.update({k: cg[k] for k in ("q", "q2", "td", "td2", "loss", "target_q", "target_q2", "target_actions", "logp2", "r_soft", "m2", "x2")})
+        out["loss"] = float(out["loss"])
+        out["routes"] = []      # the conv trunks' pool and ReLU routes (none on a low-dimensional state; the fully connected ReLUs are not listed)
+        for cache in (ag["cache_actor"], cg["cache_critic"]):
+            for name, _k, _co in O.CONV_DEFS if self.actor.spec.pixel else ():
+                out["routes"].append(np.where(cache[name][1] > 0, cache[name + ":amax_own"], 255).astype(np.uint8))
+        return out
+
+    def update_targets(self):      # the critic's alone: the target actor is a copy
+        self.target_critic = self._critic(O.soft_update(self.target_critic.flat(), self.critic.flat(), self.hp.target_update_rate, self.dt))
+
+    def set_state(self, vec):
+        """take over vectors() of another run (the float64 restatement's, or the device's): every minibatch is then compared from one
+        common start, and no comparison carries the roundings of the minibatches before it"""
+        dt = self.dt
+        self.actor = O.Net(self.actor.spec, np.asarray(vec["actor"], dt), dt)
+        self.target_actor = O.Net(self.actor.spec, np.asarray(vec["actor"], dt), dt)
+        self.critic, self.target_critic = self._critic(np.asarray(vec["critic"], dt)), self._critic(np.asarray(vec["target_critic"], dt))
+        na = len(self.slots["actor"].m)
+        for w, sl in ((w, slice(0, na) if w == "actor" else slice(na, None)) for w in R.LISTS):
+            self.slots[w].m, self.slots[w].v = np.asarray(vec["m"][sl], dt).copy(), np.asarray(vec["v"][sl], dt).copy()
+        self.slots["actor"].t, self.slots["critic"].t = (int(t) for t in vec["step"])
+        self._shared.m[:], self._shared.v[:] = 0, 0      # (the fault "slots_shared": one buffer, the actor's values over the critic's)
+        for w in ("critic", "actor"):
+            self._shared.m[:len(self.slots[w].m)], self._shared.v[:len(self.slots[w].v)] = self.slots[w].m, self.slots[w].v
+        s = self.sac
+        s.log_alpha, s.m, s.v, s.step = np.float32(vec["log_alpha"]), np.float32(vec["alpha_m"]), np.float32(vec["alpha_v"]), int(vec["alpha_step"])
+        self.target_log_alpha = s.log_alpha
+
+    def vectors(self):
+        """{name: float64 vector or scalar} of everything the device tests compare after an apply"""
+        f = lambda v: np.asarray(v, np.float64)
+        return {"actor": f(self.actor.flat()), "critic": f(self.critic.flat()), "target_critic": f(self.target_critic.flat()),
+                "m": np.concatenate([f(self.slots[w].m) for w in R.LISTS]), "v": np.concatenate([f(self.slots[w].v) for w in R.LISTS]),
+                "step": [0 if self.opt[w].kind == "sgd" else int(self.slots[w].t) for w in R.LISTS],      # (gradient descent keeps no count)
+                "log_alpha": float(self.sac.log_alpha), "alpha_m": float(self.sac.m),
+                "alpha_v": float(self.sac.v), "alpha_step": int(self.sac.step)}
+
+
+# ---- the composed cases (tests/test_sac_host.py holds them to their conditions, tests/test_gpu_sac_composed.py runs them on the device).
+# tests.helpers.host_case's critic, episodes and rows; a Gaussian actor from a stream of its own with host_case's perturbation and the
+# same again on its head layer (HEAD_PERTURBATION); the twin variables and the shift of head 2's bias as tests.twin_np.host_case has them.
+# The head is not perturbed harder: d a / d x = (1 - a^2) 6 exp(ls) |eps| (1 - tanh(x)^2) grows with the standard deviations -- with 0.3
+# on the head it reaches 10 on these networks, and the float32 twin's own error on x at 64x64x18, 3e-6, is then 3e-5 of a', where the
+# project's 1e-5 on a and a' is the plain learner's, whose a = tanh(head) has d a / d head <= 1.  (At 0.3 the device's a' sat at
+# 1.08e-5 in one minibatch of the 64x64x18 case, the twin's at 5.5e-6; at 0.05 the twin's is 1.5e-6.)
+# (id, shape, A, B, optimiser, clip, tau, twin, weighted, n-step, random-shift pad).  Rates: tests.td3_np.hyper_of's (tests.helpers.LOUD's
+# for gradient descent and Momentum, tests.ddpg_opt_np.RATES' for Adam); the temperature's rate is 1e-2.
+C_SHAPES = {"16x16x6": (16, 16, 3, 1, 2), "64x64x18": (64, 64, 3, 2, 3), "lowdim": (2, 2, 7)}
+C_ROWS, C_MINIBATCHES = 24, 4          # two outer steps of two minibatches
+C_TEMPERATURE, C_TEMPERATURE_LR, C_NOISE_SEED, C_SHIFT_SEED, C_DISCOUNT = 0.2, 1e-2, 0x5AC, 3, 0.9
+HEAD_PERTURBATION = 0.05
+SPLIT_CLIP = 30.0                      # between the two lists' norms of its case: the actor's above, the critic's below
+C_CASES = (("twin-sgd-clip0.5-A2-B8", "16x16x6", 2, 8, "gradient-descent", 0.5, 0.25, True, False, 1, 0),
+           ("twin-adam-unclipped-A1-B5", "16x16x6", 1, 5, "adam", 1e4, 1.0, True, False, 1, 0),
+           ("twin-momentum-split-A3-B7", "16x16x6", 3, 7, "momentum-0.5", SPLIT_CLIP, 0.25, True, False, 1, 0),
+           ("twin-adam-A9-B8", "16x16x6", 9, 8, "adam", 0.5, 0.25, True, False, 1, 0),
+           ("scalar-adam-clip0.5-A2-B8", "16x16x6", 2, 8, "adam", 0.5, 0.25, False, False, 1, 0),
+           ("twin-adam-weighted-A2-B8", "16x16x6", 2, 8, "adam", 0.5, 0.25, True, True, 1, 0),
+           ("twin-adam-nstep3-A2-B8", "16x16x6", 2, 8, "adam", 0.5, 0.25, True, False, 3, 0),
+           ("lowdim-twin-adam-A3-B16", "lowdim", 3, 16, "adam", 0.5, 0.25, True, False, 1, 0),
+           ("drq-64x64x18-A2-B8", "64x64x18", 2, 8, "adam", 0.5, 0.25, True, False, 1, 0),
+           ("drq-u8-shift2-A2-B8", "16x16x6", 2, 8, "adam", 0.5, 0.25, True, False, 1, 2))
+# which side of the clip each list's pre-clip norm lies on, by a factor of 1.2 at the least, in every minibatch: (actor, critic)
+C_SIDES = dict({c[0]: ("above", "above") for c in C_CASES}, **{"twin-adam-unclipped-A1-B5": ("below", "below"),
+                                                                "twin-momentum-split-A3-B7": ("above", "below")})
+# host_case seeds: per case the first of 1, 2, ... on which every condition of tests/test_sac_host.py holds (a case that fails one is
+# given another seed, never a relaxed condition)
+C_SEEDS = {"twin-sgd-clip0.5-A2-B8": 1, "twin-adam-unclipped-A1-B5": 230, "twin-momentum-split-A3-B7": 11, "twin-adam-A9-B8": 3,
+           "scalar-adam-clip0.5-A2-B8": 1, "twin-adam-weighted-A2-B8": 1, "twin-adam-nstep3-A2-B8": 6, "lowdim-twin-adam-A3-B16": 1,
+           "drq-64x64x18-A2-B8": 9, "drq-u8-shift2-A2-B8": 6}
+# (twin-adam-unclipped-A1-B5: what rejects seeds 1 .. 229 is the share of the minimum.  With B = 5 only 2 or 3 rows of 5 meet "each head
+# the minimum on a quarter of the rows", and all four minibatches must: under Adam at tau = 1 the heads drift apart by more than the
+# rows' spread within a minibatch or two, so the share is 0 or 1 somewhere on nearly every seed.  Every other condition holds on most of
+# them -- the case is the fragile one, not the condition.  64x64x18: seeds 1 .. 8 fail the same condition.)
+
+
+# the single ops' case (actor.train then critic.train on host arrays, three minibatches): low-dimensional, twin, Momentum, both lists clipped
+C_SINGLE_OPS = (("single-ops-lowdim-twin-momentum", "lowdim", 3, 16, "momentum-0.5", 0.5, 0.25, True, False, 1, 0), 3, 3)      # case, seed, minibatches
+
+
+def composed_case(cid):
+    return [c for c in C_CASES if c[0] == cid][0]
+
+
+def composed_hyper(case):
+    return T3.hyper_of(case[4], case[5], case[6])._replace(discount=C_DISCOUNT)
+
+
+def composed_specs(shape, A):
+    from tests.helpers import DEFAULT_ACTOR_HIDDEN
+    pixel = len(shape) == 5
+    kw = dict(pixel=True, H=shape[0], W=shape[1], C=int(np.prod(shape[2:]))) if pixel else dict(pixel=False, state_elems=int(np.prod(shape)))
+    return gaussian_spec(A, DEFAULT_ACTOR_HIDDEN, **kw), O.NetSpec("critic", A, DEFAULT_ACTOR_HIDDEN, **kw)
+
+
+def composed_restatement(case, inputs, dt=np.float64, fault=None):
+    _cid, _sn, A, _B, opt, _clip, _tau, twin, _w, _n, _pad = case
+    specs, P = inputs[0], inputs[1]
+    name, args = T3.OPTIMISERS[opt]
+    ref = ComposedSac(specs[0], specs[1], P[0], P[1], dt, composed_hyper(case),
+                      SacState(C_TEMPERATURE, -float(A), C_TEMPERATURE_LR, C_NOISE_SEED), name, args, twin, fault)
+    ref.set_target_critic(P[3])
+    return ref
+
+
+def composed_batches(case, episodes, idxs):
+    """the minibatches the rows select: the one-step transitions, the n-step memory's columns (tests.nstep_np), or the shifted images
+    (tests.shift_np: the k-th augmented gather of the memory)"""
+    from oracle.replay_np import OracleReplayMemory
+    from tests import nstep_np, shift_np
+    _cid, shape_name, A, B, _opt, _clip, _tau, _twin, _w, n_step, pad = case
+    orm = OracleReplayMemory(C_ROWS, C_SHAPES[shape_name], A)
+    for ep in episodes:
+        orm.add_episode(*ep)
+    out = []
+    for k in range(len(idxs) // B):
+        rows = np.asarray(idxs[k * B:(k + 1) * B])
+        ob = orm.batch(idxs=rows)
+        s1, r, m, s2 = ob.state_1, ob.reward, ob.terminal_mask, ob.state_2
+        if n_step > 1:
+            r, m, slots = nstep_np.columns(rows, orm.state_1_idx, orm.state_2_idx, orm.reward, orm.terminal_mask, orm.size(), C_ROWS, n_step,
+                                           C_DISCOUNT)
+            s2 = orm.state[slots]
+        if pad:
+            sh = shift_np.shifts(C_SHIFT_SEED, k, B, pad)
+            s1, s2 = shift_np.shift_images(s1, sh[0]), shift_np.shift_images(s2, sh[1])
+        out.append((s1, ob.action, r, m, s2))
+    return out
+
+
+def composed_inputs(case, seed=None, nb=C_MINIBATCHES):
+    """(specs, P, episodes, idxs, batches): P = [actor, critic (+ twin variables), actor, target critic (+ twin variables)]"""
+    from tests.helpers import host_case as plain_case
+    cid, shape_name, A, B, _opt, _clip, _tau, twin, _w, _n, _pad = case
+    seed = C_SEEDS[cid] if seed is None else seed
+    shape = C_SHAPES[shape_name]
+    _specs, P, episodes, idxs, _b = plain_case(shape, B, nb, seed, rows=C_ROWS, action_dim=A)
+    specs = composed_specs(shape, A)
+    rng = np.random.default_rng(7000 + seed)
+    pa = O.init_params(specs[0], rng)
+    pa = pa + rng.normal(0, 0.05, pa.shape).astype(np.float32)
+    n_head = specs[0].fc[-1][1] * 2 * A + 2 * A
+    pa[-n_head:] += rng.normal(0, HEAD_PERTURBATION, n_head).astype(np.float32)
+    P = [pa, P[1], pa, P[3]]
+    batches = composed_batches(case, episodes, idxs)
+    if twin:
+        on, tg = W.twin_tail(specs[1], np.random.default_rng(5000 + seed))
+        P[1], P[3] = np.concatenate([P[1], on]), np.concatenate([P[3], tg])
+        ref = composed_restatement(case, (specs, P))
+        cg = ref.critic_gradients(batches[0], noise(C_NOISE_SEED, 0, B, A, STREAM_S2))
+        shift = np.float32(np.median(cg["target_q"] - cg["target_q2"]))
+        P[1][-1] += shift
+        P[3][-1] += shift
+    return specs, P, episodes, idxs, batches
+
+
+# the weighted case: a prioritized memory (tests.per_np restates its tree, its stratified draw and its weights), every priority set from
+# a lognormal draw before the first minibatch, beta held at 0.5; the sampler's key is the sample seed and the minibatch's number
+PER = dict(alpha=0.6, eps=1e-6, beta=0.5, sample_seed=11, priorities_seed=9)
+
+
+def per_priorities():
+    return np.random.default_rng(PER["priorities_seed"]).lognormal(0.0, 1.0, C_ROWS).astype(np.float32)
+
+
+class RestatedPer(object):
+    def __init__(self):
+        from tests import per_np as PN
+        self.PN, self.L = PN, PN.levels(C_ROWS)
+        self.tree = PN.build(PN.priority(per_priorities(), PER["alpha"], PER["eps"]).astype(np.float64), self.L)
+
+    def draw(self, k, B):
+        rows, _g = self.PN.draw(self.tree, self.L, C_ROWS, B, PER["sample_seed"], k)
+        return rows.astype(np.int32), self.PN.weights(self.tree, self.L, C_ROWS, rows, PER["beta"])
+
+    def update(self, rows, td):
+        self.PN.write(self.tree, self.L, rows, self.PN.priority(np.abs(np.asarray(td, np.float64)).ravel(), PER["alpha"], PER["eps"]))
+
+
+def run_composed(case, inputs, dt=np.float64, fault=None, eps=None, rows=None, weights=None, states=None):
+    """C_MINIBATCHES minibatches, the target update behind each (one minibatch per call of the device's step): per-minibatch outputs,
+    the vectors after each apply, the restatement.  eps: per minibatch (eps1, eps2), default the restated draws.  The weighted case
+    draws its rows and weights by priority (RestatedPer; rows / weights: the device's own instead, per minibatch).  states: per
+    minibatch the vectors() of another run that minibatch k + 1 starts from (ComposedSac.set_state)"""
+    _cid, _sn, A, B, _opt, _clip, _tau, _twin, weighted, _n, _pad = case
+    ref = composed_restatement(case, inputs, dt, fault)
+    per = RestatedPer() if weighted and rows is None else None
+    outs, vecs = [], []
+    for k in range(len(inputs[4])):
+        e1, e2 = eps[k] if eps is not None else (noise(C_NOISE_SEED, k, B, A, STREAM_S1), noise(C_NOISE_SEED, k, B, A, STREAM_S2))
+        w, b, r = None, inputs[4][k], inputs[3][k * B:(k + 1) * B]
+        if states is not None and k > 0:
+            ref.set_state(states[k - 1])
+            ref.sac.n = k
+        if weighted:
+            r, w = per.draw(k, B) if per is not None else (rows[k], weights[k])
+            b = composed_batches(case, inputs[2], r)[0]
+        out = ref.train_minibatch(b, e1, e2, weights=w)
+        if per is not None:
+            per.update(r, out["td"])
+        out["rows"], out["weights"], out["batch"] = np.asarray(r), w, b
+        outs.append(out)
+        ref.update_targets()
+        vecs.append(ref.vectors())
+    return outs, vecs, ref
+
+
+# ---- the comparison both test modules make: one minibatch from a common start, every compared quantity as error / bar ------------------
+C_LOG_ALPHA_F32_ERROR = 0.0      # the float32 restatement's worst |log_alpha - float64's| over the composed cases (tests/test_sac_host.py
+                                 # re-measures it): Adam's first steps are lr sign(g) whatever g's last bits are
+ROW_BARS = ("actions", "target_actions", "q", "q2", "td", "td2", "dq_da", "logp", "logp2", "r_soft", "g_alpha")
+
+
+def composed_bar(key):
+    """the project's 1e-5 on a, a', Q, td and dQ/da; bar(key) of the head cases on logp, r_soft and g_alpha; log_alpha by the same
+    rule from C_LOG_ALPHA_F32_ERROR"""
+    if key == "log_alpha":
+        b = 8.0 * C_LOG_ALPHA_F32_ERROR
+        return P_BAR if b < P_BAR / 4 else b
+    return bar({"actions": "a", "target_actions": "a2", "q2": "q", "td2": "td", "logp2": "logp"}.get(key, key))
+
+
+def initial_state(inputs):
+    P = inputs[1]
+    n = len(P[0]) + len(P[1])
+    f = lambda v: np.asarray(v, np.float64)
+    return {"actor": f(P[0]), "critic": f(P[1]), "target_critic": f(P[3]), "m": np.zeros(n), "v": np.zeros(n), "step": [0, 0],
+            "log_alpha": float(np.float32(np.log(np.float32(C_TEMPERATURE)))), "alpha_m": 0.0, "alpha_v": 0.0, "alpha_step": 0}
+
+
+def flat_ratio(spec, got, want, rel, rel_of=None, abs_floor=0.0):
+    """tests.helpers.assert_flat_close as a figure: the largest, over the variables, of error / tolerance (<= 1 where it passes)"""
+    from tests.helpers import per_var_report
+    single = set(name for name, shp in spec.layout() if int(np.prod(shp)) == 1)
+    scale = float(np.linalg.norm(np.asarray(want, np.float64))) / np.sqrt(len(want)) + 1e-30
+    worst = 0.0
+    for name, max_abs, rel_l2 in per_var_report(spec, np.asarray(got), want):
+        tol = max(rel, (rel_of or {}).get(name, 0.0))
+        r = min(rel_l2 / tol, max_abs / (tol * scale))
+        if name in single and abs_floor > 0:
+            r = min(r, max_abs / abs_floor)
+        worst = max(worst, r)
+    return worst
+
+
+def f32_rel_of(spec, got32, want):
+    from tests.helpers import F32_GRAD_FACTOR, per_var_report
+    return {n: F32_GRAD_FACTOR * r for n, _m, r in per_var_report(spec, np.asarray(got32, np.float64), want)}
+
+
+def critic_layout(case, specs):
+    return W.TwinLayoutSpec(specs[1]) if case[7] else specs[1]
+
+
+def ratios(case, specs, start, got, got_vec, want, want_vec, twin32, twin32_vec):
+    """{quantity: error / bar} of one minibatch and its apply.  got / want / twin32: the per-minibatch outputs of the device (or of a
+    faulted or float32 restatement), of the float64 restatement and of its float32 twin from the same start; *_vec: vectors() behind
+    the apply.  The bars: composed_bar on the rows; 1e-5 relative on the loss; 1e-4 max(1, norm) on both pre-clip norms; rel 2e-5 per
+    variable on both lists, or F32_GRAD_FACTOR x the twin's own where larger, one-element variables not below 2 max|td error|;
+    tests.helpers.delta_bound on the parameter and target deltas with r = max(5e-5, F32_GRAD_FACTOR x the twin's relative delta
+    error), on the slots with tests.ddpg_opt_np.R's 5e-5; the counts exact.  The temperature: composed_bar on log_alpha; its m and v
+    are one Adam element from a common start, m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2 with b1 = 0.9, b2 = 0.999: a g_alpha
+    inside its bar e moves them by (1 - b1) e and (1 - b2) (2 |g| + e) e, plus one float32 rounding of each"""
+    from tests.helpers import F32_GRAD_FACTOR, delta_bound
+    f = lambda v: np.asarray(v, np.float64).reshape(-1)
+    out = {}
+    for k in ROW_BARS:
+        if want.get(k) is not None:
+            out[k] = float(np.max(np.abs(f(got[k]) - f(want[k])))) / composed_bar(k)
+    out["loss"] = abs(float(got["loss"]) - float(want["loss"])) / (1e-5 * abs(float(want["loss"])))
+    for k in ("actor_norm", "critic_norm"):
+        out[k] = abs(float(got[k]) - float(want[k])) / (1e-4 * max(1.0, float(want[k])))
+    cspec = critic_layout(case, specs)
+    floor = 2.0 * max(float(np.max(np.abs(f(got["td"]) - f(want["td"])))), float(np.max(np.abs(f(got["td2"]) - f(want["td2"])))))
+    out["actor_grads"] = flat_ratio(specs[0], got["actor_grads"], want["actor_grads"], 2e-5, f32_rel_of(specs[0], twin32["actor_grads"], want["actor_grads"]))
+    out["critic_grads"] = flat_ratio(cspec, got["critic_grads"], want["critic_grads"], 2e-5,
+                                     f32_rel_of(cspec, twin32["critic_grads"], want["critic_grads"]), abs_floor=floor)
+    for k in ("actor", "critic", "target_critic", "m", "v"):
+        d_want = want_vec[k] - start[k]
+        size = float(np.linalg.norm(d_want))
+        if size == 0:
+            out[k + "_delta"] = 0.0 if not np.any(f(got_vec[k]) - start[k]) else np.inf
+            continue
+        r = 5e-5
+        if k not in ("m", "v"):
+            r = max(r, F32_GRAD_FACTOR * float(np.linalg.norm(twin32_vec[k] - want_vec[k])) / size)
+        out[k + "_delta"] = float(np.linalg.norm(f(got_vec[k]) - want_vec[k])) / delta_bound(start[k], d_want, r, 1)
+    out["counts"] = 0.0 if list(got_vec["step"]) == list(want_vec["step"]) and got_vec["alpha_step"] == want_vec["alpha_step"] else np.inf
+    out["log_alpha"] = abs(got_vec["log_alpha"] - want_vec["log_alpha"]) / composed_bar("log_alpha")
+    e, g = composed_bar("g_alpha"), abs(float(want["g_alpha"]))
+    out["alpha_m"] = abs(got_vec["alpha_m"] - want_vec["alpha_m"]) / (0.1 * e + 2.0 ** -23 * abs(want_vec["alpha_m"]) + 1e-30)
+    out["alpha_v"] = abs(got_vec["alpha_v"] - want_vec["alpha_v"]) / (1e-3 * (2 * g + e) * e + 2.0 ** -23 * abs(want_vec["alpha_v"]) + 1e-30)
+    return out

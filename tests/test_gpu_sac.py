@@ -225,14 +225,21 @@ def test_outer_steps_on_pixels_against_the_float64_restatement_and_the_target_ac
 RIDER = (64, 64, 3, 2, 3)      # conv1's operand images and their rider in the optimiser's launch exist at 64 x 64 only
 
 
-def test_where_the_image_rider_runs_the_target_forward_reads_the_copied_parameters():
+# (optimiser, actor's rate): gradient descent and Momentum at 0.1; Adam's update is ~ its rate per element whatever the gradient's size, so
+# it runs at tests.ddpg_opt_np.RATES' 2e-3 -- under Adam the rider restates Adam's element for conv1, another piece of the optimiser's launch
+RIDER_OPTIMISERS = {"gradient-descent": 0.1, "momentum-0.5": 0.1, "adam": 2e-3}
+
+
+@pytest.mark.parametrize("opt", sorted(RIDER_OPTIMISERS))
+def test_where_the_image_rider_runs_the_target_forward_reads_the_copied_parameters(opt):
     """three minibatches in one call at 64x64x18: the optimiser's launch of minibatch 2 builds the target actor's conv1 operand image
     from its parameters BEFORE the copy behind it.  a' of minibatch 3 must come from the actor as minibatch 2 left it: compared with a
     forward of a second agent that stopped there, at the device's own eps.  (Two device evaluations, each held to 1e-5 of the float64
-    value elsewhere: 2e-5 between them.  The actor's rate is 0.1, so that one minibatch moves a' by far more.)"""
+    value elsewhere: 2e-5 between them.  The actor's rate is RIDER_OPTIMISERS', so that one minibatch moves a' by far more.)"""
     B, nb = 8, 3
     idxs = np.random.default_rng(12).integers(0, 40, nb * B).astype(np.int32)
-    kw = dict(actor_learning_rate=0.1, sac_seed=6, sac_init_temperature=0.2)
+    from tests import td3_np as T3
+    kw = dict(T3.opt_kw(opt), actor_learning_rate=RIDER_OPTIMISERS[opt], sac_seed=6, sac_init_temperature=0.2)
     before = _agent(RIDER, B, True, 2, **kw)
     try:
         fill_with_rendered_episodes(before, RIDER, 40)
