@@ -106,7 +106,7 @@ static int sac_sync_target(cpp_ddpg* d) {
   d->tactor->wimg_key = nullptr;      // (the image the rider built is of the parameters before the copy)
   return CPP_OK;
 }
-static void invalidate_graphs(cpp_ddpg* d);
+static void reconfigured(cpp_ddpg* d);
 static int sac_configure(cpp_ddpg* d, float init_temperature, float target_entropy, float lr, uint64_t seed) {
   cpp_ctx* ctx = d->ctx;
   HIP_CHECK(ctx_sync_stream(ctx));
@@ -118,8 +118,7 @@ static int sac_configure(cpp_ddpg* d, float init_temperature, float target_entro
   RC(sac_sync_target(d));
   HIP_CHECK(ctx_sync_stream(ctx));
   d->sac_hbar = target_entropy; d->sac_lr = lr; d->sac_seed = seed; d->sac_B = 0; d->tps_pending = false;
-  invalidate_graphs(d);
-  d->pre_variant = 0;
+  reconfigured(d);
   return CPP_OK;
 }
 
@@ -227,6 +226,8 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
 // Everything the captured launches hold by value has changed (the conv1 route, the optimiser's rule, target smoothing): every cached graph
 // of this trainer, the half steps' variants included, misses at its next use.  A new cache needs no line here: gen is part of its key.
 static void invalidate_graphs(cpp_ddpg* d) { ++d->graph_gen; }
+// ... which is how every setter ends; a minibatch presampled for the half steps goes with the graphs that would have consumed it
+static void reconfigured(cpp_ddpg* d) { invalidate_graphs(d); d->pre_variant = 0; }
 
 // What a replay must leave on the host as the eager body would have: how cpp_ddpg_last_stats finds the loss, and -- step: the body was
 // step_body -- no presampled minibatch for the half steps (it lived in the step_batch the step has just used).
@@ -243,12 +244,7 @@ static int step_ran(cpp_ddpg* d, int rc, StepRan how) {
 // constant channels: common.h, cpp_ctx::conv1_f32) -- the cached graphs then hold the wrong launches and a presampled minibatch may be
 // in the wrong form (sampled slots against a gathered copy): everything is rebuilt by the calls' own "key changed" paths.
 static void route_check(cpp_ddpg* d) {
-  ctx_route_update(d->ctx);
-  if (d->epoch == d->ctx->kernel_epoch) return;
-  d->epoch = d->ctx->kernel_epoch;
-  invalidate_graphs(d);
-  d->pre_variant = 0;
-  for (cpp_net* n : {d->actor, d->critic, d->tactor, d->tcritic}) n->wimg_key = nullptr;
+  if (route_check(d->ctx, &d->epoch, &d->graph_gen, {d->actor, d->critic, d->tactor, d->tcritic})) d->pre_variant = 0;
 }
 
 extern "C" int cpp_ddpg_destroy(cpp_ddpg* d) {
@@ -410,27 +406,24 @@ static int critic_gradients_impl(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_d
 
 // folded: take the lists' squared norms from the partials the gradient pass left (compute_gradients: sq_scope) instead of running
 // the sumsq kernel -- only for gradients that are applied as computed (both lists, no scaling, nothing in between)
-// next: the minibatch whose sample pass has already run (its per-row statistics are in next->part): its whitening tables are
-// computed by this launch's rider instead of a stats_finalize launch behind it
+// nx: the minibatch whose sample pass has already run (rt_internal.h: NextBatch): its whitening tables are computed by this launch's
+// rider instead of a stats_finalize launch behind it
 static int apply(cpp_ddpg* d, bool do_actor, bool do_critic, float grad_scale, uint64_t* bump = nullptr, bool folded = false,
-                 const cpp_batch* next = nullptr, int next_B = 0, int next_C = 0, long elems = 0, bool tables_done = false) {
+                 const NextBatch& nx = NextBatch()) {
   OptSegs s; memset(&s, 0, sizeof(s));
   s.bump = bump;
   if (d->tps_pending) { s.bump2 = d->tps_n; d->tps_pending = false; }      // (the pass in front read the count; nobody in this launch does)
-  if (d->targets_in_apply && !next && do_actor && do_critic) {      // (the outer step's last launch: both target updates leave with it)
+  if (d->targets_in_apply && !nx.b && do_actor && do_critic) {      // (the outer step's last launch: both target updates leave with it)
     s.tgt[0] = d->tactor->params; s.tgt[1] = d->tcritic->params; s.tgt_coeff = d->hp.target_update_rate;
     d->tactor->wimg_key = nullptr; d->tcritic->wimg_key = nullptr;
     d->targets_applied = true;
   }
   d->targets_in_apply = false;
-  if (d->publish_in_apply && !next && d->ctx->route_pin_dev) {      // (the call's last launch: step_body)
+  if (d->publish_in_apply && !nx.b && d->ctx->route_pin_dev) {      // (the call's last launch: step_body)
     s.pub_wmax = d->ctx->white_max_dev; s.pub_tag = d->ctx->route_tag_dev; s.pub_pin = d->ctx->route_pin_dev;
   }
   d->publish_in_apply = false;
-  if (next && next_C > 0 && !tables_done) {
-    s.st_part = next->part; s.st_white = next->white; s.st_nparts = next_B; s.st_jobs = 2 * next_C; s.st_C = next_C;
-    s.st_count = (double)next_B * (double)(elems / next_C); s.st_eps = 1e-6; s.st_wmax = d->ctx->white_max_dev;
-  }
+  opt_next_stats(d->ctx, s, nx);
   d->actor->wimg_key = nullptr; d->critic->wimg_key = nullptr;      // (the parameters change)
   s.nseg = 2; s.kind = d->opt_kind;
   const bool bumped = d->step_bumped;
@@ -467,33 +460,23 @@ static int apply(cpp_ddpg* d, bool do_actor, bool do_critic, float grad_scale, u
   // (CPP_RIDE_IMAGE_UPDATE=0, ablation build: no image workgroups at all -- conv1's parameters and slots are advanced by the update's
   // plain workgroups and the forward builds its image by a launch of its own: what the rider's restated update is compared with)
   static const bool no_img = cpp_switch_off("CPP_RIDE_IMAGE_UPDATE");
-  const bool img = next && next_C > 0 && do_actor && do_critic && L0 && !d->actor->spec.use_batch_norm && !d->critic->spec.use_batch_norm &&
-                   conv_rs16_ok(d->ctx, L0->Cin, L0->H, L0->W, kConvOut) && next_B >= 2 && !no_img;
+  const bool img = nx.b && nx.C > 0 && do_actor && do_critic && L0 && !d->actor->spec.use_batch_norm && !d->critic->spec.use_batch_norm &&
+                   conv_rs16_ok(d->ctx, L0->Cin, L0->H, L0->W, kConvOut) && nx.B >= 2 && !no_img &&
+                   conv1_opens_params(d->actor) && conv1_opens_params(d->critic);
   if (img) {
     s.img_n = 4; s.img_cin = L0->Cin;
-    for (int k = 0; k < 2; ++k) {      // conv1's weights and biases open the flat buffers (cpp_net_var_info order): [w_off, b_off + nout)
-      const ConvL& L = inets[k]->conv[0];
-      if (L.w_off != 0 || L.b_off != L.w_off + (long)L.ks * L.ks * L.Cin * kConvOut) { s.img_n = 0; break; }
-      s.img_skip[k] = L.b_off + kConvOut;
-    }
-  }
-  if (img && s.img_n) {
-    for (int j = 0; j < 4; ++j) {
-      cpp_net* n = inets[j];
-      const ConvL& L = n->conv[0];
-      s.img[j].w = n->params + L.w_off; s.img[j].bias = n->params + L.b_off;
-      s.img[j].gw = j < 2 ? s.g[j] + L.w_off : nullptr; s.img[j].gb = j < 2 ? s.g[j] + L.b_off : nullptr;
+    for (int j = 0; j < 4; ++j) {      // (the trained networks read state_1's tables, the targets state_2's)
+      opt_img_net(s, j, inets[j], j < 2 ? j : -1, j < 2 ? 0 : 1, nx);
+      const ConvL& L = inets[j]->conv[0];
       if (j < 2 && s.kind != OPT_SGD) { s.img[j].mw = s.m[j] + L.w_off; s.img[j].mb = s.m[j] + L.b_off; }
       if (j < 2 && s.kind == OPT_ADAM) { s.img[j].vw = s.v[j] + L.w_off; s.img[j].vb = s.v[j] + L.b_off; }
-      s.img[j].rec = reinterpret_cast<unsigned char*>(n->wimg); s.img[j].seg = j < 2 ? j : 0; s.img[j].col = j < 2 ? 0 : 1; s.img[j].nout = kConvOut;
-      s.img[j].white = tables_done ? next->white + (long)s.img[j].col * 2 * next_C : nullptr;
     }
   }
   // soft actor-critic: the temperature's update leaves with the actor's list, a launch of its own (rate 0: a fixed temperature, none)
   if (d->sac && do_actor && d->sac_lr > 0.f && d->sac_B > 0) RC(launch_sac_temperature(d->ctx, d->sac_part, d->sac_B, d->sac_lr, d->sac_w, d->sac_step));
   // norms_out[group] is only written for lists that were applied (n > 0)
   RC(launch_opt_apply(d->ctx, s, grad_scale, d->hp.gradient_clip, d->norm_part, NORM_PARTS, d->loss_norms + 1));
-  if (img && s.img_n) for (int j = 0; j < 4; ++j) inets[j]->wimg_key = next->white + (long)(j < 2 ? 0 : 1) * 2 * next_C;
+  opt_img_built(s, inets, nx);
   // ... and the critic's list closes a minibatch: the target actor becomes the actor as this launch left it (behind the soft update)
   if (d->sac && do_critic) RC(sac_sync_target(d));
   return CPP_OK;
@@ -528,14 +511,11 @@ extern "C" int cpp_ddpg_check_loss(cpp_ddpg* d, cpp_batch* b, float* loss, float
   HIP_CHECK(hipSetDevice(d->ctx->device));
   RC(prep_batch(d, b));
   RC(critic_gradients(d, b, false, false));
-  hipStream_t st = d->ctx->stream;
   double parts[DDPG_HEADS_MAX_WGS];      // (a distributional trainer: the cross-entropy from its per-workgroup partials, as cpp_ddpg_last_stats)
   const int nparts = d->dist_n ? d->loss_parts : 0;
-  if (loss && nparts) HIP_CHECK(hipMemcpyAsync(parts, d->heads_part, (size_t)nparts * sizeof(double), hipMemcpyDeviceToHost, st));
-  else if (loss) HIP_CHECK(hipMemcpyAsync(loss, d->loss_norms, sizeof(float), hipMemcpyDeviceToHost, st));
-  if (td) HIP_CHECK(hipMemcpyAsync(td, d->td, (size_t)b->B * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (q) HIP_CHECK(hipMemcpyAsync(q, d->critic->ws[0].out, (size_t)b->B * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
+  const size_t nB = (size_t)b->B * sizeof(float);
+  RC(read_back(d->ctx, {{loss && nparts ? parts : nullptr, d->heads_part, (size_t)nparts * sizeof(double)}, {nparts ? nullptr : loss, d->loss_norms, sizeof(float)},
+                        {td, d->td, nB}, {q, d->critic->ws[0].out, nB}}));
   if (loss && nparts) *loss = loss_of_parts(parts, nparts, d->loss_B);
   return CPP_OK;
 }
@@ -545,13 +525,8 @@ extern "C" int cpp_ddpg_q_gradients_wrt_actions(cpp_ddpg* d, cpp_batch* b, float
   HIP_CHECK(hipSetDevice(d->ctx->device));
   RC(prep_batch(d, b));
   RC(actor_gradients(d, b, false, false));
-  hipStream_t st = d->ctx->stream;
-  const int A = d->actor->spec.action_dim;
-  if (dq_da) HIP_CHECK(hipMemcpyAsync(dq_da, d->dq_da, (size_t)b->B * A * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (actions) HIP_CHECK(hipMemcpyAsync(actions, d->actor->ws[0].out, (size_t)b->B * A * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (q) HIP_CHECK(hipMemcpyAsync(q, d->critic->ws[1].out, (size_t)b->B * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  return CPP_OK;
+  const size_t nB = (size_t)b->B * sizeof(float), nA = nB * d->actor->spec.action_dim;
+  return read_back(d->ctx, {{dq_da, d->dq_da, nA}, {actions, d->actor->ws[0].out, nA}, {q, d->critic->ws[1].out, nB}});
 }
 
 // Both gradient sets of one minibatch (ddpg_cartpole.py:331-334) as one dependency graph: 4 conv trunk
@@ -565,13 +540,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   const int B = b->B, A = a->spec.action_dim, C = a->spec.pixel ? a->spec.C : 0;
   const float *w1 = white_of(b, 0, C), *w2 = white_of(b, 1, C);
   const void *s1 = b->direct_store ? b->direct_store : b->s[0], *s2 = b->direct_store ? b->direct_store : b->s[1];
-  struct SlotScope {      // conv1 of the four networks addresses its images through the sampled slots while this graph runs
-    cpp_net* n[4];
-    SlotScope(cpp_net* a_, cpp_net* c_, cpp_net* ta_, cpp_net* tc_, cpp_batch* b_) : n{a_, c_, ta_, tc_} {
-      if (b_->direct_store) { a_->img_slot = c_->img_slot = b_->slot[0]; ta_->img_slot = tc_->img_slot = b_->slot[1]; }
-    }
-    ~SlotScope() { for (cpp_net* x : n) x->img_slot = nullptr; }
-  } slot_scope(a, c, ta, tc, b);
+  SlotScope slot_scope(b, {a, c}, {ta, tc});      // (conv1 of the four networks addresses its images through the sampled slots while this graph runs)
   const int dt = b->dtype;
   const int na = (int)a->fc.size(), nc = (int)c->fc.size(), cat = c->cat_layer;
   const FcL& Lcat = c->fc[cat];
@@ -579,24 +548,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   OpGraph G;
   // The kernels that write the gradients also leave their share of the two lists' squared norms (cpp_ctx::sq_part): list 0 = actor,
   // list 1 = critic.  Not with batch norm (dbeta comes out of the BN backward kernels) and not for a split pass.
-  struct SqScope {
-    cpp_ctx* c; cpp_ddpg* d;
-    SqScope(cpp_ctx* c_, cpp_ddpg* d_, bool on) : c(c_), d(d_) {
-      d->sq_cnt[0] = d->sq_cnt[1] = 0;
-      if (on) { c->sq_n[0] = c->sq_n[1] = 0; c->sq_conv_group[0] = 0; c->sq_conv_group[1] = 1; }
-    }
-    ~SqScope() {
-      if (c->sq_n[0] > 0 && c->sq_n[1] > 0) { d->sq_cnt[0] = c->sq_n[0]; d->sq_cnt[1] = c->sq_n[1]; }
-      c->sq_n[0] = c->sq_n[1] = -1;
-      for (int& g : c->sq_conv_group) g = -1;
-    }
-  } sq_scope(ctx, d, phase == 0 && !a->spec.use_batch_norm && !c->spec.use_batch_norm);
-  auto sqg = [&](int list, GemmArgs g) {
-    const int tiles = gemm_tiles(g.M, g.N, g.K);
-    if (ctx->sq_n[list] >= 0 && ctx->sq_n[list] + tiles <= SQ_REGION) { g.sq_part = ctx->sq_part + list * SQ_REGION + ctx->sq_n[list]; ctx->sq_n[list] += tiles; }
-    else ctx->sq_n[list] = -1;
-    return g;
-  };
+  SqScope sq_scope(ctx, d->sq_cnt, 2, {0, 1}, phase == 0 && !a->spec.use_batch_norm && !c->spec.use_batch_norm);
 
   // ---- forward: the four conv trunks.  conv1 saturates the chip per network; the narrow conv2 / conv3 layers
   // of all four networks share one launch each.
@@ -694,35 +646,18 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     const int hk = G.fn([=] { return launch_ddpg_heads(ctx, hd); }, {aF, taF, cP, tcP});
     if (d->per_hook) G.fn(d->per_hook, {hk});      // (prioritized replay: as soon as the TD values are known)
     // ---- actor backward below its head (the head's dX is part of the fused kernel)
-    G.gemm(sqg(0, fc_dw_args(a, a->ws[0], na - 1, B, a->ws[0].dz[na - 1])), {hk});
-    adz = hk;
-    for (int l = na - 2; l >= 0; --l) {
-      const FcL& L = a->fc[l];
-      G.gemm(sqg(0, fc_dw_args(a, a->ws[0], l, B, a->ws[0].dz[l])), {adz});
-      if (pre && l == na - 2) continue;       // dz[l - 1] came out of the heads kernel
-      if (l > 0)
-        adz = G.gemm(fc_dx_args(a, l, B, a->ws[0].dz[l], L.n_out, 0, L.n_in, a->ws[0].dz[l - 1], L.n_in, relu_grad_epi(a, l - 1),
-                                a->ws[0].fcin[l], L.n_in + 1), {adz});
-      else if (a->spec.pixel)
-        adz = G.gemm(fc_dx_args(a, 0, B, a->ws[0].dz[0], L.n_out, 0, a->flat, a->ws[0].dpool[2], a->flat, GE_NONE, nullptr, 0), {adz});
-    }
+    G.gemm(sq_gemm(ctx, 0, fc_dw_args(a, a->ws[0], na - 1, B, a->ws[0].dz[na - 1])), {hk});
+    adz = add_fc_backward(G, a, a->ws[0], B, na - 2, hk, 0, pre ? na - 2 : -1);      // (pre: dz[na - 3] came out of the heads kernel)
     // ---- critic backward below its concat layer
-    G.gemm(sqg(1, fc_dw_args(c, c->ws[0], nc - 1, B, c->ws[0].dz[nc - 1])), {hk});
-    G.gemm(sqg(1, fc_dw_args(c, c->ws[0], cat, B, c->ws[0].dz[cat])), {hk});
+    G.gemm(sq_gemm(ctx, 1, fc_dw_args(c, c->ws[0], nc - 1, B, c->ws[0].dz[nc - 1])), {hk});
+    G.gemm(sq_gemm(ctx, 1, fc_dw_args(c, c->ws[0], cat, B, c->ws[0].dz[cat])), {hk});
     if (twin) {      // head 2's two dW GEMMs depend on the heads launch alone: they ride in this level
-      G.gemm(sqg(1, twin_dw_args(c, c->ws[0], nc - 1, B)), {hk});
-      G.gemm(sqg(1, twin_dw_args(c, c->ws[0], cat, B)), {hk});
+      G.gemm(sq_gemm(ctx, 1, twin_dw_args(c, c->ws[0], nc - 1, B)), {hk});
+      G.gemm(sq_gemm(ctx, 1, twin_dw_args(c, c->ws[0], cat, B)), {hk});
     }
-    cdz = hk;
-    for (int l = cat - 1; l >= 0; --l) {
-      const FcL& L = c->fc[l];
-      G.gemm(sqg(1, fc_dw_args(c, c->ws[0], l, B, c->ws[0].dz[l])), {cdz});
-      if (l > 0)
-        cdz = G.gemm(fc_dx_args(c, l, B, c->ws[0].dz[l], L.n_out, 0, L.n_in, c->ws[0].dz[l - 1], L.n_in, GE_MUL_RELU_GRAD,
-                                c->ws[0].fcin[l], L.n_in + 1), {cdz});
-      else if (c->spec.pixel)
-        cdz = G.gemm(fc_dx_args(c, 0, B, c->ws[0].dz[0], L.n_out, 0, c->flat, c->ws[0].dpool[2], c->flat, GE_NONE, nullptr, 0), {cdz});
-    }
+    // (the helper's relu_grad_epi(c, l) is GE_MUL_RELU_GRAD for every critic: a CPP_CRITIC's hidden layers are built with GE_RELU,
+    // dropout or not -- rt_net.cpp's constructor gives GE_RELU_DROPOUT to actors and NAF heads only)
+    cdz = add_fc_backward(G, c, c->ws[0], B, cat - 1, hk, 1);
   } else {
   const int cb = G.fn([=] { return launch_copy_cols(ctx, c->ws[0].fcin[cat], ldcat, Lcat.n_in - A, b->a, A, 0, A, B); }, {});
   int aF = tA, taF = tTA;
@@ -797,15 +732,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   }
 
   // ---- actor backward
-  for (int l = na - 1; l >= 0; --l) {
-    const FcL& L = a->fc[l];
-    G.gemm(sqg(0, fc_dw_args(a, a->ws[0], l, B, a->ws[0].dz[l])), {adz});
-    if (l > 0)
-      adz = G.gemm(fc_dx_args(a, l, B, a->ws[0].dz[l], L.n_out, 0, L.n_in, a->ws[0].dz[l - 1], L.n_in, relu_grad_epi(a, l - 1),
-                              a->ws[0].fcin[l], L.n_in + 1), {adz});
-    else if (a->spec.pixel)
-      adz = G.gemm(fc_dx_args(a, 0, B, a->ws[0].dz[0], L.n_out, 0, a->flat, a->ws[0].dpool[2], a->flat, GE_NONE, nullptr, 0), {adz});
-  }
+  adz = add_fc_backward(G, a, a->ws[0], B, na - 1, adz, 0);
 
   // ---- TD target + critic backward on the first evaluation (fed actions)
   const float* per_w = d->per_w;
@@ -822,10 +749,10 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   int cdz2 = cdz;      // head 2's chain down to the concat layer, level by level beside head 1's
   for (int l = nc - 1; l >= 0; --l) {
     const FcL& L = c->fc[l];
-    G.gemm(sqg(1, fc_dw_args(c, c->ws[0], l, B, c->ws[0].dz[l])), {cdz});
+    G.gemm(sq_gemm(ctx, 1, fc_dw_args(c, c->ws[0], l, B, c->ws[0].dz[l])), {cdz});
     const int ncols = L.cat ? L.n_in - A : L.n_in;
     if (twin && l >= cat) {
-      G.gemm(sqg(1, twin_dw_args(c, c->ws[0], l, B)), {cdz2});
+      G.gemm(sq_gemm(ctx, 1, twin_dw_args(c, c->ws[0], l, B)), {cdz2});
       if (l > cat) cdz2 = G.gemm(twin_dx_args(c, c->ws[0], l, B), {cdz2});
     }
     if (twin && l == cat && l > 0) {      // the shared layer's dz: (head 1) + (head 2), then the mask
@@ -895,8 +822,7 @@ extern "C" int cpp_ddpg_set_optimiser(cpp_ddpg* d, int kind, float momentum, flo
   HIP_CHECK(ctx_sync_stream(ctx));
   d->opt_kind = kind; d->opt_momentum = momentum; d->opt_beta1 = beta1; d->opt_beta2 = beta2; d->opt_epsilon = epsilon;
   d->step_bumped = false;
-  invalidate_graphs(d);      // (the captured launches carry the old rule)
-  d->pre_variant = 0;
+  reconfigured(d);      // (the captured launches carry the old rule)
   return CPP_OK;
 }
 
@@ -921,8 +847,7 @@ extern "C" int cpp_ddpg_set_target_smoothing(cpp_ddpg* d, float sigma, float cli
   if (d->tps_eps) HIP_CHECK(hipMemsetAsync(d->tps_eps, 0, n * sizeof(float), ctx->stream));
   HIP_CHECK(ctx_sync_stream(ctx));
   d->tps_on = sigma > 0.f; d->tps_sigma = sigma; d->tps_clip = clip; d->tps_seed = seed; d->tps_pending = false;
-  invalidate_graphs(d);      // (the captured launches carry the old values, or none)
-  d->pre_variant = 0;
+  reconfigured(d);      // (the captured launches carry the old values, or none)
   return CPP_OK;
 }
 
@@ -940,8 +865,7 @@ extern "C" int cpp_ddpg_set_policy_delay(cpp_ddpg* d, int delay) {
   HIP_CHECK(ctx_sync_stream(ctx));
   d->pd_d = delay;
   d->step_bumped = false;
-  invalidate_graphs(d);      // (the captured launches carry the old delay, or none)
-  d->pre_variant = 0;
+  reconfigured(d);      // (the captured launches carry the old delay, or none)
   return CPP_OK;
 }
 
@@ -964,11 +888,7 @@ extern "C" int cpp_ddpg_last_target_noise(cpp_ddpg* d, int B, float* eps, uint64
   ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_target_noise: batch %d outside [1,%d]", B, d->maxB);
   if (!d->tps_on) { cpp_set_error("cpp_ddpg_last_target_noise: target policy smoothing is off"); return CPP_ERR_STATE; }
   HIP_CHECK(hipSetDevice(d->ctx->device));
-  hipStream_t st = d->ctx->stream;
-  if (eps) HIP_CHECK(hipMemcpyAsync(eps, d->tps_eps, (size_t)B * d->actor->spec.action_dim * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (n) HIP_CHECK(hipMemcpyAsync(n, d->tps_n + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(ctx_sync_stream(d->ctx));
-  return CPP_OK;
+  return read_back(d->ctx, {{eps, d->tps_eps, (size_t)B * d->actor->spec.action_dim * sizeof(float)}, {n, d->tps_n + 1, sizeof(uint64_t)}}, true);
 }
 
 // the slots and the two step counts for checkpoints (util.py:88-90: tf.train.Saver saves the slot variables of both 'optimiser' scopes,
@@ -979,12 +899,8 @@ extern "C" int cpp_ddpg_get_opt_state(cpp_ddpg* d, float* m, float* v, int64_t n
   ARG_CHECK(d->opt_kind != OPT_SGD, "cpp_ddpg_get_opt_state: GradientDescent has no slots");
   ARG_CHECK(n == d->nA + d->nC, "cpp_ddpg_get_opt_state: asked %ld values, the optimisers have %ld", (long)n, d->nA + d->nC);
   HIP_CHECK(hipSetDevice(d->ctx->device));
-  hipStream_t st = d->ctx->stream;
-  if (m) HIP_CHECK(hipMemcpyAsync(m, d->opt_m, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (v && d->opt_kind == OPT_ADAM) HIP_CHECK(hipMemcpyAsync(v, d->opt_v, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipMemcpyAsync(steps, d->opt_step, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(ctx_sync_stream(d->ctx));
-  return CPP_OK;
+  return read_back(d->ctx, {{m, d->opt_m, (size_t)n * sizeof(float)}, {d->opt_kind == OPT_ADAM ? v : nullptr, d->opt_v, (size_t)n * sizeof(float)},
+                            {steps, d->opt_step, 2 * sizeof(uint64_t)}}, true);
 }
 extern "C" int cpp_ddpg_set_opt_state(cpp_ddpg* d, const float* m, const float* v, int64_t n, const uint64_t steps[2]) {
   ARG_CHECK(d && m && steps, "cpp_ddpg_set_opt_state: NULL argument");
@@ -1021,101 +937,35 @@ bool direct_replay_ok(cpp_net* a, cpp_replay* r, int B) {
   return conv1_f16_pipes_ok(a->ctx, C, a->conv[0].H, a->conv[0].W, B, a->spec.use_batch_norm != 0);
 }
 
+// The inner step ddpg_cartpole.py:331-337: the shared minibatch loop (rt_step.cpp: run_minibatches -- the sample rider, the prioritized
+// draws), then the target updates.  On a prioritized memory the optimiser's launch moves the sampler's counter, as on a uniform one.
 // dp: this rank's part of the data-parallel step (cpp_ddpg_dp_train_step): between a minibatch's gradients and its update the flat
 // gradient buffer is summed over the ranks (comm; NULL: a single learner on the same path) and the update takes the mean -- the
 // all-reduce is issued on the context's stream, i.e. it is PART OF THE CAPTURED GRAPH (RCCL's kernels capture like any other).
 static int step_body(cpp_ddpg* d, cpp_replay* r, int B, int n_batches, const int32_t* rows_dev, uint64_t seed, bool targets = true,
                      bool dp = false, cpp_comm* comm = nullptr) {
   d->pre_variant = 0;        // (the half steps' presampled minibatch lives in the same step_batch)
-  const int C = d->actor->spec.pixel ? d->actor->spec.C : 0;
   cpp_ctx* ctx = d->ctx;
-  const bool direct = direct_replay_ok(d->actor, r, B);
-  // The sample + statistics pass of minibatch i + 1 depends on nothing minibatch i computes: it rides in the launch of i's
-  // dW reductions (reduce_gather_kernel, replay.hip), keyed by the sampler's counter + 1 -- the counter itself moves in i's
-  // optimiser kernel as before, so the rows drawn are the same.  Conv trunks on f16 / u8 stores; CPP_RIDE_GATHER=0: in sequence.
-  static const bool no_ride = cpp_switch_off("CPP_RIDE_GATHER");
-  const bool ride_ok = !no_ride && C > 0 && (r->store_dtype == CPP_F16 || r->store_dtype == CPP_U8);
-  // Prioritized memory (per.hip): minibatch i's rows are the caller's or a stratified draw by priority, keyed by the sampler's counter as
-  // the uniform draw is; its importance weights scale the critic's loss.  As soon as its TD values are known, ONE launch writes its
-  // priorities into the tree and draws minibatch i + 1 (counter + 1: the optimiser's launch moves the counter, as before) -- before the
-  // pass that gathers i + 1, wherever that rides.  The gathers take the drawn rows as a row list.
-  const bool per = r->per_tree != nullptr;
-  auto rows_of = [&](int i) -> const int32_t* { return rows_dev ? rows_dev + (size_t)i * B : per ? r->per_rows : nullptr; };
-  struct PerScope {
-    cpp_ddpg* d;
-    PerScope(cpp_ddpg* d_, cpp_replay* r_) : d(d_) { d->per_w = r_->per_tree ? r_->per_w : nullptr; }
-    ~PerScope() { d->per_w = nullptr; d->per_hook = nullptr; }
-  } per_scope(d, r);
-  if (per) {
-    PerArgs p = per_args(r);
-    p.B = B; p.w_rows = rows_dev; p.seed = seed; p.counter = rows_dev ? nullptr : r->counter; p.out_rows = r->per_rows; p.out_w = r->per_w;
-    RC(launch_per_update_sample(ctx, p));
-  }
-  RC(replay_sample_device(r, B, rows_of(0), seed, rows_of(0) ? nullptr : r->counter, C, d->step_batch, direct));
-  for (int i = 0; i < n_batches; ++i) {
-    GatherArgs ga; int Cg = 0;
-    const bool more = i + 1 < n_batches;
-    if (per) {
-      PerArgs p = per_args(r);
-      p.up_rows = rows_of(i); p.n_up = B; p.up_td = d->td;
-      if (more) {
-        p.B = B; p.w_rows = rows_dev ? rows_of(i + 1) : nullptr; p.seed = seed; p.counter = rows_dev ? nullptr : r->counter; p.counter_add = 1;
-        p.out_rows = r->per_rows; p.out_w = r->per_w;
-      }
-      d->per_hook = [ctx, p] { return launch_per_update_sample(ctx, p); };
-    }
-    if (more && ride_ok) {
-      ga = replay_gather_args(r, B, rows_of(i + 1), seed, rows_of(i + 1) ? nullptr : r->counter, C,
-                              d->step_batch, direct, &Cg);
-      ga.counter_add = 1;
-      // with the slots double-buffered the pass can leave as early as conv1's dW (MFMA-bound, HBM idle, and its second
-      // round of workgroups leaves the CUs half empty: conv1_dw_gather.hip); otherwise it waits for the dW reductions
-      static const bool no_dwride = cpp_switch_off("CPP_RIDE_DW");
-      ctx->ride_at_dw = direct && !no_dwride;
-      if (direct) { ga.out_slot[0] = d->step_batch->slot_alt[0]; ga.out_slot[1] = d->step_batch->slot_alt[1]; }
-      ctx->ride = &ga; ctx->ride_done = false; ctx->ride_dtype = r->store_dtype;
-    }
-    // ... and when it leaves with conv1's dW, its statistics can be finished in the dW reductions' launch (flush_dw_reduce): the tables
-    // are in memory before the optimiser's launch, whose conv1 image rider reads them (apply)
-    static const bool no_stats_ride = cpp_switch_off("CPP_RIDE_STATS");
-    StatsRide sr;
-    if (ctx->ride && ctx->ride_at_dw && Cg > 0 && !no_stats_ride) {
-      sr.part = d->step_batch->part; sr.white = d->step_batch->white; sr.nparts = B; sr.jobs = 2 * Cg; sr.C = Cg;
-      sr.count = (double)B * (double)(r->elems / Cg); sr.eps = 1e-6; sr.wmax = ctx->white_max_dev;
-      ctx->st_ride = &sr; ctx->st_ride_done = false;
-    }
-    d->bump_in_heads = true;      // (the apply() below takes both lists)
+  MinibatchLoop L;
+  L.ctx = ctx; L.r = r; L.step_batch = d->step_batch; L.trunk = d->actor;
+  L.per_w = &d->per_w; L.per_hook = &d->per_hook; L.td = d->td; L.stats_switch = true;
+  L.gradients = [=] {
+    d->bump_in_heads = true;      // (the apply() behind it takes both lists)
     const int rc = compute_gradients(d, d->step_batch);
     d->bump_in_heads = false;
     if (rc) { d->step_bumped = false; d->tps_pending = false; }
-    d->per_hook = nullptr;
-    const bool rode = ctx->ride != nullptr && ctx->ride_done;
-    const bool tables_done = ctx->st_ride != nullptr && ctx->st_ride_done && rode;
-    ctx->ride = nullptr; ctx->st_ride = nullptr;
-    if (rode && direct) { std::swap(d->step_batch->slot[0], d->step_batch->slot_alt[0]); std::swap(d->step_batch->slot[1], d->step_batch->slot_alt[1]); }
-    RC(rc);
-    // (also advances the sampler's counter and, when the next minibatch's sample pass rode along above, finishes its statistics --
-    // unless the dW reductions' launch already has)
-    const bool stats_ride = rode && Cg > 0 && !no_stats_ride;
-    if (dp && comm) {
-      prof_begin(ctx);
-      NCCL_CHECK(ncclAllReduce(d->gradbuf, d->gradbuf, (size_t)(d->nA + d->nC), ncclFloat, ncclSum, comm->comm, ctx->stream));
-      prof_end(ctx, K_ALLREDUCE);
-    }
+    return rc;
+  };
+  L.apply = [=](bool more, const NextBatch& next) {
     // (dp: the norm is the reduced gradient's -- the partials the gradient kernels folded in are this rank's only: sumsq runs)
+    if (dp) RC(step_allreduce(ctx, comm, d->gradbuf, (size_t)(d->nA + d->nC)));
     static const bool no_tgt_ride = cpp_switch_off("CPP_RIDE_TARGETS");
     d->targets_applied = false;
     d->targets_in_apply = !more && targets && !dp && !no_tgt_ride;      // (the last minibatch of an outer step: the target updates ride in its optimiser launch)
     d->publish_in_apply = !more && (!targets || d->targets_in_apply);   // (... which then closes the call)
-    RC(apply(d, true, true, (dp && comm) ? 1.0f / (float)comm->world : 1.0f, rows_dev ? nullptr : r->counter, !dp,
-             stats_ride ? d->step_batch : nullptr, B, Cg, r->elems, tables_done));
-    if (more) {
-      if (stats_ride) { d->step_batch->B = B; d->step_batch->dtype = CPP_F16; d->step_batch->stats_C = Cg; }     // (replay_sample_finish's bookkeeping)
-      else if (rode) RC(replay_sample_finish(r, B, Cg, C, d->step_batch));
-      else RC(replay_sample_device(r, B, rows_of(i + 1), seed, rows_of(i + 1) ? nullptr : r->counter, C,
-                                   d->step_batch, direct));
-    }
-  }
+    return apply(d, true, true, (dp && comm) ? 1.0f / (float)comm->world : 1.0f, rows_dev ? nullptr : r->counter, !dp, next);
+  };
+  RC(run_minibatches(L, B, n_batches, rows_dev, seed));
   if (targets && d->targets_applied) { d->targets_applied = false; return CPP_OK; }      // (both target updates and the route's publish left with the optimiser's launch)
   if (targets) { ctx->route_rider = true; return cpp_ddpg_update_targets(d); }      // (the largest whitening scale of this step rides to the host in that launch)
   return CPP_OK;      // (... or has left with the last minibatch's optimiser launch)
@@ -1149,9 +999,7 @@ extern "C" int cpp_ddpg_train_step(cpp_ddpg* d, cpp_replay* r, int B, int n_batc
   HIP_CHECK(hipSetDevice(ctx->device));
   if (!d->step_batch) RC(cpp_batch_create(ctx, d->maxB, r->elems, r->A, &d->step_batch));
   if (idxs) {
-    for (int i = 0; i < n_batches * B; ++i)
-      ARG_CHECK(idxs[i] >= 0 && idxs[i] < r->size, "cpp_ddpg_train_step: index %d outside [0,%d)", idxs[i], r->size);
-    HIP_CHECK(hipMemcpyAsync(r->rows_in, idxs, (size_t)n_batches * B * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    RC(replay_upload_rows(r, idxs, n_batches * B, "cpp_ddpg_train_step"));
     return step_body(d, r, B, n_batches, r->rows_in, seed);
   }
   static const bool no_graph = cpp_switch_set("CPP_NO_GRAPH");   // plain in-order stream launches (A/B measurements)
@@ -1183,14 +1031,13 @@ static int half_step_body(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed, int 
   }
   if (phase == 1) return tps_settle(d, compute_gradients(d, b, 1));
   const bool ride_ok = !no_ride && direct && Cg > 0 && r->store_dtype == CPP_F16;
-  if (ride_ok) {
-    ga.out_slot[0] = b->slot_alt[0]; ga.out_slot[1] = b->slot_alt[1];
-    ctx->ride = &ga; ctx->ride_done = false; ctx->ride_dtype = r->store_dtype; ctx->ride_at_dw = true;
+  int rc;
+  {
+    RideScope ride(ctx);
+    if (ride_ok) ride.arm(&ga, b, r->store_dtype, true, true);
+    rc = tps_settle(d, compute_gradients(d, b, phase));      // (phase 2 reads no count and owes nothing)
+    *next = ride.rode() ? (cur == 0 ? 1 : 2) : 0;
   }
-  const int rc = tps_settle(d, compute_gradients(d, b, phase));      // (phase 2 reads no count and owes nothing)
-  const bool rode = ctx->ride != nullptr && ctx->ride_done;
-  ctx->ride = nullptr;
-  *next = rode ? (cur == 0 ? 1 : 2) : 0;
   if (rc) return rc;
   return ctx_route_publish(ctx);
 }
@@ -1387,11 +1234,8 @@ extern "C" int cpp_ddpg_dp_status(const cpp_ddpg* d, int* mode, char* reason, in
 
 extern "C" int cpp_ddpg_last_stats(cpp_ddpg* d, float out[3]) {
   ARG_CHECK(d && out, "cpp_ddpg_last_stats: NULL argument");
-  HIP_CHECK(hipMemcpyAsync(out, d->loss_norms, 3 * sizeof(float), hipMemcpyDeviceToHost, d->ctx->stream));
   double parts[DDPG_HEADS_MAX_WGS];
-  if (d->loss_parts > 0)
-    HIP_CHECK(hipMemcpyAsync(parts, d->heads_part, (size_t)d->loss_parts * sizeof(double), hipMemcpyDeviceToHost, d->ctx->stream));
-  HIP_CHECK(ctx_sync_stream(d->ctx));
+  RC(read_back(d->ctx, {{out, d->loss_norms, 3 * sizeof(float)}, {d->loss_parts > 0 ? parts : nullptr, d->heads_part, (size_t)d->loss_parts * sizeof(double)}}, true));
   if (d->loss_parts > 0) out[0] = loss_of_parts(parts, d->loss_parts, d->loss_B);      // fused heads kernel: mean(td^2); dist.hip: mean(w L)
   return CPP_OK;
 }
@@ -1400,14 +1244,8 @@ extern "C" int cpp_ddpg_last_values(cpp_ddpg* d, int B, float* actions, float* d
   ARG_CHECK(d, "cpp_ddpg_last_values: NULL argument");
   ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_values: batch %d outside [1,%d]", B, d->maxB);
   HIP_CHECK(hipSetDevice(d->ctx->device));
-  hipStream_t st = d->ctx->stream;
-  const int A = d->actor->spec.action_dim;
-  if (actions) HIP_CHECK(hipMemcpyAsync(actions, d->actor->ws[0].out, (size_t)B * A * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (dq_da) HIP_CHECK(hipMemcpyAsync(dq_da, d->dq_da, (size_t)B * A * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (q) HIP_CHECK(hipMemcpyAsync(q, d->critic->ws[0].out, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (td) HIP_CHECK(hipMemcpyAsync(td, d->td, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  return CPP_OK;
+  const size_t nB = (size_t)B * sizeof(float), nA = nB * d->actor->spec.action_dim;
+  return read_back(d->ctx, {{actions, d->actor->ws[0].out, nA}, {dq_da, d->dq_da, nA}, {q, d->critic->ws[0].out, nB}, {td, d->td, nB}});
 }
 
 
@@ -1418,14 +1256,8 @@ extern "C" int cpp_ddpg_last_twin_values(cpp_ddpg* d, int B, float* q2, float* t
   ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_twin_values: batch %d outside [1,%d]", B, d->maxB);
   if (!d->twin) { cpp_set_error("cpp_ddpg_last_twin_values: the trainer's critics are not twin critics"); return CPP_ERR_STATE; }
   HIP_CHECK(hipSetDevice(d->ctx->device));
-  hipStream_t st = d->ctx->stream;
   const size_t n = (size_t)B * sizeof(float);
-  if (q2) HIP_CHECK(hipMemcpyAsync(q2, d->critic->ws[0].out2, n, hipMemcpyDeviceToHost, st));
-  if (target_q1) HIP_CHECK(hipMemcpyAsync(target_q1, d->tcritic->ws[0].out, n, hipMemcpyDeviceToHost, st));
-  if (target_q2) HIP_CHECK(hipMemcpyAsync(target_q2, d->tcritic->ws[0].out2, n, hipMemcpyDeviceToHost, st));
-  if (td2) HIP_CHECK(hipMemcpyAsync(td2, d->td2, n, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  return CPP_OK;
+  return read_back(d->ctx, {{q2, d->critic->ws[0].out2, n}, {target_q1, d->tcritic->ws[0].out, n}, {target_q2, d->tcritic->ws[0].out2, n}, {td2, d->td2, n}});
 }
 
 // Quantile trainers (Dabney et al. 2018; Kuznetsov et al. 2020; an extension of the target ddpg_cartpole.py:199-214): the Huber threshold
@@ -1438,8 +1270,7 @@ extern "C" int cpp_ddpg_set_quantile_target(cpp_ddpg* d, float kappa, int drop_t
   HIP_CHECK(hipSetDevice(d->ctx->device));
   HIP_CHECK(ctx_sync_stream(d->ctx));
   d->quant_kappa = kappa; d->quant_drop = drop_top;
-  invalidate_graphs(d);      // (the captured launches carry the old values)
-  d->pre_variant = 0;
+  reconfigured(d);      // (the captured launches carry the old values)
   return CPP_OK;
 }
 
@@ -1451,13 +1282,8 @@ extern "C" int cpp_ddpg_last_quantiles(cpp_ddpg* d, int B, float* theta, float* 
   ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_quantiles: batch %d outside [1,%d]", B, d->maxB);
   if (!d->quant) { cpp_set_error("cpp_ddpg_last_quantiles: the trainer's critics are not quantile critics"); return CPP_ERR_STATE; }
   HIP_CHECK(hipSetDevice(d->ctx->device));
-  hipStream_t st = d->ctx->stream;
   const size_t n = (size_t)B * d->dist_n * sizeof(float);
-  if (theta) HIP_CHECK(hipMemcpyAsync(theta, d->dist_p, n, hipMemcpyDeviceToHost, st));
-  if (sorted_target_theta) HIP_CHECK(hipMemcpyAsync(sorted_target_theta, d->dist_tp, n, hipMemcpyDeviceToHost, st));
-  if (y) HIP_CHECK(hipMemcpyAsync(y, d->dist_m, n, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  return CPP_OK;
+  return read_back(d->ctx, {{theta, d->dist_p, n}, {sorted_target_theta, d->dist_tp, n}, {y, d->dist_m, n}});
 }
 
 // Distributional trainers: what the last minibatch's gradient pass left -- p of the fed evaluation, p' of the target evaluation at the
@@ -1467,13 +1293,8 @@ extern "C" int cpp_ddpg_last_distribution(cpp_ddpg* d, int B, float* p, float* t
   ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_distribution: batch %d outside [1,%d]", B, d->maxB);
   if (!d->dist_n || d->quant) { cpp_set_error("cpp_ddpg_last_distribution: the trainer's critics are not distributional"); return CPP_ERR_STATE; }
   HIP_CHECK(hipSetDevice(d->ctx->device));
-  hipStream_t st = d->ctx->stream;
   const size_t n = (size_t)B * d->dist_n * sizeof(float);
-  if (p) HIP_CHECK(hipMemcpyAsync(p, d->dist_p, n, hipMemcpyDeviceToHost, st));
-  if (target_p) HIP_CHECK(hipMemcpyAsync(target_p, d->dist_tp, n, hipMemcpyDeviceToHost, st));
-  if (m) HIP_CHECK(hipMemcpyAsync(m, d->dist_m, n, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  return CPP_OK;
+  return read_back(d->ctx, {{p, d->dist_p, n}, {target_p, d->dist_tp, n}, {m, d->dist_m, n}});
 }
 
 // Soft actor-critic (Haarnoja et al. 2018; an extension of the actor's train op ddpg_cartpole.py:102-119 and of the critic's target
@@ -1499,22 +1320,13 @@ extern "C" int cpp_ddpg_last_sac(cpp_ddpg* d, int B, float* eps, float* a, float
   ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_sac: batch %d outside [1,%d]", B, d->maxB);
   if (!d->sac) { cpp_set_error("cpp_ddpg_last_sac: the trainer's actors are not Gaussian actors"); return CPP_ERR_STATE; }
   HIP_CHECK(hipSetDevice(d->ctx->device));
-  hipStream_t st = d->ctx->stream;
   const size_t nA = (size_t)B * d->actor->spec.action_dim * sizeof(float), nB = (size_t)B * sizeof(float);
-  if (eps) HIP_CHECK(hipMemcpyAsync(eps, d->sac_eps[0], nA, hipMemcpyDeviceToHost, st));
-  if (a) HIP_CHECK(hipMemcpyAsync(a, d->actor->ws[0].out, nA, hipMemcpyDeviceToHost, st));
-  if (logp) HIP_CHECK(hipMemcpyAsync(logp, d->sac_logp[0], nB, hipMemcpyDeviceToHost, st));
-  if (eps2) HIP_CHECK(hipMemcpyAsync(eps2, d->sac_eps[1], nA, hipMemcpyDeviceToHost, st));
-  if (a2) HIP_CHECK(hipMemcpyAsync(a2, d->tactor->ws[0].out, nA, hipMemcpyDeviceToHost, st));
-  if (logp2) HIP_CHECK(hipMemcpyAsync(logp2, d->sac_logp[1], nB, hipMemcpyDeviceToHost, st));
-  if (r_soft) HIP_CHECK(hipMemcpyAsync(r_soft, d->sac_rsoft, nB, hipMemcpyDeviceToHost, st));
-  if (dz) HIP_CHECK(hipMemcpyAsync(dz, d->actor->ws[0].dz[d->actor->fc.size() - 1], 2 * nA, hipMemcpyDeviceToHost, st));
-  if (alpha) HIP_CHECK(hipMemcpyAsync(alpha, d->sac_w + SAC_W_ALPHA, sizeof(float), hipMemcpyDeviceToHost, st));
-  if (n) HIP_CHECK(hipMemcpyAsync(n, d->tps_n + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   double parts[DDPG_HEADS_MAX_WGS];
   const int np = d->sac_B > 0 ? sac_grid(d->sac_B) : 0;
-  if (g_alpha && np) HIP_CHECK(hipMemcpyAsync(parts, d->sac_part, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
+  RC(read_back(d->ctx, {{eps, d->sac_eps[0], nA}, {a, d->actor->ws[0].out, nA}, {logp, d->sac_logp[0], nB},
+                        {eps2, d->sac_eps[1], nA}, {a2, d->tactor->ws[0].out, nA}, {logp2, d->sac_logp[1], nB}, {r_soft, d->sac_rsoft, nB},
+                        {dz, d->actor->ws[0].dz[d->actor->fc.size() - 1], 2 * nA}, {alpha, d->sac_w + SAC_W_ALPHA, sizeof(float)},
+                        {n, d->tps_n + 1, sizeof(uint64_t)}, {g_alpha && np ? parts : nullptr, d->sac_part, (size_t)np * sizeof(double)}}));
   if (g_alpha) {      // (the fixed-order finalisation of sac.hip's job 4)
     double s = 0.0;
     for (int i = 0; i < np; ++i) s += parts[i];

@@ -128,7 +128,7 @@ struct cpp_batch {
   // device-sampled minibatch that was NOT gathered: state k of row b is row slot[k][b] of direct_store (the replay store);
   // only the f16-pipe conv1 kernels can consume it (direct_store == nullptr: s[] holds the gathered copy)
   int32_t* slot[2]; const void* direct_store;
-  int32_t* slot_alt[2];   // the set the NEXT minibatch's sample pass writes while conv1's dW still reads slot[] (step_body)
+  int32_t* slot_alt[2];   // the set the NEXT minibatch's sample pass writes while conv1's dW still reads slot[] (run_minibatches)
   Arena arena;
 };
 
@@ -284,7 +284,7 @@ static const int kFwdKid[3] = {K_CONV1_FWD, K_CONV2_FWD, K_CONV3_FWD};
 static const int kDwKid[3] = {K_CONV1_DW, K_CONV2_DW, K_CONV3_DW};
 static const int kDxKid[3] = {-1, K_CONV2_DX, K_CONV3_DX};
 
-// ---- launch-sequence helpers shared by the translation units (definitions: rt_net.cpp, rt_replay.cpp, rt_ddpg.cpp)
+// ---- launch-sequence helpers shared by the translation units (definitions: rt_net.cpp, rt_replay.cpp, rt_ddpg.cpp; what the two learners share of a step: the end of this file)
 int gemm(cpp_ctx* ctx, const float* A, long sAm, long sAk, const float* Bm, long sBk, long sBn, float* C, long ldc, int M, int N, int K, int epi, const float* Y = nullptr, long ldy = 0, int accumulate = 0);
 ConvArgs conv_fwd_args(cpp_net* n, Workspace& w, int i, const void* state, int dtype, const float* white, int B, int* mode, long white_bstride = 0);
 void conv_dy_desc(cpp_net* n, Workspace& w, int i, ConvArgs& a, int B);
@@ -334,6 +334,7 @@ int replay_sample_device(cpp_replay* r, int B, const int32_t* rows_dev, uint64_t
 int replay_stage_rows(cpp_replay* r, const int32_t* idxs, int n, const char* who);
 PerArgs per_args(const cpp_replay* r);            // the memory's tree, size word, maximum and beta; nothing to write, nothing to draw
 int per_refuse(const cpp_replay* r, const char* who);   // CPP_ERR_ARG (with the message) on a prioritized memory
+int replay_upload_rows(cpp_replay* r, const int32_t* idxs, int n, const char* who);      // the same check, a plain copy (the eager step on the caller's rows)
 const float* white_of(cpp_batch* b, int which, int C);
 bool direct_replay_ok(cpp_net* a, cpp_replay* r, int B);
 
@@ -354,3 +355,98 @@ struct cpp_comm {
       return CPP_ERR_HIP;                                                                  \
     }                                                                                      \
   } while (0)
+
+// ---------------------------------------------------------------------------------------------
+// What the DDPG and the NAF learner share of a training call (definitions: rt_step.cpp; add_fc_backward: rt_net.cpp)
+// ---------------------------------------------------------------------------------------------
+// The squared norms of `lists` gradient lists (1 or 2), folded into the kernels that write the gradients (cpp_ctx::sq_part) while the
+// scope lives; groups: the list of each network of the conv backward.  cnt[l]: the partials the pass left for list l -- for every list,
+// or for none (a list whose region overflowed: the sumsq kernel runs).  on == false: the counts are zeroed, nothing is folded.
+struct SqScope {
+  cpp_ctx* c; int* cnt; int lists;
+  SqScope(cpp_ctx* c_, int* cnt_, int lists_, std::initializer_list<int> groups, bool on) : c(c_), cnt(cnt_), lists(lists_) {
+    for (int l = 0; l < lists; ++l) cnt[l] = 0;
+    if (!on) return;
+    for (int l = 0; l < 2; ++l) c->sq_n[l] = l < lists ? 0 : -1;
+    int k = 0;
+    for (int g : groups) c->sq_conv_group[k++] = g;
+  }
+  ~SqScope() {
+    bool all = true;
+    for (int l = 0; l < lists; ++l) all = all && c->sq_n[l] > 0;
+    for (int l = 0; l < lists && all; ++l) cnt[l] = c->sq_n[l];
+    c->sq_n[0] = c->sq_n[1] = -1;
+    for (int& g : c->sq_conv_group) g = -1;
+  }
+};
+// a dW GEMM of `list` takes the next slots of its region -- in call order, which is the order the optimiser adds them in
+GemmArgs sq_gemm(cpp_ctx* ctx, int list, GemmArgs g);
+// conv1 addresses its images through the sampled slots while the scope lives: `s1` read state_1's, `s2` state_2's (at most four networks)
+struct SlotScope {
+  cpp_net* n[4]; int nn = 0;
+  SlotScope(const cpp_batch* b, std::initializer_list<cpp_net*> s1, std::initializer_list<cpp_net*> s2) {
+    for (cpp_net* x : s1) { n[nn++] = x; if (b->direct_store) x->img_slot = b->slot[0]; }
+    for (cpp_net* x : s2) { n[nn++] = x; if (b->direct_store) x->img_slot = b->slot[1]; }
+  }
+  ~SlotScope() { for (int k = 0; k < nn; ++k) n[k]->img_slot = nullptr; }
+};
+// the prioritized-replay state of one gradient pass or step (the weights the pass reads, the launch behind its TD values), cleared on
+// every way out
+struct PerScope {
+  const float** w; std::function<int()>* hook;
+  PerScope(const float** w_, std::function<int()>* hook_, const cpp_replay* r) : w(w_), hook(hook_) { *w = r->per_tree ? r->per_w : nullptr; }
+  ~PerScope() { *w = nullptr; *hook = nullptr; }
+};
+// The next minibatch's sample pass as a rider of this gradient pass (cpp_ctx::ride: conv1's dW when at_dw, else the dW reductions), and
+// its whitening tables as a rider of the dW reductions (cpp_ctx::st_ride).  Both point into the caller's frame: disarmed on every way out.
+struct RideScope {
+  cpp_ctx* c;
+  explicit RideScope(cpp_ctx* c_) : c(c_) {}
+  ~RideScope() { c->ride = nullptr; c->st_ride = nullptr; }
+  void arm(GatherArgs* ga, const cpp_batch* b, int store_dtype, bool direct, bool at_dw) {      // direct: into the second set of slot arrays
+    if (direct) { ga->out_slot[0] = b->slot_alt[0]; ga->out_slot[1] = b->slot_alt[1]; }
+    c->ride = ga; c->ride_done = false; c->ride_dtype = store_dtype; c->ride_at_dw = at_dw;
+  }
+  void arm_stats(const StatsRide* sr) { c->st_ride = sr; c->st_ride_done = false; }
+  bool rode() const { return c->ride != nullptr && c->ride_done; }
+  bool tables_done() const { return c->st_ride != nullptr && c->st_ride_done && rode(); }
+};
+
+// The minibatch whose sample pass has already run when the optimiser's launch of the one before it leaves: b->part holds its per-row
+// statistics (B rows, C channels, `elems` values per state); tables_done: the dW reductions' launch has finished its whitening tables.
+// b == nullptr: none.
+struct NextBatch { const cpp_batch* b = nullptr; int B = 0, C = 0; long elems = 0; bool tables_done = false; };
+StatsRide next_stats_ride(cpp_ctx* ctx, const NextBatch& nx);              // its tables as the dW reductions' rider
+void opt_next_stats(cpp_ctx* ctx, OptSegs& s, const NextBatch& nx);        // ... or as the optimiser launch's (unless they are done)
+// conv1's operand image of the next minibatch as a rider of the optimiser's launch: record j is network n's on state column col.
+// seg >= 0: n is the network of segment seg, whose leading conv1 parameters the image workgroup updates itself (gradient pointers; the
+// learner adds its optimiser's slots); seg < 0: a target network.  conv1_opens_params: the layout the rider's update assumes.
+bool conv1_opens_params(const cpp_net* n);
+void opt_img_net(OptSegs& s, int j, cpp_net* n, int seg, int col, const NextBatch& nx);
+void opt_img_built(const OptSegs& s, cpp_net* const* nets, const NextBatch& nx);      // behind the launch: the images are current for those tables
+
+// What a learner supplies to run_minibatches.  Plain fields for what differs between the learners, two callables for their own launches.
+struct MinibatchLoop {
+  cpp_ctx* ctx; cpp_replay* r; cpp_batch* step_batch;
+  cpp_net* trunk;                         // the network whose conv1 decides the form of the minibatch (direct_replay_ok) and its channels
+  const float** per_w; std::function<int()>* per_hook;      // where the learner keeps them (PerScope)
+  const float* td;                        // the TD values the priorities are written from
+  const int* skip_if_set = nullptr;       // prioritized memory: the priority writes stand down while this flag is set
+  bool draws_bump = false;                // prioritized memory: the draws advance the sampler's counter themselves (else: the optimiser's launch)
+  bool ride_ok = true;                    // the learner's own condition on the sample rider
+  bool stats_switch = false;              // CPP_RIDE_STATS=0 also keeps the tables out of the optimiser's launch
+  std::function<int()> gradients;         // the gradient pass on step_batch
+  std::function<int(bool more, const NextBatch& next)> apply;      // the all-reduce if any, then the optimiser's launch
+};
+int run_minibatches(const MinibatchLoop& L, int B, int n_batches, const int32_t* rows_dev, uint64_t seed);
+int step_allreduce(cpp_ctx* ctx, cpp_comm* comm, float* grads, size_t n);      // in place, on the context's stream (inside a captured step)
+// Every training entry point starts here: the context may have moved conv1 to the other kernel family (cpp_ctx::conv1_f32).  true: it has --
+// *gen has moved (every cached graph of the trainer misses at its next use) and the networks' conv1 images are stale.
+bool route_check(cpp_ctx* ctx, uint64_t* epoch, uint64_t* gen, std::initializer_list<cpp_net*> nets);
+// dst <- src for every item with a destination, then ONE synchronisation of the context's stream (through_ctx: ctx_sync_stream)
+struct Readback { void* dst; const void* src; size_t bytes; };
+int read_back(cpp_ctx* ctx, std::initializer_list<Readback> items, bool through_ctx = false);
+// backward of the fully connected stack of a network without an action splice, from layer `start` down: per layer [dW; db] (into the
+// list's norm partials: sq_gemm) then dX, two independent GEMMs.  skip_dx: the layer whose dX a kernel in front has already produced.
+// Returns the op that completes d(flat) (pixel) / dz[0].
+int add_fc_backward(OpGraph& G, cpp_net* n, Workspace& w, int B, int start, int dep, int list, int skip_dx = -1);

@@ -21,7 +21,7 @@ struct cpp_naf {
   StepGraph agraph;          // ... and including it, the loss coming back later (cpp_naf_train_rows_async / cpp_naf_loss_wait): pinned (loss, flag) slots
   uint64_t graph_gen = 0;    // part of every graph's key: moved by naf_route_check, every graph is then captured again
   uint64_t epoch;            // cpp_ctx::kernel_epoch the cached graphs were captured under (naf_route_check)
-  bool targets_in_apply, targets_applied;      // the next naf_apply closes an outer step: its launch carries the target update (rt_ddpg.cpp's twin)
+  bool targets_in_apply, targets_applied;      // the next naf_apply closes an outer step: its launch carries the target update (as the DDPG learner's)
   float* res_pin; hipEvent_t res_ev[CPP_NAF_TICKETS]; uint64_t next_ticket;
   uint64_t dp_local;       // minibatches applied locally since the last parameter averaging (periodic mode)
   cpp_batch* step_batch;
@@ -29,13 +29,6 @@ struct cpp_naf {
   // minibatch (its priorities into the tree, the next minibatch's rows and weights)
   const float* per_w; std::function<int()> per_hook;
   Arena arena;
-};
-
-// the prioritized-replay state of one gradient pass or step, cleared on every way out
-struct NafPerScope {
-  cpp_naf* f;
-  NafPerScope(cpp_naf* f_, const cpp_replay* r) : f(f_) { f->per_w = r->per_tree ? r->per_w : nullptr; }
-  ~NafPerScope() { f->per_w = nullptr; f->per_hook = nullptr; }
 };
 
 extern "C" int cpp_naf_create(cpp_ctx* ctx, cpp_net* value, cpp_net* tvalue, cpp_net* mu, cpp_net* lv, int share,
@@ -148,21 +141,6 @@ static int naf_head(cpp_naf* f, cpp_batch* b, bool backward) {
   return launch_naf_head(f->ctx, a, f->per_w);
 }
 
-// backward of the fully connected stack of a network without an action splice, from layer `start` down:
-// per layer {[dW;db], dX} as two independent GEMMs.  Returns the op that completes d(flat) (pixel) / dz[0].
-static int add_fc_backward(OpGraph& G, cpp_net* n, Workspace& w, int B, int start, int dep,
-                           const std::function<GemmArgs(GemmArgs)>& dw = [](GemmArgs g) { return g; }) {
-  for (int l = start; l >= 0; --l) {
-    const FcL& L = n->fc[l];
-    G.gemm(dw(fc_dw_args(n, w, l, B, w.dz[l])), {dep});
-    if (l > 0)
-      dep = G.gemm(fc_dx_args(n, l, B, w.dz[l], L.n_out, 0, L.n_in, w.dz[l - 1], L.n_in, relu_grad_epi(n, l - 1), w.fcin[l], L.n_in + 1), {dep});
-    else if (n->spec.pixel)
-      dep = G.gemm(fc_dx_args(n, 0, B, w.dz[0], L.n_out, 0, n->flat, w.dpool[2], n->flat, GE_NONE, nullptr, 0), {dep});
-  }
-  return dep;
-}
-
 // One NAF minibatch (naf_cartpole.py:264-272 without the apply) as a dependency graph, batched like the DDPG
 // step: conv layers of the networks that run them share launches, independent GEMMs share launches.
 // fold (the fused single-learner step only: the gradients are applied as computed): the kernels that write the gradients leave
@@ -171,35 +149,13 @@ static int add_fc_backward(OpGraph& G, cpp_net* n, Workspace& w, int B, int star
 // bump_step: the heads kernel also advances the optimiser's step counter (only where no check_numerics flag can stand the update down)
 static int naf_compute_gradients(cpp_naf* f, cpp_batch* b, bool fold = false, bool bump_step = true) {
   cpp_ctx* ctx = f->ctx;
-  f->sq_cnt = 0; f->step_bumped = false;
-  struct SqScope {
-    cpp_ctx* c; cpp_naf* f;
-    SqScope(cpp_ctx* c_, cpp_naf* f_, bool on) : c(c_), f(f_) {
-      if (on) { c->sq_n[0] = 0; c->sq_n[1] = -1; for (int& g : c->sq_conv_group) g = 0; }
-    }
-    ~SqScope() {
-      if (c->sq_n[0] > 0) f->sq_cnt = c->sq_n[0];
-      c->sq_n[0] = c->sq_n[1] = -1;
-      for (int& g : c->sq_conv_group) g = -1;
-    }
-  } sq_scope(ctx, f, fold && !f->value->spec.use_batch_norm);
-  auto sqg = [ctx](GemmArgs g) {
-    const int tiles = gemm_tiles(g.M, g.N, g.K);
-    if (ctx->sq_n[0] >= 0 && ctx->sq_n[0] + tiles <= SQ_REGION) { g.sq_part = ctx->sq_part + ctx->sq_n[0]; ctx->sq_n[0] += tiles; }
-    else ctx->sq_n[0] = -1;
-    return g;
-  };
+  f->step_bumped = false;
+  SqScope sq_scope(ctx, &f->sq_cnt, 1, {0, 0, 0, 0}, fold && !f->value->spec.use_batch_norm);      // ONE list, every conv network's in it
   cpp_net *v = f->value, *tv = f->tvalue, *mu = f->mu, *lv = f->lv;
   const int B = b->B, C = v->spec.pixel ? v->spec.C : 0, dt = b->dtype;
   const float *w1 = white_of(b, 0, C), *w2 = white_of(b, 1, C);
   const void *s1 = b->direct_store ? b->direct_store : b->s[0], *s2 = b->direct_store ? b->direct_store : b->s[1];
-  struct SlotScope {      // conv1 addresses its images through the sampled slots while this graph runs
-    cpp_net* n[4];
-    SlotScope(cpp_net* v_, cpp_net* mu_, cpp_net* lv_, cpp_net* tv_, cpp_batch* b_) : n{v_, mu_, lv_, tv_} {
-      if (b_->direct_store) { v_->img_slot = mu_->img_slot = lv_->img_slot = b_->slot[0]; tv_->img_slot = b_->slot[1]; }
-    }
-    ~SlotScope() { for (cpp_net* x : n) x->img_slot = nullptr; }
-  } slot_scope(v, mu, lv, tv, b);
+  SlotScope slot_scope(b, {v, mu, lv}, {tv});      // (conv1 addresses its images through the sampled slots while this graph runs)
   const bool share = f->share != 0;
   OpGraph G;
 
@@ -289,9 +245,9 @@ static int naf_compute_gradients(cpp_naf* f, cpp_batch* b, bool fold = false, bo
 
   // ---- backward
   if (!share) {
-    const int dv = add_fc_backward(G, v, v->ws[0], B, (int)v->fc.size() - 1, head, sqg);
-    const int dm = add_fc_backward(G, mu, mu->ws[0], B, (int)mu->fc.size() - 1, head, sqg);
-    const int dl = add_fc_backward(G, lv, lv->ws[0], B, (int)lv->fc.size() - 1, head, sqg);
+    const int dv = add_fc_backward(G, v, v->ws[0], B, (int)v->fc.size() - 1, head, 0);
+    const int dm = add_fc_backward(G, mu, mu->ws[0], B, (int)mu->fc.size() - 1, head, 0);
+    const int dl = add_fc_backward(G, lv, lv->ws[0], B, (int)lv->fc.size() - 1, head, 0);
     if (v->spec.pixel) {
       cpp_net* bn[3] = {v, mu, lv};
       G.fn([=] { return nets_backward_conv(ctx, bn, 3, B, s1, dt, w1); }, {dv, dm, dl});
@@ -309,7 +265,7 @@ static int naf_compute_gradients(cpp_naf* f, cpp_batch* b, bool fold = false, bo
     for (int k = 0; k < 3; ++k) {
       const Head& h = heads[k];
       const float* x = v->ws[0].fcin[Lh];        // [rep, 1] rows, shared by the three heads
-      G.gemm(sqg(mk_gemm(x, 1, rep + 1, h.dz, h.L->n_out, 1, h.n->grads + h.L->w_off, h.L->n_out, rep + 1, h.L->n_out, B, GE_NONE)), {head});
+      G.gemm(sq_gemm(ctx, 0, mk_gemm(x, 1, rep + 1, h.dz, h.L->n_out, 1, h.n->grads + h.L->w_off, h.L->n_out, rep + 1, h.L->n_out, B, GE_NONE)), {head});
       if (drep && !fused) {
         GemmArgs g = mk_gemm(h.dz, h.L->n_out, 1, h.n->params + h.L->w_off, 1, h.L->n_out, drep, ldd, B, rep, h.L->n_out,
                              k == 2 ? final_epi : GE_NONE, k == 2 ? Y : nullptr, ldy);
@@ -317,8 +273,8 @@ static int naf_compute_gradients(cpp_naf* f, cpp_batch* b, bool fold = false, bo
         dep = G.gemm(g, {dep});                  // accumulation order value -> mu -> l_values is fixed
       }
     }
-    if (mlp) G.gemm(sqg(fc_dw_args(v, v->ws[0], 1, B, v->ws[0].dz[1])), {head});      // (dz[1] and dz[0] came out of naf_mlp_kernel)
-    const int dv = add_fc_backward(G, v, v->ws[0], B, mlp ? 0 : Lh - 1, dep, sqg);
+    if (mlp) G.gemm(sq_gemm(ctx, 0, fc_dw_args(v, v->ws[0], 1, B, v->ws[0].dz[1])), {head});      // (dz[1] and dz[0] came out of naf_mlp_kernel)
+    const int dv = add_fc_backward(G, v, v->ws[0], B, mlp ? 0 : Lh - 1, dep, 0);
     if (v->spec.pixel) {     // conv3's and conv2's dW + dX as one launch each, like the DDPG step (nets_backward_conv)
       cpp_net* bn[1] = {v};
       G.fn([=] { return nets_backward_conv(ctx, bn, 1, B, s1, dt, w1); }, {dv});
@@ -329,21 +285,17 @@ static int naf_compute_gradients(cpp_naf* f, cpp_batch* b, bool fold = false, bo
   return flush_dw_reduce(ctx);
 }
 
-// bump: the replay sampler's counter, advanced by this launch; next (+ next_B, next_C, elems): the minibatch whose sample pass has
-// already run -- its whitening tables are finished by this launch's extra grid row (as in the DDPG step, rt_ddpg.cpp: apply)
-static int naf_apply(cpp_naf* f, float grad_scale, bool unless_nonfinite = false, uint64_t* bump = nullptr,
-                     const cpp_batch* next = nullptr, int next_B = 0, int next_C = 0, long elems = 0, bool folded = false,
-                     bool tables_done = false) {
+// bump: the replay sampler's counter, advanced by this launch; nx: the minibatch whose sample pass has already run -- its whitening
+// tables are finished by this launch's extra grid row unless they are done (rt_internal.h: NextBatch)
+static int naf_apply(cpp_naf* f, float grad_scale, bool unless_nonfinite = false, uint64_t* bump = nullptr, bool folded = false,
+                     const NextBatch& nx = NextBatch()) {
   OptSegs s; memset(&s, 0, sizeof(s));
   if (unless_nonfinite) s.skip_if = f->nonfinite;
   s.bump = bump;
   f->value->wimg_key = nullptr; f->mu->wimg_key = nullptr;      // (the parameters change)
-  const bool with_targets = f->targets_in_apply && !next && !unless_nonfinite;      // (the outer step's last launch: naf_step_body)
+  const bool with_targets = f->targets_in_apply && !nx.b && !unless_nonfinite;      // (the outer step's last launch: naf_step_body)
   f->targets_in_apply = false;
-  if (next && next_C > 0 && !tables_done) {
-    s.st_part = next->part; s.st_white = next->white; s.st_nparts = next_B; s.st_jobs = 2 * next_C; s.st_C = next_C;
-    s.st_count = (double)next_B * (double)(elems / next_C); s.st_eps = 1e-6; s.st_wmax = f->ctx->white_max_dev;
-  }
+  opt_next_stats(f->ctx, s, nx);
   s.nseg = 3; s.kind = f->hp.optimiser; s.momentum = f->hp.momentum; s.beta1 = f->hp.beta1; s.beta2 = f->hp.beta2;
   s.epsilon = f->hp.epsilon; s.step = f->opt_step;
   cpp_net* nets[3] = {f->value, f->mu, f->lv};
@@ -366,28 +318,21 @@ static int naf_apply(cpp_naf* f, float grad_scale, bool unless_nonfinite = false
   if (!bumped) RC(launch_counter_add(f->ctx, f->opt_step, 1, unless_nonfinite ? f->nonfinite : nullptr));
   if (folded && sq_cnt > 0 && grad_scale == 1.0f) { s.sq = f->ctx->sq_part; s.sq_begin[0] = 0; s.sq_count[0] = sq_cnt; }
   else RC(launch_sumsq(f->ctx, s, grad_scale, f->norm_part, NORM_PARTS));
-  // conv1's operand images of the next minibatch ride along (as rt_ddpg.cpp's apply; shared trunk: the value network's conv1 on
-  // state_1, the target value network's on state_2; SGD or Momentum -- Adam's update is not restated in the rider)
+  // conv1's operand images of the next minibatch ride along (shared trunk: the value network's conv1 on state_1, the target value
+  // network's on state_2; SGD or Momentum -- Adam's update is not restated in this learner's rider)
   cpp_net* inets[2] = {f->value, f->tvalue};
   const ConvL* L0 = (f->share && f->value->spec.pixel) ? &f->value->conv[0] : nullptr;
-  bool img = next && next_C > 0 && L0 && !unless_nonfinite && !f->value->spec.use_batch_norm && next_B >= 2 &&
-             (s.kind == OPT_SGD || s.kind == OPT_MOMENTUM) && conv_rs16_ok(f->ctx, L0->Cin, L0->H, L0->W, kConvOut) &&
-             L0->w_off == 0 && L0->b_off == (long)L0->ks * L0->ks * L0->Cin * kConvOut;
+  const bool img = nx.b && nx.C > 0 && L0 && !unless_nonfinite && !f->value->spec.use_batch_norm && nx.B >= 2 &&
+                   (s.kind == OPT_SGD || s.kind == OPT_MOMENTUM) && conv_rs16_ok(f->ctx, L0->Cin, L0->H, L0->W, kConvOut) &&
+                   conv1_opens_params(f->value);
   if (img) {
     s.img_n = 2; s.img_cin = L0->Cin;
-    s.img_skip[0] = L0->b_off + kConvOut;
-    for (int j = 0; j < 2; ++j) {
-      cpp_net* n = inets[j];
-      const ConvL& L = n->conv[0];
-      s.img[j].w = n->params + L.w_off; s.img[j].bias = n->params + L.b_off;
-      s.img[j].gw = j == 0 ? s.g[0] + L.w_off : nullptr; s.img[j].gb = j == 0 ? s.g[0] + L.b_off : nullptr;
-      s.img[j].mw = j == 0 ? s.m[0] + L.w_off : nullptr; s.img[j].mb = j == 0 ? s.m[0] + L.b_off : nullptr;
-      s.img[j].rec = reinterpret_cast<unsigned char*>(n->wimg); s.img[j].seg = 0; s.img[j].col = j; s.img[j].nout = kConvOut;
-      s.img[j].white = tables_done ? next->white + (long)j * 2 * next_C : nullptr;
-    }
+    opt_img_net(s, 0, f->value, 0, 0, nx);
+    s.img[0].mw = s.m[0] + L0->w_off; s.img[0].mb = s.m[0] + L0->b_off;
+    opt_img_net(s, 1, f->tvalue, -1, 1, nx);
   }
   RC(launch_opt_apply(f->ctx, s, grad_scale, f->hp.gradient_clip, f->norm_part, NORM_PARTS, f->stats + 1));
-  if (img) for (int j = 0; j < 2; ++j) inets[j]->wimg_key = next->white + (long)j * 2 * next_C;
+  opt_img_built(s, inets, nx);
   return CPP_OK;
 }
 
@@ -444,9 +389,7 @@ extern "C" int cpp_naf_train(cpp_naf* f, cpp_batch* b, float* loss) {
   HIP_CHECK(hipMemsetAsync(f->nonfinite, 0, sizeof(int), ctx->stream));
   RC(naf_compute_gradients(f, b));
   int bad = 0; float l = 0.f;
-  HIP_CHECK(hipMemcpyAsync(&bad, f->nonfinite, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipMemcpyAsync(&l, f->stats, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(ctx_sync_stream(ctx));
+  RC(read_back(ctx, {{&bad, f->nonfinite, sizeof(int)}, {&l, f->stats, sizeof(float)}}, true));
   if (loss) *loss = l;
   if (bad) { cpp_set_error("check_numerics: l_values / L / loss is not finite (naf_cartpole.py:242-245)"); return CPP_ERR_NUMERIC; }
   return naf_apply(f, 1.0f);
@@ -463,105 +406,34 @@ extern "C" int cpp_naf_debug_values(cpp_naf* f, cpp_batch* b, float* l_values, f
   for (cpp_net* n : {f->value, f->tvalue, f->mu, f->lv}) n->is_training = true;
   if (frc) return frc;
   RC(naf_head(f, b, false));
-  hipStream_t st = ctx->stream;
-  if (l_values) HIP_CHECK(hipMemcpyAsync(l_values, f->lv->ws[0].out, (size_t)B * f->NL * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (loss) HIP_CHECK(hipMemcpyAsync(loss, f->stats, sizeof(float), hipMemcpyDeviceToHost, st));
-  if (value) HIP_CHECK(hipMemcpyAsync(value, f->value->ws[0].out, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (advantage) HIP_CHECK(hipMemcpyAsync(advantage, f->adv, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (target_value) HIP_CHECK(hipMemcpyAsync(target_value, f->tvalue->ws[0].out, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  return CPP_OK;
+  const size_t nB = (size_t)B * sizeof(float);
+  return read_back(ctx, {{l_values, f->lv->ws[0].out, nB * f->NL}, {loss, f->stats, sizeof(float)}, {value, f->value->ws[0].out, nB},
+                         {advantage, f->adv, nB}, {target_value, f->tvalue->ws[0].out, nB}});
 }
 
-static void invalidate_graphs(cpp_naf* f) { ++f->graph_gen; }      // (every cached graph misses at its next use: gen is part of every key)
+static void naf_route_check(cpp_naf* f) { route_check(f->ctx, &f->epoch, &f->graph_gen, {f->value, f->tvalue, f->mu}); }
 
-// (as rt_ddpg.cpp's route_check: the context may have moved conv1 to the other kernel family -- every cached graph is rebuilt)
-static void naf_route_check(cpp_naf* f) {
-  ctx_route_update(f->ctx);
-  if (f->epoch == f->ctx->kernel_epoch) return;
-  f->epoch = f->ctx->kernel_epoch;
-  invalidate_graphs(f);
-  f->value->wimg_key = nullptr; f->tvalue->wimg_key = nullptr; f->mu->wimg_key = nullptr;
-}
-
-// The inner step naf_cartpole.py:367-373.  As in the DDPG step (rt_ddpg.cpp: step_body) the sample pass of minibatch i + 1 depends on
-// nothing minibatch i computes: it rides in the launch of i's conv1 dW (or of its dW reductions), keyed by the sampler's counter + 1
-// -- the counter itself moves in i's optimiser launch, which also finishes the whitening tables of i + 1.  CPP_RIDE_GATHER=0: in sequence.
-// dp / comm: as rt_ddpg.cpp's step_body -- the gradient all-reduce sits between a minibatch's gradients and its update, inside the graph
-// Prioritized memory (per.hip; the data-parallel step refuses one): as rt_ddpg.cpp's step_body -- minibatch i's rows are the caller's or
-// a stratified draw by priority keyed by the sampler's counter, its importance weights scale the loss, and ONE launch behind its head
-// kernel writes its priorities into the tree and draws minibatch i + 1.  Here the draws advance the counter themselves (bump), not the
+// The inner step naf_cartpole.py:367-373: the shared minibatch loop (rt_step.cpp: run_minibatches), then the target update.
+// dp / comm: the gradient all-reduce sits between a minibatch's gradients and its update, inside the graph.
+// Prioritized memory (per.hip; the data-parallel step refuses one): the draws advance the sampler's counter themselves, not the
 // optimiser's launch: that launch stands down while the check_numerics flag is set (unless_nonfinite, as on the asynchronous rows path)
 // and the priority writes with it (skip_if_set), the draws and the counter going on as before.
 static int naf_step_body(cpp_naf* f, cpp_replay* r, int B, int n_batches, const int32_t* rows_dev, uint64_t seed, bool dp = false, cpp_comm* comm = nullptr) {
-  const int C = f->value->spec.pixel ? f->value->spec.C : 0;
   cpp_ctx* ctx = f->ctx;
-  const bool direct = direct_replay_ok(f->value, r, B);
-  static const bool no_ride = cpp_switch_off("CPP_RIDE_GATHER");
-  const bool ride_ok = !no_ride && C > 0 && !f->value->spec.use_batch_norm && (r->store_dtype == CPP_F16 || r->store_dtype == CPP_U8);
   const bool per = r->per_tree != nullptr;
-  auto rows_of = [&](int i) -> const int32_t* { return rows_dev ? rows_dev + (size_t)i * B : per ? r->per_rows : nullptr; };
-  NafPerScope per_scope(f, r);
-  auto per_draw = [&](PerArgs& p, int i) {       // minibatch i's rows (unless the caller's) and weights
-    p.B = B; p.w_rows = rows_dev ? rows_of(i) : nullptr; p.seed = seed; p.counter = rows_dev ? nullptr : r->counter; p.bump = rows_dev ? 0 : 1;
-    p.out_rows = r->per_rows; p.out_w = r->per_w;
-  };
-  if (per) {
-    PerArgs p = per_args(r);
-    per_draw(p, 0);
-    RC(launch_per_update_sample(ctx, p));
-  }
-  RC(replay_sample_device(r, B, rows_of(0), seed, rows_of(0) ? nullptr : r->counter, C, f->step_batch, direct));
-  for (int i = 0; i < n_batches; ++i) {
-    GatherArgs ga; int Cg = 0;
-    const bool more = i + 1 < n_batches;
-    if (per) {
-      PerArgs p = per_args(r);
-      p.up_rows = rows_of(i); p.n_up = B; p.up_td = f->td; p.skip_if_set = f->nonfinite;
-      if (more) per_draw(p, i + 1);
-      f->per_hook = [ctx, p] { return launch_per_update_sample(ctx, p); };
-    }
-    if (more && ride_ok) {
-      ga = replay_gather_args(r, B, rows_of(i + 1), seed, rows_of(i + 1) ? nullptr : r->counter, C,
-                              f->step_batch, direct, &Cg);
-      ga.counter_add = 1;
-      static const bool no_dwride = cpp_switch_off("CPP_RIDE_DW");
-      ctx->ride_at_dw = direct && !no_dwride;
-      if (direct) { ga.out_slot[0] = f->step_batch->slot_alt[0]; ga.out_slot[1] = f->step_batch->slot_alt[1]; }
-      ctx->ride = &ga; ctx->ride_done = false; ctx->ride_dtype = r->store_dtype;
-    }
-    // (its statistics are finished in the dW reductions' launch when it leaves with conv1's dW: rt_ddpg.cpp, step_body)
-    static const bool no_stats_ride = cpp_switch_off("CPP_RIDE_STATS");
-    StatsRide sr;
-    if (ctx->ride && ctx->ride_at_dw && Cg > 0 && !no_stats_ride) {
-      sr.part = f->step_batch->part; sr.white = f->step_batch->white; sr.nparts = B; sr.jobs = 2 * Cg; sr.C = Cg;
-      sr.count = (double)B * (double)(r->elems / Cg); sr.eps = 1e-6; sr.wmax = ctx->white_max_dev;
-      ctx->st_ride = &sr; ctx->st_ride_done = false;
-    }
-    const int rc = naf_compute_gradients(f, f->step_batch, true, !per);
-    f->per_hook = nullptr;
-    const bool rode = ctx->ride != nullptr && ctx->ride_done;
-    const bool tables_done = ctx->st_ride != nullptr && ctx->st_ride_done && rode;
-    ctx->ride = nullptr; ctx->st_ride = nullptr;
-    if (rode && direct) { std::swap(f->step_batch->slot[0], f->step_batch->slot_alt[0]); std::swap(f->step_batch->slot[1], f->step_batch->slot_alt[1]); }
-    RC(rc);
-    const bool stats_ride = rode && Cg > 0;
-    if (dp && comm) {
-      prof_begin(ctx);
-      NCCL_CHECK(ncclAllReduce(f->gradbuf, f->gradbuf, (size_t)(f->nV + f->nM + f->nL), ncclFloat, ncclSum, comm->comm, ctx->stream));
-      prof_end(ctx, K_ALLREDUCE);
-    }
+  MinibatchLoop L;
+  L.ctx = ctx; L.r = r; L.step_batch = f->step_batch; L.trunk = f->value;
+  L.per_w = &f->per_w; L.per_hook = &f->per_hook; L.td = f->td; L.skip_if_set = f->nonfinite; L.draws_bump = true;
+  L.ride_ok = !f->value->spec.use_batch_norm;
+  L.gradients = [=] { return naf_compute_gradients(f, f->step_batch, true, !per); };
+  L.apply = [=](bool more, const NextBatch& next) {
+    if (dp) RC(step_allreduce(ctx, comm, f->gradbuf, (size_t)(f->nV + f->nM + f->nL)));
     static const bool no_tgt_ride = cpp_switch_off("CPP_RIDE_TARGETS");
     f->targets_applied = false;
     f->targets_in_apply = !more && !dp && !no_tgt_ride;      // (the last minibatch of an outer step: the target update rides in its optimiser launch)
-    RC(naf_apply(f, (dp && comm) ? 1.0f / (float)comm->world : 1.0f, per, (rows_dev || per) ? nullptr : r->counter, stats_ride ? f->step_batch : nullptr, B, Cg, r->elems, !dp, tables_done));
-    if (more) {
-      if (stats_ride) { f->step_batch->B = B; f->step_batch->dtype = CPP_F16; f->step_batch->stats_C = Cg; }     // (replay_sample_finish's bookkeeping)
-      else if (rode) RC(replay_sample_finish(r, B, Cg, C, f->step_batch));
-      else RC(replay_sample_device(r, B, rows_of(i + 1), seed, rows_of(i + 1) ? nullptr : r->counter, C,
-                                   f->step_batch, direct));
-    }
-  }
+    return naf_apply(f, (dp && comm) ? 1.0f / (float)comm->world : 1.0f, per, (rows_dev || per) ? nullptr : r->counter, !dp, next);
+  };
+  RC(run_minibatches(L, B, n_batches, rows_dev, seed));
   if (f->targets_applied) { f->targets_applied = false; return CPP_OK; }      // (the target update and the route's publish left with the optimiser's launch)
   ctx->route_rider = true;                          // (the largest whitening scale of this step rides to the host in that launch)
   return cpp_naf_update_targets(f);      // (the largest whitening scale of this step, for the next call's choice of conv1 kernels)
@@ -575,9 +447,7 @@ extern "C" int cpp_naf_train_step(cpp_naf* f, cpp_replay* r, int B, int n_batche
   HIP_CHECK(hipSetDevice(ctx->device));
   if (!f->step_batch) RC(cpp_batch_create(ctx, f->maxB, r->elems, r->A, &f->step_batch));
   if (idxs) {
-    for (int i = 0; i < n_batches * B; ++i)
-      ARG_CHECK(idxs[i] >= 0 && idxs[i] < r->size, "cpp_naf_train_step: index %d outside [0,%d)", idxs[i], r->size);
-    HIP_CHECK(hipMemcpyAsync(r->rows_in, idxs, (size_t)n_batches * B * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    RC(replay_upload_rows(r, idxs, n_batches * B, "cpp_naf_train_step"));
     return naf_step_body(f, r, B, n_batches, r->rows_in, seed);
   }
   return run_step_graph(ctx, f->graph, GraphKey{B, n_batches, seed, r->uid, 0, f->graph_gen}, [&] { return naf_step_body(f, r, B, n_batches, nullptr, seed); });
@@ -596,7 +466,7 @@ extern "C" int cpp_naf_train_step(cpp_naf* f, cpp_replay* r, int B, int n_batche
 static int naf_rows_body(cpp_naf* f, cpp_replay* r, int B, bool fold = false, bool sticky = false) {
   const int C = f->value->spec.pixel ? f->value->spec.C : 0;
   if (!sticky) HIP_CHECK(hipMemsetAsync(f->nonfinite, 0, sizeof(int), f->ctx->stream));
-  NafPerScope per_scope(f, r);
+  PerScope per_scope(&f->per_w, &f->per_hook, r);
   if (r->per_tree) {
     PerArgs p = per_args(r);
     p.B = B; p.w_rows = r->rows_in; p.out_w = r->per_w;
@@ -620,9 +490,7 @@ extern "C" int cpp_naf_train_rows(cpp_naf* f, cpp_replay* r, int B, const int32_
   RC(replay_stage_rows(r, idxs, B, "cpp_naf_train_rows"));
   RC(run_step_graph(ctx, f->rgraph, GraphKey{B, 1, 0, r->uid, 0, f->graph_gen}, [&] { return naf_rows_body(f, r, B); }));
   int bad = 0; float l = 0.f;
-  HIP_CHECK(hipMemcpyAsync(&bad, f->nonfinite, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipMemcpyAsync(&l, f->stats, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(ctx_sync_stream(ctx));
+  RC(read_back(ctx, {{&bad, f->nonfinite, sizeof(int)}, {&l, f->stats, sizeof(float)}}, true));
   if (loss) *loss = l;
   if (bad) { cpp_set_error("check_numerics: l_values / L / loss is not finite (naf_cartpole.py:242-245)"); return CPP_ERR_NUMERIC; }
   return naf_apply(f, 1.0f);
@@ -635,7 +503,7 @@ extern "C" int cpp_naf_train_rows(cpp_naf* f, cpp_replay* r, int B, const int32_
 // At most CPP_NAF_TICKETS results are outstanding: a slot is reused CPP_NAF_TICKETS calls later.
 static int naf_rows_apply_body(cpp_naf* f, cpp_replay* r, int B) {
   RC(naf_rows_body(f, r, B, true, true));  // (gradients and optimiser in ONE captured body: the fold's host-side state is consistent)
-  return naf_apply(f, 1.0f, true, nullptr, nullptr, 0, 0, 0, true);
+  return naf_apply(f, 1.0f, true, nullptr, true);
 }
 extern "C" int cpp_naf_train_rows_async(cpp_naf* f, cpp_replay* r, int B, const int32_t* idxs, uint64_t* ticket) {
   if (f) naf_route_check(f);
@@ -764,9 +632,7 @@ extern "C" int cpp_naf_dp_train_step(cpp_naf* f, cpp_replay* r, cpp_comm* c, int
 extern "C" int cpp_naf_last_stats(cpp_naf* f, float out[3]) {
   ARG_CHECK(f && out, "cpp_naf_last_stats: NULL argument");
   int bad = 0;
-  HIP_CHECK(hipMemcpyAsync(out, f->stats, 2 * sizeof(float), hipMemcpyDeviceToHost, f->ctx->stream));
-  HIP_CHECK(hipMemcpyAsync(&bad, f->nonfinite, sizeof(int), hipMemcpyDeviceToHost, f->ctx->stream));
-  HIP_CHECK(ctx_sync_stream(f->ctx));
+  RC(read_back(f->ctx, {{out, f->stats, 2 * sizeof(float)}, {&bad, f->nonfinite, sizeof(int)}}, true));
   out[2] = (float)bad;
   return CPP_OK;
 }
@@ -777,13 +643,8 @@ extern "C" int64_t cpp_naf_opt_state_size(const cpp_naf* f) { return f ? (int64_
 extern "C" int cpp_naf_get_opt_state(cpp_naf* f, float* m, float* v, int64_t n, uint64_t* step) {
   ARG_CHECK(f, "cpp_naf_get_opt_state: NULL argument");
   ARG_CHECK(n == f->nV + f->nM + f->nL, "cpp_naf_get_opt_state: asked %ld values, the optimiser has %ld", (long)n, f->nV + f->nM + f->nL);
-  hipStream_t st = f->ctx->stream;
   HIP_CHECK(hipSetDevice(f->ctx->device));
-  if (m) HIP_CHECK(hipMemcpyAsync(m, f->m, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (v) HIP_CHECK(hipMemcpyAsync(v, f->v, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (step) HIP_CHECK(hipMemcpyAsync(step, f->opt_step, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  return CPP_OK;
+  return read_back(f->ctx, {{m, f->m, (size_t)n * sizeof(float)}, {v, f->v, (size_t)n * sizeof(float)}, {step, f->opt_step, sizeof(uint64_t)}});
 }
 extern "C" int cpp_naf_set_opt_state(cpp_naf* f, const float* m, const float* v, int64_t n, uint64_t step) {
   ARG_CHECK(f, "cpp_naf_set_opt_state: NULL argument");

@@ -689,6 +689,19 @@ GemmArgs fc_dx_args(cpp_net* n, int l, int B, const float* dz, long dz_ld, int c
   const FcL& L = n->fc[l];
   return mk_gemm(dz, dz_ld, 1, n->params + L.w_off + (long)col0 * L.n_out, 1, L.n_out, C, ldc, B, ncols, L.n_out, epi, Y, ldy);
 }
+// (rt_internal.h.  dW before dX per layer, top down: sq_gemm hands out the norm partials' slots in this order)
+int add_fc_backward(OpGraph& G, cpp_net* n, Workspace& w, int B, int start, int dep, int list, int skip_dx) {
+  for (int l = start; l >= 0; --l) {
+    const FcL& L = n->fc[l];
+    G.gemm(sq_gemm(n->ctx, list, fc_dw_args(n, w, l, B, w.dz[l])), {dep});
+    if (l == skip_dx) continue;
+    if (l > 0)
+      dep = G.gemm(fc_dx_args(n, l, B, w.dz[l], L.n_out, 0, L.n_in, w.dz[l - 1], L.n_in, relu_grad_epi(n, l - 1), w.fcin[l], L.n_in + 1), {dep});
+    else if (n->spec.pixel)
+      dep = G.gemm(fc_dx_args(n, 0, B, w.dz[0], L.n_out, 0, n->flat, w.dpool[2], n->flat, GE_NONE, nullptr, 0), {dep});
+  }
+  return dep;
+}
 
 // ---- head 2 of a twin critic: layers [cat, nfc) of the first workspace
 GemmArgs twin_fwd_args(cpp_net* n, Workspace& w, int l, int B) {

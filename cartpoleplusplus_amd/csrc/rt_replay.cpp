@@ -348,6 +348,13 @@ extern "C" int cpp_replay_read_states(cpp_replay* r, const int32_t* slots, int n
   return CPP_OK;
 }
 
+// the caller's rows of an eager step -> r->rows_in, checked: a plain copy in stream order
+int replay_upload_rows(cpp_replay* r, const int32_t* idxs, int n, const char* who) {
+  for (int i = 0; i < n; ++i)
+    ARG_CHECK(idxs[i] >= 0 && idxs[i] < r->size, "%s: index %d outside [0,%d)", who, idxs[i], r->size);
+  HIP_CHECK(hipMemcpyAsync(r->rows_in, idxs, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, r->ctx->stream));
+  return CPP_OK;
+}
 // n host-drawn row indexes (replay_memory.py:123-129: numpy's RNG on the host) -> r->rows_in, checked, without waiting for the
 // stream: through a ring of pinned slots (slot k is reused once the copy that read it has completed)
 int replay_stage_rows(cpp_replay* r, const int32_t* idxs, int n, const char* who) {
