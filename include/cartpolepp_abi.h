@@ -131,7 +131,15 @@ typedef struct cpp_net_spec {
   int32_t use_dropout;   /* opts.use_dropout (base_network.py:69-70): slim.dropout (keep 0.5) after the ReLU of every layer made by
                           * hidden_layers_starting_at *with opts* -- the actor's and the NAF networks' hidden stacks; the critics
                           * have none (ddpg_cartpole.py:168-177).  Training-mode entry points draw the keep bits from
-                          * Philox4x32-10(key = dropout_seed; counter = (row * units + unit, layer, forward count)). */
+                          * Philox4x32-10(key = dropout_seed; counter = (row * units + unit, layer, forward count)).
+                          * The forward count is per network: the number of training-mode forwards of its hidden stack so far.  Every
+                          * minibatch of every training entry point (the fused steps, *_train_rows*, *_sample_and_compute, the
+                          * data-parallel steps, eager or replayed from a captured graph) advances it by one, behind the layers that
+                          * read it; the stand-alone actor op counts the actor, the critic op the target actor.  Inference-mode entry
+                          * points neither drop a unit nor count.  Delayed policy updates (cpp_ddpg_set_policy_delay, d > 1) hold the
+                          * actor's optimiser step alone: a minibatch whose actor update is held still runs the actor's and the target
+                          * actor's forward in training mode, so it draws masks and is counted -- minibatch k of a trainer (from 0)
+                          * draws count k in both networks whatever d is. */
   uint32_t dropout_seed;
 } cpp_net_spec;
 

@@ -152,17 +152,28 @@ def philox4x32_10(ctr, key):
 
 def dropout_masks(namespace, hidden, B, step):
     """the keep masks the device draws for the `step`-th training-mode forward of network `namespace`
-    (include/cartpolepp_abi.h, cpp_net_spec.use_dropout): {'h<i>': (B, units) of 0/1}."""
+    (include/cartpolepp_abi.h, cpp_net_spec.use_dropout): {'h<i>': (B, units) of 0/1}.  Word 0 of
+    philox4x32_10([row * units + unit, layer, step & 0xFFFFFFFF, step >> 32], [crc32(namespace), 0]), lowest bit -- computed with
+    the vectorised philox4x32_10_np (tests/test_dropout_sensitivity.py holds the two to each other bit for bit)."""
     import zlib
     seed = zlib.crc32(namespace.encode()) & 0xffffffff
+    step = int(step)
     out = {}
     for layer, units in enumerate(hidden):
-        m = np.empty((B, units), np.float64)
-        for b in range(B):
-            for j in range(units):
-                m[b, j] = philox4x32_10([b * units + j, layer, step & 0xFFFFFFFF, step >> 32], [seed, 0])[0] & 1
-        out["h%d" % layer] = m
+        idx = np.arange(B * units, dtype=np.uint64)
+        assert B * units <= 1 << 32
+        w0 = philox4x32_10_np(idx, np.full_like(idx, layer), np.full_like(idx, step & 0xFFFFFFFF), np.full_like(idx, step >> 32), seed, 0)[0]
+        out["h%d" % layer] = (w0 & np.uint64(1)).astype(np.float64).reshape(B, units)
     return out
+
+
+def set_actor_masks(ref, B, count):
+    """hand an oracle DDPG (or a restatement built on it) the masks of training-mode forward number `count` of the actor and of the
+    target actor; nothing to do without --use-dropout"""
+    spec = ref.actor.spec
+    if spec.dropout:
+        ref.actor.drop_masks = dropout_masks("actor", spec.hidden, B, count)
+        ref.target_actor.drop_masks = dropout_masks("target_actor", spec.hidden, B, count)
 
 
 def device_relu_active(net, B):
@@ -283,12 +294,13 @@ def ddpg_path(agent, B, actor_hidden, critic_hidden, pixel):
     return "|".join(fit)
 
 
-def naf_path(agent, B, hidden, share):
-    """the same for NAF: 'mlp' (naf_mlp_kernel), 'heads' (naf_heads_kernel) or 'gemm' (GEMM levels + naf_head_kernel)."""
+def naf_path(agent, B, hidden, share, dropout=False):
+    """the same for NAF: 'mlp' (naf_mlp_kernel), 'heads' (naf_heads_kernel) or 'gemm' (GEMM levels + naf_head_kernel).
+    dropout: naf_mlp_kernel knows no masks and is no candidate (launch counts that fit only 'mlp' then fit nothing)."""
     n = _profiled_step(agent, agent.value_net.ctx, B)
     gemm = n.get("gemm", 0)
     assert n.get("naf_head", 0) == 1, n
-    cand = (["mlp"] if len(hidden) == 2 else []) + ["heads", "gemm"] if share else ["gemm"]
+    cand = (["mlp"] if len(hidden) == 2 and not dropout else []) + ["heads", "gemm"] if share else ["gemm"]
     fit = [p for p in cand if naf_gemm_levels(p, hidden, share) == gemm]
     assert len(fit) == 1, "launch counts %s fit %s of the NAF head paths (hidden %s, share %s)" % (n, fit, hidden, share)
     return fit[0]
@@ -557,14 +569,17 @@ def delta_bound(theta, d_want, r, nb=1):
     return 2.0 ** -23 * nb * float(np.linalg.norm(np.asarray(theta, np.float64))) + r * float(np.linalg.norm(d_want))
 
 
-def host_case(shape, B, nb, seed, rows=24, action_dim=2, batch_norm=False):
+def host_case(shape, B, nb, seed, rows=24, action_dim=2, batch_norm=False, dropout=False, actor_hidden=None):
     """specs, starting parameters of the four DDPG networks (xavier + make_pair's perturbations), `rows` transitions as episodes
     (pixel: codes k / 255 in f16, what the replay store holds exactly) and nb * B row numbers with the minibatches they select.
-    batch_norm: --use-batch-norm networks (the same numbers: the conv bias slots then hold BatchNorm/beta)."""
+    batch_norm: --use-batch-norm networks (the same numbers: the conv bias slots then hold BatchNorm/beta).  dropout: --use-dropout
+    (the same numbers: the actor's spec asks for masks).  actor_hidden: --actor-hidden-layers (None: the default; other widths draw
+    other numbers)."""
     from oracle.replay_np import OracleReplayMemory
     pixel = len(shape) == 5
     kw = dict(pixel=True, H=shape[0], W=shape[1], C=int(np.prod(shape[2:])), batch_norm=batch_norm) if pixel else dict(pixel=False, state_elems=int(np.prod(shape)))
-    aspec, cspec = O.NetSpec("actor", action_dim, DEFAULT_ACTOR_HIDDEN, **kw), O.NetSpec("critic", action_dim, DEFAULT_ACTOR_HIDDEN, **kw)
+    aspec = O.NetSpec("actor", action_dim, DEFAULT_ACTOR_HIDDEN if actor_hidden is None else tuple(actor_hidden), dropout=dropout, **kw)
+    cspec = O.NetSpec("critic", action_dim, DEFAULT_ACTOR_HIDDEN, **kw)
     rng = np.random.default_rng(1000 + seed)
     P = []
     for spec in (aspec, cspec):
@@ -660,15 +675,23 @@ NAF_OPTIMISERS = {"momentum-0.5": ("Momentum", {"learning_rate": 0.01, "momentum
 NAF_RIDER_CASE = ((64, 64, 3, 2, 3), 8, 3, 30, 5)         # shape, B, minibatches, rows, seed: the shared trunk, conv1 on the operand image
 
 
-def naf_host_case(shape, B, nb, rows, seed, hidden=(100, 50), action_dim=2):
+def naf_host_case(shape, B, nb, rows, seed, hidden=(100, 50), action_dim=2, share=True, dropout=False):
     """host_case for the shared-trunk NAF agent: (value, mu, l) specs, the three parameter vectors + the target value network's,
-    episodes, rows and the minibatches they select"""
+    episodes, rows and the minibatches they select.  share=False: mu and l_values on trunks and hidden stacks of their own; dropout:
+    --use-dropout; a low-dimensional `shape` gives networks without a trunk."""
     from oracle import naf_np as N
     from oracle.replay_np import OracleReplayMemory
-    kw = dict(pixel=True, H=shape[0], W=shape[1], C=int(np.prod(shape[2:])))
-    specs = (N.HeadSpec(1, "linear", list(hidden), **kw),
-             N.HeadSpec(action_dim, "tanh", [], False, state_elems=hidden[-1], head_only=True),
-             N.HeadSpec(N.num_l_values(action_dim), "linear", [], False, state_elems=hidden[-1], head_only=True))
+    if len(shape) == 5:
+        kw = dict(pixel=True, H=shape[0], W=shape[1], C=int(np.prod(shape[2:])), dropout=dropout)
+    else:
+        kw = dict(pixel=False, state_elems=int(np.prod(shape)), dropout=dropout)
+    if share:
+        specs = (N.HeadSpec(1, "linear", list(hidden), **kw),
+                 N.HeadSpec(action_dim, "tanh", [], False, state_elems=hidden[-1], head_only=True),
+                 N.HeadSpec(N.num_l_values(action_dim), "linear", [], False, state_elems=hidden[-1], head_only=True))
+    else:
+        specs = (N.HeadSpec(1, "linear", list(hidden), **kw), N.HeadSpec(action_dim, "tanh", list(hidden), **kw),
+                 N.HeadSpec(N.num_l_values(action_dim), "linear", list(hidden), **kw))
     rng = np.random.default_rng(2000 + seed)
     flats = []
     for sp in specs:
@@ -676,7 +699,8 @@ def naf_host_case(shape, B, nb, rows, seed, hidden=(100, 50), action_dim=2):
         flats.append(p + rng.normal(0, 0.05, p.shape).astype(np.float32))
     flats.append(flats[0] + rng.normal(0, 0.01, flats[0].shape).astype(np.float32))
     orm = OracleReplayMemory(rows, shape, action_dim)
-    mk = lambda: rng.integers(0, 256, shape).astype(np.float16) / np.float16(255)
+    mk = (lambda: rng.integers(0, 256, shape).astype(np.float16) / np.float16(255)) if len(shape) == 5 else \
+         (lambda: rng.standard_normal(shape).astype(np.float32))
     episodes, left = [], rows
     while left > 0:
         n = min(left, int(rng.integers(2, 6)))
@@ -716,3 +740,86 @@ def naf_twin_case(specs, flats, batches, optimiser, optimiser_args, action_dim=2
         want.append(w)
         rs.append(max(5e-5, F32_GRAD_FACTOR * float(np.linalg.norm(t - w) / np.linalg.norm(w - start))))
     return want, rs, norms, same
+
+
+# ---- --use-dropout over several minibatches and several calls: the inputs and the float64 expectation that tests/test_gpu_dropout.py
+# ---- holds the device to and tests/test_dropout_sensitivity.py plants faults in.  Minibatch k of call c is training-mode forward number
+# ---- nb * c + k of every network with a dropout stack (include/cartpolepp_abi.h, cpp_net_spec.use_dropout)
+DROP_PIX, DROP_LOWDIM = (16, 16, 3, 1, 2), (2, 2, 7)
+DROP_B, DROP_NB, DROP_CALLS, DROP_ROWS, DROP_SEED = 6, 3, 2, 24, 7
+DROP_NAF_OPTIMISER = ("Momentum", {"learning_rate": 0.01, "momentum": 0.5})
+DROP_NAF_HIDDEN = {True: (100, 50), False: (32, 16)}          # share: the hidden stack (own trunks: test_gpu_head_shapes.py's widths)
+NAF_DROP_NAMESPACES = ("value", "target_value", "naf/output_action", "naf/l_values")
+
+
+def ddpg_dropout_case(shape):
+    return host_case(shape, DROP_B, DROP_NB * DROP_CALLS, DROP_SEED, rows=DROP_ROWS, dropout=True)
+
+
+def naf_dropout_case(shape, share):
+    return naf_host_case(shape, DROP_B, DROP_NB * DROP_CALLS, DROP_ROWS, DROP_SEED, hidden=DROP_NAF_HIDDEN[share], share=share, dropout=True)
+
+
+def ddpg_dropout_calls(specs, P, batches, dt=np.float64, hyper=LOUD, nb=DROP_NB, masks=dropout_masks, wrap=None):
+    """oracle.DDPG over len(batches) / nb calls of nb minibatches + the target updates, the actor and the target actor drawing
+    masks(namespace, hidden, B, nb * c + k) in minibatch k of call c.  wrap(ref): called before every minibatch (the sensitivity
+    test swaps faulted networks in).  Returns per call (the four vectors after it, oracle_minibatch's outputs, a snapshot of the
+    oracle after it)."""
+    import copy
+    ref = oracle_of(specs, P, dt, hyper)
+    hidden, B = specs[0].hidden, int(np.asarray(batches[0][1]).shape[0])
+    out = []
+    for c in range(len(batches) // nb):
+        outs = []
+        for k in range(nb):
+            count = nb * c + k
+            if wrap is not None:
+                wrap(ref)
+            ref.actor.drop_masks = masks("actor", hidden, B, count)
+            ref.target_actor.drop_masks = masks("target_actor", hidden, B, count)
+            outs.append(oracle_minibatch(ref, batches[count]))
+        ref.update_targets()
+        out.append((four_vectors(ref), outs, copy.copy(ref)))
+    return out
+
+
+def naf_oracle(specs, flats, share, dt, optimiser=DROP_NAF_OPTIMISER, action_dim=2):
+    from oracle import naf_np as N
+    r = N.NAF(specs[0], specs[1], specs[2], flats[0], flats[1], flats[2], share, action_dim, dt, discount=NAF_HYPER["discount"],
+              gradient_clip=NAF_HYPER["clip"], target_update_rate=NAF_HYPER["target_update_rate"], optimiser=N.make_optimiser(*optimiser))
+    r.target_value = O.Net(specs[0], flats[3], dt)
+    return r
+
+
+def naf_dropout_calls(specs, flats, batches, share, dt=np.float64, nb=DROP_NB, masks=dropout_masks, wrap=None):
+    """the same for oracle.NAF (NAF_HYPER, DROP_NAF_OPTIMISER): the masks are set before each train(), update_targets() once per call.
+    Returns per call ((params, target value params), the pre-clip norms, the value trunk's routes per minibatch, a snapshot)."""
+    import copy
+    ref = naf_oracle(specs, flats, share, dt)
+    hidden, B = specs[0].hidden, int(np.asarray(batches[0][1]).shape[0])
+    out = []
+    for c in range(len(batches) // nb):
+        norms, routes = [], []
+        for k in range(nb):
+            count = nb * c + k
+            if wrap is not None:
+                wrap(ref)
+            nets = (ref.value, ref.target_value) + (() if share else (ref.mu, ref.l))
+            for net, ns in zip(nets, NAF_DROP_NAMESPACES):
+                net.drop_masks = masks(ns, hidden, B, count)
+            b = batches[count]
+            cv = ref._forward(b[0])[0]
+            routes += [np.where(cv[cn][1] > 0, cv[cn + ":amax_own"], 255) for cn, _k, _co in O.CONV_DEFS] if specs[0].pixel else []
+            norms.append(float(ref.train(b)["norm"]))
+        ref.update_targets()
+        out.append(((np.asarray(ref.flat(), np.float64), np.asarray(ref.target_value.flat(), np.float64)), norms, routes, copy.copy(ref)))
+    return out
+
+
+def twin_rs(want, twin, start):
+    """f32_twin_case's rule per vector: r = max(5e-5, F32_GRAD_FACTOR x the float32 numpy twin's relative delta error)"""
+    rs = []
+    for w, t, p in zip(want, twin, start):
+        d = float(np.linalg.norm(w - p))
+        rs.append(max(5e-5, F32_GRAD_FACTOR * float(np.linalg.norm(t - w)) / d) if d > 0 else 5e-5)
+    return rs

@@ -311,11 +311,11 @@ def q_value_tail(spec, n, rng):
     return p, p + rng.normal(0, 0.05, p.shape).astype(np.float32)
 
 
-def host_case(shape, B, nb, seed, n, rows=ROWS, action_dim=2, n_step=1, discount=0.9):
+def host_case(shape, B, nb, seed, n, rows=ROWS, action_dim=2, n_step=1, discount=0.9, **plain_kw):
     """tests.helpers.host_case with quantile critics: (specs, P, episodes, idxs, batches); specs[1] is quant_spec's, P[1] and P[3] end in
     the wider q_value layer.  n_step > 1: the minibatches carry the n-step columns the device's gather forms."""
     from tests.helpers import host_case as plain_case
-    specs, P, episodes, idxs, batches = plain_case(shape, B, nb, seed, rows=rows, action_dim=action_dim)
+    specs, P, episodes, idxs, batches = plain_case(shape, B, nb, seed, rows=rows, action_dim=action_dim, **plain_kw)      # (dropout, actor_hidden)
     cspec = specs[1]
     _name, n_in, _one, _a, _c = cspec.fc[-1]
     cut = n_in + 1
@@ -326,10 +326,10 @@ def host_case(shape, B, nb, seed, n, rows=ROWS, action_dim=2, n_step=1, discount
     return (specs[0], quant_spec(cspec, n)), P, episodes, idxs, batches
 
 
-def case_inputs(case, nb=NB, seed=None):
+def case_inputs(case, nb=NB, seed=None, **kw):
     cid, shape_name, A, B, N = case[:5]
     return host_case(SHAPES[shape_name], B, nb, SEEDS[cid] if seed is None else seed, N, rows=ROWS, action_dim=A, n_step=case[13],
-                     discount=case[7])
+                     discount=case[7], **kw)
 
 
 def structure(case):

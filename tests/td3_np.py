@@ -30,6 +30,9 @@ class DelayedDDPG(R.DDPGWithOptimiser):
         self.pd_fault = fault
         self.smoothing, self.tps_n = smoothing, 0      # (sigma, clip, seed) or None; the count of target-forming passes
         self.schedule = []                             # per counted minibatch: was the actor's list applied
+        # --use-dropout (include/cartpolepp_abi.h, cpp_net_spec.use_dropout): training-mode forwards so far of the actor and of the target
+        # actor.  The hold reaches the optimiser alone -- a held minibatch still runs both forwards, draws masks and is counted
+        self.drop_n = {"actor": 0, "target_actor": 0}
 
     # ---- the rule
     def _applies(self, n_new):
@@ -64,8 +67,18 @@ class DelayedDDPG(R.DDPGWithOptimiser):
         self.tps_n += 1
         return T.SmoothedDDPG.critic_gradients(self, batch, noise)
 
+    def _draw_masks(self, B, *which):
+        """the masks of the next training-mode forward of the named networks; their counts advance (nothing to do without dropout)"""
+        if not self.actor.spec.dropout:
+            return
+        from tests.helpers import dropout_masks
+        for name in which:
+            getattr(self, name).drop_masks = dropout_masks(name, self.actor.spec.hidden, B, self.drop_n[name])
+            self.drop_n[name] += 1
+
     # ---- the entry points
     def train_minibatch(self, batch):
+        self._draw_masks(np.asarray(batch[1]).shape[0], "actor", "target_actor")
         ag, cg = self.actor_gradients(batch[0]), self.critic_gradients(batch)
         routes, tie = [], np.inf
         for cache in (ag["cache_actor"], cg["cache_critic"]):
@@ -96,6 +109,7 @@ class DelayedDDPG(R.DDPGWithOptimiser):
         else:
             applied = self._applies(self.n + 1)
         self.held = not applied
+        self._draw_masks(np.asarray(s1).shape[0], "actor")
         ag = self.actor_gradients(s1)
         return {"actor_norm": float(self._actor(ag["grads"], applied)), "applied": applied}
 
@@ -104,6 +118,7 @@ class DelayedDDPG(R.DDPGWithOptimiser):
         applied = self._applies(self.n)
         self.held = not applied
         self.schedule.append(applied)
+        self._draw_masks(np.asarray(batch[1]).shape[0], "target_actor")
         cg = self.critic_gradients(batch)
         if self.pd_fault == "critic_held_too" and not applied:
             return {"critic_norm": float(O.clip_by_global_norm(cg["grads"], self.hp.gradient_clip, self.dt)[1]), "td": cg["td"]}

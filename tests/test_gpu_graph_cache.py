@@ -271,3 +271,107 @@ def test_ddpg_half_steps_after_a_replayed_fused_step():
     loss and gradient norms of the last call; with the reset in place they agree bit for bit, like every other case of this file)."""
     order = (("fused", 2), ("half", 2), ("fused", 1), ("half", 2))
     _assert_equal(_graph_and_eager(lambda: _ddpg_agent(PIXEL), lambda a: _mixed_script(a, order)), "ddpg fused / half / replayed fused / half")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 6. --use-dropout: every entry point assembles or captures the step on its own, and each must advance every dropout counter exactly
+# once per training-mode forward -- a replay that drew the masks of its capture's count, or an entry point that counted twice, leaves
+# the eager sequence of masks at once.  (tests/test_gpu_dropout.py pins the eager counts to the float64 oracle; here the replays are
+# pinned to the eager counts, bit for bit.)
+# ---------------------------------------------------------------------------------------------------------------------
+def _ddpg_dropout_agent(shape, maxB=8):
+    agent, _ref, _ = make_pair(shape, maxB, len(shape) == 5, replay_size=300, use_dropout=True)
+    agent.replay_memory.fill_synthetic(ROWS, seed=11)
+    return agent
+
+
+def _naf_dropout_agent(shape, share, maxB=8):
+    from tests.test_gpu_naf import make_naf
+    agent, _ref, _ = make_naf(shape, maxB, share, "Adam", {"learning_rate": 0.001}, seed=4, replay_size=300, use_dropout=True)
+    agent.replay_memory.fill_synthetic(ROWS, seed=9)
+    return agent
+
+
+_DP_PATHS = []          # the data-parallel step's path per learner, in call order (agent G's two, then agent E's two)
+
+
+def _dp_steps(agent, B=8):
+    from cartpoleplusplus_amd.distributed import NativeLearner
+    for sync_every in (1, 2):
+        learner = NativeLearner(agent, B, 1234, None, sync_every=sync_every)
+        for _ in range(2):
+            learner.train_step(3)
+        _DP_PATHS.append(learner.dp_status()["path"])
+
+
+def _assert_dp_paths():
+    """agent G replayed a captured graph at sync_every 1 (at 2, without a communicator, it may hold on to that graph or launch eagerly:
+    not asserted); agent E never did"""
+    paths = list(_DP_PATHS)
+    del _DP_PATHS[:]
+    assert len(paths) == 4 and paths[0] == "hipgraph" and paths[2:] == ["none", "none"], paths
+
+
+def ddpg_dropout_script(agent):
+    _lib, lib, check, ptr = _abi()
+    t, rm, B = agent.trainer, agent.replay_memory, 8
+
+    def fused(times, n):
+        for _ in range(times):
+            check(lib.cpp_ddpg_train_step(t.handle, rm.handle, B, n, None, 1234))
+    fused(3, 2)                          # capture, replay, replay
+    fused(2, 3)
+    for idxs in _row_draws(3, B):
+        check(lib.cpp_ddpg_train_rows(t.handle, rm.handle, B, ptr(idxs)))
+    check(lib.cpp_ddpg_update_targets(t.handle))
+    for _ in range(2):
+        check(lib.cpp_ddpg_sample_and_compute(t.handle, rm.handle, B, 1234))
+        check(lib.cpp_ddpg_apply_gradients(t.handle, 1.0))
+    _dp_steps(agent, B)
+    fused(2, 2)
+    return [t.last_stats(), agent.actor.get_grads(), agent.critic.get_grads()]
+
+
+def naf_dropout_script(agent):
+    _lib, lib, check, ptr = _abi()
+    h, rm, B, losses = agent.naf.handle, agent.replay_memory, 8, []
+
+    def fused(times, n):
+        for _ in range(times):
+            check(lib.cpp_naf_train_step(h, rm.handle, B, n, None, 1234))
+    fused(3, 2)
+    fused(2, 3)
+    for idxs in _row_draws(3, B):
+        loss = ctypes.c_float()
+        check(lib.cpp_naf_train_rows(h, rm.handle, B, ptr(idxs), ctypes.byref(loss)))
+        losses.append(loss.value)
+    for idxs in _row_draws(3, B, seed=6):
+        loss, ticket = ctypes.c_float(), ctypes.c_uint64()
+        check(lib.cpp_naf_train_rows_async(h, rm.handle, B, ptr(idxs), ctypes.byref(ticket)))
+        check(lib.cpp_naf_loss_wait(h, ticket.value, ctypes.byref(loss)))
+        losses.append(loss.value)
+    for _ in range(2):
+        check(lib.cpp_naf_sample_and_compute(h, rm.handle, B, 1234))
+        check(lib.cpp_naf_apply_gradients(h, 1.0))
+    _dp_steps(agent, B)
+    fused(2, 2)
+    slots = agent.naf.get_optimiser_state()
+    return [np.array(losses, np.float32), slots["m"], slots["v"], agent.naf.last_stats(), agent.naf.get_grads()]
+
+
+@pytest.mark.parametrize("shape", [PIXEL, LOWDIM], ids=["pixel", "low-dimensional"])
+def test_ddpg_entry_points_with_dropout(shape):
+    del _DP_PATHS[:]
+    res = _graph_and_eager(lambda: _ddpg_dropout_agent(shape), ddpg_dropout_script)
+    _assert_equal(res, "ddpg --use-dropout, every entry point")
+    _assert_dp_paths()
+
+
+@pytest.mark.parametrize("shape,share", [(PIXEL, True), (PIXEL, False), (LOWDIM, True), (LOWDIM, False)],
+                         ids=["pixel-shared", "pixel-own-trunks", "low-dimensional-shared", "low-dimensional-own-trunks"])
+def test_naf_entry_points_with_dropout(shape, share):
+    del _DP_PATHS[:]
+    res = _graph_and_eager(lambda: _naf_dropout_agent(shape, share), naf_dropout_script)
+    _assert_equal(res, "naf --use-dropout, every entry point")
+    _assert_dp_paths()
+    assert res[0][3][2] == 0          # (check_numerics never fired)

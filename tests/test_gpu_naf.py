@@ -283,14 +283,18 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, p
     update and the target update.  Second case: the reference's own defaults (50 x 50 x 6 render, batch 128,
     naf_cartpole.py's three networks on trunks of their own).  naf_kw: make_naf's widths and action size; probe: one profiled
     minibatch first, its head path (tests.helpers.naf_path) returned.  grad_rel: the bar of the gradient list (batch-norm networks:
-    tests/test_gpu_batchnorm.py's 5e-5)."""
+    tests/test_gpu_batchnorm.py's 5e-5).  use_dropout=True (naf_kw): the checked replay is training-mode forward number
+    (probe ? 1 : 0) + warm_steps of every network with a hidden stack, and the oracle is handed the masks of that count."""
     import ctypes
     from cartpoleplusplus_amd import _lib
-    from tests.helpers import (device_pool_codes, device_relu_active, naf_path, pool_flips_are_near_ties, relu_flips_are_at_the_boundary)
+    from tests.helpers import (device_pool_codes, device_relu_active, dropout_masks, naf_path, pool_flips_are_near_ties,
+                               relu_flips_are_at_the_boundary)
     oargs = {"learning_rate": 0.01, "momentum": 0.9} if optimiser_args is None else optimiser_args
     agent, _ref, specs = make_naf(shape, B, share, optimiser, oargs, seed=4, replay_size=rows + 50, clip=clip, discount=discount,
                                   target_update_rate=target_update_rate, **naf_kw)
     path = None
+    dropout = bool(naf_kw.get("use_dropout", False))
+    forwards = 0                                                  # training-mode forwards before the one checked (dropout masks)
     try:
         rm = agent.replay_memory
         if fill == "noise":
@@ -300,9 +304,11 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, p
             from tests.helpers import fill_with_rendered_episodes
             fill_with_rendered_episodes(agent, shape, rows, seed=33, blind_camera=(fill == "render-blind"), opts=F.opts)
         if probe:
-            path = naf_path(agent, B, specs[0].hidden, share)
+            path = naf_path(agent, B, specs[0].hidden, share, dropout=dropout)
+            forwards += 1
         for _ in range(warm_steps):
             agent.train_step(B, 1)                                # eager pass + capture (also fills the Momentum slots)
+            forwards += 1
         nets = (agent.value_net, agent.naf.mu_net, agent.naf.l_net, agent.target_value_net)
         P = [n.get_params() for n in nets]
         opt = agent.naf.get_optimiser_state()
@@ -328,6 +334,13 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, p
         ref.v, ref.t = opt["v"].astype(np.float64), int(opt["step"])
         assert ref.t == warm_steps + (1 if probe else 0), (ref.t, warm_steps)
     rnets = [ref.value] if share else [ref.value, ref.mu, ref.l]
+    if dropout:
+        hidden = specs[0].hidden
+        ref.value.drop_masks = dropout_masks("value", hidden, B, forwards)
+        ref.target_value.drop_masks = dropout_masks("target_value", hidden, B, forwards)
+        if not share:
+            ref.mu.drop_masks = dropout_masks("naf/output_action", hidden, B, forwards)
+            ref.l.drop_masks = dropout_masks("naf/l_values", hidden, B, forwards)
     for net, cd, rl in zip(rnets, codes, relu):
         net.amax_override, net.relu_override = cd, rl
     out = ref.forward_backward(batch)

@@ -111,6 +111,31 @@ def test_outer_steps_against_the_float64_restatement(case, targets):
     _compare(cid + "-" + targets, opt, P, got + slots, want, steps * nb)
 
 
+def test_a_held_minibatch_still_draws_masks_and_is_counted():
+    """--use-dropout under --policy-delay 2, four minibatches in one eager call on a 16x16x6 render at B = 6 (applied at 2 and 4, held at
+    1 and 3): the hold reaches the optimiser alone, so minibatch k draws the masks of forward count k in the actor and in the target
+    actor, held or not (include/cartpolepp_abi.h, cpp_net_spec.use_dropout; the restatement's DelayedDDPG._draw_masks).  A device that
+    skipped the count on held minibatches would draw counts 0, 0, 1, 1 in the actor."""
+    from tests.helpers import DROP_B, DROP_PIX, DROP_ROWS, DROP_SEED, LOUD, host_case
+    opt, d, nb = "gradient-descent", 2, 4
+    agent, (_specs, P, _ep, idxs, batches) = _pair_from_host_case(DROP_PIX, DROP_B, nb, DROP_SEED, LOUD, rows=DROP_ROWS, policy_delay=d,
+                                                                  use_dropout=True)
+    try:
+        agent.train_step(DROP_B, nb, idxs=idxs)
+        got, stats = _params(agent), agent.trainer.last_stats()
+        slots, _counts = _state(agent)
+        status = agent.trainer.policy_delay_status()
+    finally:
+        agent.close()
+    specs = host_case(DROP_PIX, DROP_B, nb, DROP_SEED, rows=DROP_ROWS, dropout=True)[0]          # (the same numbers, an actor spec that asks for masks)
+    want, _wc, outs, ref = T3.run_case(specs, P, batches, LOUD, opt, d, nb, 1)
+    assert ref.drop_n == {"actor": nb, "target_actor": nb} and [o["applied"] for o in outs] == [False, True, False, True]
+    na, nc = outs[-1]["actor_norm"], outs[-1]["critic_norm"]
+    assert abs(stats[1] - na) < 1e-4 * max(1.0, na) and abs(stats[2] - nc) < 1e-4 * max(1.0, nc), (stats, na, nc)
+    assert status == (d, nb, False), status
+    _compare("dropout-d2-1x4", opt, P, got + slots, want, nb)
+
+
 # ---- 1b / 4. graph replay on the rows the device draws; the first case is "one graph, a schedule that does not divide it"
 @pytest.mark.parametrize("case", T3.GRAPH_CASES, ids=[c[0] for c in T3.GRAPH_CASES])
 def test_graph_replays_against_the_float64_restatement(case):

@@ -24,7 +24,7 @@ from tests import ddpg_opt_np as R
 from tests import quant_np as W
 from tests import td3_np as T3
 from tests import tps_np as T
-from tests.helpers import FakeEnv, _profiled_calls, assert_flat_close, hyper_options, make_opts
+from tests.helpers import FakeEnv, _profiled_calls, assert_flat_close, hyper_options, make_opts, set_actor_masks
 
 pytestmark = pytest.mark.gpu
 CPP_ERR_ARG, CPP_ERR_STATE = 1, 3          # include/cartpolepp_abi.h
@@ -142,16 +142,37 @@ def _assert_rows(err):
 # ---- 1. one minibatch: the atoms, the sorted and truncated targets, every per-row value, the loss, both gradient sets
 @pytest.mark.parametrize("cid", [c[0] for c in W.CASES])
 def test_one_minibatch_against_the_float64_restatement(cid):
+    _one_minibatch(cid)
+
+
+def test_a_minibatch_with_dropout_against_the_float64_restatement():
+    """--use-dropout under the quantile critic (quant.hip behind the GEMM levels), forward count 1: the actor and the target actor draw masks, the backward takes the GEMM x2 epilogue"""
+    _one_minibatch("A2-B8-N25-d0-sgd", use_dropout=True, warm=1, launches={"quant": 2, "heads": 0, "td": 0})
+
+
+def _one_minibatch(cid, use_dropout=False, warm=0, launches=None):
+    """use_dropout: --use-dropout, the restatement's actor and target actor drawing the masks of forward count `warm` -- `warm` training
+    calls on the same rows run first and the parameters are put back behind them (plain gradient descent only: no slots, no noise count).
+    launches: {kernel family: count} the checked minibatch, profiled, must show."""
     case = W.case_of(cid)
     B, N, drop, opt, d, sm = case[3], case[4], case[5], case[8], case[9], case[10]
-    inputs = W.case_inputs(case)
+    inputs = W.case_inputs(case, **(dict(dropout=True) if use_dropout else {}))
     specs, P, _ep, idxs, batches = inputs
     weighted = "weighted" in cid
-    agent = _case_agent(case, inputs)
+    assert warm == 0 or (opt == "gradient-descent" and sm is None and d == 1 and not weighted and case[13] == 1)
+    agent = _case_agent(case, inputs, **(dict(use_dropout=True) if use_dropout else {}))
     try:
         if weighted:
             _set_priorities(agent)
-        agent.train_step(B, 1, idxs=idxs[:B])
+        for _ in range(warm):
+            agent.train_step(B, 1, idxs=idxs[:B])
+        if warm:
+            for net, p in zip(agent.networks(), P):
+                net.set_params(p)
+        seen = _profiled_calls(agent.actor.ctx, lambda: agent.train_step(B, 1, idxs=idxs[:B])) if launches is not None else \
+            agent.train_step(B, 1, idxs=idxs[:B])
+        if launches is not None:
+            assert {k: seen.get(k, 0) for k in launches} == launches, seen
         dev = tuple(agent.trainer.last_values(B)) + tuple(agent.trainer.last_quantiles(B))
         stats = agent.trainer.last_stats()
         g_a, g_c = agent.actor.get_grads(), agent.critic.get_grads()
@@ -167,6 +188,7 @@ def test_one_minibatch_against_the_float64_restatement(cid):
     finally:
         agent.close()
     ref = W.restatement(specs, P, W.quant_of(case), np.float64, W.hyper_of(case), opt, d, sm)
+    set_actor_masks(ref, B, warm)
     ag = ref.actor_gradients(batches[0][0])
     cg = ref.critic_gradients(batches[0], noise=noise, w=w)
     if weighted:

@@ -22,7 +22,7 @@ from oracle import ddpg_np as O
 from tests import ddpg_opt_np as R
 from tests import td3_np as T3
 from tests import twin_np as W
-from tests.helpers import FakeEnv, _profiled_calls, assert_flat_close, hyper_options, make_opts
+from tests.helpers import FakeEnv, _profiled_calls, assert_flat_close, hyper_options, make_opts, set_actor_masks
 
 pytestmark = pytest.mark.gpu
 CPP_ERR_ARG, CPP_ERR_STATE = 1, 3          # include/cartpolepp_abi.h
@@ -109,16 +109,38 @@ def _set_priorities(agent):
 # ---- 1. one minibatch: every per-row value, the loss, both gradient sets
 @pytest.mark.parametrize("cid", [c[0] for c in W.CASES])
 def test_one_minibatch_against_the_float64_restatement(cid):
+    _one_minibatch(cid)
+
+
+def _one_minibatch(cid, use_dropout=False, actor_hidden=None, warm=0, launches=None):
+    """use_dropout: --use-dropout, the restatement's actor and target actor drawing the masks of forward count `warm` -- `warm` training
+    calls on the same rows run first and the parameters are put back behind them (plain gradient descent only: no slots, no noise count).
+    actor_hidden: --actor-hidden-layers.  launches: {kernel family: count} the checked minibatch, profiled, must show."""
     case = W.case_of(cid)
     _c, shape_name, A, B, opt, d, sm, _clip, _tau = case
-    inputs = W.case_inputs(case)
+    plain_kw, agent_kw = {}, {}
+    if use_dropout:
+        plain_kw, agent_kw = dict(dropout=True, drop_count=warm), dict(use_dropout=True)
+    if actor_hidden is not None:
+        plain_kw["actor_hidden"] = actor_hidden
+        agent_kw["actor_hidden_layers"] = ",".join(str(int(h)) for h in actor_hidden)
+    inputs = W.case_inputs(case, **plain_kw)
     specs, P, _ep, idxs, batches = inputs
     weighted = "weighted" in cid
-    agent = _case_agent(case, inputs)
+    assert warm == 0 or (opt == "gradient-descent" and sm is None and d == 1 and not weighted)
+    agent = _case_agent(case, inputs, **agent_kw)
     try:
         if weighted:
             _set_priorities(agent)
-        agent.train_step(B, 1, idxs=idxs[:B])
+        for _ in range(warm):
+            agent.train_step(B, 1, idxs=idxs[:B])
+        if warm:
+            for net, p in zip(agent.networks(), P):
+                net.set_params(p)
+        seen = _profiled_calls(agent.actor.ctx, lambda: agent.train_step(B, 1, idxs=idxs[:B])) if launches is not None else \
+            agent.train_step(B, 1, idxs=idxs[:B])
+        if launches is not None:
+            assert {k: seen.get(k, 0) for k in launches} == launches, seen
         actions, dq_da, q1, td1 = agent.trainer.last_values(B)
         q2, tq1, tq2, td2 = agent.trainer.last_twin_values(B)
         stats = agent.trainer.last_stats()
@@ -127,6 +149,7 @@ def test_one_minibatch_against_the_float64_restatement(cid):
     finally:
         agent.close()
     ref = W.restatement(specs, P, np.float64, W.hyper_of(case), opt, d, sm)
+    set_actor_masks(ref, B, warm)
     ag = ref.actor_gradients(batches[0][0])
     cg = ref.critic_gradients(batches[0], w=w)
     if weighted:
@@ -159,6 +182,14 @@ def test_one_minibatch_against_the_float64_restatement(cid):
         grads, _ = ref.critic.backward(c, 2.0 * td1.astype(np.float64) * ww / B, 2.0 * td2.astype(np.float64) * ww / B)
         assert_flat_close(W.TwinLayoutSpec(specs[1]), g_c, W.flatten_grads(specs[1], grads, np.float64), rel=2e-5,
                           what="twin critic pre-clip grads vs the restatement's backward pass of the device's TDs", abs_floor=floor)
+
+
+@pytest.mark.parametrize("actor_hidden,launches", [(None, {"heads": 1, "td": 0}), ([100, 100, 65], {"heads": 0, "td": 1})],
+                         ids=["heads_twin-relu_x2", "100-100-65-td_twin_kernel"])
+def test_a_minibatch_with_dropout_against_the_float64_restatement(actor_hidden, launches):
+    """--use-dropout under twin critics, forward count 1: heads_twin.hip's x2 ReLU gradient into the actor's last hidden layer, and one
+    lane past the heads kernel the GEMM x2 epilogue in front of td_twin_kernel; the target actor drops out in both"""
+    _one_minibatch("A2-B8-sgd", use_dropout=True, actor_hidden=actor_hidden, warm=1, launches=launches)
 
 
 # ---- 2. the cases' outer steps: parameters, targets, slots, counts

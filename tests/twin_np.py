@@ -285,14 +285,16 @@ def twin_tail(spec, rng):
     return p, p + rng.normal(0, 0.01, p.shape).astype(np.float32)
 
 
-def host_case(shape, B, nb, seed, rows=24, action_dim=2, batch_norm=False):
-    """tests.helpers.host_case with twin critics: (specs, P, episodes, idxs, batches); P[1] and P[3] carry the twin variables"""
-    from tests.helpers import host_case as plain_case
-    specs, P, episodes, idxs, batches = plain_case(shape, B, nb, seed, rows=rows, action_dim=action_dim, batch_norm=batch_norm)
+def host_case(shape, B, nb, seed, rows=24, action_dim=2, batch_norm=False, drop_count=0, **plain_kw):
+    """tests.helpers.host_case with twin critics: (specs, P, episodes, idxs, batches); P[1] and P[3] carry the twin variables.
+    plain_kw: dropout, actor_hidden (--use-dropout: the bias shift below is taken under the masks of forward count drop_count)"""
+    from tests.helpers import host_case as plain_case, set_actor_masks
+    specs, P, episodes, idxs, batches = plain_case(shape, B, nb, seed, rows=rows, action_dim=action_dim, batch_norm=batch_norm, **plain_kw)
     on, tg = twin_tail(specs[1], np.random.default_rng(5000 + seed))
     P = [P[0], np.concatenate([P[1], on]), P[2], np.concatenate([P[3], tg])]
     ref = TwinDDPG(specs[0], specs[1], P[0], P[1], np.float64)
     ref.set_targets(P[2], P[3])
+    set_actor_masks(ref, B, drop_count)
     s2 = batches[0][4]
     w2 = ref._white(ref.target_actor, s2)
     tq = ref.target_critic.forward(s2, action=ref.target_actor.forward(s2, white=w2)["out"], white=w2)
@@ -330,10 +332,10 @@ def case_of(cid):
     return [c for c in CASES if c[0] == cid][0]
 
 
-def case_inputs(case, nb=NB, seed=None):
+def case_inputs(case, nb=NB, seed=None, **kw):
     cid, shape_name, A, B, _opt, _d, _sm, _clip, _tau = case
     shape = SHAPES[shape_name]
-    return host_case(shape, B, nb, SEEDS[cid] if seed is None else seed, rows=ROWS, action_dim=A)
+    return host_case(shape, B, nb, SEEDS[cid] if seed is None else seed, rows=ROWS, action_dim=A, **kw)
 
 
 def hyper_of(case):
