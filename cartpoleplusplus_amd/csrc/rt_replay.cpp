@@ -688,7 +688,10 @@ int train_entry_checks(const char* who, const cpp_replay* r, int B, int maxB, lo
 // ---------------------------------------------------------------------------------------------
 extern "C" int cpp_replay_set_random_shift(cpp_replay* r, int H, int W, int pad, uint64_t seed) {
   ARG_CHECK(r, "cpp_replay_set_random_shift: NULL argument");
-  ARG_CHECK(r->stats_C > 0, "cpp_replay_set_random_shift: not a pixel memory (cpp_replay_set_stats_channels has not been called with channels > 0)");
+  // (stats_C == 0: cpp_replay_set_stats_channels was never called with channels > 0 -- a low-dimensional memory -- or it turned the
+  // vector path off for this state: the shifted gather moves whole vectors of 8 elements)
+  ARG_CHECK(r->stats_C > 0, "cpp_replay_set_random_shift: states of %ld elements: the random shift needs a pixel state whose element count H x W x "
+            "channels is a multiple of 8 (%ld %% 8 = %ld) and whose channel count cpp_replay_set_stats_channels has accepted", r->elems, r->elems, r->elems % 8);
   ARG_CHECK(H >= 1 && W >= 1 && (double)H * (double)W * (double)r->stats_C == (double)r->elems,
             "cpp_replay_set_random_shift: H %d x W %d x %d channels is not the state's %ld elements", H, W, r->stats_C, r->elems);
   ARG_CHECK(pad >= 0 && pad <= SHIFT_MAX_PAD && pad < (H < W ? H : W), "cpp_replay_set_random_shift: pad %d outside [0,%d] or >= min(H, W) = %d", pad,

@@ -418,7 +418,8 @@ int cpp_replay_get_n_step(cpp_replay* replay, int* n, float* discount);       /*
  *    directly.  n-step: the shift is applied to the state in the slot the walk ends on.  Prioritized replay, batch norm and dropout
  *    are unaffected.  Data-parallel learners: each rank's memory has its own seed and counter; distinct seeds per rank are the
  *    caller's business.
- *  - cpp_replay_set_random_shift returns CPP_ERR_ARG and writes nothing if the memory is not a pixel memory, if H * W * C !=
+ *  - cpp_replay_set_random_shift returns CPP_ERR_ARG and writes nothing if the memory is not a pixel memory or its state_elems is no
+ *    multiple of 8 (the shifted gather moves whole vectors of 8 elements; the message names the element count), if H * W * C !=
  *    state_elems (C: the memory's statistics channels), if pad is outside [0, 16] or >= min(H, W), or if a row holds fewer than 8
  *    elements (W * C < 8).  pad = 0 switches the feature off (the direct path again).  Every effective change re-issues the memory's
  *    graph key: the trainers capture their step graphs again at the next call, none replays the old form. */
