@@ -112,13 +112,12 @@ struct cpp_ctx {
   // caller has synchronised the stream since.  Two runs of the same program take the same routes at the same steps.
   unsigned* white_max_dev; bool conv1_f32; uint64_t kernel_epoch; float route_threshold;
   unsigned long long* route_pin;       // pinned: slot t & 1 = (tag t << 32 | float bits of the largest scale of call t)
-  unsigned long long* route_pin_dev;   // ... its device address: the call's closing soft-update kernel (route_rider) or route_publish_kernel writes it
+  unsigned long long* route_pin_dev;   // ... its device address: the call's closing launch (the optimiser's, or the soft update's: launch_soft_update) or route_publish_kernel writes it
   unsigned* route_tag_dev;             // the number of the call that is running (written in stream order at every training entry point)
   bool route_tag_signal;               // ... by hipStreamWriteValue32 (signal memory) instead of a one-dword fill kernel
   hipEvent_t route_ev[2];              // recorded at the entry of call k (slot k & 1): everything before call k has finished when it fires
   uint64_t route_calls, route_done, route_min_tag;      // calls entered; calls known complete (a stream synchronisation since); tags below are ignored (threshold changed)
   float route_last_max;                // the last scale a decision or cpp_ctx_get_route read
-  bool route_rider;               // set by a step body in front of its target update: that launch also publishes and resets the scale word
   int n_trainers;                 // live cpp_ddpg / cpp_naf objects: their captured graphs pin the precision mode
 };
 #define SQ_REGION 2048
@@ -451,8 +450,9 @@ __host__ __device__ inline float soft_update_value(float t, float s, float coeff
 int launch_sumsq(cpp_ctx* ctx, const OptSegs& s, float grad_scale, double* part, int nparts);
 int launch_opt_apply(cpp_ctx* ctx, const OptSegs& s, float grad_scale, float clip, const double* part,
                      int nparts, float* norms_out);
+// publish_route: the launch closes a training call -- it also publishes the call's largest whitening scale and resets the scale word
 int launch_soft_update(cpp_ctx* ctx, float* t0, const float* s0, long n0, float* t1, const float* s1,
-                       long n1, float coeff);
+                       long n1, float coeff, bool publish_route);
 
 // Target policy smoothing (TD3: Fujimoto et al. 2018, section 5.3; an extension of the target of ddpg_cartpole.py:199-209): the target
 // critic reads a' = clamp(mu'(s2) + clamp(sigma z, -c, c), -1, 1) with z ~ N(0, 1), a fresh draw per row and component in every

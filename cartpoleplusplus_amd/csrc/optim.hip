@@ -306,10 +306,9 @@ __global__ void soft_update_kernel(float* t0, const float* s0, long n0, float* t
 }
 
 int launch_soft_update(cpp_ctx* ctx, float* t0, const float* s0, long n0, float* t1, const float* s1,
-                       long n1, float coeff) {
+                       long n1, float coeff, bool publish_route) {
   prof_begin(ctx);
-  const bool pub = ctx->route_rider && ctx->route_pin_dev != nullptr;
-  ctx->route_rider = false;
+  const bool pub = publish_route && ctx->route_pin_dev != nullptr;
   hipLaunchKernelGGL(soft_update_kernel, dim3(128, t1 ? 2 : 1), dim3(256), 0, ctx->stream, t0, s0, n0,
                      t1, s1, n1, coeff, pub ? ctx->white_max_dev : nullptr, ctx->route_tag_dev, ctx->route_pin_dev);
   LAUNCH_CHECK();

@@ -10,9 +10,11 @@ struct cpp_ddpg {
   int maxB; long nA, nC;
   float* gradbuf; float *dq_da, *td, *dq, *loss_norms /* [0] loss [1] actor norm [2] critic norm */, *ones;
   double* norm_part;
-  double* heads_part;                              // fused heads kernel: per-workgroup partial sums of td^2
-  int heads_grid, heads_B;                         // ... of the last graph built by compute_gradients (0: GEMM levels + td_kernel; a distributional trainer's GEMM levels: dist_td_kernel's grid, its partials live in heads_part too)
-  int loss_parts, loss_B;                          // how cpp_ddpg_last_stats finds the loss of the last call: partials to add, or loss_norms[0]
+  double* heads_part;                              // fused heads kernel: per-workgroup partial sums of td^2 (a distributional trainer: dist_td_kernel's)
+  // how the accessors find what the last gradient pass left: the loss (cpp_ddpg_last_stats: heads_part's partials to add, or
+  // loss_norms[0]) and the rows behind sac_part (cpp_ddpg_last_sac; cpp_ddpg_apply_gradients).  Written by whoever ran the pass; a
+  // replayed graph puts back its own (step_ran)
+  LossAt last;
   // graph replay of the full inner step (the sampler's range is read from the replay's device size word: one graph survives growth)
   StepGraph graph;
   cpp_batch* step_batch;
@@ -20,8 +22,6 @@ struct cpp_ddpg {
   StepGraph rgraph;
   uint64_t graph_gen = 0;    // part of every graph's key: invalidate_graphs() moves it
   uint64_t epoch;            // cpp_ctx::kernel_epoch the cached graphs were captured under (route_check)
-  bool publish_in_apply;     // the next apply() closes a training call: its launch publishes the call's whitening scale
-  bool targets_in_apply, targets_applied;      // ... and an outer step: its launch carries both target updates (step_body)
   DpGraph dgraph;            // the data-parallel step (default mode)
   // graph replay of the data-parallel half step (sample + both gradient sets)
   // three variants: 0 samples its own minibatch; 1 / 2 find it presampled (by the previous call's rider, conv1_dw_gather.hip)
@@ -31,24 +31,18 @@ struct cpp_ddpg {
   struct HalfGraphs { StepGraph g[3][2]; int next[3] = {0, 0, 0}; } hg[2];   // next: variant of the following call
   GraphKey half_key; uint64_t h_write_gen;
   uint64_t dp_local;       // minibatches applied locally since the last parameter averaging (periodic mode)
-  int sq_cnt[2];           // norm partials the last gradient pass left per list in cpp_ctx::sq_part (<= 0: none, run the sumsq kernel)
   int pre_variant;         // variant of the next cpp_ddpg_sample_and_compute call if its key still matches (0: sample)
   int32_t* slot_set[2][2]; // the two sets of slot arrays of step_batch
-  // prioritized replay (step_body, per.hip): the importance weights the gradient pass reads, and the launch that follows the TD values
-  // of the minibatch (its priorities into the tree, the next minibatch's rows and weights)
-  const float* per_w; std::function<int()> per_hook;
   // the update rule of the two 'optimiser' scopes (ddpg_cartpole.py:118-119, :218; cpp_ddpg_set_optimiser).  GradientDescent has no state.
   // Momentum / Adam: slots over gradbuf's layout [actor | critic], and one step count per list on the device (captured graphs replay
   // them): [0] counts the actor's applies, [1] the critic's.
   int opt_kind; float opt_momentum, opt_beta1, opt_beta2, opt_epsilon;
   float *opt_m, *opt_v; uint64_t* opt_step;
-  bool bump_in_heads;      // step_body: the gradient pass in front of an apply() of both lists advances both counts in its heads kernel ...
-  bool step_bumped;        // ... and has (the next apply must not)
   // target policy smoothing (cpp_ddpg_set_target_smoothing; common.h: TpsArgs).  tps_n[0]: the count of target-forming gradient passes (a
   // device word: captured graphs replay it), tps_n[1]: the count the last pass drew at; tps_eps: its clipped noise, maxB x A;
   // tps_act: the smoothed action of the single train op (cpp_ddpg_train_critic), maxB x A
   bool tps_on; float tps_sigma, tps_clip; uint64_t tps_seed; uint64_t* tps_n; float *tps_eps, *tps_act;
-  bool tps_pending;        // a pass has read tps_n[0] and its increment is still owed: the apply() behind it carries it, or tps_settle()
+  // A pass that reads tps_n[0] owes it one increment (PassLeft::noise_owed): the apply() behind it carries it, or tps_settle()
   // delayed policy updates (cpp_ddpg_set_policy_delay; common.h: DdpgHeadsArgs::pd, OptSegs::hold).  pd_d: the delay (1: off, and pd is
   // never passed to a launch); pd: three device words (captured graphs replay them) -- the critic updates applied since the configuring
   // call, whether the last minibatch held the actor, the count modulo pd_d
@@ -67,11 +61,11 @@ struct cpp_ddpg {
   bool quant = false; float quant_kappa = 1.f; int quant_drop = 0;
   // soft actor-critic (cpp_net_create_gaussian: both actors Gaussian with one (lo, hi), or neither; cpp_ddpg_set_sac).  sac_w: the
   // temperature words (common.h: SAC_W_*), sac_step: Adam's count, sac_part: the partials of g_alpha the last actor pass left for a batch
-  // of sac_B rows (0: none yet); [0] / [1]: the draw at state_1 / state_2 -- eps (maxB x A), logp (maxB); sac_rsoft: the soft reward the
-  // TD kernels read where they read the batch's reward.  The noise count is tps_n (smoothing is refused with SAC), its increment tps_pending's.
+  // of last.sac_rows rows (0: none yet); [0] / [1]: the draw at state_1 / state_2 -- eps (maxB x A), logp (maxB); sac_rsoft: the soft reward the
+  // TD kernels read where they read the batch's reward.  The noise count is tps_n (smoothing is refused with SAC), owed as smoothing's is.
   // Target entropy, rate and seed are captured by value.
   bool sac = false; float sac_hbar = 0.f, sac_lr = 0.f; uint64_t sac_seed = 0;
-  float* sac_w = nullptr; uint64_t* sac_step = nullptr; double* sac_part = nullptr; int sac_B = 0;
+  float* sac_w = nullptr; uint64_t* sac_step = nullptr; double* sac_part = nullptr;
   float *sac_eps[2] = {nullptr, nullptr}, *sac_logp[2] = {nullptr, nullptr}, *sac_rsoft = nullptr;
 };
 
@@ -117,7 +111,7 @@ static int sac_configure(cpp_ddpg* d, float init_temperature, float target_entro
   HIP_CHECK(hipMemsetAsync(d->tps_n, 0, 2 * sizeof(uint64_t), ctx->stream));
   RC(sac_sync_target(d));
   HIP_CHECK(ctx_sync_stream(ctx));
-  d->sac_hbar = target_entropy; d->sac_lr = lr; d->sac_seed = seed; d->sac_B = 0; d->tps_pending = false;
+  d->sac_hbar = target_entropy; d->sac_lr = lr; d->sac_seed = seed; d->last.sac_rows = 0;
   reconfigured(d);
   return CPP_OK;
 }
@@ -169,15 +163,13 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   d->nA = actor->nparams; d->nC = critic->nparams;
   d->step_batch = nullptr;
   d->epoch = ctx->kernel_epoch;
-  d->dp_local = 0; d->sq_cnt[0] = d->sq_cnt[1] = 0;
+  d->dp_local = 0;
   d->h_write_gen = 0; d->pre_variant = 0;
   memset(d->slot_set, 0, sizeof(d->slot_set));
-  d->heads_grid = d->heads_B = d->loss_parts = d->loss_B = 0;
-  d->per_w = nullptr;
   d->opt_kind = OPT_SGD; d->opt_momentum = 0.f; d->opt_beta1 = 0.9f; d->opt_beta2 = 0.999f; d->opt_epsilon = 1e-8f;
-  d->opt_m = d->opt_v = nullptr; d->opt_step = nullptr; d->bump_in_heads = d->step_bumped = false;
+  d->opt_m = d->opt_v = nullptr; d->opt_step = nullptr;
   d->pd_d = 1; d->pd = nullptr;
-  d->tps_on = d->tps_pending = false; d->tps_sigma = d->tps_clip = 0.f; d->tps_seed = 0; d->tps_n = nullptr; d->tps_eps = d->tps_act = nullptr;
+  d->tps_on = false; d->tps_sigma = d->tps_clip = 0.f; d->tps_seed = 0; d->tps_n = nullptr; d->tps_eps = d->tps_act = nullptr;
   const int A = actor->spec.action_dim;
   int rc = dalloc(d->arena, &d->gradbuf, (size_t)(d->nA + d->nC));
   if (!rc) rc = dalloc(d->arena, &d->dq_da, (size_t)d->maxB * A);
@@ -229,15 +221,14 @@ static void invalidate_graphs(cpp_ddpg* d) { ++d->graph_gen; }
 // ... which is how every setter ends; a minibatch presampled for the half steps goes with the graphs that would have consumed it
 static void reconfigured(cpp_ddpg* d) { invalidate_graphs(d); d->pre_variant = 0; }
 
-// What a replay must leave on the host as the eager body would have: how cpp_ddpg_last_stats finds the loss, and -- step: the body was
-// step_body -- no presampled minibatch for the half steps (it lived in the step_batch the step has just used).
-static void after_replay(cpp_ddpg* d, bool step) {
-  if (step) d->pre_variant = 0;
-  d->loss_parts = d->heads_grid; d->loss_B = d->heads_B;
-}
-static int step_ran(cpp_ddpg* d, int rc, StepRan how) {
-  if (!rc && how == STEP_REPLAYED) after_replay(d, true);
-  return rc;
+// What a cached step_body leaves on the host: its record for the accessors is kept with the graph it was captured into and put back by
+// a replay of that graph, which -- as the eager body -- also leaves no presampled minibatch for the half steps (it lived in the
+// step_batch the step has just used).
+static int step_ran(cpp_ddpg* d, StepGraph& G, int rc, StepRan how) {
+  if (rc) return rc;
+  if (how == STEP_CAPTURED) G.left = d->last;
+  if (how == STEP_REPLAYED) { d->last = G.left; d->pre_variant = 0; }
+  return CPP_OK;
 }
 
 // Every training entry point starts here: the context may have moved conv1 to the other kernel family since the last call (nearly
@@ -273,11 +264,8 @@ static TpsArgs tps_args(const cpp_ddpg* d) {
 }
 // the increment of a target-forming pass that no apply() follows (cpp_ddpg_compute_gradients, the half steps): a launch of its own
 // behind the pass -- only with smoothing on
-static int tps_settle(cpp_ddpg* d, int rc) {
-  const bool owed = d->tps_pending;
-  d->tps_pending = false;
-  if (rc) return rc;
-  return owed ? launch_counter_add(d->ctx, d->tps_n, 1) : CPP_OK;
+static int tps_settle(cpp_ddpg* d, const PassLeft& left) {
+  return left.noise_owed ? launch_counter_add(d->ctx, d->tps_n, 1) : CPP_OK;
 }
 
 const float* white_of(cpp_batch* b, int which, int C) { return b->white + (long)which * 2 * C; }
@@ -311,7 +299,7 @@ static int critic_head(cpp_net* c, int wi, const float* action, int B) {
 
 // ddpg_cartpole.py:111-113 + :220-222.  critic_prefix_done: the critic prefix for batch.state_1 is
 // already in critic->ws[0] (fused step computes it once for both updates).
-static int actor_gradients(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, bool draw = true) {
+static int actor_gradients(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, PassLeft* left, bool draw = true) {
   cpp_net *a = d->actor, *c = d->critic;
   const int B = b->B, C = a->spec.pixel ? a->spec.C : 0;
   const float* w1 = white_of(b, 0, C);
@@ -344,26 +332,45 @@ static int actor_gradients(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, b
     SacGradArgs sg = sac_grad_args(d, B);
     if (!draw) { sg.part = nullptr; sg.alpha_out = nullptr; }
     RC(launch_sac_actor_grad(d->ctx, sg));
-    if (draw) d->sac_B = B;
   }
   else
   RC(launch_actor_head_grad(d->ctx, a->ws[0].dz[alast], d->dq_da, a->ws[0].out, B * a->spec.action_dim));
   RC(net_backward(a, a->ws[0], B, true, nullptr, b->s[0], b->dtype, w1));
+  if (d->sac && draw) left->loss.sac_rows = B;
   return CPP_OK;
 }
 
+// The critic's loss on the fed and the target evaluation the forward passes left in the first workspaces (ddpg_cartpole.py:210-214):
+// the TD values, the loss (d->heads_part's partials of a distributional trainer, else d->loss_norms[0]) and -- backward -- dz of the q layer
+static int critic_td(cpp_ddpg* d, const cpp_batch* b, int B, bool backward, const float* w) {
+  cpp_net *c = d->critic, *tc = d->tcritic;
+  if (d->dist_n) return dist_td(d, b, B, backward, w);
+  const int last = (int)c->fc.size() - 1;
+  const float* rw = d->sac ? d->sac_rsoft : b->r;      // (r_soft: written by sac.hip's job 2 on the target actor's head)
+  if (d->twin)
+    return launch_td_twin(d->ctx, c->ws[0].out, c->ws[0].out2, tc->ws[0].out, tc->ws[0].out2, rw, b->m, d->hp.discount, B, d->td, d->td2,
+                          backward ? c->ws[0].dz[last] : nullptr, backward ? c->ws[0].dz2[last] : nullptr, d->loss_norms, w);
+  return launch_td(d->ctx, c->ws[0].out, tc->ws[0].out, rw, b->m, d->hp.discount, B, d->td, backward ? c->ws[0].dz[last] : nullptr, d->loss_norms, w);
+}
+// ... and where that leaves the loss
+static LossAt critic_loss_at(const cpp_ddpg* d, int B, bool fused_heads) {
+  LossAt at;
+  at.parts = fused_heads ? (B + 3) / 4 : (d->dist_n ? dist_td_grid(B) : 0); at.B = B;
+  return at;
+}
+
 // ddpg_cartpole.py:199-214
-static int critic_gradients_impl(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, bool backward);
+static int critic_gradients_impl(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, bool backward, PassLeft* left);
 // backward == false is check_loss (ddpg_cartpole.py:239-248), which feeds IS_TRAINING False; the train op (:237) feeds
 // True for the whole graph, target networks included
-static int critic_gradients(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, bool backward) {
+static int critic_gradients(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, bool backward, PassLeft* left) {
   cpp_net* nets[3] = {d->critic, d->tactor, d->tcritic};
   for (cpp_net* n : nets) n->is_training = backward;
-  const int rc = critic_gradients_impl(d, b, critic_prefix_done, backward);
+  const int rc = critic_gradients_impl(d, b, critic_prefix_done, backward, left);
   for (cpp_net* n : nets) n->is_training = true;
   return rc;
 }
-static int critic_gradients_impl(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, bool backward) {
+static int critic_gradients_impl(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, bool backward, PassLeft* left) {
   cpp_net *c = d->critic, *ta = d->tactor, *tc = d->tcritic;
   const int B = b->B, C = c->spec.pixel ? c->spec.C : 0;
   const float *w1 = white_of(b, 0, C), *w2 = white_of(b, 1, C);
@@ -374,60 +381,38 @@ static int critic_gradients_impl(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_d
   if (d->sac) {      // a' and logp' from the target actor's head (the actor's, to the bit); check_loss: eps = 0, nothing drawn
     SacSampleArgs st = sac_sample_args(d, true, backward, b); st.B = B;
     RC(launch_sac_sample(d->ctx, st));
-    if (backward) d->tps_pending = true;
   }
-  const float* rw = d->sac ? d->sac_rsoft : b->r;
   if (backward && d->tps_on) {      // (the train op only: check_loss is an evaluation and draws nothing)
     const int A = ta->spec.action_dim;
     RC(launch_tps_smooth(d->ctx, tps_args(d), tact, A, d->tps_act, A, B, A));
     tact = d->tps_act;
-    d->tps_pending = true;
   }
   RC(critic_head(tc, 0, tact, B));
   if (!critic_prefix_done) RC(critic_prefix(c, b->s[0], b->dtype, w1, B));
   RC(critic_head(c, 0, b->a, B));
-  const int last = (int)c->fc.size() - 1;
-  if (d->dist_n) {
-    RC(dist_td(d, b, B, backward, nullptr));
-    d->loss_parts = dist_td_grid(B); d->loss_B = B;
-    if (backward) RC(net_backward(c, c->ws[0], B, true, nullptr, b->s[0], b->dtype, w1));
-    return CPP_OK;
-  }
-  if (d->twin)
-    RC(launch_td_twin(d->ctx, c->ws[0].out, c->ws[0].out2, tc->ws[0].out, tc->ws[0].out2, rw, b->m, d->hp.discount, B, d->td, d->td2,
-                      backward ? c->ws[0].dz[last] : nullptr, backward ? c->ws[0].dz2[last] : nullptr, d->loss_norms));
-  else
-  RC(launch_td(d->ctx, c->ws[0].out, tc->ws[0].out, rw, b->m, d->hp.discount, B, d->td,
-               backward ? c->ws[0].dz[last] : nullptr, d->loss_norms));
-  d->loss_parts = 0;
+  RC(critic_td(d, b, B, backward, nullptr));
   if (backward) RC(net_backward(c, c->ws[0], B, true, nullptr, b->s[0], b->dtype, w1));
+  left->noise_owed = backward && (d->sac || d->tps_on);      // (the train op only: check_loss is an evaluation and draws nothing)
+  left->loss = critic_loss_at(d, B, false);
   return CPP_OK;
 }
 
-// folded: take the lists' squared norms from the partials the gradient pass left (compute_gradients: sq_scope) instead of running
-// the sumsq kernel -- only for gradients that are applied as computed (both lists, no scaling, nothing in between)
-// nx: the minibatch whose sample pass has already run (rt_internal.h: NextBatch): its whitening tables are computed by this launch's
-// rider instead of a stats_finalize launch behind it
-static int apply(cpp_ddpg* d, bool do_actor, bool do_critic, float grad_scale, uint64_t* bump = nullptr, bool folded = false,
-                 const NextBatch& nx = NextBatch()) {
+// The optimiser's launch of the lists the plan names (rt_internal.h: OptPlan).  folded: only for gradients that are applied as computed
+// (both lists, no scaling, nothing in between); next: that minibatch's whitening tables are computed by this launch's rider instead of
+// a stats_finalize launch behind it.  *targets_left: both target updates left with this launch (the plan closes an outer step).
+static int apply(cpp_ddpg* d, const OptPlan& plan, bool* targets_left = nullptr) {
+  const bool do_actor = plan.actor, do_critic = plan.critic;
+  const float grad_scale = plan.grad_scale;
+  const NextBatch& nx = plan.next;
   OptSegs s; memset(&s, 0, sizeof(s));
-  s.bump = bump;
-  if (d->tps_pending) { s.bump2 = d->tps_n; d->tps_pending = false; }      // (the pass in front read the count; nobody in this launch does)
-  if (d->targets_in_apply && !nx.b && do_actor && do_critic) {      // (the outer step's last launch: both target updates leave with it)
-    s.tgt[0] = d->tactor->params; s.tgt[1] = d->tcritic->params; s.tgt_coeff = d->hp.target_update_rate;
-    d->tactor->wimg_key = nullptr; d->tcritic->wimg_key = nullptr;
-    d->targets_applied = true;
-  }
-  d->targets_in_apply = false;
-  if (d->publish_in_apply && !nx.b && d->ctx->route_pin_dev) {      // (the call's last launch: step_body)
-    s.pub_wmax = d->ctx->white_max_dev; s.pub_tag = d->ctx->route_tag_dev; s.pub_pin = d->ctx->route_pin_dev;
-  }
-  d->publish_in_apply = false;
+  s.bump = plan.bump;
+  if (plan.pass.noise_owed) s.bump2 = d->tps_n;      // (the pass in front read the count; nobody in this launch does)
+  const bool ride = opt_closing_riders(d->ctx, s, plan, {d->tactor, d->tcritic}, d->hp.target_update_rate);
+  if (targets_left) *targets_left = ride;
   opt_next_stats(d->ctx, s, nx);
   d->actor->wimg_key = nullptr; d->critic->wimg_key = nullptr;      // (the parameters change)
   s.nseg = 2; s.kind = d->opt_kind;
-  const bool bumped = d->step_bumped;
-  d->step_bumped = false;
+  const bool bumped = plan.pass.counted;
   // delayed policy updates: the launch in front has counted this minibatch and left the actor's hold word -- the heads kernel of the
   // gradient pass (step_body), or one tick launch here, which then moves the step counts as well.  The critic's half alone counts the
   // minibatch; the actor's half alone looks one ahead (it belongs to the minibatch whose critic half follows) and counts nothing.
@@ -448,11 +433,7 @@ static int apply(cpp_ddpg* d, bool do_actor, bool do_critic, float grad_scale, u
   }
   s.p[0] = d->actor->params; s.g[0] = d->gradbuf; s.n[0] = do_actor ? d->nA : 0; s.lr[0] = d->hp.actor_learning_rate; s.group[0] = 0;
   s.p[1] = d->critic->params; s.g[1] = d->gradbuf + d->nA; s.n[1] = do_critic ? d->nC : 0; s.lr[1] = d->hp.critic_learning_rate; s.group[1] = 1;
-  if (folded && do_actor && do_critic && grad_scale == 1.0f && d->sq_cnt[0] > 0 && d->sq_cnt[1] > 0) {
-    s.sq = d->ctx->sq_part; s.sq_begin[0] = 0; s.sq_begin[1] = SQ_REGION; s.sq_count[0] = d->sq_cnt[0]; s.sq_count[1] = d->sq_cnt[1];
-  } else {
-    RC(launch_sumsq(d->ctx, s, grad_scale, d->norm_part, NORM_PARTS));
-  }
+  RC(opt_norms(d->ctx, s, plan, 2, d->norm_part));
   // conv1's operand images of the next minibatch ride along too (conv_rs16.h; opt_apply_kernel's second rider): both updates are in
   // this launch, the next minibatch's statistics are, conv1 of all four networks will run on that kernel
   cpp_net* inets[4] = {d->actor, d->critic, d->tactor, d->tcritic};
@@ -473,7 +454,8 @@ static int apply(cpp_ddpg* d, bool do_actor, bool do_critic, float grad_scale, u
     }
   }
   // soft actor-critic: the temperature's update leaves with the actor's list, a launch of its own (rate 0: a fixed temperature, none)
-  if (d->sac && do_actor && d->sac_lr > 0.f && d->sac_B > 0) RC(launch_sac_temperature(d->ctx, d->sac_part, d->sac_B, d->sac_lr, d->sac_w, d->sac_step));
+  const int sac_rows = plan.pass.loss.sac_rows;
+  if (d->sac && do_actor && d->sac_lr > 0.f && sac_rows > 0) RC(launch_sac_temperature(d->ctx, d->sac_part, sac_rows, d->sac_lr, d->sac_w, d->sac_step));
   // norms_out[group] is only written for lists that were applied (n > 0)
   RC(launch_opt_apply(d->ctx, s, grad_scale, d->hp.gradient_clip, d->norm_part, NORM_PARTS, d->loss_norms + 1));
   opt_img_built(s, inets, nx);
@@ -491,32 +473,35 @@ extern "C" int cpp_ddpg_train_actor(cpp_ddpg* d, cpp_batch* b) {
   RC(check_batch(d, b, "cpp_ddpg_train_actor"));
   HIP_CHECK(hipSetDevice(d->ctx->device));
   RC(prep_batch(d, b));
-  RC(actor_gradients(d, b, false));
-  RC(apply(d, true, false, 1.0f));
-  return CPP_OK;
+  OptPlan plan; plan.critic = false;
+  RC(actor_gradients(d, b, false, &plan.pass));
+  d->last.sac_rows = plan.pass.loss.sac_rows;
+  return apply(d, plan);
 }
 
 extern "C" int cpp_ddpg_train_critic(cpp_ddpg* d, cpp_batch* b) {
   RC(check_batch(d, b, "cpp_ddpg_train_critic"));
   HIP_CHECK(hipSetDevice(d->ctx->device));
   RC(prep_batch(d, b));
-  const int rc = critic_gradients(d, b, false, true);
-  if (rc) { d->tps_pending = false; return rc; }
-  RC(apply(d, false, true, 1.0f));
-  return CPP_OK;
+  OptPlan plan; plan.actor = false;
+  RC(critic_gradients(d, b, false, true, &plan.pass));
+  d->last.parts = plan.pass.loss.parts; d->last.B = plan.pass.loss.B;
+  return apply(d, plan);
 }
 
 extern "C" int cpp_ddpg_check_loss(cpp_ddpg* d, cpp_batch* b, float* loss, float* td, float* q) {
   RC(check_batch(d, b, "cpp_ddpg_check_loss"));
   HIP_CHECK(hipSetDevice(d->ctx->device));
   RC(prep_batch(d, b));
-  RC(critic_gradients(d, b, false, false));
+  PassLeft left;
+  RC(critic_gradients(d, b, false, false, &left));
+  d->last.parts = left.loss.parts; d->last.B = left.loss.B;      // (the evaluation's loss stands where a train op's would)
   double parts[DDPG_HEADS_MAX_WGS];      // (a distributional trainer: the cross-entropy from its per-workgroup partials, as cpp_ddpg_last_stats)
-  const int nparts = d->dist_n ? d->loss_parts : 0;
+  const int nparts = left.loss.parts;
   const size_t nB = (size_t)b->B * sizeof(float);
   RC(read_back(d->ctx, {{loss && nparts ? parts : nullptr, d->heads_part, (size_t)nparts * sizeof(double)}, {nparts ? nullptr : loss, d->loss_norms, sizeof(float)},
                         {td, d->td, nB}, {q, d->critic->ws[0].out, nB}}));
-  if (loss && nparts) *loss = loss_of_parts(parts, nparts, d->loss_B);
+  if (loss && nparts) *loss = loss_of_parts(parts, nparts, left.loss.B);
   return CPP_OK;
 }
 
@@ -524,7 +509,8 @@ extern "C" int cpp_ddpg_q_gradients_wrt_actions(cpp_ddpg* d, cpp_batch* b, float
   RC(check_batch(d, b, "cpp_ddpg_q_gradients_wrt_actions"));
   HIP_CHECK(hipSetDevice(d->ctx->device));
   RC(prep_batch(d, b));
-  RC(actor_gradients(d, b, false, false));
+  PassLeft left;      // (an evaluation: nothing drawn, nothing left)
+  RC(actor_gradients(d, b, false, &left, false));
   const size_t nB = (size_t)b->B * sizeof(float), nA = nB * d->actor->spec.action_dim;
   return read_back(d->ctx, {{dq_da, d->dq_da, nA}, {actions, d->actor->ws[0].out, nA}, {q, d->critic->ws[1].out, nB}});
 }
@@ -534,7 +520,9 @@ extern "C" int cpp_ddpg_q_gradients_wrt_actions(cpp_ddpg* d, cpp_batch* b, float
 // front of the action splice run once for both uses of critic(s1, .).
 // phase 0: everything.  The data-parallel step can split the pass at the conv backward: phase 1 = everything before it (all
 // gradients of the fully connected layers are then final), phase 2 = the conv backward + the dW reductions.
-static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
+// count_in_heads: the apply() behind this pass takes both lists (step_body) -- the heads kernel, where there is one, advances both step
+// counts and the policy-delay words itself.  per: rt_internal.h, PerPass.  *left: what the pass left, written only when it succeeds.
+static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phase = 0, bool count_in_heads = false, const PerPass& per = PerPass()) {
   cpp_ctx* ctx = d->ctx;
   cpp_net *a = d->actor, *c = d->critic, *ta = d->tactor, *tc = d->tcritic;
   const int B = b->B, A = a->spec.action_dim, C = a->spec.pixel ? a->spec.C : 0;
@@ -548,7 +536,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   OpGraph G;
   // The kernels that write the gradients also leave their share of the two lists' squared norms (cpp_ctx::sq_part): list 0 = actor,
   // list 1 = critic.  Not with batch norm (dbeta comes out of the BN backward kernels) and not for a split pass.
-  SqScope sq_scope(ctx, d->sq_cnt, 2, {0, 1}, phase == 0 && !a->spec.use_batch_norm && !c->spec.use_batch_norm);
+  SqScope sq_scope(ctx, 2, {0, 1}, phase == 0 && !a->spec.use_batch_norm && !c->spec.use_batch_norm);
 
   // ---- forward: the four conv trunks.  conv1 saturates the chip per network; the narrow conv2 / conv3 layers
   // of all four networks share one launch each.
@@ -600,10 +588,10 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     hd.q_out = c->ws[0].out; hd.tq_out = tc->ws[0].out; hd.td = d->td; hd.dzq = c->ws[0].dz[nc - 1];
     hd.dz3 = c->ws[0].dz[cat]; hd.dz2c = c->ws[0].dz[cat - 1];
     hd.loss_part = d->heads_part;
-    hd.w = d->per_w;
-    hd.step_bump = (d->bump_in_heads && d->opt_kind != OPT_SGD && phase == 0) ? (unsigned long long*)d->opt_step : nullptr;
+    hd.w = per.w;
+    hd.step_bump = (count_in_heads && d->opt_kind != OPT_SGD && phase == 0) ? (unsigned long long*)d->opt_step : nullptr;
     hd.tps = tps_args(d);
-    if (d->bump_in_heads && d->pd_d > 1 && phase == 0) { hd.pd = (unsigned long long*)d->pd; hd.pd_d = (unsigned)d->pd_d; }
+    if (count_in_heads && d->pd_d > 1 && phase == 0) { hd.pd = (unsigned long long*)d->pd; hd.pd_d = (unsigned)d->pd_d; }
     if (twin) {      // twin Q heads: head 2's two layers of both critics (nc - cat == 2), its buffers of the first workspace
       const FcL &L3b = c->fc2[cat], &Lqb = c->fc2[nc - 1];
       hd.W3b = c->params + L3b.w_off; hd.W3b_t = tc->params + L3b.w_off; hd.wqb = c->params + Lqb.w_off; hd.wqb_t = tc->params + Lqb.w_off;
@@ -624,9 +612,6 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     }
   }
   const int pre = (fused && hd.n1a > 0) ? 1 : 0;
-  d->step_bumped = fused && (hd.step_bump != nullptr || hd.pd != nullptr);
-  d->heads_grid = fused ? (B + 3) / 4 : (dist ? dist_td_grid(B) : 0); d->heads_B = B;
-  d->loss_parts = d->heads_grid; d->loss_B = B;
   int adz, cdz;
   if (fused) {
     int aF = tA, taF = tTA;
@@ -644,7 +629,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
       tcP = G.gemm(fc_fwd_args(tc, tc->ws[0], l, B), {tcP});
     }
     const int hk = G.fn([=] { return launch_ddpg_heads(ctx, hd); }, {aF, taF, cP, tcP});
-    if (d->per_hook) G.fn(d->per_hook, {hk});      // (prioritized replay: as soon as the TD values are known)
+    if (per.hook) G.fn(per.hook, {hk});      // (prioritized replay: as soon as the TD values are known)
     // ---- actor backward below its head (the head's dX is part of the fused kernel)
     G.gemm(sq_gemm(ctx, 0, fc_dw_args(a, a->ws[0], na - 1, B, a->ws[0].dz[na - 1])), {hk});
     adz = add_fc_backward(G, a, a->ws[0], B, na - 2, hk, 0, pre ? na - 2 : -1);      // (pre: dz[na - 3] came out of the heads kernel)
@@ -727,7 +712,6 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     if (sac) {      // job 3: the (B, 2A) head gradient and the temperature gradient's partials
       const SacGradArgs sg = sac_grad_args(d, B);
       adz = G.fn([=] { return launch_sac_actor_grad(ctx, sg); }, {adz});
-      d->sac_B = B;
     }
   }
 
@@ -735,17 +719,9 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
   adz = add_fc_backward(G, a, a->ws[0], B, na - 1, adz, 0);
 
   // ---- TD target + critic backward on the first evaluation (fed actions)
-  const float* per_w = d->per_w;
-  const float* rw = sac ? d->sac_rsoft : b->r;      // (r_soft: written by job 2, which tcH follows)
-  if (dist)
-    cdz = G.fn([=] { return dist_td(d, b, B, true, per_w); }, {c0, tcH});
-  else if (twin)
-    cdz = G.fn([=] { return launch_td_twin(ctx, c->ws[0].out, c->ws[0].out2, tc->ws[0].out, tc->ws[0].out2, rw, b->m, d->hp.discount, B, d->td, d->td2,
-                                           c->ws[0].dz[nc - 1], c->ws[0].dz2[nc - 1], d->loss_norms, per_w); }, {c0, tcH, c0b, tcHb});
-  else
-  cdz = G.fn([=] { return launch_td(ctx, c->ws[0].out, tc->ws[0].out, rw, b->m, d->hp.discount, B, d->td,
-                                        c->ws[0].dz[nc - 1], d->loss_norms, per_w); }, {c0, tcH});
-  if (d->per_hook) G.fn(d->per_hook, {cdz});
+  const float* per_w = per.w;
+  cdz = G.fn([=] { return critic_td(d, b, B, true, per_w); }, {c0, tcH, c0b, tcHb});      // (twin: both heads of both critics; r_soft: job 2's, which tcH follows)
+  if (per.hook) G.fn(per.hook, {cdz});
   int cdz2 = cdz;      // head 2's chain down to the concat layer, level by level beside head 1's
   for (int l = nc - 1; l >= 0; --l) {
     const FcL& L = c->fc[l];
@@ -771,21 +747,29 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, int phase = 0) {
     conv_bwd = G.fn([=] { return nets_backward_conv(ctx, bn, 2, B, s1, dt, w1); }, {adz, cdz});
   }
   DwPendingGuard pending(ctx);      // (a failure below drops what was queued)
-  if ((d->tps_on || sac) && phase != 2) d->tps_pending = true;      // (this pass reads the count: exactly one increment follows it)
   if (phase == 2) {
     if (conv_bwd >= 0) RC(G.ops[conv_bwd].fn());
-    return flush_dw_reduce(ctx);
+  } else {
+    RC(G.run(ctx, phase == 1 ? conv_bwd : -1));
   }
-  RC(G.run(ctx, phase == 1 ? conv_bwd : -1));
-  if (phase == 1) { pending.keep(); return CPP_OK; }
-  return flush_dw_reduce(ctx);      // all six dW reductions (3 layers x 2 networks) in one launch
+  if (phase == 1) pending.keep();
+  else RC(flush_dw_reduce(ctx));      // all six dW reductions (3 layers x 2 networks) in one launch
+  left->counted = fused && (hd.step_bump != nullptr || hd.pd != nullptr);
+  left->noise_owed = (d->tps_on || sac) && phase != 2;      // (this pass read the count: exactly one increment follows it)
+  sq_scope.left(left->sq_cnt);
+  left->loss = critic_loss_at(d, B, fused);
+  if (sac) left->loss.sac_rows = B;
+  return CPP_OK;
 }
 
 extern "C" int cpp_ddpg_compute_gradients(cpp_ddpg* d, cpp_batch* b) {
   RC(check_batch(d, b, "cpp_ddpg_compute_gradients"));
   HIP_CHECK(hipSetDevice(d->ctx->device));
   RC(prep_batch(d, b));
-  return tps_settle(d, compute_gradients(d, b));
+  PassLeft left;
+  RC(compute_gradients(d, b, &left));
+  d->last = left.loss;
+  return tps_settle(d, left);
 }
 
 extern "C" int cpp_ddpg_grad_buffer(cpp_ddpg* d, void** p, int64_t* n) {
@@ -797,7 +781,9 @@ extern "C" int cpp_ddpg_grad_buffer(cpp_ddpg* d, void** p, int64_t* n) {
 extern "C" int cpp_ddpg_apply_gradients(cpp_ddpg* d, float grad_scale) {
   ARG_CHECK(d, "cpp_ddpg_apply_gradients: NULL argument");
   HIP_CHECK(hipSetDevice(d->ctx->device));
-  return apply(d, true, true, grad_scale);
+  OptPlan plan; plan.grad_scale = grad_scale;
+  plan.pass.loss.sac_rows = d->last.sac_rows;      // (the temperature's gradient of the pass cpp_ddpg_compute_gradients ran)
+  return apply(d, plan);
 }
 
 // ddpg_cartpole.py:118-119 and :218 build the two train ops with tf.train.GradientDescentOptimizer; util.py:73-76 is the reference's
@@ -821,7 +807,6 @@ extern "C" int cpp_ddpg_set_optimiser(cpp_ddpg* d, int kind, float momentum, flo
   if (d->opt_step) HIP_CHECK(hipMemsetAsync(d->opt_step, 0, 2 * sizeof(uint64_t), ctx->stream));
   HIP_CHECK(ctx_sync_stream(ctx));
   d->opt_kind = kind; d->opt_momentum = momentum; d->opt_beta1 = beta1; d->opt_beta2 = beta2; d->opt_epsilon = epsilon;
-  d->step_bumped = false;
   reconfigured(d);      // (the captured launches carry the old rule)
   return CPP_OK;
 }
@@ -846,7 +831,7 @@ extern "C" int cpp_ddpg_set_target_smoothing(cpp_ddpg* d, float sigma, float cli
   if (d->tps_n) HIP_CHECK(hipMemsetAsync(d->tps_n, 0, 2 * sizeof(uint64_t), ctx->stream));
   if (d->tps_eps) HIP_CHECK(hipMemsetAsync(d->tps_eps, 0, n * sizeof(float), ctx->stream));
   HIP_CHECK(ctx_sync_stream(ctx));
-  d->tps_on = sigma > 0.f; d->tps_sigma = sigma; d->tps_clip = clip; d->tps_seed = seed; d->tps_pending = false;
+  d->tps_on = sigma > 0.f; d->tps_sigma = sigma; d->tps_clip = clip; d->tps_seed = seed;
   reconfigured(d);      // (the captured launches carry the old values, or none)
   return CPP_OK;
 }
@@ -864,7 +849,6 @@ extern "C" int cpp_ddpg_set_policy_delay(cpp_ddpg* d, int delay) {
   if (d->pd) HIP_CHECK(hipMemsetAsync(d->pd, 0, PD_WORDS * sizeof(uint64_t), ctx->stream));
   HIP_CHECK(ctx_sync_stream(ctx));
   d->pd_d = delay;
-  d->step_bumped = false;
   reconfigured(d);      // (the captured launches carry the old delay, or none)
   return CPP_OK;
 }
@@ -916,12 +900,16 @@ extern "C" int cpp_ddpg_set_opt_state(cpp_ddpg* d, const float* m, const float* 
   return CPP_OK;
 }
 
-extern "C" int cpp_ddpg_update_targets(cpp_ddpg* d) {
-  ARG_CHECK(d, "cpp_ddpg_update_targets: NULL argument");
+// publish_route: the launch closes a training call -- it also publishes the call's largest whitening scale and resets the scale word
+static int soft_update_targets(cpp_ddpg* d, bool publish_route) {
   HIP_CHECK(hipSetDevice(d->ctx->device));
   d->tactor->wimg_key = nullptr; d->tcritic->wimg_key = nullptr;
   return launch_soft_update(d->ctx, d->tactor->params, d->actor->params, d->nA, d->tcritic->params, d->critic->params,
-                            d->nC, d->hp.target_update_rate);
+                            d->nC, d->hp.target_update_rate, publish_route);
+}
+extern "C" int cpp_ddpg_update_targets(cpp_ddpg* d) {
+  ARG_CHECK(d, "cpp_ddpg_update_targets: NULL argument");
+  return soft_update_targets(d, false);
 }
 
 // The fused step does not need a gathered copy of the minibatch when conv1 runs on the f16-pipe kernels: they take the
@@ -948,27 +936,27 @@ static int step_body(cpp_ddpg* d, cpp_replay* r, int B, int n_batches, const int
   cpp_ctx* ctx = d->ctx;
   MinibatchLoop L;
   L.ctx = ctx; L.r = r; L.step_batch = d->step_batch; L.trunk = d->actor;
-  L.per_w = &d->per_w; L.per_hook = &d->per_hook; L.td = d->td; L.stats_switch = true;
-  L.gradients = [=] {
-    d->bump_in_heads = true;      // (the apply() behind it takes both lists)
-    const int rc = compute_gradients(d, d->step_batch);
-    d->bump_in_heads = false;
-    if (rc) { d->step_bumped = false; d->tps_pending = false; }
-    return rc;
+  L.td = d->td; L.stats_switch = true;
+  L.gradients = [=](const PerPass& per, PassLeft* left) {
+    RC(compute_gradients(d, d->step_batch, left, 0, true, per));      // (the apply() behind it takes both lists)
+    d->last = left->loss;
+    return (int)CPP_OK;
   };
-  L.apply = [=](bool more, const NextBatch& next) {
+  bool targets_left = false;
+  L.apply = [=, &targets_left](bool more, const NextBatch& next, const PassLeft& left) {
     // (dp: the norm is the reduced gradient's -- the partials the gradient kernels folded in are this rank's only: sumsq runs)
     if (dp) RC(step_allreduce(ctx, comm, d->gradbuf, (size_t)(d->nA + d->nC)));
     static const bool no_tgt_ride = cpp_switch_off("CPP_RIDE_TARGETS");
-    d->targets_applied = false;
-    d->targets_in_apply = !more && targets && !dp && !no_tgt_ride;      // (the last minibatch of an outer step: the target updates ride in its optimiser launch)
-    d->publish_in_apply = !more && (!targets || d->targets_in_apply);   // (... which then closes the call)
-    return apply(d, true, true, (dp && comm) ? 1.0f / (float)comm->world : 1.0f, rows_dev ? nullptr : r->counter, !dp, next);
+    OptPlan plan;
+    plan.grad_scale = (dp && comm) ? 1.0f / (float)comm->world : 1.0f; plan.bump = rows_dev ? nullptr : r->counter; plan.folded = !dp;
+    plan.next = next; plan.pass = left;
+    plan.closes_step = !more && targets && !dp && !no_tgt_ride;      // (the last minibatch of an outer step: the target updates ride in its optimiser launch)
+    plan.closes_call = !more && (!targets || plan.closes_step);      // (... which then closes the call)
+    return apply(d, plan, &targets_left);
   };
   RC(run_minibatches(L, B, n_batches, rows_dev, seed));
-  if (targets && d->targets_applied) { d->targets_applied = false; return CPP_OK; }      // (both target updates and the route's publish left with the optimiser's launch)
-  if (targets) { ctx->route_rider = true; return cpp_ddpg_update_targets(d); }      // (the largest whitening scale of this step rides to the host in that launch)
-  return CPP_OK;      // (... or has left with the last minibatch's optimiser launch)
+  if (!targets || targets_left) return CPP_OK;      // (both target updates and the route's publish left with the optimiser's launch)
+  return soft_update_targets(d, true);      // (the largest whitening scale of this step rides to the host in that launch)
 }
 
 // ddpg_cartpole.py:332-334 for ONE minibatch whose rows the HOST drew (replay_memory.random_indexes: numpy's RNG, :123-129):
@@ -988,7 +976,7 @@ extern "C" int cpp_ddpg_train_rows(cpp_ddpg* d, cpp_replay* r, int B, const int3
   static const bool no_graph = cpp_switch_set("CPP_NO_GRAPH");
   StepRan how;
   const int rc = run_step_graph(ctx, d->rgraph, GraphKey{B, 1, 0, r->uid, 0, d->graph_gen}, [&] { return step_body(d, r, B, 1, r->rows_in, 0, false); }, &how, no_graph);
-  return step_ran(d, rc, how);
+  return step_ran(d, d->rgraph, rc, how);
 }
 
 extern "C" int cpp_ddpg_train_step(cpp_ddpg* d, cpp_replay* r, int B, int n_batches, const int32_t* idxs, uint64_t seed) {
@@ -1005,7 +993,7 @@ extern "C" int cpp_ddpg_train_step(cpp_ddpg* d, cpp_replay* r, int B, int n_batc
   static const bool no_graph = cpp_switch_set("CPP_NO_GRAPH");   // plain in-order stream launches (A/B measurements)
   StepRan how;
   const int rc = run_step_graph(ctx, d->graph, GraphKey{B, n_batches, seed, r->uid, 0, d->graph_gen}, [&] { return step_body(d, r, B, n_batches, nullptr, seed); }, &how, no_graph);
-  return step_ran(d, rc, how);
+  return step_ran(d, d->graph, rc, how);
 }
 
 // variant 0: sample + gather + statistics of this call's minibatch; 1 / 2: it was presampled by the previous call's rider into
@@ -1029,16 +1017,19 @@ static int half_step_body(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed, int 
     RC(replay_sample_finish(r, B, Cg, C, b, r->counter, &bumped));
     if (!bumped) RC(launch_counter_add(ctx, r->counter, 1));
   }
-  if (phase == 1) return tps_settle(d, compute_gradients(d, b, 1));
+  PassLeft left;
+  if (phase == 1) { RC(compute_gradients(d, b, &left, 1)); d->last = left.loss; return tps_settle(d, left); }
   const bool ride_ok = !no_ride && direct && Cg > 0 && r->store_dtype == CPP_F16;
   int rc;
   {
     RideScope ride(ctx);
     if (ride_ok) ride.arm(&ga, b, r->store_dtype, true, true);
-    rc = tps_settle(d, compute_gradients(d, b, phase));      // (phase 2 reads no count and owes nothing)
+    rc = compute_gradients(d, b, &left, phase);
     *next = ride.rode() ? (cur == 0 ? 1 : 2) : 0;
   }
   if (rc) return rc;
+  d->last = left.loss;
+  RC(tps_settle(d, left));      // (phase 2 reads no count and owes nothing)
   return ctx_route_publish(ctx);
 }
 
@@ -1072,6 +1063,7 @@ static int half_step(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed, bool spli
   auto capture = [&](int variant, int* nx) -> int {
     for (int k = 0; k < parts; ++k)
       RC(H.g[variant][k].capture(ctx, key, [&] { return half_step_body(d, r, B, seed, variant, nx, split ? k + 1 : 0); }));
+    H.g[variant][parts - 1].left = d->last;      // (the record of the body just captured: its replays put it back)
     return CPP_OK;
   };
   int next = 0;
@@ -1098,7 +1090,7 @@ static int half_step(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed, bool spli
     if (between) RC(between());
     RC(H.g[v][1].launch(ctx));
   }
-  after_replay(d, false);
+  d->last = H.g[v][parts - 1].left;
   d->pre_variant = H.next[v];
   return CPP_OK;
 }
@@ -1186,12 +1178,12 @@ extern "C" int cpp_ddpg_dp_train_step(cpp_ddpg* d, cpp_replay* r, cpp_comm* c, i
     StepRan how;
     const int rc = run_dp_graph(ctx, d->dgraph, GraphKey{B, n_batches, seed, r->uid, c ? c->uid : 0, d->graph_gen}, "DDPG",
                                 [&] { return step_body(d, r, B, n_batches, nullptr, seed, true, true, c); }, &how);
-    return step_ran(d, rc, how);
+    return step_ran(d, d->dgraph.graph, rc, how);
   }
   for (int i = 0; i < n_batches; ++i) {
     if (sync_every > 1) {                           // local update; every k-th one is followed by the parameter averaging
       RC(half_step(d, r, B, seed, false, nullptr));
-      RC(apply(d, true, true, 1.0f));
+      RC(apply(d, OptPlan()));
       if (++d->dp_local >= (uint64_t)sync_every && c) RC(cpp_ddpg_average_params(d, c));
       continue;
     }
@@ -1218,7 +1210,8 @@ extern "C" int cpp_ddpg_dp_train_step(cpp_ddpg* d, cpp_replay* r, cpp_comm* c, i
       RC(half_step(d, r, B, seed, false, nullptr));
       if (c) RC(cpp_ddpg_allreduce_grads(d, c));
     }
-    RC(apply(d, true, true, inv));
+    OptPlan plan; plan.grad_scale = inv;
+    RC(apply(d, plan));
   }
   return cpp_ddpg_update_targets(d);
 }
@@ -1235,8 +1228,9 @@ extern "C" int cpp_ddpg_dp_status(const cpp_ddpg* d, int* mode, char* reason, in
 extern "C" int cpp_ddpg_last_stats(cpp_ddpg* d, float out[3]) {
   ARG_CHECK(d && out, "cpp_ddpg_last_stats: NULL argument");
   double parts[DDPG_HEADS_MAX_WGS];
-  RC(read_back(d->ctx, {{out, d->loss_norms, 3 * sizeof(float)}, {d->loss_parts > 0 ? parts : nullptr, d->heads_part, (size_t)d->loss_parts * sizeof(double)}}, true));
-  if (d->loss_parts > 0) out[0] = loss_of_parts(parts, d->loss_parts, d->loss_B);      // fused heads kernel: mean(td^2); dist.hip: mean(w L)
+  const LossAt& at = d->last;
+  RC(read_back(d->ctx, {{out, d->loss_norms, 3 * sizeof(float)}, {at.parts > 0 ? parts : nullptr, d->heads_part, (size_t)at.parts * sizeof(double)}}, true));
+  if (at.parts > 0) out[0] = loss_of_parts(parts, at.parts, at.B);      // fused heads kernel: mean(td^2); dist.hip: mean(w L)
   return CPP_OK;
 }
 
@@ -1322,7 +1316,7 @@ extern "C" int cpp_ddpg_last_sac(cpp_ddpg* d, int B, float* eps, float* a, float
   HIP_CHECK(hipSetDevice(d->ctx->device));
   const size_t nA = (size_t)B * d->actor->spec.action_dim * sizeof(float), nB = (size_t)B * sizeof(float);
   double parts[DDPG_HEADS_MAX_WGS];
-  const int np = d->sac_B > 0 ? sac_grid(d->sac_B) : 0;
+  const int rows = d->last.sac_rows, np = rows > 0 ? sac_grid(rows) : 0;
   RC(read_back(d->ctx, {{eps, d->sac_eps[0], nA}, {a, d->actor->ws[0].out, nA}, {logp, d->sac_logp[0], nB},
                         {eps2, d->sac_eps[1], nA}, {a2, d->tactor->ws[0].out, nA}, {logp2, d->sac_logp[1], nB}, {r_soft, d->sac_rsoft, nB},
                         {dz, d->actor->ws[0].dz[d->actor->fc.size() - 1], 2 * nA}, {alpha, d->sac_w + SAC_W_ALPHA, sizeof(float)},
@@ -1330,7 +1324,7 @@ extern "C" int cpp_ddpg_last_sac(cpp_ddpg* d, int B, float* eps, float* a, float
   if (g_alpha) {      // (the fixed-order finalisation of sac.hip's job 4)
     double s = 0.0;
     for (int i = 0; i < np; ++i) s += parts[i];
-    *g_alpha = np ? (float)(-(s / (double)d->sac_B)) : 0.f;
+    *g_alpha = np ? (float)(-(s / (double)rows)) : 0.f;
   }
   return CPP_OK;
 }

@@ -234,8 +234,12 @@ struct GraphKey {
   }
 };
 enum StepRan { STEP_EAGER, STEP_CAPTURED, STEP_REPLAYED, STEP_CAPTURE_FAILED };
+// Where a gradient pass left the minibatch's loss for the accessors that read it later: `parts` per-workgroup partials to add and divide
+// by B (0: the loss word itself); sac_rows: the rows behind the partials of the temperature's gradient (0: none)
+struct LossAt { int parts = 0, B = 0, sac_rows = 0; };
 struct StepGraph {
   hipGraph_t g = nullptr; hipGraphExec_t e = nullptr; bool ok = false; GraphKey key;
+  LossAt left;      // what the captured body left for the owner's accessors: kept at the capture, put back behind every launch of THIS graph
   StepGraph() = default;
   StepGraph(const StepGraph&) = delete;
   StepGraph& operator=(const StepGraph&) = delete;
@@ -360,21 +364,22 @@ struct cpp_comm {
 // What the DDPG and the NAF learner share of a training call (definitions: rt_step.cpp; add_fc_backward: rt_net.cpp)
 // ---------------------------------------------------------------------------------------------
 // The squared norms of `lists` gradient lists (1 or 2), folded into the kernels that write the gradients (cpp_ctx::sq_part) while the
-// scope lives; groups: the list of each network of the conv backward.  cnt[l]: the partials the pass left for list l -- for every list,
-// or for none (a list whose region overflowed: the sumsq kernel runs).  on == false: the counts are zeroed, nothing is folded.
+// scope lives; groups: the list of each network of the conv backward.  left(cnt), once the pass has run: the partials it left for list
+// l -- for every list, or for none (a list whose region overflowed: the sumsq kernel runs).  on == false: nothing is folded, none are left.
 struct SqScope {
-  cpp_ctx* c; int* cnt; int lists;
-  SqScope(cpp_ctx* c_, int* cnt_, int lists_, std::initializer_list<int> groups, bool on) : c(c_), cnt(cnt_), lists(lists_) {
-    for (int l = 0; l < lists; ++l) cnt[l] = 0;
+  cpp_ctx* c; int lists;
+  SqScope(cpp_ctx* c_, int lists_, std::initializer_list<int> groups, bool on) : c(c_), lists(lists_) {
     if (!on) return;
     for (int l = 0; l < 2; ++l) c->sq_n[l] = l < lists ? 0 : -1;
     int k = 0;
     for (int g : groups) c->sq_conv_group[k++] = g;
   }
-  ~SqScope() {
+  void left(int* cnt) const {
     bool all = true;
     for (int l = 0; l < lists; ++l) all = all && c->sq_n[l] > 0;
-    for (int l = 0; l < lists && all; ++l) cnt[l] = c->sq_n[l];
+    for (int l = 0; l < lists; ++l) cnt[l] = all ? c->sq_n[l] : 0;
+  }
+  ~SqScope() {
     c->sq_n[0] = c->sq_n[1] = -1;
     for (int& g : c->sq_conv_group) g = -1;
   }
@@ -390,12 +395,32 @@ struct SlotScope {
   }
   ~SlotScope() { for (int k = 0; k < nn; ++k) n[k]->img_slot = nullptr; }
 };
-// the prioritized-replay state of one gradient pass or step (the weights the pass reads, the launch behind its TD values), cleared on
-// every way out
-struct PerScope {
-  const float** w; std::function<int()>* hook;
-  PerScope(const float** w_, std::function<int()>* hook_, const cpp_replay* r) : w(w_), hook(hook_) { *w = r->per_tree ? r->per_w : nullptr; }
-  ~PerScope() { *w = nullptr; *hook = nullptr; }
+// The minibatch whose sample pass has already run when the optimiser's launch of the one before it leaves: b->part holds its per-row
+// statistics (B rows, C channels, `elems` values per state); tables_done: the dW reductions' launch has finished its whitening tables.
+// b == nullptr: none.
+struct NextBatch { const cpp_batch* b = nullptr; int B = 0, C = 0; long elems = 0; bool tables_done = false; };
+// What prioritized replay hands a gradient pass: the importance weights its loss reads, and the launch the pass places behind the TD
+// values of its minibatch (priorities into the tree, the next minibatch's rows and weights).  Default: a uniform memory, neither.
+struct PerPass { const float* w = nullptr; std::function<int()> hook; };
+// What a gradient pass that succeeded left on the host for the optimiser's launch behind it.  Default: nothing (no pass in this call,
+// or one inside a replayed graph: the launches that settle it are in that graph too).
+struct PassLeft {
+  bool counted = false;         // its heads kernel advanced the optimiser's step counts / the policy-delay words (the launch behind must not)
+  bool noise_owed = false;      // it read the noise count: exactly one increment follows it
+  int sq_cnt[2] = {0, 0};       // squared-norm partials folded per list into cpp_ctx::sq_part (0: none, the sumsq kernel runs)
+  LossAt loss;
+};
+// One optimiser launch, as its caller wants it
+struct OptPlan {
+  bool actor = true, critic = true;      // DDPG: the lists to apply
+  bool unless_nonfinite = false;         // NAF: the update stands down while the check_numerics flag is set
+  float grad_scale = 1.0f;
+  uint64_t* bump = nullptr;              // the replay sampler's counter, advanced by this launch
+  bool folded = false;                   // take the norms from pass.sq_cnt's partials -- gradients applied as computed only (opt_norms)
+  NextBatch next;                        // the minibatch whose sample pass has already run
+  bool closes_step = false;              // the last launch of an outer step: the target updates ride in it
+  bool closes_call = false;              // ... of the training call: the route's publish rides in it
+  PassLeft pass;                         // what the gradient pass in front left
 };
 // The next minibatch's sample pass as a rider of this gradient pass (cpp_ctx::ride: conv1's dW when at_dw, else the dW reductions), and
 // its whitening tables as a rider of the dW reductions (cpp_ctx::st_ride).  Both point into the caller's frame: disarmed on every way out.
@@ -412,12 +437,13 @@ struct RideScope {
   bool tables_done() const { return c->st_ride != nullptr && c->st_ride_done && rode(); }
 };
 
-// The minibatch whose sample pass has already run when the optimiser's launch of the one before it leaves: b->part holds its per-row
-// statistics (B rows, C channels, `elems` values per state); tables_done: the dW reductions' launch has finished its whitening tables.
-// b == nullptr: none.
-struct NextBatch { const cpp_batch* b = nullptr; int B = 0, C = 0; long elems = 0; bool tables_done = false; };
 StatsRide next_stats_ride(cpp_ctx* ctx, const NextBatch& nx);              // its tables as the dW reductions' rider
 void opt_next_stats(cpp_ctx* ctx, OptSegs& s, const NextBatch& nx);        // ... or as the optimiser launch's (unless they are done)
+// What closes an outer step or a call rides in the optimiser's last launch of it (no next minibatch, every list applied): the soft
+// update of `targets` (OptSegs::tgt, one per segment in order) and the route's publish (OptSegs::pub_*).  true: the target updates ride.
+bool opt_closing_riders(cpp_ctx* ctx, OptSegs& s, const OptPlan& p, std::initializer_list<cpp_net*> targets, float coeff);
+// the squared norms of the `lists` gradient lists: the partials the pass folded (list l's region of cpp_ctx::sq_part), or the sumsq kernel
+int opt_norms(cpp_ctx* ctx, OptSegs& s, const OptPlan& p, int lists, double* norm_part);
 // conv1's operand image of the next minibatch as a rider of the optimiser's launch: record j is network n's on state column col.
 // seg >= 0: n is the network of segment seg, whose leading conv1 parameters the image workgroup updates itself (gradient pointers; the
 // learner adds its optimiser's slots); seg < 0: a target network.  conv1_opens_params: the layout the rider's update assumes.
@@ -429,14 +455,13 @@ void opt_img_built(const OptSegs& s, cpp_net* const* nets, const NextBatch& nx);
 struct MinibatchLoop {
   cpp_ctx* ctx; cpp_replay* r; cpp_batch* step_batch;
   cpp_net* trunk;                         // the network whose conv1 decides the form of the minibatch (direct_replay_ok) and its channels
-  const float** per_w; std::function<int()>* per_hook;      // where the learner keeps them (PerScope)
   const float* td;                        // the TD values the priorities are written from
   const int* skip_if_set = nullptr;       // prioritized memory: the priority writes stand down while this flag is set
   bool draws_bump = false;                // prioritized memory: the draws advance the sampler's counter themselves (else: the optimiser's launch)
   bool ride_ok = true;                    // the learner's own condition on the sample rider
   bool stats_switch = false;              // CPP_RIDE_STATS=0 also keeps the tables out of the optimiser's launch
-  std::function<int()> gradients;         // the gradient pass on step_batch
-  std::function<int(bool more, const NextBatch& next)> apply;      // the all-reduce if any, then the optimiser's launch
+  std::function<int(const PerPass& per, PassLeft* left)> gradients;      // the gradient pass on step_batch
+  std::function<int(bool more, const NextBatch& next, const PassLeft& left)> apply;      // the all-reduce if any, then the optimiser's launch
 };
 int run_minibatches(const MinibatchLoop& L, int B, int n_batches, const int32_t* rows_dev, uint64_t seed);
 int step_allreduce(cpp_ctx* ctx, cpp_comm* comm, float* grads, size_t n);      // in place, on the context's stream (inside a captured step)

@@ -12,8 +12,6 @@ struct cpp_naf {
   float *adv, *q, *td, *stats;            // stats: [0] loss [1] norm
   int* nonfinite; uint64_t* opt_step; double* norm_part;
   double* heads_part; unsigned* heads_ticket;      // fused heads kernel (naf_heads_kernel): per-workgroup td^2 sums + bad flags, arrival counter
-  int sq_cnt;              // norm partials the last folded gradient pass left in cpp_ctx::sq_part (<= 0: none, run the sumsq kernel)
-  bool step_bumped;        // the last gradient pass advanced opt_step in its heads kernel (the next apply must not)
   StepGraph graph;           // the full inner step (cpp_naf_train_step)
   StepGraph hgraph;          // the data-parallel half step (sample + gradients) as a graph of its own
   StepGraph rgraph;          // ONE minibatch on host-drawn rows up to (not including) the optimiser (cpp_naf_train_rows)
@@ -21,13 +19,9 @@ struct cpp_naf {
   StepGraph agraph;          // ... and including it, the loss coming back later (cpp_naf_train_rows_async / cpp_naf_loss_wait): pinned (loss, flag) slots
   uint64_t graph_gen = 0;    // part of every graph's key: moved by naf_route_check, every graph is then captured again
   uint64_t epoch;            // cpp_ctx::kernel_epoch the cached graphs were captured under (naf_route_check)
-  bool targets_in_apply, targets_applied;      // the next naf_apply closes an outer step: its launch carries the target update (as the DDPG learner's)
   float* res_pin; hipEvent_t res_ev[CPP_NAF_TICKETS]; uint64_t next_ticket;
   uint64_t dp_local;       // minibatches applied locally since the last parameter averaging (periodic mode)
   cpp_batch* step_batch;
-  // prioritized replay (per.hip): the importance weights the head kernel reads, and the launch that follows the TD values of the
-  // minibatch (its priorities into the tree, the next minibatch's rows and weights)
-  const float* per_w; std::function<int()> per_hook;
   Arena arena;
 };
 
@@ -63,11 +57,9 @@ extern "C" int cpp_naf_create(cpp_ctx* ctx, cpp_net* value, cpp_net* tvalue, cpp
   for (cpp_net* n : {tvalue, mu, lv}) if (n->maxB < f->maxB) f->maxB = n->maxB;
   f->nV = value->nparams; f->nM = mu->nparams; f->nL = lv->nparams;
   f->step_batch = nullptr;
-  f->sq_cnt = 0; f->step_bumped = false;
   f->epoch = ctx->kernel_epoch;
   f->res_pin = nullptr; f->next_ticket = 0; memset(f->res_ev, 0, sizeof(f->res_ev));
   f->dp_local = 0;
-  f->per_w = nullptr;
   const size_t nall = (size_t)(f->nV + f->nM + f->nL);
   int rc = dalloc(f->arena, &f->gradbuf, nall);
   if (!rc) rc = dalloc(f->arena, &f->m, nall);
@@ -129,7 +121,7 @@ static int naf_forward(cpp_naf* f, const void* s1, const void* s2, int dtype, co
   return CPP_OK;
 }
 
-static int naf_head(cpp_naf* f, cpp_batch* b, bool backward) {
+static int naf_head(cpp_naf* f, cpp_batch* b, bool backward, const float* per_w = nullptr) {
   NafHeadArgs a; memset(&a, 0, sizeof(a));
   a.value = f->value->ws[0].out; a.mu = f->mu->ws[0].out; a.lv = f->lv->ws[0].out;
   a.action = b->a; a.reward = b->r; a.mask = b->m; a.target_value = f->tvalue->ws[0].out;
@@ -138,7 +130,7 @@ static int naf_head(cpp_naf* f, cpp_batch* b, bool backward) {
   if (backward) {
     a.d_value = f->value->ws[0].dz.back(); a.d_mu_z = f->mu->ws[0].dz.back(); a.d_l = f->lv->ws[0].dz.back();
   }
-  return launch_naf_head(f->ctx, a, f->per_w);
+  return launch_naf_head(f->ctx, a, per_w);
 }
 
 // One NAF minibatch (naf_cartpole.py:264-272 without the apply) as a dependency graph, batched like the DDPG
@@ -147,10 +139,10 @@ static int naf_head(cpp_naf* f, cpp_batch* b, bool backward) {
 // their share of the list's squared norm in cpp_ctx::sq_part (as the DDPG step, rt_ddpg.cpp) and the heads kernel advances the
 // optimiser's step counter -- naf_apply then runs neither the sumsq nor the counter kernel
 // bump_step: the heads kernel also advances the optimiser's step counter (only where no check_numerics flag can stand the update down)
-static int naf_compute_gradients(cpp_naf* f, cpp_batch* b, bool fold = false, bool bump_step = true) {
+// per: rt_internal.h, PerPass.  *left: what the pass left for the naf_apply behind it, written only when it succeeds.
+static int naf_compute_gradients(cpp_naf* f, cpp_batch* b, PassLeft* left, bool fold = false, bool bump_step = true, const PerPass& per = PerPass()) {
   cpp_ctx* ctx = f->ctx;
-  f->step_bumped = false;
-  SqScope sq_scope(ctx, &f->sq_cnt, 1, {0, 0, 0, 0}, fold && !f->value->spec.use_batch_norm);      // ONE list, every conv network's in it
+  SqScope sq_scope(ctx, 1, {0, 0, 0, 0}, fold && !f->value->spec.use_batch_norm);      // ONE list, every conv network's in it
   cpp_net *v = f->value, *tv = f->tvalue, *mu = f->mu, *lv = f->lv;
   const int B = b->B, C = v->spec.pixel ? v->spec.C : 0, dt = b->dtype;
   const float *w1 = white_of(b, 0, C), *w2 = white_of(b, 1, C);
@@ -219,7 +211,6 @@ static int naf_compute_gradients(cpp_naf* f, cpp_batch* b, bool fold = false, bo
   for (int l = 0; l < Lh - (mlp ? 1 : 0); ++l) vrep = G.gemm(fc_fwd_args(v, v->ws[0], l, B), {vrep});
   int vout, tvout, muout, lvout;
   if (fused) {
-    f->step_bumped = nh.step_bump != nullptr;
     int tvrep = t1;
     for (int l = 0; l < Lh - (mlp ? 1 : 0); ++l) tvrep = G.gemm(fc_fwd_args(tv, tv->ws[0], l, B), {tvrep});
     vout = vrep; tvout = tvrep; muout = lvout = vrep;
@@ -234,14 +225,14 @@ static int naf_compute_gradients(cpp_naf* f, cpp_batch* b, bool fold = false, bo
     G.fn([=] { return bump_dropout(tv); }, {tvout});
     if (!share) { G.fn([=] { return bump_dropout(mu); }, {muout}); G.fn([=] { return bump_dropout(lv); }, {lvout}); }
   }
-  // ---- NAF head: L, advantage, TD loss and the gradients of the three head outputs (prioritized replay: weighted by f->per_w)
-  const float* per_w = f->per_w;
+  // ---- NAF head: L, advantage, TD loss and the gradients of the three head outputs (prioritized replay: weighted by per.w)
+  const float* per_w = per.w;
   const int head = mlp ? G.fn([=] { return launch_naf_mlp(ctx, nm, per_w); }, {vout, tvout})
                  : fused ? G.fn([=] { return launch_naf_heads(ctx, nh, per_w); }, {vout, tvout})
-                         : G.fn([=] { return naf_head(f, b, true); }, {vout, tvout, muout, lvout});
+                         : G.fn([=] { return naf_head(f, b, true, per_w); }, {vout, tvout, muout, lvout});
   // (prioritized replay: as soon as the TD values are known -- the next op level, ahead of the conv backward that carries the next
   // minibatch's gather)
-  if (f->per_hook) G.fn(f->per_hook, {head});
+  if (per.hook) G.fn(per.hook, {head});
 
   // ---- backward
   if (!share) {
@@ -282,19 +273,22 @@ static int naf_compute_gradients(cpp_naf* f, cpp_batch* b, bool fold = false, bo
   }
   DwPendingGuard pending(ctx);      // (a failure below drops what was queued)
   RC(G.run(ctx));
-  return flush_dw_reduce(ctx);
+  RC(flush_dw_reduce(ctx));
+  left->counted = fused && nh.step_bump != nullptr;
+  sq_scope.left(left->sq_cnt);
+  return CPP_OK;
 }
 
-// bump: the replay sampler's counter, advanced by this launch; nx: the minibatch whose sample pass has already run -- its whitening
-// tables are finished by this launch's extra grid row unless they are done (rt_internal.h: NextBatch)
-static int naf_apply(cpp_naf* f, float grad_scale, bool unless_nonfinite = false, uint64_t* bump = nullptr, bool folded = false,
-                     const NextBatch& nx = NextBatch()) {
+// The optimiser's launch (rt_internal.h: OptPlan).  next: that minibatch's whitening tables are finished by this launch's extra grid
+// row unless they are done.  *targets_left: the target update and the route's publish left with this launch (the plan closes an outer step).
+static int naf_apply(cpp_naf* f, const OptPlan& plan, bool* targets_left = nullptr) {
+  const bool unless_nonfinite = plan.unless_nonfinite;
+  const float grad_scale = plan.grad_scale;
+  const NextBatch& nx = plan.next;
   OptSegs s; memset(&s, 0, sizeof(s));
   if (unless_nonfinite) s.skip_if = f->nonfinite;
-  s.bump = bump;
+  s.bump = plan.bump;
   f->value->wimg_key = nullptr; f->mu->wimg_key = nullptr;      // (the parameters change)
-  const bool with_targets = f->targets_in_apply && !nx.b && !unless_nonfinite;      // (the outer step's last launch: naf_step_body)
-  f->targets_in_apply = false;
   opt_next_stats(f->ctx, s, nx);
   s.nseg = 3; s.kind = f->hp.optimiser; s.momentum = f->hp.momentum; s.beta1 = f->hp.beta1; s.beta2 = f->hp.beta2;
   s.epsilon = f->hp.epsilon; s.step = f->opt_step;
@@ -305,19 +299,14 @@ static int naf_apply(cpp_naf* f, float grad_scale, bool unless_nonfinite = false
     s.n[k] = nets[k]->nparams; s.lr[k] = f->hp.learning_rate; s.group[k] = 0;      // ONE list, one global norm
     off += nets[k]->nparams;
   }
-  if (with_targets) {      // the target value network's soft update (naf_cartpole.py:373) and the route's publish leave with this launch
-    s.tgt[0] = f->tvalue->params; s.tgt_coeff = f->hp.target_update_rate;
-    f->tvalue->wimg_key = nullptr;
-    if (f->ctx->route_pin_dev) { s.pub_wmax = f->ctx->white_max_dev; s.pub_tag = f->ctx->route_tag_dev; s.pub_pin = f->ctx->route_pin_dev; }
-    f->targets_applied = true;
-  }
-  const bool bumped = f->step_bumped; const int sq_cnt = f->sq_cnt;
-  f->step_bumped = false; f->sq_cnt = 0;
+  // the target value network's soft update (naf_cartpole.py:373) and the route's publish leave with an outer step's last launch
+  const bool ride = opt_closing_riders(f->ctx, s, plan, {f->tvalue}, f->hp.target_update_rate);
+  if (targets_left) *targets_left = ride;
+  const bool bumped = plan.pass.counted;
   // (unless_nonfinite: a skipped update must not count as an optimiser step -- Adam's bias correction reads the count; the heads
   // kernel's bump was undone below by never happening: naf_compute_gradients leaves it to this launch when the flag can stand the update down)
   if (!bumped) RC(launch_counter_add(f->ctx, f->opt_step, 1, unless_nonfinite ? f->nonfinite : nullptr));
-  if (folded && sq_cnt > 0 && grad_scale == 1.0f) { s.sq = f->ctx->sq_part; s.sq_begin[0] = 0; s.sq_count[0] = sq_cnt; }
-  else RC(launch_sumsq(f->ctx, s, grad_scale, f->norm_part, NORM_PARTS));
+  RC(opt_norms(f->ctx, s, plan, 1, f->norm_part));
   // conv1's operand images of the next minibatch ride along (shared trunk: the value network's conv1 on state_1, the target value
   // network's on state_2; SGD or Momentum -- Adam's update is not restated in this learner's rider)
   cpp_net* inets[2] = {f->value, f->tvalue};
@@ -363,7 +352,8 @@ extern "C" int cpp_naf_action(cpp_naf* f, const void* state, int dtype, int B, f
 extern "C" int cpp_naf_compute_gradients(cpp_naf* f, cpp_batch* b) {
   RC(naf_check_batch(f, b, "cpp_naf_compute_gradients"));
   HIP_CHECK(hipSetDevice(f->ctx->device));
-  return naf_compute_gradients(f, b);
+  PassLeft left;      // (nothing folded, nothing counted: cpp_naf_apply_gradients needs none of it)
+  return naf_compute_gradients(f, b, &left);
 }
 extern "C" int cpp_naf_grad_buffer(cpp_naf* f, void** p, int64_t* n) {
   ARG_CHECK(f && p && n, "cpp_naf_grad_buffer: NULL argument");
@@ -373,13 +363,18 @@ extern "C" int cpp_naf_grad_buffer(cpp_naf* f, void** p, int64_t* n) {
 extern "C" int cpp_naf_apply_gradients(cpp_naf* f, float grad_scale) {
   ARG_CHECK(f, "cpp_naf_apply_gradients: NULL argument");
   HIP_CHECK(hipSetDevice(f->ctx->device));
-  return naf_apply(f, grad_scale);
+  OptPlan plan; plan.grad_scale = grad_scale;
+  return naf_apply(f, plan);
+}
+// publish_route: the launch closes a training call -- it also publishes the call's largest whitening scale and resets the scale word
+static int naf_soft_update_target(cpp_naf* f, bool publish_route) {
+  HIP_CHECK(hipSetDevice(f->ctx->device));
+  f->tvalue->wimg_key = nullptr;
+  return launch_soft_update(f->ctx, f->tvalue->params, f->value->params, f->nV, nullptr, nullptr, 0, f->hp.target_update_rate, publish_route);
 }
 extern "C" int cpp_naf_update_targets(cpp_naf* f) {
   ARG_CHECK(f, "cpp_naf_update_targets: NULL argument");
-  HIP_CHECK(hipSetDevice(f->ctx->device));
-  f->tvalue->wimg_key = nullptr;
-  return launch_soft_update(f->ctx, f->tvalue->params, f->value->params, f->nV, nullptr, nullptr, 0, f->hp.target_update_rate);
+  return naf_soft_update_target(f, false);
 }
 
 extern "C" int cpp_naf_train(cpp_naf* f, cpp_batch* b, float* loss) {
@@ -387,12 +382,13 @@ extern "C" int cpp_naf_train(cpp_naf* f, cpp_batch* b, float* loss) {
   cpp_ctx* ctx = f->ctx;
   HIP_CHECK(hipSetDevice(ctx->device));
   HIP_CHECK(hipMemsetAsync(f->nonfinite, 0, sizeof(int), ctx->stream));
-  RC(naf_compute_gradients(f, b));
+  OptPlan plan;
+  RC(naf_compute_gradients(f, b, &plan.pass));
   int bad = 0; float l = 0.f;
   RC(read_back(ctx, {{&bad, f->nonfinite, sizeof(int)}, {&l, f->stats, sizeof(float)}}, true));
   if (loss) *loss = l;
   if (bad) { cpp_set_error("check_numerics: l_values / L / loss is not finite (naf_cartpole.py:242-245)"); return CPP_ERR_NUMERIC; }
-  return naf_apply(f, 1.0f);
+  return naf_apply(f, plan);
 }
 
 extern "C" int cpp_naf_debug_values(cpp_naf* f, cpp_batch* b, float* l_values, float* loss, float* value, float* advantage,
@@ -423,20 +419,23 @@ static int naf_step_body(cpp_naf* f, cpp_replay* r, int B, int n_batches, const 
   const bool per = r->per_tree != nullptr;
   MinibatchLoop L;
   L.ctx = ctx; L.r = r; L.step_batch = f->step_batch; L.trunk = f->value;
-  L.per_w = &f->per_w; L.per_hook = &f->per_hook; L.td = f->td; L.skip_if_set = f->nonfinite; L.draws_bump = true;
+  L.td = f->td; L.skip_if_set = f->nonfinite; L.draws_bump = true;
   L.ride_ok = !f->value->spec.use_batch_norm;
-  L.gradients = [=] { return naf_compute_gradients(f, f->step_batch, true, !per); };
-  L.apply = [=](bool more, const NextBatch& next) {
+  L.gradients = [=](const PerPass& pp, PassLeft* left) { return naf_compute_gradients(f, f->step_batch, left, true, !per, pp); };
+  bool targets_left = false;
+  L.apply = [=, &targets_left](bool more, const NextBatch& next, const PassLeft& left) {
     if (dp) RC(step_allreduce(ctx, comm, f->gradbuf, (size_t)(f->nV + f->nM + f->nL)));
     static const bool no_tgt_ride = cpp_switch_off("CPP_RIDE_TARGETS");
-    f->targets_applied = false;
-    f->targets_in_apply = !more && !dp && !no_tgt_ride;      // (the last minibatch of an outer step: the target update rides in its optimiser launch)
-    return naf_apply(f, (dp && comm) ? 1.0f / (float)comm->world : 1.0f, per, (rows_dev || per) ? nullptr : r->counter, !dp, next);
+    OptPlan plan;
+    plan.grad_scale = (dp && comm) ? 1.0f / (float)comm->world : 1.0f; plan.unless_nonfinite = per;
+    plan.bump = (rows_dev || per) ? nullptr : r->counter; plan.folded = !dp; plan.next = next; plan.pass = left;
+    // (the last minibatch of an outer step: the target update and the publish ride in its optimiser launch -- unless that launch can stand down)
+    plan.closes_step = plan.closes_call = !more && !dp && !no_tgt_ride && !per;
+    return naf_apply(f, plan, &targets_left);
   };
   RC(run_minibatches(L, B, n_batches, rows_dev, seed));
-  if (f->targets_applied) { f->targets_applied = false; return CPP_OK; }      // (the target update and the route's publish left with the optimiser's launch)
-  ctx->route_rider = true;                          // (the largest whitening scale of this step rides to the host in that launch)
-  return cpp_naf_update_targets(f);      // (the largest whitening scale of this step, for the next call's choice of conv1 kernels)
+  if (targets_left) return CPP_OK;      // (the target update and the route's publish left with the optimiser's launch)
+  return naf_soft_update_target(f, true);      // (the largest whitening scale of this step rides to the host in that launch, for the next call's choice of conv1 kernels)
 }
 
 extern "C" int cpp_naf_train_step(cpp_naf* f, cpp_replay* r, int B, int n_batches, const int32_t* idxs, uint64_t seed) {
@@ -463,21 +462,22 @@ extern "C" int cpp_naf_train_step(cpp_naf* f, cpp_replay* r, int B, int n_batche
 // Prioritized memory: the importance weights of the caller's rows against the tree as it stands (the rows of cpp_replay_draw_prioritized
 // get the weights that draw computed), and the priorities of the minibatch written behind its head kernel -- unless the check_numerics
 // flag is set (sticky: as long as it stays set)
-static int naf_rows_body(cpp_naf* f, cpp_replay* r, int B, bool fold = false, bool sticky = false) {
+static int naf_rows_body(cpp_naf* f, cpp_replay* r, int B, PassLeft* left, bool fold = false, bool sticky = false) {
   const int C = f->value->spec.pixel ? f->value->spec.C : 0;
   if (!sticky) HIP_CHECK(hipMemsetAsync(f->nonfinite, 0, sizeof(int), f->ctx->stream));
-  PerScope per_scope(&f->per_w, &f->per_hook, r);
+  PerPass per;
   if (r->per_tree) {
+    per.w = r->per_w;
     PerArgs p = per_args(r);
     p.B = B; p.w_rows = r->rows_in; p.out_w = r->per_w;
     RC(launch_per_update_sample(f->ctx, p));
     PerArgs u = per_args(r);
     u.up_rows = r->rows_in; u.n_up = B; u.up_td = f->td; u.skip_if_set = f->nonfinite;
     cpp_ctx* ctx = f->ctx;
-    f->per_hook = [ctx, u] { return launch_per_update_sample(ctx, u); };
+    per.hook = [ctx, u] { return launch_per_update_sample(ctx, u); };
   }
   RC(replay_sample_device(r, B, r->rows_in, 0, nullptr, C, f->step_batch, direct_replay_ok(f->value, r, B)));
-  RC(naf_compute_gradients(f, f->step_batch, fold, !sticky));
+  RC(naf_compute_gradients(f, f->step_batch, left, fold, !sticky, per));
   return ctx_route_publish(f->ctx);
 }
 extern "C" int cpp_naf_train_rows(cpp_naf* f, cpp_replay* r, int B, const int32_t* idxs, float* loss) {
@@ -488,12 +488,12 @@ extern "C" int cpp_naf_train_rows(cpp_naf* f, cpp_replay* r, int B, const int32_
   HIP_CHECK(hipSetDevice(ctx->device));
   if (!f->step_batch) RC(cpp_batch_create(ctx, f->maxB, r->elems, r->A, &f->step_batch));
   RC(replay_stage_rows(r, idxs, B, "cpp_naf_train_rows"));
-  RC(run_step_graph(ctx, f->rgraph, GraphKey{B, 1, 0, r->uid, 0, f->graph_gen}, [&] { return naf_rows_body(f, r, B); }));
+  RC(run_step_graph(ctx, f->rgraph, GraphKey{B, 1, 0, r->uid, 0, f->graph_gen}, [&] { PassLeft left; return naf_rows_body(f, r, B, &left); }));      // (nothing folded, nothing counted)
   int bad = 0; float l = 0.f;
   RC(read_back(ctx, {{&bad, f->nonfinite, sizeof(int)}, {&l, f->stats, sizeof(float)}}, true));
   if (loss) *loss = l;
   if (bad) { cpp_set_error("check_numerics: l_values / L / loss is not finite (naf_cartpole.py:242-245)"); return CPP_ERR_NUMERIC; }
-  return naf_apply(f, 1.0f);
+  return naf_apply(f, OptPlan());
 }
 
 // The same minibatch without the host in the loop: gradients AND the optimiser in one hipGraph -- the optimiser kernel itself stands
@@ -502,8 +502,9 @@ extern "C" int cpp_naf_train_rows(cpp_naf* f, cpp_replay* r, int B, const int32_
 // reads the loss (the agents only log its mean) -- so a loop of train calls keeps the GPU fed like cpp_naf_train_step does.
 // At most CPP_NAF_TICKETS results are outstanding: a slot is reused CPP_NAF_TICKETS calls later.
 static int naf_rows_apply_body(cpp_naf* f, cpp_replay* r, int B) {
-  RC(naf_rows_body(f, r, B, true, true));  // (gradients and optimiser in ONE captured body: the fold's host-side state is consistent)
-  return naf_apply(f, 1.0f, true, nullptr, true);
+  OptPlan plan; plan.unless_nonfinite = true; plan.folded = true;
+  RC(naf_rows_body(f, r, B, &plan.pass, true, true));  // (gradients and optimiser in ONE captured body: the fold's partials go from one to the other)
+  return naf_apply(f, plan);
 }
 extern "C" int cpp_naf_train_rows_async(cpp_naf* f, cpp_replay* r, int B, const int32_t* idxs, uint64_t* ticket) {
   if (f) naf_route_check(f);
@@ -544,7 +545,8 @@ static int naf_half_body(cpp_naf* f, cpp_replay* r, int B, uint64_t seed) {
   bool bumped = false;       // (the statistics kernel advances the sampler's counter when there is one: replay_sample_finish)
   RC(replay_sample_device(r, B, nullptr, seed, r->counter, C, f->step_batch, direct_replay_ok(f->value, r, B), r->counter, &bumped));
   if (!bumped) RC(launch_counter_add(f->ctx, r->counter, 1));
-  RC(naf_compute_gradients(f, f->step_batch));
+  PassLeft left;      // (nothing folded, nothing counted)
+  RC(naf_compute_gradients(f, f->step_batch, &left));
   return ctx_route_publish(f->ctx);
 }
 
@@ -619,11 +621,12 @@ extern "C" int cpp_naf_dp_train_step(cpp_naf* f, cpp_replay* r, cpp_comm* c, int
   for (int i = 0; i < n_batches; ++i) {
     RC(cpp_naf_sample_and_compute(f, r, B, seed));
     if (sync_every > 1) {
-      RC(naf_apply(f, 1.0f));
+      RC(naf_apply(f, OptPlan()));
       if (++f->dp_local >= (uint64_t)sync_every && c) RC(cpp_naf_average_params(f, c));
     } else {
       if (c) RC(cpp_naf_allreduce_grads(f, c));
-      RC(naf_apply(f, inv));
+      OptPlan plan; plan.grad_scale = inv;
+      RC(naf_apply(f, plan));
     }
   }
   return cpp_naf_update_targets(f);

@@ -312,7 +312,7 @@ extern "C" int cpp_net_soft_update(cpp_net* target, const cpp_net* source, float
   ARG_CHECK(target->nparams == source->nparams, "cpp_net_soft_update: shapes differ (%ld vs %ld)",
             target->nparams, source->nparams);                                             // base_network.py:30
   target->wimg_key = nullptr;
-  return launch_soft_update(target->ctx, target->params, source->params, target->nparams, nullptr, nullptr, 0, coeff);
+  return launch_soft_update(target->ctx, target->params, source->params, target->nparams, nullptr, nullptr, 0, coeff, false);
 }
 
 // --- launch sequences -------------------------------------------------------------------------

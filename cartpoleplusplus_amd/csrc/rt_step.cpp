@@ -22,6 +22,25 @@ void opt_next_stats(cpp_ctx* ctx, OptSegs& s, const NextBatch& nx) {
   s.st_part = sr.part; s.st_white = sr.white; s.st_nparts = sr.nparts; s.st_jobs = sr.jobs; s.st_C = sr.C;
   s.st_count = sr.count; s.st_eps = sr.eps; s.st_wmax = sr.wmax;
 }
+bool opt_closing_riders(cpp_ctx* ctx, OptSegs& s, const OptPlan& p, std::initializer_list<cpp_net*> targets, float coeff) {
+  const bool last = !p.next.b;
+  const bool ride = p.closes_step && last && p.actor && p.critic;
+  if (ride) {
+    int k = 0;
+    for (cpp_net* t : targets) { s.tgt[k++] = t->params; t->wimg_key = nullptr; }
+    s.tgt_coeff = coeff;
+  }
+  if (p.closes_call && last && ctx->route_pin_dev) { s.pub_wmax = ctx->white_max_dev; s.pub_tag = ctx->route_tag_dev; s.pub_pin = ctx->route_pin_dev; }
+  return ride;
+}
+int opt_norms(cpp_ctx* ctx, OptSegs& s, const OptPlan& p, int lists, double* norm_part) {
+  bool fold = p.folded && p.actor && p.critic && p.grad_scale == 1.0f;
+  for (int l = 0; l < lists; ++l) fold = fold && p.pass.sq_cnt[l] > 0;
+  if (!fold) return launch_sumsq(ctx, s, p.grad_scale, norm_part, NORM_PARTS);
+  s.sq = ctx->sq_part;
+  for (int l = 0; l < lists; ++l) { s.sq_begin[l] = l * SQ_REGION; s.sq_count[l] = p.pass.sq_cnt[l]; }
+  return CPP_OK;
+}
 
 // conv1's weights and biases open the flat buffer (cpp_net_var_info order): [w_off, b_off + nout)
 bool conv1_opens_params(const cpp_net* n) {
@@ -72,7 +91,7 @@ int read_back(cpp_ctx* ctx, std::initializer_list<Readback> items, bool through_
 // (flush_dw_reduce): they are in memory before the optimiser's launch, whose conv1 image rider reads them; otherwise that launch
 // finishes them.
 // Prioritized memory (per.hip): minibatch i's rows are the caller's or a stratified draw by priority, keyed by the sampler's counter as
-// the uniform draw is; its importance weights scale the loss.  As soon as its TD values are known, ONE launch (per_hook: the gradient pass
+// the uniform draw is; its importance weights scale the loss.  As soon as its TD values are known, ONE launch (PerPass::hook: the gradient pass
 // places it behind its TD kernel) writes its priorities into the tree and draws minibatch i + 1 -- before the pass that gathers i + 1,
 // wherever that rides.  The gathers take the drawn rows as a row list.  Who moves the counter then: the optimiser's launch as before
 // (the draw looks one ahead: counter_add), or -- draws_bump, for a learner whose optimiser launch can stand down -- the draws themselves.
@@ -94,8 +113,9 @@ int run_minibatches(const MinibatchLoop& L, int B, int n_batches, const int32_t*
     else p.counter_add = ahead;
     p.out_rows = r->per_rows; p.out_w = r->per_w;
   };
-  PerScope per_scope(L.per_w, L.per_hook, r);
+  PerPass pp;
   if (per) {
+    pp.w = r->per_w;
     PerArgs p = per_args(r);
     per_draw(p, 0, 0);
     RC(launch_per_update_sample(ctx, p));
@@ -108,9 +128,9 @@ int run_minibatches(const MinibatchLoop& L, int B, int n_batches, const int32_t*
       PerArgs p = per_args(r);
       p.up_rows = rows_of(i); p.n_up = B; p.up_td = L.td; p.skip_if_set = L.skip_if_set;
       if (more) per_draw(p, i + 1, 1);
-      *L.per_hook = [ctx, p] { return launch_per_update_sample(ctx, p); };
+      pp.hook = [ctx, p] { return launch_per_update_sample(ctx, p); };
     }
-    bool rode, tables_done; int rc;
+    bool rode, tables_done; int rc; PassLeft left;
     {
       RideScope ride(ctx);
       if (more && ride_ok) {
@@ -122,15 +142,14 @@ int run_minibatches(const MinibatchLoop& L, int B, int n_batches, const int32_t*
         sr = next_stats_ride(ctx, NextBatch{sb, B, Cg, r->elems, false});
         ride.arm_stats(&sr);
       }
-      rc = L.gradients();
-      *L.per_hook = nullptr;
+      rc = L.gradients(pp, &left);
       rode = ride.rode(); tables_done = ride.tables_done();
     }
     if (rode && direct) { std::swap(sb->slot[0], sb->slot_alt[0]); std::swap(sb->slot[1], sb->slot_alt[1]); }
     RC(rc);
     // (the optimiser's launch also finishes the statistics of a sample pass that rode along above, unless the dW reductions' launch has)
     const bool stats_ride = rode && Cg > 0 && !(L.stats_switch && no_stats_ride);
-    RC(L.apply(more, stats_ride ? NextBatch{sb, B, Cg, r->elems, tables_done} : NextBatch{}));
+    RC(L.apply(more, stats_ride ? NextBatch{sb, B, Cg, r->elems, tables_done} : NextBatch{}, left));
     if (more) {
       if (stats_ride) { sb->B = B; sb->dtype = CPP_F16; sb->stats_C = Cg; }     // (replay_sample_finish's bookkeeping)
       else if (rode) RC(replay_sample_finish(r, B, Cg, C, sb));
