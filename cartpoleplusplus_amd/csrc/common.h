@@ -276,7 +276,6 @@ int launch_copy_cols(cpp_ctx* ctx, float* dst, long ldd, int dcol0, const float*
 int launch_fill(cpp_ctx* ctx, float* dst, long ld, int col0, int ncols, int rows, float v);
 int launch_state_to_f32(cpp_ctx* ctx, float* dst, long ldd, const void* src, int dtype, long elems,
                         int rows);
-int launch_actor_head_grad(cpp_ctx* ctx, float* dz, const float* dq_da, const float* act, int n);
 int launch_td(cpp_ctx* ctx, const float* q, const float* tq, const float* r, const float* mask,
               float discount, int B, float* td, float* dq, float* loss, const float* w = nullptr);   // w: importance weights (per.hip)
 // twin Q heads: one target from min(tq1, tq2), both TDs, both dq (nullptr: none, check_loss), loss = mean(w (td1^2 + td2^2))

@@ -328,23 +328,6 @@ int launch_state_to_f32(cpp_ctx* ctx, float* dst, long ldd, const void* src, int
   return 0;
 }
 
-// grad_ys of ddpg_cartpole.py:111-113 pushed through the tanh head: dz = -dq_da * (1 - a^2)
-__global__ void actor_head_grad_kernel(float* dz, const float* dq_da, const float* act, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float a = act[i];
-  dz[i] = -dq_da[i] * (1.f - a * a);
-}
-
-int launch_actor_head_grad(cpp_ctx* ctx, float* dz, const float* dq_da, const float* act, int n) {
-  prof_begin(ctx);
-  hipLaunchKernelGGL(actor_head_grad_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dz,
-                     dq_da, act, n);
-  LAUNCH_CHECK();
-  prof_end(ctx, K_ELEMENTWISE);
-  return 0;
-}
-
 // ddpg_cartpole.py:199-209: y = r + (mask*discount)*Q'(s2, mu'(s2)); td = Q - y; loss = mean(td^2);
 // dq = d loss / d Q = 2 td / B.  WEIGHTED (prioritized replay): loss = mean(w td^2), dq = (td w) 2 / B.
 template <bool WEIGHTED>

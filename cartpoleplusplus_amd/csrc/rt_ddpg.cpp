@@ -39,9 +39,8 @@ struct cpp_ddpg {
   int opt_kind; float opt_momentum, opt_beta1, opt_beta2, opt_epsilon;
   float *opt_m, *opt_v; uint64_t* opt_step;
   // target policy smoothing (cpp_ddpg_set_target_smoothing; common.h: TpsArgs).  tps_n[0]: the count of target-forming gradient passes (a
-  // device word: captured graphs replay it), tps_n[1]: the count the last pass drew at; tps_eps: its clipped noise, maxB x A;
-  // tps_act: the smoothed action of the single train op (cpp_ddpg_train_critic), maxB x A
-  bool tps_on; float tps_sigma, tps_clip; uint64_t tps_seed; uint64_t* tps_n; float *tps_eps, *tps_act;
+  // device word: captured graphs replay it), tps_n[1]: the count the last pass drew at; tps_eps: its clipped noise, maxB x A
+  bool tps_on; float tps_sigma, tps_clip; uint64_t tps_seed; uint64_t* tps_n; float* tps_eps;
   // A pass that reads tps_n[0] owes it one increment (PassLeft::noise_owed): the apply() behind it carries it, or tps_settle()
   // delayed policy updates (cpp_ddpg_set_policy_delay; common.h: DdpgHeadsArgs::pd, OptSegs::hold).  pd_d: the delay (1: off, and pd is
   // never passed to a launch); pd: three device words (captured graphs replay them) -- the critic updates applied since the configuring
@@ -169,7 +168,7 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   d->opt_kind = OPT_SGD; d->opt_momentum = 0.f; d->opt_beta1 = 0.9f; d->opt_beta2 = 0.999f; d->opt_epsilon = 1e-8f;
   d->opt_m = d->opt_v = nullptr; d->opt_step = nullptr;
   d->pd_d = 1; d->pd = nullptr;
-  d->tps_on = false; d->tps_sigma = d->tps_clip = 0.f; d->tps_seed = 0; d->tps_n = nullptr; d->tps_eps = d->tps_act = nullptr;
+  d->tps_on = false; d->tps_sigma = d->tps_clip = 0.f; d->tps_seed = 0; d->tps_n = nullptr; d->tps_eps = nullptr;
   const int A = actor->spec.action_dim;
   int rc = dalloc(d->arena, &d->gradbuf, (size_t)(d->nA + d->nC));
   if (!rc) rc = dalloc(d->arena, &d->dq_da, (size_t)d->maxB * A);
@@ -270,76 +269,6 @@ static int tps_settle(cpp_ddpg* d, const PassLeft& left) {
 
 const float* white_of(cpp_batch* b, int which, int C) { return b->white + (long)which * 2 * C; }
 
-// critic "prefix": conv trunk + the fully connected layers in front of the action splice
-static int critic_prefix(cpp_net* c, const void* state, int dtype, const float* white, int B) {
-  RC(net_forward_trunk(c, c->ws[0], state, dtype, white, B));
-  if (c->cat_layer > 0) {
-    // run layers [0, cat) only
-    for (int l = 0; l < c->cat_layer; ++l) {
-      const FcL& L = c->fc[l];
-      RC(gemm(c->ctx, c->ws[0].fcin[l], L.n_in + 1, 1, c->params + L.w_off, L.n_out, 1, c->ws[0].fcin[l + 1],
-              c->fc[l + 1].n_in + 1, B, L.n_out, L.n_in + 1, L.act));
-    }
-  }
-  return CPP_OK;
-}
-
-// evaluate the critic head from the splice on, in workspace `wi`, with the given device action batch
-static int critic_head(cpp_net* c, int wi, const float* action, int B) {
-  const int cl = c->cat_layer, A = c->spec.action_dim;
-  if (wi == 1) {
-    const FcL& L = c->fc[cl];
-    RC(launch_copy_cols(c->ctx, c->ws[1].fcin[cl], L.n_in + 1, 0, c->ws[0].fcin[cl], L.n_in + 1, 0, L.n_in - A, B));
-  }
-  RC(net_forward_fc(c, c->ws[wi], cl, B, action));
-  // (a distributional critic's second evaluation: Q, and p (z - Q) where the scalar critic's q layer is fed ones)
-  if (c->dist_n && wi == 1) return dist_expect(c, c->ws[1], B, c->ws[1].dz[c->fc.size() - 1]);
-  return (c->twin && wi == 0) ? twin_forward_fc(c, c->ws[0], B) : CPP_OK;      // (head 2 reads the same concat input)
-}
-
-// ddpg_cartpole.py:111-113 + :220-222.  critic_prefix_done: the critic prefix for batch.state_1 is
-// already in critic->ws[0] (fused step computes it once for both updates).
-static int actor_gradients(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, PassLeft* left, bool draw = true) {
-  cpp_net *a = d->actor, *c = d->critic;
-  const int B = b->B, C = a->spec.pixel ? a->spec.C : 0;
-  const float* w1 = white_of(b, 0, C);
-  RC(net_forward_trunk(a, a->ws[0], b->s[0], b->dtype, w1, B));
-  RC(net_forward_fc(a, a->ws[0], 0, B, nullptr));
-  if (d->sac) {      // (draw == false: an evaluation, eps = 0 and the count unread)
-    SacSampleArgs sa = sac_sample_args(d, false, draw); sa.B = B;
-    RC(launch_sac_sample(d->ctx, sa));
-  }
-  if (!critic_prefix_done) RC(critic_prefix(c, b->s[0], b->dtype, w1, B));
-  RC(critic_head(c, 1, a->ws[0].out, B));
-  // d(sum_b Q)/da: dz of the linear q layer is 1
-  const int last = (int)c->fc.size() - 1;
-  if (!c->dist_n) RC(launch_copy_cols(d->ctx, c->ws[1].dz[last], 1, 0, d->ones, 1, 0, 1, B));
-  // walk back to the splice (hidden layers after the splice are ReLU)
-  for (int l = last; l > c->cat_layer; --l) {
-    const FcL& L = c->fc[l];
-    RC(gemm(d->ctx, c->ws[1].dz[l], L.n_out, 1, c->params + L.w_off, 1, L.n_out, c->ws[1].dz[l - 1], L.n_in, B, L.n_in,
-            L.n_out, GE_MUL_RELU_GRAD, c->ws[1].fcin[l], L.n_in + 1));
-  }
-  {
-    const FcL& L = c->fc[c->cat_layer];
-    const int A = c->spec.action_dim;
-    RC(gemm(d->ctx, c->ws[1].dz[c->cat_layer], L.n_out, 1, c->params + L.w_off + (long)(L.n_in - A) * L.n_out, 1, L.n_out,
-            d->dq_da, A, B, A, L.n_out, GE_NONE));
-  }
-  // grad_ys = -dQ/da through the tanh head, then the whole actor backward
-  const int alast = (int)a->fc.size() - 1;
-  if (d->sac) {      // (an evaluation, draw == false, leaves the partials, their batch size and the recorded temperature to the last gradient pass)
-    SacGradArgs sg = sac_grad_args(d, B);
-    if (!draw) { sg.part = nullptr; sg.alpha_out = nullptr; }
-    RC(launch_sac_actor_grad(d->ctx, sg));
-  }
-  else
-  RC(launch_actor_head_grad(d->ctx, a->ws[0].dz[alast], d->dq_da, a->ws[0].out, B * a->spec.action_dim));
-  RC(net_backward(a, a->ws[0], B, true, nullptr, b->s[0], b->dtype, w1));
-  if (d->sac && draw) left->loss.sac_rows = B;
-  return CPP_OK;
-}
-
 // The critic's loss on the fed and the target evaluation the forward passes left in the first workspaces (ddpg_cartpole.py:210-214):
 // the TD values, the loss (d->heads_part's partials of a distributional trainer, else d->loss_norms[0]) and -- backward -- dz of the q layer
 static int critic_td(cpp_ddpg* d, const cpp_batch* b, int B, bool backward, const float* w) {
@@ -357,44 +286,6 @@ static LossAt critic_loss_at(const cpp_ddpg* d, int B, bool fused_heads) {
   LossAt at;
   at.parts = fused_heads ? (B + 3) / 4 : (d->dist_n ? dist_td_grid(B) : 0); at.B = B;
   return at;
-}
-
-// ddpg_cartpole.py:199-214
-static int critic_gradients_impl(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, bool backward, PassLeft* left);
-// backward == false is check_loss (ddpg_cartpole.py:239-248), which feeds IS_TRAINING False; the train op (:237) feeds
-// True for the whole graph, target networks included
-static int critic_gradients(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, bool backward, PassLeft* left) {
-  cpp_net* nets[3] = {d->critic, d->tactor, d->tcritic};
-  for (cpp_net* n : nets) n->is_training = backward;
-  const int rc = critic_gradients_impl(d, b, critic_prefix_done, backward, left);
-  for (cpp_net* n : nets) n->is_training = true;
-  return rc;
-}
-static int critic_gradients_impl(cpp_ddpg* d, cpp_batch* b, bool critic_prefix_done, bool backward, PassLeft* left) {
-  cpp_net *c = d->critic, *ta = d->tactor, *tc = d->tcritic;
-  const int B = b->B, C = c->spec.pixel ? c->spec.C : 0;
-  const float *w1 = white_of(b, 0, C), *w2 = white_of(b, 1, C);
-  RC(net_forward_trunk(ta, ta->ws[0], b->s[1], b->dtype, w2, B));
-  RC(net_forward_fc(ta, ta->ws[0], 0, B, nullptr));
-  RC(critic_prefix(tc, b->s[1], b->dtype, w2, B));
-  const float* tact = ta->ws[0].out;
-  if (d->sac) {      // a' and logp' from the target actor's head (the actor's, to the bit); check_loss: eps = 0, nothing drawn
-    SacSampleArgs st = sac_sample_args(d, true, backward, b); st.B = B;
-    RC(launch_sac_sample(d->ctx, st));
-  }
-  if (backward && d->tps_on) {      // (the train op only: check_loss is an evaluation and draws nothing)
-    const int A = ta->spec.action_dim;
-    RC(launch_tps_smooth(d->ctx, tps_args(d), tact, A, d->tps_act, A, B, A));
-    tact = d->tps_act;
-  }
-  RC(critic_head(tc, 0, tact, B));
-  if (!critic_prefix_done) RC(critic_prefix(c, b->s[0], b->dtype, w1, B));
-  RC(critic_head(c, 0, b->a, B));
-  RC(critic_td(d, b, B, backward, nullptr));
-  if (backward) RC(net_backward(c, c->ws[0], B, true, nullptr, b->s[0], b->dtype, w1));
-  left->noise_owed = backward && (d->sac || d->tps_on);      // (the train op only: check_loss is an evaluation and draws nothing)
-  left->loss = critic_loss_at(d, B, false);
-  return CPP_OK;
 }
 
 // The optimiser's launch of the lists the plan names (rt_internal.h: OptPlan).  folded: only for gradients that are applied as computed
@@ -469,51 +360,11 @@ static int prep_batch(cpp_ddpg* d, cpp_batch* b) {
   return CPP_OK;
 }
 
-extern "C" int cpp_ddpg_train_actor(cpp_ddpg* d, cpp_batch* b) {
-  RC(check_batch(d, b, "cpp_ddpg_train_actor"));
-  HIP_CHECK(hipSetDevice(d->ctx->device));
-  RC(prep_batch(d, b));
-  OptPlan plan; plan.critic = false;
-  RC(actor_gradients(d, b, false, &plan.pass));
-  d->last.sac_rows = plan.pass.loss.sac_rows;
-  return apply(d, plan);
-}
-
-extern "C" int cpp_ddpg_train_critic(cpp_ddpg* d, cpp_batch* b) {
-  RC(check_batch(d, b, "cpp_ddpg_train_critic"));
-  HIP_CHECK(hipSetDevice(d->ctx->device));
-  RC(prep_batch(d, b));
-  OptPlan plan; plan.actor = false;
-  RC(critic_gradients(d, b, false, true, &plan.pass));
-  d->last.parts = plan.pass.loss.parts; d->last.B = plan.pass.loss.B;
-  return apply(d, plan);
-}
-
-extern "C" int cpp_ddpg_check_loss(cpp_ddpg* d, cpp_batch* b, float* loss, float* td, float* q) {
-  RC(check_batch(d, b, "cpp_ddpg_check_loss"));
-  HIP_CHECK(hipSetDevice(d->ctx->device));
-  RC(prep_batch(d, b));
-  PassLeft left;
-  RC(critic_gradients(d, b, false, false, &left));
-  d->last.parts = left.loss.parts; d->last.B = left.loss.B;      // (the evaluation's loss stands where a train op's would)
-  double parts[DDPG_HEADS_MAX_WGS];      // (a distributional trainer: the cross-entropy from its per-workgroup partials, as cpp_ddpg_last_stats)
-  const int nparts = left.loss.parts;
-  const size_t nB = (size_t)b->B * sizeof(float);
-  RC(read_back(d->ctx, {{loss && nparts ? parts : nullptr, d->heads_part, (size_t)nparts * sizeof(double)}, {nparts ? nullptr : loss, d->loss_norms, sizeof(float)},
-                        {td, d->td, nB}, {q, d->critic->ws[0].out, nB}}));
-  if (loss && nparts) *loss = loss_of_parts(parts, nparts, left.loss.B);
-  return CPP_OK;
-}
-
-extern "C" int cpp_ddpg_q_gradients_wrt_actions(cpp_ddpg* d, cpp_batch* b, float* dq_da, float* actions, float* q) {
-  RC(check_batch(d, b, "cpp_ddpg_q_gradients_wrt_actions"));
-  HIP_CHECK(hipSetDevice(d->ctx->device));
-  RC(prep_batch(d, b));
-  PassLeft left;      // (an evaluation: nothing drawn, nothing left)
-  RC(actor_gradients(d, b, false, &left, false));
-  const size_t nB = (size_t)b->B * sizeof(float), nA = nB * d->actor->spec.action_dim;
-  return read_back(d->ctx, {{dq_da, d->dq_da, nA}, {actions, d->actor->ws[0].out, nA}, {q, d->critic->ws[1].out, nB}});
-}
+// What a caller wants of the gradient pass: the halves to run -- the actor's (ddpg_cartpole.py:111-113, :220-222: dQ/da at actor(s1),
+// pushed through the actor) and the critic's (:199-214: the TD loss against the target networks) -- and whether it trains.  train ==
+// false is an evaluation (cpp_ddpg_check_loss, cpp_ddpg_q_gradients_wrt_actions): no critic backward, no noise drawn and nothing owed;
+// soft actor-critic runs at eps = 0 and leaves the partials and the recorded temperature to the last training pass.
+struct PassParts { bool actor = true, critic = true, train = true; };
 
 // Both gradient sets of one minibatch (ddpg_cartpole.py:331-334) as one dependency graph: 4 conv trunk
 // forwards, the MLP GEMMs batched level by level, 2 conv trunk backwards.  The critic trunk + the layers in
@@ -522,7 +373,12 @@ extern "C" int cpp_ddpg_q_gradients_wrt_actions(cpp_ddpg* d, cpp_batch* b, float
 // gradients of the fully connected layers are then final), phase 2 = the conv backward + the dW reductions.
 // count_in_heads: the apply() behind this pass takes both lists (step_body) -- the heads kernel, where there is one, advances both step
 // counts and the policy-delay words itself.  per: rt_internal.h, PerPass.  *left: what the pass left, written only when it succeeds.
-static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phase = 0, bool count_in_heads = false, const PerPass& per = PerPass()) {
+// want: the parts of the pass (PassParts).  One half alone builds only its own nodes on the GEMM levels: per-network conv launches, no
+// fused heads, no folded norms, nothing counted, no phase split.
+static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phase = 0, bool count_in_heads = false, const PerPass& per = PerPass(),
+                             const PassParts& want = PassParts()) {
+  const bool doA = want.actor, doC = want.critic, both = doA && doC, train = want.train;
+  if (!both && (phase != 0 || count_in_heads)) { cpp_set_error("compute_gradients: one half of the pass has no phases and counts nothing"); return CPP_ERR_STATE; }
   cpp_ctx* ctx = d->ctx;
   cpp_net *a = d->actor, *c = d->critic, *ta = d->tactor, *tc = d->tcritic;
   const int B = b->B, A = a->spec.action_dim, C = a->spec.pixel ? a->spec.C : 0;
@@ -536,12 +392,12 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
   OpGraph G;
   // The kernels that write the gradients also leave their share of the two lists' squared norms (cpp_ctx::sq_part): list 0 = actor,
   // list 1 = critic.  Not with batch norm (dbeta comes out of the BN backward kernels) and not for a split pass.
-  SqScope sq_scope(ctx, 2, {0, 1}, phase == 0 && !a->spec.use_batch_norm && !c->spec.use_batch_norm);
+  SqScope sq_scope(ctx, 2, {0, 1}, both && phase == 0 && !a->spec.use_batch_norm && !c->spec.use_batch_norm);
 
   // ---- forward: the four conv trunks.  conv1 saturates the chip per network; the narrow conv2 / conv3 layers
-  // of all four networks share one launch each.
-  int tA, tC, tTA, tTC;
-  if (a->spec.pixel && !a->spec.use_batch_norm) {
+  // of all four networks share one launch each.  (One half: its own networks, one by one -- batch norm follows each network's is_training.)
+  int tA = -1, tC, tTA = -1, tTC = -1;
+  if (both && a->spec.pixel && !a->spec.use_batch_norm) {
     cpp_net* nets[4] = {a, c, ta, tc};
     const void* sts[4] = {s1, s1, s2, s2};
     const float* whs[4] = {w1, w1, w2, w2};
@@ -549,17 +405,17 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
     // backward pass (nets_forward_trunk_fused, rt_net.cpp)
     const int t1 = G.fn([=] { return nets_forward_trunk_fused(ctx, nets, 4, sts, whs, 2, dt, B); }, {});
     tA = tC = tTA = tTC = t1;
-  } else if (a->spec.pixel) {       // batch norm (training mode for the whole graph, ddpg_cartpole.py:145,237)
+  } else if (both && a->spec.pixel) {       // batch norm (training mode for the whole graph, ddpg_cartpole.py:145,237)
     cpp_net* nets[4] = {a, c, ta, tc};
     const void* sts[4] = {s1, s1, s2, s2};
     const float* whs[4] = {w1, w1, w2, w2};
     const int t1 = G.fn([=] { return nets_forward_trunk_bn(ctx, nets, 4, sts, whs, dt, B); }, {});
     tA = tC = tTA = tTC = t1;
-  } else {
-    tA = G.fn([=] { return net_forward_trunk(a, a->ws[0], s1, dt, w1, B); }, {});
+  } else {      // the low-dimensional state's conversion; one half of a pixel pass: its own networks, each by its own is_training
+    if (doA) tA = G.fn([=] { return net_forward_trunk(a, a->ws[0], s1, dt, w1, B); }, {});
     tC = G.fn([=] { return net_forward_trunk(c, c->ws[0], s1, dt, w1, B); }, {});
-    tTA = G.fn([=] { return net_forward_trunk(ta, ta->ws[0], s2, dt, w2, B); }, {});
-    tTC = G.fn([=] { return net_forward_trunk(tc, tc->ws[0], s2, dt, w2, B); }, {});
+    if (doC) tTA = G.fn([=] { return net_forward_trunk(ta, ta->ws[0], s2, dt, w2, B); }, {});
+    if (doC) tTC = G.fn([=] { return net_forward_trunk(tc, tc->ws[0], s2, dt, w2, B); }, {});
   }
   // ---- fused heads (heads.hip): when the critic is "[prefix, action] -> relu layer -> linear q" and the actor ends in a tanh
   // layer (the reference's networks, ddpg_cartpole.py:95-100, :166-171), everything from the actors' / critics' last hidden
@@ -570,7 +426,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
   const bool twin = d->twin;
   const bool sac = d->sac;         // (its actor's head is 2A wide and linear: never the fused heads)
   const int dist = d->dist_n;      // (its q layer has N outputs: never the fused heads)
-  bool fused = !dist && !no_heads && na >= 2 && cat >= 1 && nc - cat == 2 && a->fc[na - 1].act == GE_TANH && Lcat.act == GE_RELU &&
+  bool fused = both && !dist && !no_heads && na >= 2 && cat >= 1 && nc - cat == 2 && a->fc[na - 1].act == GE_TANH && Lcat.act == GE_RELU &&
                c->fc[nc - 1].n_out == 1 && c->fc[nc - 1].act == GE_NONE && a->fc[na - 1].n_out == A;
   if (fused) {
     const FcL& Lo = a->fc[na - 1];
@@ -612,7 +468,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
     }
   }
   const int pre = (fused && hd.n1a > 0) ? 1 : 0;
-  int adz, cdz;
+  int adz = -1, cdz = -1;
   if (fused) {
     int aF = tA, taF = tTA;
     for (int l = 0; l < na - 1 - pre; ++l) {
@@ -643,8 +499,8 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
     // (the helper's relu_grad_epi(c, l) is GE_MUL_RELU_GRAD for every critic: a CPP_CRITIC's hidden layers are built with GE_RELU,
     // dropout or not -- rt_net.cpp's constructor gives GE_RELU_DROPOUT to actors and NAF heads only)
     cdz = add_fc_backward(G, c, c->ws[0], B, cat - 1, hk, 1);
-  } else {
-  const int cb = G.fn([=] { return launch_copy_cols(ctx, c->ws[0].fcin[cat], ldcat, Lcat.n_in - A, b->a, A, 0, A, B); }, {});
+  } else {      // the GEMM levels, each half's nodes only where one half is asked for
+  const int cb = doC ? G.fn([=] { return launch_copy_cols(ctx, c->ws[0].fcin[cat], ldcat, Lcat.n_in - A, b->a, A, 0, A, B); }, {}) : -1;
   int aF = tA, taF = tTA;
   for (int l = 0; l < na; ++l) {
     GemmArgs g = fc_fwd_args(a, a->ws[0], l, B), t = fc_fwd_args(ta, ta->ws[0], l, B);
@@ -652,39 +508,41 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
       g.C2 = c->ws[1].fcin[cat] + (Lcat.n_in - A); g.ldc2 = ldcat;
       t.C2 = tc->ws[0].fcin[cat] + (Lcat.n_in - A); t.ldc2 = ldcat;
     }
-    aF = G.gemm(g, {aF}); taF = G.gemm(t, {taF});
+    if (doA) aF = G.gemm(g, {aF});
+    if (doC) taF = G.gemm(t, {taF});
   }
   if (a->drop_counter) {     // --use-dropout: this forward is counted once its layers have read the counter
-    G.fn([=] { return bump_dropout(a); }, {aF});
-    G.fn([=] { return bump_dropout(ta); }, {taF});
+    if (doA) G.fn([=] { return bump_dropout(a); }, {aF});
+    if (doC) G.fn([=] { return bump_dropout(ta); }, {taF});
   }
   if (sac) {      // sac.hip's jobs 1 and 2 stand where the tanh epilogue stood: sample, log-density, splice columns, the soft reward
-    SacSampleArgs sa = sac_sample_args(d, false, true), st = sac_sample_args(d, true, true, b);
+    SacSampleArgs sa = sac_sample_args(d, false, train), st = sac_sample_args(d, true, train, b);      // (an evaluation: eps = 0, the count unread)
     sa.B = st.B = B; sa.ld_splice = st.ld_splice = ldcat;
     sa.splice = c->ws[1].fcin[cat] + (Lcat.n_in - A); st.splice = tc->ws[0].fcin[cat] + (Lcat.n_in - A);
-    aF = G.fn([=] { return launch_sac_sample(ctx, sa); }, {aF});
-    taF = G.fn([=] { return launch_sac_sample(ctx, st); }, {taF});
+    if (doA) aF = G.fn([=] { return launch_sac_sample(ctx, sa); }, {aF});
+    if (doC) taF = G.fn([=] { return launch_sac_sample(ctx, st); }, {taF});
   }
   int cP = tC, tcP = tTC;
   for (int l = 0; l < cat; ++l) {
     GemmArgs g = fc_fwd_args(c, c->ws[0], l, B);
-    if (l == cat - 1) { g.C2 = c->ws[1].fcin[cat]; g.ldc2 = ldcat; }   // same prefix for the second evaluation
+    if (l == cat - 1 && doA) { g.C2 = c->ws[1].fcin[cat]; g.ldc2 = ldcat; }   // same prefix for the second evaluation
     cP = G.gemm(g, {cP});
-    tcP = G.gemm(fc_fwd_args(tc, tc->ws[0], l, B), {tcP});
+    if (doC) tcP = G.gemm(fc_fwd_args(tc, tc->ws[0], l, B), {tcP});
   }
-  if (cat == 0)     // low-dim critic: the "prefix" is the converted state itself
+  if (cat == 0 && doA)     // low-dim critic: the "prefix" is the converted state itself
     cP = G.fn([=] { return launch_copy_cols(ctx, c->ws[1].fcin[0], ldcat, 0, c->ws[0].fcin[0], ldcat, 0, Lcat.n_in - A, B); }, {tC});
   // target policy smoothing: the target actor's action in the target critic's splice columns, between the GEMM that wrote it and the
-  // concat GEMM that reads it (ta->ws[0].out keeps the unsmoothed action)
+  // concat GEMM that reads it (ta->ws[0].out keeps the unsmoothed action).  An evaluation draws nothing
   int taS = taF;
-  if (d->tps_on) {
+  if (d->tps_on && doC && train) {
     const TpsArgs ts = tps_args(d);
     float* col = tc->ws[0].fcin[cat] + (Lcat.n_in - A);
     taS = G.fn([=] { return launch_tps_smooth(ctx, ts, col, (int)ldcat, col, (int)ldcat, B, A); }, {taF});
   }
   int c1 = -1, c0 = -1, tcH = -1, c0b = -1, tcHb = -1;
   for (int l = cat; l < nc; ++l) {
-    c1 = G.gemm(fc_fwd_args(c, c->ws[1], l, B), {l == cat ? cP : c1, l == cat ? aF : -1});
+    if (doA) c1 = G.gemm(fc_fwd_args(c, c->ws[1], l, B), {l == cat ? cP : c1, l == cat ? aF : -1});
+    if (!doC) continue;
     c0 = G.gemm(fc_fwd_args(c, c->ws[0], l, B), {l == cat ? cP : c0, l == cat ? cb : -1, l == cat ? tC : -1});
     tcH = G.gemm(fc_fwd_args(tc, tc->ws[0], l, B), {l == cat ? tcP : tcH, l == cat ? taS : -1});
     if (twin) {      // head 2 of both critics on the same concat inputs (one smoothed action for both target heads), in head 1's levels
@@ -693,6 +551,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
     }
   }
 
+  if (doA) {
   // ---- dQ/da at a = actor(s1): back through q_value .. splice on the second evaluation (dz of q is 1)
   int g = c1;
   // (a distributional critic: the gradient of the expectation, p (z - Q), stands where the scalar critic's q layer is fed ones)
@@ -710,20 +569,22 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
     if (!sac) { ga.C2 = a->ws[0].dz[na - 1]; ga.ldc2 = A; }
     adz = G.gemm(ga, {g, aF});
     if (sac) {      // job 3: the (B, 2A) head gradient and the temperature gradient's partials
-      const SacGradArgs sg = sac_grad_args(d, B);
+      SacGradArgs sg = sac_grad_args(d, B);
+      if (!train) { sg.part = nullptr; sg.alpha_out = nullptr; }      // (an evaluation leaves both to the last training pass)
       adz = G.fn([=] { return launch_sac_actor_grad(ctx, sg); }, {adz});
     }
   }
 
   // ---- actor backward
   adz = add_fc_backward(G, a, a->ws[0], B, na - 1, adz, 0);
+  }
 
   // ---- TD target + critic backward on the first evaluation (fed actions)
   const float* per_w = per.w;
-  cdz = G.fn([=] { return critic_td(d, b, B, true, per_w); }, {c0, tcH, c0b, tcHb});      // (twin: both heads of both critics; r_soft: job 2's, which tcH follows)
-  if (per.hook) G.fn(per.hook, {cdz});
+  if (doC) cdz = G.fn([=] { return critic_td(d, b, B, train, per_w); }, {c0, tcH, c0b, tcHb});      // (twin: both heads of both critics; r_soft: job 2's, which tcH follows)
+  if (doC && per.hook) G.fn(per.hook, {cdz});
   int cdz2 = cdz;      // head 2's chain down to the concat layer, level by level beside head 1's
-  for (int l = nc - 1; l >= 0; --l) {
+  for (int l = nc - 1; l >= 0 && doC && train; --l) {
     const FcL& L = c->fc[l];
     G.gemm(sq_gemm(ctx, 1, fc_dw_args(c, c->ws[0], l, B, c->ws[0].dz[l])), {cdz});
     const int ncols = L.cat ? L.n_in - A : L.n_in;
@@ -742,9 +603,12 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
   }
   }
   int conv_bwd = -1;
-  if (c->spec.pixel) {     // both conv backward passes, layer by layer, two networks per launch
+  if (c->spec.pixel && both) {     // both conv backward passes, layer by layer, two networks per launch
     cpp_net* bn[2] = {a, c};
     conv_bwd = G.fn([=] { return nets_backward_conv(ctx, bn, 2, B, s1, dt, w1); }, {adz, cdz});
+  } else if (c->spec.pixel && (doA || train)) {      // one half: its trained network's
+    cpp_net* n = doA ? a : c;
+    conv_bwd = G.fn([=] { return net_backward_conv(n, n->ws[0], B, s1, dt, w1); }, {doA ? adz : cdz});
   }
   DwPendingGuard pending(ctx);      // (a failure below drops what was queued)
   if (phase == 2) {
@@ -755,11 +619,71 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
   if (phase == 1) pending.keep();
   else RC(flush_dw_reduce(ctx));      // all six dW reductions (3 layers x 2 networks) in one launch
   left->counted = fused && (hd.step_bump != nullptr || hd.pd != nullptr);
-  left->noise_owed = (d->tps_on || sac) && phase != 2;      // (this pass read the count: exactly one increment follows it)
+  left->noise_owed = (d->tps_on || sac) && phase != 2 && doC && train;      // (this pass read the count: exactly one increment follows it)
   sq_scope.left(left->sq_cnt);
-  left->loss = critic_loss_at(d, B, fused);
-  if (sac) left->loss.sac_rows = B;
+  if (doC) left->loss = critic_loss_at(d, B, fused);
+  if (sac && doA && train) left->loss.sac_rows = B;
   return CPP_OK;
+}
+
+// The single ops are the pass with one half asked for.  The actor's half (ddpg_cartpole.py:111-113 + :220-222) ...
+static int actor_half(cpp_ddpg* d, cpp_batch* b, bool train, PassLeft* left) {
+  return compute_gradients(d, b, left, 0, false, PerPass(), PassParts{true, false, train});
+}
+// ... and the critic's (:199-214).  train == false is check_loss (:239-248), which feeds IS_TRAINING False; the train op (:237) feeds
+// True for the whole graph, target networks included.  Set around the pass: its nodes read the flag while the graph is built
+static int critic_gradients(cpp_ddpg* d, cpp_batch* b, bool train, PassLeft* left) {
+  cpp_net* nets[3] = {d->critic, d->tactor, d->tcritic};
+  for (cpp_net* n : nets) n->is_training = train;
+  const int rc = compute_gradients(d, b, left, 0, false, PerPass(), PassParts{false, true, train});
+  for (cpp_net* n : nets) n->is_training = true;
+  return rc;
+}
+
+extern "C" int cpp_ddpg_train_actor(cpp_ddpg* d, cpp_batch* b) {
+  RC(check_batch(d, b, "cpp_ddpg_train_actor"));
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  RC(prep_batch(d, b));
+  OptPlan plan; plan.critic = false;
+  RC(actor_half(d, b, true, &plan.pass));
+  d->last.sac_rows = plan.pass.loss.sac_rows;
+  return apply(d, plan);
+}
+
+extern "C" int cpp_ddpg_train_critic(cpp_ddpg* d, cpp_batch* b) {
+  RC(check_batch(d, b, "cpp_ddpg_train_critic"));
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  RC(prep_batch(d, b));
+  OptPlan plan; plan.actor = false;
+  RC(critic_gradients(d, b, true, &plan.pass));
+  d->last.parts = plan.pass.loss.parts; d->last.B = plan.pass.loss.B;
+  return apply(d, plan);
+}
+
+extern "C" int cpp_ddpg_check_loss(cpp_ddpg* d, cpp_batch* b, float* loss, float* td, float* q) {
+  RC(check_batch(d, b, "cpp_ddpg_check_loss"));
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  RC(prep_batch(d, b));
+  PassLeft left;
+  RC(critic_gradients(d, b, false, &left));
+  d->last.parts = left.loss.parts; d->last.B = left.loss.B;      // (the evaluation's loss stands where a train op's would)
+  double parts[DDPG_HEADS_MAX_WGS];      // (a distributional trainer: the cross-entropy from its per-workgroup partials, as cpp_ddpg_last_stats)
+  const int nparts = left.loss.parts;
+  const size_t nB = (size_t)b->B * sizeof(float);
+  RC(read_back(d->ctx, {{loss && nparts ? parts : nullptr, d->heads_part, (size_t)nparts * sizeof(double)}, {nparts ? nullptr : loss, d->loss_norms, sizeof(float)},
+                        {td, d->td, nB}, {q, d->critic->ws[0].out, nB}}));
+  if (loss && nparts) *loss = loss_of_parts(parts, nparts, left.loss.B);
+  return CPP_OK;
+}
+
+extern "C" int cpp_ddpg_q_gradients_wrt_actions(cpp_ddpg* d, cpp_batch* b, float* dq_da, float* actions, float* q) {
+  RC(check_batch(d, b, "cpp_ddpg_q_gradients_wrt_actions"));
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  RC(prep_batch(d, b));
+  PassLeft left;      // (an evaluation: nothing drawn, nothing left; the actor's backward runs all the same -- cpp_ddpg_grad_buffer shows it)
+  RC(actor_half(d, b, false, &left));
+  const size_t nB = (size_t)b->B * sizeof(float), nA = nB * d->actor->spec.action_dim;
+  return read_back(d->ctx, {{dq_da, d->dq_da, nA}, {actions, d->actor->ws[0].out, nA}, {q, d->critic->ws[1].out, nB}});
 }
 
 extern "C" int cpp_ddpg_compute_gradients(cpp_ddpg* d, cpp_batch* b) {
@@ -827,7 +751,6 @@ extern "C" int cpp_ddpg_set_target_smoothing(cpp_ddpg* d, float sigma, float cli
   const size_t n = (size_t)d->maxB * d->actor->spec.action_dim;
   if (sigma > 0.f && !d->tps_n) RC(dalloc(d->arena, &d->tps_n, (size_t)2));
   if (sigma > 0.f && !d->tps_eps) RC(dalloc(d->arena, &d->tps_eps, n));
-  if (sigma > 0.f && !d->tps_act) RC(dalloc(d->arena, &d->tps_act, n));
   if (d->tps_n) HIP_CHECK(hipMemsetAsync(d->tps_n, 0, 2 * sizeof(uint64_t), ctx->stream));
   if (d->tps_eps) HIP_CHECK(hipMemsetAsync(d->tps_eps, 0, n * sizeof(float), ctx->stream));
   HIP_CHECK(ctx_sync_stream(ctx));

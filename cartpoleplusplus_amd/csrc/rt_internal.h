@@ -308,7 +308,6 @@ int bump_dropout(cpp_net* n);
 int net_forward_fc(cpp_net* n, Workspace& w, int from, int B, const float* action);
 int net_backward_conv(cpp_net* n, Workspace& w, int B, const void* state, int dtype, const float* white);
 int nets_backward_conv(cpp_ctx* ctx, cpp_net* const* nets, int nn, int B, const void* state, int dtype, const float* white);
-int net_backward(cpp_net* n, Workspace& w, int B, bool want_params, float* d_action, const void* state, int dtype, const float* white, int start_layer = -2);
 GemmArgs fc_fwd_args(cpp_net* n, Workspace& w, int l, int B);
 GemmArgs fc_dw_args(cpp_net* n, Workspace& w, int l, int B, const float* dz);
 GemmArgs fc_dx_args(cpp_net* n, int l, int B, const float* dz, long dz_ld, int col0, int ncols, float* C, long ldc, int epi, const float* Y, long ldy);
@@ -317,7 +316,6 @@ GemmArgs fc_dx_args(cpp_net* n, int l, int B, const float* dz, long dz_ld, int c
 GemmArgs twin_fwd_args(cpp_net* n, Workspace& w, int l, int B);
 GemmArgs twin_dw_args(cpp_net* n, Workspace& w, int l, int B);
 GemmArgs twin_dx_args(cpp_net* n, Workspace& w, int l, int B);
-int twin_forward_fc(cpp_net* n, Workspace& w, int B);
 // where the last layer's GEMM writes: the logits of a distributional critic, `out` otherwise
 inline float* fc_last_out(const Workspace& w) { return w.logits ? w.logits : w.out; }
 // Q (and, dz != nullptr, p (z - Q); a quantile critic: 1 / N) from the logits the forward left in w: a no-op for every other network

@@ -602,51 +602,6 @@ int nets_backward_conv(cpp_ctx* ctx, cpp_net* const* nets, int nn, int B, const 
   return CPP_OK;
 }
 
-// Backward from w.dz[last] (gradient w.r.t. the last layer's pre-activation).  want_params: write
-// [dW; db] of every layer into n->grads, otherwise stop once d_action is known.  d_action: (B, A) out.
-int net_backward(cpp_net* n, Workspace& w, int B, bool want_params, float* d_action,
-                        const void* state, int dtype, const float* white, int start_layer) {
-  cpp_ctx* ctx = n->ctx;
-  const int nfc = (int)n->fc.size(), A = n->spec.action_dim;
-  if (want_params && !n->grads) { cpp_set_error("network has no gradient buffer"); return CPP_ERR_STATE; }
-  if (start_layer == -2) start_layer = nfc - 1;       // -1: only the conv trunk (w.dpool[2] already holds d flat)
-  // twin Q heads (the critic's train op): head 2's chain down to the concat layer first; its term joins the shared layer's dz below
-  const bool twin = n->twin && want_params && start_layer == nfc - 1 && !w.dz2.empty();
-  if (twin)
-    for (int l = nfc - 1; l >= n->cat_layer; --l) {
-      RC(launch_gemm(ctx, twin_dw_args(n, w, l, B)));
-      if (l > n->cat_layer) RC(launch_gemm(ctx, twin_dx_args(n, w, l, B)));
-    }
-  for (int l = start_layer; l >= 0; --l) {
-    const FcL& L = n->fc[l];
-    const float* dz = w.dz[l];
-    const float* W = n->params + L.w_off;
-    if (want_params)    // [dW; db] = [x, 1]^T dz
-      RC(gemm(ctx, w.fcin[l], 1, L.n_in + 1, dz, L.n_out, 1, n->grads + L.w_off, L.n_out, L.n_in + 1, L.n_out, B, GE_NONE));
-    if (L.cat) {
-      if (d_action)     // dQ/da: the action columns of dz W^T (ddpg_cartpole.py:222)
-        RC(gemm(ctx, dz, L.n_out, 1, W + (long)(L.n_in - A) * L.n_out, 1, L.n_out, d_action, A, B, A, L.n_out, GE_NONE));
-      if (!want_params) return CPP_OK;
-      if (l > 0 && twin) {      // (head 1) + (head 2), then the mask
-        RC(gemm(ctx, dz, L.n_out, 1, W, 1, L.n_out, w.dz[l - 1], L.n_in - A, B, L.n_in - A, L.n_out, GE_NONE));
-        RC(launch_gemm(ctx, twin_dx_args(n, w, l, B)));
-      } else if (l > 0)
-        RC(gemm(ctx, dz, L.n_out, 1, W, 1, L.n_out, w.dz[l - 1], L.n_in - A, B, L.n_in - A, L.n_out,
-                relu_grad_epi(n, l - 1), w.fcin[l], L.n_in + 1));
-    } else if (l > 0) {
-      RC(gemm(ctx, dz, L.n_out, 1, W, 1, L.n_out, w.dz[l - 1], L.n_in, B, L.n_in, L.n_out,
-              relu_grad_epi(n, l - 1), w.fcin[l], L.n_in + 1));
-    } else if (n->spec.pixel && want_params) {
-      RC(gemm(ctx, dz, L.n_out, 1, W, 1, L.n_out, w.dpool[2], n->flat, B, n->flat, L.n_out, GE_NONE));
-    }
-  }
-  if (!want_params || !n->spec.pixel) return CPP_OK;
-  DwPendingGuard pending(ctx);      // (a failure below drops what was queued)
-  RC(net_backward_conv(n, w, B, state, dtype, white));
-  return flush_dw_reduce(ctx);
-}
-
-
 GemmArgs mk_gemm(const float* A, long sAm, long sAk, const float* Bm, long sBk, long sBn, float* C, long ldc,
                         int M, int N, int K, int epi, const float* Y, long ldy) {
   GemmArgs g; memset(&g, 0, sizeof(g));
@@ -724,11 +679,6 @@ GemmArgs twin_dx_args(cpp_net* n, Workspace& w, int l, int B) {
   GemmArgs g = mk_gemm(w.dz2[l], L.n_out, 1, n->params + L.w_off, 1, L.n_out, w.dz[l - 1], ncols, B, ncols, L.n_out, relu_grad_epi(n, l - 1), w.fcin[l], L.n_in + 1);
   g.accumulate = 1;
   return g;
-}
-// head 2's forward behind head 1's on the same concat input (the single train ops, check_loss)
-int twin_forward_fc(cpp_net* n, Workspace& w, int B) {
-  for (int l = n->cat_layer; l < (int)n->fc2.size(); ++l) RC(launch_gemm(n->ctx, twin_fwd_args(n, w, l, B)));
-  return CPP_OK;
 }
 
 // whitening statistics of a device-resident (B, H*W*C) batch -> white[2][C]

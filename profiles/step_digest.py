@@ -12,7 +12,10 @@ nothing -- and on the head, then merge:
     step_digest.py > parent_a.json; step_digest.py > parent_b.json; step_digest.py > head.json        (each in its own tree)
     CARTPOLEPP_ABLATION=1 CPP_FUSED_HEADS=0 step_digest.py > ..._abl.json                             (the GEMM levels of the DDPG step)
     step_digest.py --merge parent_a.json parent_b.json head.json [the three _abl files] > step_digest.json
-Equality is the bar.  The merged file is a record of one comparison, not a fixture: the digests move with every intended kernel change.
+Equality is the bar.  The single_* configurations drive the four single entry points (train_actor, train_critic, check_loss,
+q_gradients_wrt_actions) on host batches, one round of the four per outer step; their digests also cover what check_loss and
+q_gradients_wrt_actions return and both networks' gradient buffers after every call.  Their launch counts are recorded and not compared
+(LAUNCHES_RECORDED_ONLY): a build that batches the GEMMs of a level launches fewer.  The merged file is a record of one comparison, not a fixture: the digests move with every intended kernel change.
 Usage: step_digest.py [config name ...] | --merge parent_a parent_b head [parent_a_abl parent_b_abl head_abl]"""
 import ctypes as C
 import hashlib, json, os, sys
@@ -21,6 +24,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 PIXEL, LOWDIM, B, NB, ROWS, OUTER = (64, 64, 3, 1, 2), (2, 2, 7), 8, 4, 64, 3
 ABLATION = os.environ.get("CARTPOLEPP_ABLATION") == "1"
+MOMENTUM = dict(optimiser="Momentum", optimiser_args='{"learning_rate": 0.001, "momentum": 0.9}')
+ADAM = dict(optimiser="Adam", optimiser_args='{"learning_rate": 0.001}')
+# the trainers of the single entry points' configurations (single_<trainer>, single_<trainer>_lowdim)
+SINGLE_TRAINERS = {
+    "plain": {},
+    "twin": dict(twin_q=True),
+    "categorical": dict(distributional_critic=True, num_atoms=51, v_min=-5.0, v_max=25.0),
+    "quantile": dict(quantile_critic=True, num_quantiles=25, drop_top_quantiles=2),
+    "sac": dict(soft_actor_critic=True),
+    "smoothing_adam_delay2": dict(target_policy_noise=0.2, ddpg_optimiser="Adam", policy_delay=2),
+}
+LAUNCHES_RECORDED_ONLY = set("single_%s%s" % (t, sfx) for t in SINGLE_TRAINERS for sfx in ("", "_lowdim"))
 
 
 def merge(paths):
@@ -32,9 +47,11 @@ def merge(paths):
         pa, pb, head = (r.get(name) for r in runs[:3])
         ran = all(r and r.get("digests") and r.get("launches") and "error" not in r for r in (pa, pb, head))      # (a refused or broken run verifies nothing)
         out[name] = {"parent": pa, "head": head, "ran": ran, "parent_deterministic": ran and pa == pb,
-                     "digests_equal": ran and pa["digests"] == head["digests"], "launches_equal": ran and pa["launches"] == head["launches"]}
+                     "digests_equal": ran and pa["digests"] == head["digests"], "launches_equal": ran and pa["launches"] == head["launches"],
+                     "launches_compared": name not in LAUNCHES_RECORDED_ONLY}
     json.dump(out, sys.stdout, indent=1, sort_keys=True)
-    bad = [n for n, v in out.items() if not v["ran"] or (v["parent_deterministic"] and not (v["digests_equal"] and v["launches_equal"]))]
+    bad = [n for n, v in out.items() if not v["ran"] or (v["parent_deterministic"] and not (
+        v["digests_equal"] and (v["launches_equal"] or not v["launches_compared"])))]
     sys.stderr.write("%d configurations, %d not deterministic on the parent, %d differ: %s\n" % (
         len(out), sum(not v["parent_deterministic"] for v in out.values()), len(bad), bad))
     sys.exit(1 if bad else 0)
@@ -44,6 +61,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "--merge":
     merge(sys.argv[2:])
 
 from cartpoleplusplus_amd import _lib, ddpg_cartpole as D, naf_cartpole as N
+from oracle import ddpg_np as O
 from tests.helpers import FakeEnv, fill_with_rendered_episodes
 lib, check, ptr = _lib.lib, _lib.check, _lib.ptr
 
@@ -124,6 +142,29 @@ def ddpg_state(a):
     return out
 
 
+class HostBatch(object):
+    def __init__(self, t):
+        self.state_1, self.action, self.reward, self.terminal_mask, self.state_2 = t
+
+
+def single_ops(a, k):      # one round of the four single entry points on host batch k; what they return and leave rides in a.single
+    grads = lambda: [a.actor.get_grads(), a.critic.get_grads()]
+    shape = a.env.observation_space.shape
+    hb = HostBatch(O.synthetic_batch(np.random.default_rng(700 + k), B, shape, 2, len(shape) == 5))
+    a.single = []
+    a.actor.train(hb.state_1)
+    a.single += grads()
+    a.critic.train(hb)
+    a.single += grads()
+    loss, td, q = a.critic.check_loss(hb)
+    a.single += [np.float32(loss), td, q] + grads()
+    a.single += [a.critic.q_gradients_wrt_actions(hb)] + grads()
+
+
+def single_state(a):
+    return ddpg_state(a) + a.single
+
+
 def naf_state(a):
     st = a.naf.get_optimiser_state()
     out = [n.get_params() for n in a.networks()] + [np.asarray(st[k]) for k in sorted(st)]
@@ -162,9 +203,7 @@ def naf_rows_async(a, k):
 def naf_dp(a, k): check(lib.cpp_naf_dp_train_step(a.naf.handle, a.replay_memory.handle, None, B, NB, 7, 1))
 
 
-MOMENTUM = dict(optimiser="Momentum", optimiser_args='{"learning_rate": 0.001, "momentum": 0.9}')
-ADAM = dict(optimiser="Adam", optimiser_args='{"learning_rate": 0.001}')
-DDPG, NAF = (ddpg_agent, ddpg_state), (naf_agent, naf_state)
+DDPG, NAF, SINGLE = (ddpg_agent, ddpg_state), (naf_agent, naf_state), (ddpg_agent, single_state)
 # name: (learner, shape, options, one outer step)
 CONFIGS = {
     "ddpg_sgd": (DDPG, PIXEL, {}, ddpg_step),
@@ -202,6 +241,10 @@ CONFIGS = {
     "naf_rows_async": (NAF, PIXEL, dict(share_input_state_representation=True, **MOMENTUM), naf_rows_async),
     "naf_dp": (NAF, PIXEL, dict(share_input_state_representation=True), naf_dp),
 }
+for _t, _kw in SINGLE_TRAINERS.items():
+    CONFIGS["single_" + _t] = (SINGLE, PIXEL, _kw, single_ops)
+    CONFIGS["single_%s_lowdim" % _t] = (SINGLE, LOWDIM, _kw, single_ops)
+assert LAUNCHES_RECORDED_ONLY == set(n for n in CONFIGS if n.startswith("single_"))
 # CPP_FUSED_HEADS=0 on the ablation library: the GEMM levels of compute_gradients under the scalar critic
 ABLATION_CONFIGS = {
     "ddpg_sgd_gemm_levels": (DDPG, PIXEL, {}, ddpg_step),
