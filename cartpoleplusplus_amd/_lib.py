@@ -28,6 +28,7 @@ CPP_F32, CPP_F16, CPP_U8 = 0, 1, 2
 CPP_ACTOR, CPP_CRITIC, CPP_HEAD = 0, 1, 2
 CPP_OPT_SGD, CPP_OPT_MOMENTUM, CPP_OPT_ADAM = 0, 1, 2
 CPP_PRECISION_FAST, CPP_PRECISION_EXACT = 0, 1      # cpp_ctx_set_precision
+CPP_NORM_TANH, CPP_NORM_RELU = 0, 1                  # cpp_net_create_feature_norm
 
 
 class NetSpec(C.Structure):
@@ -36,6 +37,12 @@ class NetSpec(C.Structure):
                 ("n_hidden", C.c_int32), ("hidden", C.c_int32 * 8), ("head_out", C.c_int32),
                 ("head_act", C.c_int32), ("use_batch_norm", C.c_int32), ("use_dropout", C.c_int32),
                 ("dropout_seed", C.c_uint32)]
+
+
+class NetVariant(C.Structure):
+    """cpp_net_variant: what a network made by cpp_net_create_feature_norm is besides (at most one of the four)."""
+    _fields_ = [("twin_q", C.c_int32), ("n_atoms", C.c_int32), ("v_min", C.c_float), ("v_max", C.c_float),
+                ("n_quantiles", C.c_int32), ("gaussian", C.c_int32), ("log_std_min", C.c_float), ("log_std_max", C.c_float)]
 
 
 class DdpgHyper(C.Structure):
@@ -84,6 +91,8 @@ SIGNATURES = {
     "cpp_net_create_gaussian": (_I, [_P, C.POINTER(NetSpec), _I, C.c_float, C.c_float, _PP]),
     "cpp_net_gaussian_info": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "cpp_net_forward_gaussian": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "cpp_net_create_feature_norm": (_I, [_P, C.POINTER(NetSpec), _I, C.POINTER(NetVariant), _I, C.c_float, _PP]),
+    "cpp_net_feature_norm_info": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_float)]),
     "cpp_net_destroy": (_I, [_P]),
     "cpp_net_num_params": (_L, [_P]),
     "cpp_net_num_vars": (_I, [_P]),
@@ -156,6 +165,7 @@ SIGNATURES = {
     "cpp_ddpg_set_sac": (_I, [_P, C.c_float, C.c_float, C.c_float, _U64]),
     "cpp_ddpg_last_sac": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_U64), _P]),
     "cpp_ddpg_sac_temperature": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_U64)]),
+    "cpp_ddpg_last_feature_norm": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "cpp_comm_unique_id": (_I, [_P, _I]),
     "cpp_comm_create": (_I, [_P, _P, _I, _I, _PP]),
     "cpp_comm_destroy": (_I, [_P]),

@@ -143,7 +143,8 @@ class Network(object):
         return self.hidden_layers_starting_at(input_state, opts.hidden_layers, opts)
 
     # ------------------------------------------------------------------ native instantiation
-    def _build_native(self, kind, action_dim, max_batch, ctx=None, head_out=0, head_act=0, twin_q=False, distribution=None, quantiles=None, gaussian=None):
+    def _build_native(self, kind, action_dim, max_batch, ctx=None, head_out=0, head_act=0, twin_q=False, distribution=None, quantiles=None, gaussian=None,
+                      feature_norm=None):
         self.ctx = ctx or _lib.default_context()
         spec = _lib.NetSpec()
         spec.kind, spec.action_dim = kind, int(action_dim)
@@ -163,7 +164,19 @@ class Network(object):
         handle = C.c_void_p()
         # (twin_q: a critic with twin Q heads, include/cartpolepp_abi.h cpp_net_create_twin_q; without it the call is what it always was)
         create = lib.cpp_net_create_twin_q if twin_q else lib.cpp_net_create
-        if gaussian is not None:          # (log_std_min, log_std_max): a Gaussian actor, cpp_net_create_gaussian
+        if feature_norm is not None:      # (activation, epsilon): Linear -> LayerNorm -> act on layer 0, cpp_net_create_feature_norm
+            activation, epsilon = feature_norm
+            v = _lib.NetVariant()
+            v.twin_q = int(bool(twin_q))
+            if distribution is not None:
+                v.n_atoms, v.v_min, v.v_max = int(distribution[0]), float(distribution[1]), float(distribution[2])
+            if quantiles is not None:
+                v.n_quantiles = int(quantiles)
+            if gaussian is not None:
+                v.gaussian, v.log_std_min, v.log_std_max = 1, float(gaussian[0]), float(gaussian[1])
+            act = {"tanh": _lib.CPP_NORM_TANH, "relu": _lib.CPP_NORM_RELU}[activation]
+            check(lib.cpp_net_create_feature_norm(self.ctx.handle, C.byref(spec), int(max_batch), C.byref(v), act, float(epsilon), C.byref(handle)))
+        elif gaussian is not None:          # (log_std_min, log_std_max): a Gaussian actor, cpp_net_create_gaussian
             check(lib.cpp_net_create_gaussian(self.ctx.handle, C.byref(spec), int(max_batch), float(gaussian[0]), float(gaussian[1]), C.byref(handle)))
         elif quantiles is not None:       # N: a quantile critic, cpp_net_create_quantile
             check(lib.cpp_net_create_quantile(self.ctx.handle, C.byref(spec), int(max_batch), int(quantiles), C.byref(handle)))
@@ -198,6 +211,10 @@ class Network(object):
         for v in self.trainable_model_vars():
             n = int(np.prod(v.shape))
             if v.name.endswith("biases:0") or v.name.endswith("BatchNorm/beta:0"):      # zeros_initializer both
+                continue
+            if "/LayerNorm/" in v.name:          # the feature layer norm: gamma 1, beta 0
+                if v.name.endswith("gamma:0"):
+                    flat[v.offset:v.offset + n] = 1.0
                 continue
             # the tanh action heads use U(-1e-3, 1e-3): 'actor/output_action/weights' (ddpg_cartpole.py:94) and
             # 'naf/output_action/fc/weights' (naf_cartpole.py:155) -- not the state networks beneath them

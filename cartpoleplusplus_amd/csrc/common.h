@@ -62,6 +62,8 @@ enum KernelId {
   K_DIST,                 // distributional critic: softmax / expectation, projected target and cross-entropy (dist.hip)
   K_QUANT,                // quantile critic: expectation, sorted and truncated targets, quantile Huber loss (quant.hip)
   K_SAC,                  // soft actor-critic: policy sample / mean, soft reward, actor head gradient, temperature (sac.hip)
+  K_LN_FWD,               // feature layer norm on fully connected layer 0, forward (ln.hip)
+  K_LN_BWD,               // ... its backward: the column sums' launch and the row-local launch
   K_NUM_KERNELS
 };
 
@@ -534,6 +536,24 @@ int quant_td_grid(int B);
 int launch_quant_td(cpp_ctx* ctx, const float* theta, const float* ttheta, const float* r, const float* mask, float discount, int B, int N,
                     float kappa, int drop_top, float* q_out, float* tq_out, float* theta_out, float* sorted_out, float* y_out, float* td,
                     float* dz, double* loss_part, const float* w = nullptr);
+// ---- feature layer norm (ln.hip; include/cartpolepp_abi.h, cpp_net_create_feature_norm): the rows of fully connected layer 0 of up to
+// LN_JOBS_MAX networks in one launch.  io: (B, n) at row stride ld -- z in, y = act(gamma xhat + beta) out, in place (the next layer's
+// input buffer; its ones column is left alone).  act: GE_TANH or GE_RELU.
+#define LN_JOBS_MAX 4
+#define LN_MAX_WIDTH 1024
+struct LnJob {
+  float* io; long ld; int n;
+  const float* gamma; const float* beta;
+  float* xhat; float* rstd;              // (B, n) and (B): kept for the backward pass
+  // backward: dz holds g = dL/dy, (B, n), and receives dL/dz in place; y is `io` as the forward left it
+  float* dz; float* dgamma; float* dbeta;
+  double* sq_part;                       // the column workgroups' shares of the list's squared norm, one slot each (nullptr: not folded)
+};
+struct LnArgs { LnJob j[LN_JOBS_MAX]; int count, B, act; float eps; };
+int ln_col_blocks(int n);                // workgroups (and sq_part slots) the column sums of one network take
+int launch_ln_forward(cpp_ctx* ctx, const LnArgs& a);
+int launch_ln_backward_cols(cpp_ctx* ctx, const LnArgs& a);      // dgamma, dbeta (b ascending) and their squared-norm shares; reads g, writes no dz
+int launch_ln_backward_rows(cpp_ctx* ctx, const LnArgs& a);      // g -> dz in place
 // ---- soft actor-critic (sac.hip; include/cartpolepp_abi.h, cpp_net_create_gaussian / cpp_ddpg_set_sac).  logits: (B, 2A), A in [1, 64]:
 // m in columns [0, A), x in [A, 2A).
 struct SacSampleArgs {

@@ -151,6 +151,11 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   ARG_CHECK(!(actor->gauss && critic->dist_n), "cpp_ddpg_create: a Gaussian actor with a distributional or quantile critic");
   for (cpp_net* n : {actor, critic, tactor, tcritic})
     ARG_CHECK(!(actor->gauss && (n->spec.use_batch_norm || n->spec.use_dropout)), "cpp_ddpg_create: a Gaussian actor with batch norm or dropout");
+  ARG_CHECK(actor->ln == critic->ln && actor->ln == tactor->ln && actor->ln == tcritic->ln,
+            "cpp_ddpg_create: a feature layer norm on some of the four networks (cpp_net_create_feature_norm: all four, or none)");
+  for (cpp_net* n : {critic, tactor, tcritic})
+    ARG_CHECK(!actor->ln || (n->ln_act == actor->ln_act && n->ln_eps == actor->ln_eps),
+              "cpp_ddpg_create: the four networks' feature layer norms differ in activation or epsilon");
   ARG_CHECK(actor->nparams == tactor->nparams && critic->nparams == tcritic->nparams, "cpp_ddpg_create: target shapes differ");
   ARG_CHECK(actor->state_elems == critic->state_elems && actor->spec.action_dim == critic->spec.action_dim,
             "cpp_ddpg_create: actor/critic input shapes differ");
@@ -428,6 +433,9 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
   const int dist = d->dist_n;      // (its q layer has N outputs: never the fused heads)
   bool fused = both && !dist && !no_heads && na >= 2 && cat >= 1 && nc - cat == 2 && a->fc[na - 1].act == GE_TANH && Lcat.act == GE_RELU &&
                c->fc[nc - 1].n_out == 1 && c->fc[nc - 1].act == GE_NONE && a->fc[na - 1].n_out == A;
+  // feature layer norm: the heads kernel writes dz[na - 2] through that layer's ReLU mask -- never the normalised layer 0, whose
+  // activation derivative is ln.hip's.  (The critic's is dz[cat - 1] = dz[1].)
+  if (a->ln && na < 3) fused = false;
   if (fused) {
     const FcL& Lo = a->fc[na - 1];
     hd.B = B; hd.A = A; hd.discount = d->hp.discount;
@@ -458,6 +466,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
     // the actors are one layer deeper than the critics' prefix (100-100-50 against 200-50): their last hidden layer joins the
     // heads kernel so that both stacks reach it, and leave it, in the same number of GEMM levels.  CPP_HEADS_PRE=0: GEMMs.
     static const bool no_pre = cpp_switch_off("CPP_HEADS_PRE");
+    // (an actor with two hidden layers and a feature layer norm: fc[na - 3] is the normalised layer, GE_NONE -- no `pre`)
     if (fused && !no_pre && na >= 3 && !a->drop_counter && a->fc[na - 2].act == GE_RELU && a->fc[na - 3].act == GE_RELU) {
       DdpgHeadsArgs hp = hd;
       const FcL& L2 = a->fc[na - 2];
@@ -469,9 +478,20 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
   }
   const int pre = (fused && hd.n1a > 0) ? 1 : 0;
   int adz = -1, cdz = -1;
+  // ---- feature layer norm: layer 0 of every network this pass runs is one GEMM level, and ONE ln launch stands behind it; its output
+  // (the critic's: shared by both evaluations) is what layer 1 reads
+  int aF = tA, taF = tTA, cP = tC, tcP = tTC, l0 = 0;
+  if (a->ln) {
+    cpp_net* ln_nets[4]; int ln_deps[4]; int nn = 0;
+    auto layer0 = [&](cpp_net* n, int dep) { ln_nets[nn] = n; ln_deps[nn++] = G.gemm(fc_fwd_args(n, n->ws[0], 0, B), {dep}); };
+    if (doA) layer0(a, tA);
+    layer0(c, tC);
+    if (doC) { layer0(ta, tTA); layer0(tc, tTC); }
+    aF = taF = cP = tcP = add_ln_forward(G, ctx, ln_nets, nn, ln_deps, B);
+    l0 = 1;
+  }
   if (fused) {
-    int aF = tA, taF = tTA;
-    for (int l = 0; l < na - 1 - pre; ++l) {
+    for (int l = l0; l < na - 1 - pre; ++l) {
       aF = G.gemm(fc_fwd_args(a, a->ws[0], l, B), {aF});
       taF = G.gemm(fc_fwd_args(ta, ta->ws[0], l, B), {taF});
     }
@@ -479,8 +499,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
       G.fn([=] { return bump_dropout(a); }, {aF});
       G.fn([=] { return bump_dropout(ta); }, {taF});
     }
-    int cP = tC, tcP = tTC;
-    for (int l = 0; l < cat; ++l) {
+    for (int l = l0; l < cat; ++l) {
       cP = G.gemm(fc_fwd_args(c, c->ws[0], l, B), {cP});
       tcP = G.gemm(fc_fwd_args(tc, tc->ws[0], l, B), {tcP});
     }
@@ -499,10 +518,14 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
     // (the helper's relu_grad_epi(c, l) is GE_MUL_RELU_GRAD for every critic: a CPP_CRITIC's hidden layers are built with GE_RELU,
     // dropout or not -- rt_net.cpp's constructor gives GE_RELU_DROPOUT to actors and NAF heads only)
     cdz = add_fc_backward(G, c, c->ws[0], B, cat - 1, hk, 1);
+    if (a->ln) {      // both chains stopped at g = dL/dy of layer 0
+      cpp_net* ln_nets[2] = {a, c}; int ln_deps[2] = {adz, cdz}; const int ln_lists[2] = {0, 1};
+      add_ln_backward(G, ctx, ln_nets, 2, ln_deps, ln_lists, B);
+      adz = ln_deps[0]; cdz = ln_deps[1];
+    }
   } else {      // the GEMM levels, each half's nodes only where one half is asked for
   const int cb = doC ? G.fn([=] { return launch_copy_cols(ctx, c->ws[0].fcin[cat], ldcat, Lcat.n_in - A, b->a, A, 0, A, B); }, {}) : -1;
-  int aF = tA, taF = tTA;
-  for (int l = 0; l < na; ++l) {
+  for (int l = l0; l < na; ++l) {
     GemmArgs g = fc_fwd_args(a, a->ws[0], l, B), t = fc_fwd_args(ta, ta->ws[0], l, B);
     if (l == na - 1 && !sac) {      // actions land directly in the critics' splice columns as well
       g.C2 = c->ws[1].fcin[cat] + (Lcat.n_in - A); g.ldc2 = ldcat;
@@ -522,8 +545,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
     if (doA) aF = G.fn([=] { return launch_sac_sample(ctx, sa); }, {aF});
     if (doC) taF = G.fn([=] { return launch_sac_sample(ctx, st); }, {taF});
   }
-  int cP = tC, tcP = tTC;
-  for (int l = 0; l < cat; ++l) {
+  for (int l = l0; l < cat; ++l) {
     GemmArgs g = fc_fwd_args(c, c->ws[0], l, B);
     if (l == cat - 1 && doA) { g.C2 = c->ws[1].fcin[cat]; g.ldc2 = ldcat; }   // same prefix for the second evaluation
     cP = G.gemm(g, {cP});
@@ -584,7 +606,7 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
   if (doC) cdz = G.fn([=] { return critic_td(d, b, B, train, per_w); }, {c0, tcH, c0b, tcHb});      // (twin: both heads of both critics; r_soft: job 2's, which tcH follows)
   if (doC && per.hook) G.fn(per.hook, {cdz});
   int cdz2 = cdz;      // head 2's chain down to the concat layer, level by level beside head 1's
-  for (int l = nc - 1; l >= 0 && doC && train; --l) {
+  for (int l = nc - 1; l >= (c->ln ? 1 : 0) && doC && train; --l) {      // (a feature layer norm: layer 0 is add_ln_backward's)
     const FcL& L = c->fc[l];
     G.gemm(sq_gemm(ctx, 1, fc_dw_args(c, c->ws[0], l, B, c->ws[0].dz[l])), {cdz});
     const int ncols = L.cat ? L.n_in - A : L.n_in;
@@ -595,11 +617,22 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
     if (twin && l == cat && l > 0) {      // the shared layer's dz: (head 1) + (head 2), then the mask
       const int h1 = G.gemm(fc_dx_args(c, l, B, c->ws[0].dz[l], L.n_out, 0, ncols, c->ws[0].dz[l - 1], ncols, GE_NONE, nullptr, 0), {cdz});
       cdz = G.gemm(twin_dx_args(c, c->ws[0], l, B), {h1, cdz2});
-    } else if (l > 0)
+    } else if (l == 1 && c->ln)      // g = dL/dy of the normalised layer: ln.hip owns its activation's derivative
+      cdz = G.gemm(fc_dx_args(c, l, B, c->ws[0].dz[l], L.n_out, 0, ncols, c->ws[0].dz[0], ncols, GE_NONE, nullptr, 0), {cdz});
+    else if (l > 0)
       cdz = G.gemm(fc_dx_args(c, l, B, c->ws[0].dz[l], L.n_out, 0, ncols, c->ws[0].dz[l - 1], ncols, GE_MUL_RELU_GRAD,
                               c->ws[0].fcin[l], L.n_in + 1), {cdz});
     else if (c->spec.pixel)
       cdz = G.gemm(fc_dx_args(c, 0, B, c->ws[0].dz[0], L.n_out, 0, c->flat, c->ws[0].dpool[2], c->flat, GE_NONE, nullptr, 0), {cdz});
+  }
+  if (a->ln) {      // the chains of the halves that ran a backward stopped at g = dL/dy of layer 0
+    cpp_net* ln_nets[2]; int ln_deps[2], ln_lists[2], nn = 0;
+    if (doA) { ln_nets[nn] = a; ln_deps[nn] = adz; ln_lists[nn++] = 0; }
+    if (doC && train) { ln_nets[nn] = c; ln_deps[nn] = cdz; ln_lists[nn++] = 1; }
+    if (nn) add_ln_backward(G, ctx, ln_nets, nn, ln_deps, ln_lists, B);
+    nn = 0;
+    if (doA) adz = ln_deps[nn++];
+    if (doC && train) cdz = ln_deps[nn++];
   }
   }
   int conv_bwd = -1;
@@ -1250,6 +1283,22 @@ extern "C" int cpp_ddpg_last_sac(cpp_ddpg* d, int B, float* eps, float* a, float
     *g_alpha = np ? (float)(-(s / (double)rows)) : 0.f;
   }
   return CPP_OK;
+}
+
+// What the last gradient pass left of the feature layer norm of the actor (which = 0) or the critic (1): include/cartpolepp_abi.h
+extern "C" int cpp_ddpg_last_feature_norm(cpp_ddpg* d, int B, int which, float* xhat, float* rstd, float* y, float* dz, float* dgamma, float* dbeta) {
+  ARG_CHECK(d, "cpp_ddpg_last_feature_norm: NULL argument");
+  ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_feature_norm: batch %d outside [1,%d]", B, d->maxB);
+  ARG_CHECK(which == 0 || which == 1, "cpp_ddpg_last_feature_norm: which %d (0: the actor, 1: the critic)", which);
+  if (!d->actor->ln) { cpp_set_error("cpp_ddpg_last_feature_norm: the trainer's networks have no feature layer norm"); return CPP_ERR_STATE; }
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  cpp_net* n = which ? d->critic : d->actor;
+  const Workspace& w = n->ws[0];
+  const int width = n->fc[0].n_out;
+  const size_t row = (size_t)width * sizeof(float), all = (size_t)B * row;
+  if (y) HIP_CHECK(hipMemcpy2DAsync(y, row, w.fcin[1], (size_t)(n->fc[1].n_in + 1) * sizeof(float), row, B, hipMemcpyDeviceToHost, d->ctx->stream));
+  return read_back(d->ctx, {{xhat, w.ln_xhat, all}, {rstd, w.ln_rstd, (size_t)B * sizeof(float)}, {dz, w.dz[0], all},
+                            {dgamma, n->grads + n->ln_g_off, row}, {dbeta, n->grads + n->ln_b_off, row}});
 }
 
 // log_alpha, Adam's slots and its count for checkpoints (util.py:88-90: tf.train.Saver saves every variable of the graph).  set == 0: read

@@ -84,6 +84,9 @@ struct Workspace {
   // distributional critic (cpp_net_create_distributional): the last layer's N logits land here, (maxB, N), and `out` holds Q = sum_i p_i z_i,
   // (maxB), which dist.hip writes -- every reader of `out` keeps its width of one.  nullptr for every other network.
   float* logits = nullptr;
+  // feature layer norm (cpp_net_create_feature_norm): xhat, (maxB, fc[0].n_out), and rstd, (maxB), of the last forward of layer 0 -- the
+  // first workspace's; a critic's second evaluation shares them with the prefix.  nullptr for every other network.
+  float *ln_xhat = nullptr, *ln_rstd = nullptr;
 };
 
 struct cpp_net {
@@ -117,6 +120,9 @@ struct cpp_net {
   // Gaussian actor (cpp_net_create_gaussian): output_action is 2A wide, (m | x), and lands in `logits`; `out` stays (maxB, A) and holds
   // the action sac.hip forms from it.  ls = lo + 0.5 (hi - lo) (tanh(x) + 1).  gauss_stage: (2, maxB, A) for cpp_net_forward_gaussian
   bool gauss = false; float ls_lo = 0.f, ls_hi = 0.f; float* gauss_stage = nullptr;
+  // feature layer norm (cpp_net_create_feature_norm): fc[0] is a plain GEMM (GE_NONE) and ln.hip stands behind it -- y = act(gamma xhat
+  // + beta) with ln_act GE_TANH or GE_RELU.  '<layer0>/LayerNorm/gamma' and '.../beta' sit behind every other variable of the flat buffer
+  bool ln = false; int ln_act = GE_TANH; float ln_eps = 0.f; long ln_g_off = 0, ln_b_off = 0;
 };
 
 struct cpp_batch {
@@ -306,6 +312,10 @@ void set_dropout(GemmArgs& g, cpp_net* n, int l);
 int relu_grad_epi(const cpp_net* n, int producer_layer);
 int bump_dropout(cpp_net* n);
 int net_forward_fc(cpp_net* n, Workspace& w, int from, int B, const float* action);
+// feature layer norm behind the layer-0 GEMMs of `nn` networks (their first workspaces), one launch: the inference path's call
+int ln_forward(cpp_ctx* ctx, cpp_net* const* nets, int nn, int B);
+// ... and the same launch as a node of a gradient pass, behind the GEMM level that holds those GEMMs (deps; -1: none).  Returns the node.
+int add_ln_forward(struct OpGraph& G, cpp_ctx* ctx, cpp_net* const* nets, int nn, const int* deps, int B);
 int net_backward_conv(cpp_net* n, Workspace& w, int B, const void* state, int dtype, const float* white);
 int nets_backward_conv(cpp_ctx* ctx, cpp_net* const* nets, int nn, int B, const void* state, int dtype, const float* white);
 GemmArgs fc_fwd_args(cpp_net* n, Workspace& w, int l, int B);
@@ -384,6 +394,8 @@ struct SqScope {
 };
 // a dW GEMM of `list` takes the next slots of its region -- in call order, which is the order the optimiser adds them in
 GemmArgs sq_gemm(cpp_ctx* ctx, int list, GemmArgs g);
+// ... and so does any other kernel that writes gradients of the list: the next `count` slots, or nullptr (folding off, or the region is full)
+double* sq_take(cpp_ctx* ctx, int list, int count);
 // conv1 addresses its images through the sampled slots while the scope lives: `s1` read state_1's, `s2` state_2's (at most four networks)
 struct SlotScope {
   cpp_net* n[4]; int nn = 0;
@@ -472,4 +484,10 @@ int read_back(cpp_ctx* ctx, std::initializer_list<Readback> items, bool through_
 // backward of the fully connected stack of a network without an action splice, from layer `start` down: per layer [dW; db] (into the
 // list's norm partials: sq_gemm) then dX, two independent GEMMs.  skip_dx: the layer whose dX a kernel in front has already produced.
 // Returns the op that completes d(flat) (pixel) / dz[0].
+// A network with a feature layer norm: the chain stops behind layer 1's dX, taken with GE_NONE into dz[0] (g = dL/dy; ln.hip owns the
+// activation's derivative), and add_ln_backward finishes it.
 int add_fc_backward(OpGraph& G, cpp_net* n, Workspace& w, int B, int start, int dep, int list, int skip_dx = -1);
+// The backward of the feature layer norm of `nn` trained networks (1 or 2) in two launches for all of them -- the column sums dgamma /
+// dbeta (into lists[k]'s norm partials), then g -> dz in place on dz[0] -- and layer 0's [dW; db] and dX behind them.  deps[k]: the op
+// that completed network k's dz[0]; on return the op that completed its d(flat).
+void add_ln_backward(OpGraph& G, cpp_ctx* ctx, cpp_net* const* nets, int nn, int* deps, const int* lists, int B);

@@ -67,6 +67,19 @@ static int net_build(cpp_net* n) {
       n->fc.pop_back();
     }
   }
+  // feature layer norm: layer 0 is a plain GEMM, its activation is ln.hip's; gamma and beta behind every other variable, twin ones
+  // included -- the plain prefix of the flat buffer keeps its names, shapes and offsets
+  if (n->ln) {
+    n->fc[0].act = GE_NONE;
+    const int width = n->fc[0].n_out;
+    for (int k = 0; k < 2; ++k) {
+      VarInfo v; v.name = n->fc[0].name + (k == 0 ? "/LayerNorm/gamma" : "/LayerNorm/beta"); v.rank = 1;
+      v.shape[0] = width; v.shape[1] = v.shape[2] = v.shape[3] = 0; v.offset = off;
+      (k == 0 ? n->ln_g_off : n->ln_b_off) = off;
+      off += width;
+      n->vars.push_back(v);
+    }
+  }
   n->nparams = off;
   return CPP_OK;
 }
@@ -104,6 +117,10 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
     }
     RC(dalloc(n->arena, &w.out2, (size_t)mb * n->fc2.back().n_out));
   }
+  if (trunk && n->ln) {
+    RC(dalloc(n->arena, &w.ln_xhat, (size_t)mb * n->fc[0].n_out));
+    RC(dalloc(n->arena, &w.ln_rstd, (size_t)mb));
+  }
   if (trunk && n->spec.pixel) {
     for (int i = 0; i < 3; ++i) {
       const ConvL& L = n->conv[i];
@@ -123,7 +140,30 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
 }
 
 static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out, int dist_n = 0, float v_min = 0.f, float v_max = 0.f,
-                      bool quant = false, bool gauss = false, float ls_lo = 0.f, float ls_hi = 0.f);
+                      bool quant = false, bool gauss = false, float ls_lo = 0.f, float ls_hi = 0.f, int ln_act = 0, float ln_eps = 0.f);
+// the variants' own argument rules, shared by their constructors and cpp_net_create_feature_norm (who: the entry point's name)
+static int check_twin(const char* who, const cpp_net_spec* spec) {
+  ARG_CHECK(spec->kind == CPP_CRITIC, "%s: kind %d (twin Q heads belong to a critic)", who, spec->kind);
+  return CPP_OK;
+}
+static int check_distributional(const char* who, const cpp_net_spec* spec, int n_atoms, float v_min, float v_max) {
+  ARG_CHECK(spec->kind == CPP_CRITIC, "%s: kind %d (a value distribution belongs to a critic)", who, spec->kind);
+  ARG_CHECK(n_atoms >= 2 && n_atoms <= 64, "%s: %d atoms outside [2, 64]", who, n_atoms);
+  ARG_CHECK(std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max, "%s: support [%g, %g] (finite, v_min < v_max)", who, (double)v_min, (double)v_max);
+  return CPP_OK;
+}
+static int check_quantile(const char* who, const cpp_net_spec* spec, int n_quantiles) {
+  ARG_CHECK(spec->kind == CPP_CRITIC, "%s: kind %d (quantiles belong to a critic)", who, spec->kind);
+  ARG_CHECK(n_quantiles >= 2 && n_quantiles <= 64, "%s: %d quantiles outside [2, 64]", who, n_quantiles);
+  return CPP_OK;
+}
+static int check_gaussian(const char* who, const cpp_net_spec* spec, float log_std_min, float log_std_max) {
+  ARG_CHECK(spec->kind == CPP_ACTOR, "%s: kind %d (a Gaussian policy belongs to an actor)", who, spec->kind);
+  ARG_CHECK(std::isfinite(log_std_min) && std::isfinite(log_std_max) && log_std_min < log_std_max, "%s: log std bounds [%g, %g] (finite, min < max)", who,
+            (double)log_std_min, (double)log_std_max);
+  ARG_CHECK(spec->action_dim >= 1 && spec->action_dim <= 64, "%s: action_dim %d outside [1, 64]", who, spec->action_dim);
+  return CPP_OK;
+}
 extern "C" int cpp_net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, cpp_net** out) {
   return net_create(ctx, spec, max_batch, false, out);
 }
@@ -131,7 +171,7 @@ extern "C" int cpp_net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_ba
 // ddpg_cartpole.py:166-171): see include/cartpolepp_abi.h
 extern "C" int cpp_net_create_twin_q(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, cpp_net** out) {
   ARG_CHECK(ctx && spec && out, "cpp_net_create_twin_q: NULL argument");
-  ARG_CHECK(spec->kind == CPP_CRITIC, "cpp_net_create_twin_q: kind %d (twin Q heads belong to a critic)", spec->kind);
+  RC(check_twin("cpp_net_create_twin_q", spec));
   return net_create(ctx, spec, max_batch, true, out);
 }
 extern "C" int cpp_net_is_twin_q(const cpp_net* n) { return (n && n->twin) ? 1 : 0; }
@@ -140,10 +180,7 @@ extern "C" int cpp_net_is_twin_q(const cpp_net* n) { return (n && n->twin) ? 1 :
 // ddpg_cartpole.py:166-177): see include/cartpolepp_abi.h
 extern "C" int cpp_net_create_distributional(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, int n_atoms, float v_min, float v_max, cpp_net** out) {
   ARG_CHECK(ctx && spec && out, "cpp_net_create_distributional: NULL argument");
-  ARG_CHECK(spec->kind == CPP_CRITIC, "cpp_net_create_distributional: kind %d (a value distribution belongs to a critic)", spec->kind);
-  ARG_CHECK(n_atoms >= 2 && n_atoms <= 64, "cpp_net_create_distributional: %d atoms outside [2, 64]", n_atoms);
-  ARG_CHECK(std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max, "cpp_net_create_distributional: support [%g, %g] (finite, v_min < v_max)",
-            (double)v_min, (double)v_max);
+  RC(check_distributional("cpp_net_create_distributional", spec, n_atoms, v_min, v_max));
   return net_create(ctx, spec, max_batch, false, out, n_atoms, v_min, v_max);
 }
 extern "C" int cpp_net_distribution_info(const cpp_net* n, int* n_atoms, float* v_min, float* v_max) {
@@ -158,8 +195,7 @@ extern "C" int cpp_net_distribution_info(const cpp_net* n, int* n_atoms, float* 
 // workspace are the distributional critic's; what reads them differs (quant.hip)
 extern "C" int cpp_net_create_quantile(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, int n_quantiles, cpp_net** out) {
   ARG_CHECK(ctx && spec && out, "cpp_net_create_quantile: NULL argument");
-  ARG_CHECK(spec->kind == CPP_CRITIC, "cpp_net_create_quantile: kind %d (quantiles belong to a critic)", spec->kind);
-  ARG_CHECK(n_quantiles >= 2 && n_quantiles <= 64, "cpp_net_create_quantile: %d quantiles outside [2, 64]", n_quantiles);
+  RC(check_quantile("cpp_net_create_quantile", spec, n_quantiles));
   return net_create(ctx, spec, max_batch, false, out, n_quantiles, 0.f, 0.f, true);
 }
 // the critic of ddpg_cartpole.py:166-177 widened: N of a network made by cpp_net_create_quantile, 0 for any other
@@ -172,10 +208,7 @@ extern "C" int cpp_net_quantile_info(const cpp_net* n, int* n_quantiles) {
 // extension of ddpg_cartpole.py:95-100): see include/cartpolepp_abi.h
 extern "C" int cpp_net_create_gaussian(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, float log_std_min, float log_std_max, cpp_net** out) {
   ARG_CHECK(ctx && spec && out, "cpp_net_create_gaussian: NULL argument");
-  ARG_CHECK(spec->kind == CPP_ACTOR, "cpp_net_create_gaussian: kind %d (a Gaussian policy belongs to an actor)", spec->kind);
-  ARG_CHECK(std::isfinite(log_std_min) && std::isfinite(log_std_max) && log_std_min < log_std_max,
-            "cpp_net_create_gaussian: log std bounds [%g, %g] (finite, min < max)", (double)log_std_min, (double)log_std_max);
-  ARG_CHECK(spec->action_dim >= 1 && spec->action_dim <= 64, "cpp_net_create_gaussian: action_dim %d outside [1, 64]", spec->action_dim);
+  RC(check_gaussian("cpp_net_create_gaussian", spec, log_std_min, log_std_max));
   return net_create(ctx, spec, max_batch, false, out, 0, 0.f, 0.f, false, true, log_std_min, log_std_max);
 }
 // the actor of ddpg_cartpole.py:95-100 widened: 1 and the bounds for a network made by cpp_net_create_gaussian, 0 for any other
@@ -186,6 +219,81 @@ extern "C" int cpp_net_gaussian_info(const cpp_net* n, int* gaussian, float* log
   if (log_std_max) *log_std_max = n->ls_hi;
   return CPP_OK;
 }
+// A pixel network whose fully connected layer 0 is Linear -> LayerNorm -> tanh / relu (the trunk of DrQ-v2, Yarats et al. 2021; an
+// extension of ddpg_cartpole.py:95 'h0' and :168 'hidden1'): see include/cartpolepp_abi.h.  v: the variant it composes with.
+extern "C" int cpp_net_create_feature_norm(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, const cpp_net_variant* v, int activation, float epsilon,
+                                           cpp_net** out) {
+  ARG_CHECK(ctx && spec && out, "cpp_net_create_feature_norm: NULL argument");
+  ARG_CHECK(spec->kind == CPP_ACTOR || spec->kind == CPP_CRITIC, "cpp_net_create_feature_norm: kind %d (an actor or a critic of the DDPG learner)", spec->kind);
+  ARG_CHECK(spec->pixel, "cpp_net_create_feature_norm: a low-dimensional network (there are no conv features to normalise)");
+  ARG_CHECK(!spec->use_batch_norm, "cpp_net_create_feature_norm: use_batch_norm (one normalisation: the feature layer norm or the convs' batch norm)");
+  ARG_CHECK(!spec->use_dropout, "cpp_net_create_feature_norm: use_dropout (the normalised layer would be dropped behind its activation)");
+  ARG_CHECK(activation == CPP_NORM_TANH || activation == CPP_NORM_RELU, "cpp_net_create_feature_norm: activation %d (CPP_NORM_TANH or CPP_NORM_RELU)", activation);
+  ARG_CHECK(std::isfinite(epsilon) && epsilon > 0.f, "cpp_net_create_feature_norm: epsilon %g (finite, positive)", (double)epsilon);
+  const int width = spec->kind == CPP_ACTOR ? (spec->n_hidden >= 1 ? spec->hidden[0] : 0) : 200;
+  ARG_CHECK(width >= 1 && width <= LN_MAX_WIDTH, "cpp_net_create_feature_norm: layer 0 has width %d outside [1, %d]", width, LN_MAX_WIDTH);
+  const int ln_act = activation == CPP_NORM_TANH ? GE_TANH : GE_RELU;
+  static const cpp_net_variant plain = {0, 0, 0.f, 0.f, 0, 0, 0.f, 0.f};
+  if (!v) v = &plain;
+  const int picked = (v->twin_q ? 1 : 0) + (v->n_atoms ? 1 : 0) + (v->n_quantiles ? 1 : 0) + (v->gaussian ? 1 : 0);
+  ARG_CHECK(picked <= 1, "cpp_net_create_feature_norm: %d variants at once (twin_q, n_atoms, n_quantiles, gaussian: at most one)", picked);
+  const char* who = "cpp_net_create_feature_norm";
+  if (v->n_atoms) {
+    RC(check_distributional(who, spec, v->n_atoms, v->v_min, v->v_max));
+    return net_create(ctx, spec, max_batch, false, out, v->n_atoms, v->v_min, v->v_max, false, false, 0.f, 0.f, ln_act, epsilon);
+  }
+  if (v->n_quantiles) {
+    RC(check_quantile(who, spec, v->n_quantiles));
+    return net_create(ctx, spec, max_batch, false, out, v->n_quantiles, 0.f, 0.f, true, false, 0.f, 0.f, ln_act, epsilon);
+  }
+  if (v->gaussian) {
+    RC(check_gaussian(who, spec, v->log_std_min, v->log_std_max));
+    return net_create(ctx, spec, max_batch, false, out, 0, 0.f, 0.f, false, true, v->log_std_min, v->log_std_max, ln_act, epsilon);
+  }
+  if (v->twin_q) RC(check_twin(who, spec));
+  return net_create(ctx, spec, max_batch, v->twin_q != 0, out, 0, 0.f, 0.f, false, false, 0.f, 0.f, ln_act, epsilon);
+}
+// on = 1, the activation and epsilon of a network made by cpp_net_create_feature_norm; on = 0 for any other
+extern "C" int cpp_net_feature_norm_info(const cpp_net* n, int* on, int* activation, float* epsilon) {
+  ARG_CHECK(n, "cpp_net_feature_norm_info: NULL argument");
+  if (on) *on = n->ln ? 1 : 0;
+  if (activation) *activation = n->ln_act == GE_RELU ? CPP_NORM_RELU : CPP_NORM_TANH;
+  if (epsilon) *epsilon = n->ln_eps;
+  return CPP_OK;
+}
+// the ln.hip job of a network's first workspace (backward pointers once a trainer has bound the gradient buffer)
+static LnJob ln_job(cpp_net* n) {
+  Workspace& w = n->ws[0];
+  LnJob j; memset(&j, 0, sizeof(j));
+  j.io = w.fcin[1]; j.ld = n->fc[1].n_in + 1; j.n = n->fc[0].n_out;
+  j.gamma = n->params + n->ln_g_off; j.beta = n->params + n->ln_b_off; j.xhat = w.ln_xhat; j.rstd = w.ln_rstd;
+  if (n->grads) { j.dz = w.dz[0]; j.dgamma = n->grads + n->ln_g_off; j.dbeta = n->grads + n->ln_b_off; }
+  return j;
+}
+static LnArgs ln_args(cpp_net* const* nets, int nn, int B) {
+  LnArgs a; memset(&a, 0, sizeof(a));
+  a.count = nn; a.B = B; a.act = nets[0]->ln_act; a.eps = nets[0]->ln_eps;
+  for (int k = 0; k < nn && k < LN_JOBS_MAX; ++k) a.j[k] = ln_job(nets[k]);
+  return a;
+}
+int ln_forward(cpp_ctx* ctx, cpp_net* const* nets, int nn, int B) { return launch_ln_forward(ctx, ln_args(nets, nn, B)); }
+int add_ln_forward(OpGraph& G, cpp_ctx* ctx, cpp_net* const* nets, int nn, const int* deps, int B) {
+  const LnArgs a = ln_args(nets, nn, B);
+  return G.fn([=] { return launch_ln_forward(ctx, a); }, {deps[0], nn > 1 ? deps[1] : -1, nn > 2 ? deps[2] : -1, nn > 3 ? deps[3] : -1});
+}
+void add_ln_backward(OpGraph& G, cpp_ctx* ctx, cpp_net* const* nets, int nn, int* deps, const int* lists, int B) {
+  LnArgs a = ln_args(nets, nn, B);
+  for (int k = 0; k < nn; ++k) a.j[k].sq_part = sq_take(ctx, lists[k], ln_col_blocks(a.j[k].n));
+  const int cols = G.fn([=] { return launch_ln_backward_cols(ctx, a); }, {deps[0], nn > 1 ? deps[1] : -1});
+  const int rows = G.fn([=] { return launch_ln_backward_rows(ctx, a); }, {cols});
+  for (int k = 0; k < nn; ++k) {
+    cpp_net* n = nets[k];
+    Workspace& w = n->ws[0];
+    G.gemm(sq_gemm(ctx, lists[k], fc_dw_args(n, w, 0, B, w.dz[0])), {rows});
+    deps[k] = G.gemm(fc_dx_args(n, 0, B, w.dz[0], n->fc[0].n_out, 0, n->flat, w.dpool[2], n->flat, GE_NONE, nullptr, 0), {rows});
+  }
+}
+
 int gauss_mean(cpp_net* n, Workspace& w, int B, float* m_out, float* ls_out) {
   if (!n->gauss) return CPP_OK;
   SacSampleArgs s; memset(&s, 0, sizeof(s));
@@ -200,7 +308,7 @@ int dist_expect(cpp_net* n, Workspace& w, int B, float* dz) {
 }
 
 static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out, int dist_n, float v_min, float v_max, bool quant,
-                      bool gauss, float ls_lo, float ls_hi) {
+                      bool gauss, float ls_lo, float ls_hi, int ln_act, float ln_eps) {
   ARG_CHECK(ctx && spec && out, "cpp_net_create: NULL argument");
   ARG_CHECK(max_batch >= 1, "cpp_net_create: max_batch %d", max_batch);
   ARG_CHECK(spec->kind == CPP_ACTOR || spec->kind == CPP_CRITIC || spec->kind == CPP_HEAD, "cpp_net_create: kind %d", spec->kind);
@@ -227,12 +335,14 @@ static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, boo
   n->twin = twin;
   n->dist_n = dist_n; n->dist_vmin = v_min; n->dist_vmax = v_max; n->quant = quant;
   n->gauss = gauss; n->ls_lo = ls_lo; n->ls_hi = ls_hi;
+  n->ln = ln_act != 0; n->ln_act = ln_act ? ln_act : GE_TANH; n->ln_eps = ln_eps;      // (ln_act: GE_TANH / GE_RELU, 0: no feature layer norm)
   int rc = net_build(n);
   if (rc) { delete n; return rc; }
   auto fail = [&](int r) { n->arena.release(); delete n; return r; };
   if ((rc = dalloc(n->arena, &n->params, (size_t)n->nparams))) return fail(rc);
   if (spec->use_dropout && (rc = n->arena.alloc((void**)&n->drop_counter, sizeof(uint64_t), true))) return fail(rc);
   if ((rc = ws_alloc(n, n->ws[0], 0, true))) return fail(rc);
+  if (n->ln && (rc = launch_fill(ctx, n->params + n->ln_g_off, 1, 0, 1, n->fc[0].n_out, 1.0f))) return fail(rc);      // (gamma = 1, beta = 0)
   if (spec->kind == CPP_CRITIC) {
     n->ws[1] = n->ws[0];
     n->ws[1].fcin2.clear(); n->ws[1].dz2.clear(); n->ws[1].out2 = nullptr;
@@ -468,6 +578,7 @@ int net_forward_fc(cpp_net* n, Workspace& w, int from, int B, const float* actio
     GemmArgs g = mk_gemm(w.fcin[l], L.n_in + 1, 1, n->params + L.w_off, L.n_out, 1, C, ldc, B, L.n_out, L.n_in + 1, L.act, nullptr, 0);
     set_dropout(g, n, l);
     RC(launch_gemm(ctx, g));
+    if (l == 0 && n->ln) RC(ln_forward(ctx, &n, 1, B));
   }
   return from == 0 ? bump_dropout(n) : CPP_OK;
 }
@@ -646,11 +757,13 @@ GemmArgs fc_dx_args(cpp_net* n, int l, int B, const float* dz, long dz_ld, int c
 }
 // (rt_internal.h.  dW before dX per layer, top down: sq_gemm hands out the norm partials' slots in this order)
 int add_fc_backward(OpGraph& G, cpp_net* n, Workspace& w, int B, int start, int dep, int list, int skip_dx) {
-  for (int l = start; l >= 0; --l) {
+  for (int l = start; l >= (n->ln ? 1 : 0); --l) {      // (a feature layer norm: layer 0 is add_ln_backward's)
     const FcL& L = n->fc[l];
     G.gemm(sq_gemm(n->ctx, list, fc_dw_args(n, w, l, B, w.dz[l])), {dep});
     if (l == skip_dx) continue;
-    if (l > 0)
+    if (l == 1 && n->ln)      // g = dL/dy of the normalised layer: ln.hip owns its activation's derivative
+      dep = G.gemm(fc_dx_args(n, l, B, w.dz[l], L.n_out, 0, L.n_in, w.dz[0], L.n_in, GE_NONE, nullptr, 0), {dep});
+    else if (l > 0)
       dep = G.gemm(fc_dx_args(n, l, B, w.dz[l], L.n_out, 0, L.n_in, w.dz[l - 1], L.n_in, relu_grad_epi(n, l - 1), w.fcin[l], L.n_in + 1), {dep});
     else if (n->spec.pixel)
       dep = G.gemm(fc_dx_args(n, 0, B, w.dz[0], L.n_out, 0, n->flat, w.dpool[2], n->flat, GE_NONE, nullptr, 0), {dep});

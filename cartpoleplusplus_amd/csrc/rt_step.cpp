@@ -10,6 +10,14 @@ GemmArgs sq_gemm(cpp_ctx* ctx, int list, GemmArgs g) {
   return g;
 }
 
+double* sq_take(cpp_ctx* ctx, int list, int count) {
+  if (ctx->sq_n[list] < 0) return nullptr;
+  if (ctx->sq_n[list] + count > SQ_REGION) { ctx->sq_n[list] = -1; return nullptr; }
+  double* p = ctx->sq_part + list * SQ_REGION + ctx->sq_n[list];
+  ctx->sq_n[list] += count;
+  return p;
+}
+
 StatsRide next_stats_ride(cpp_ctx* ctx, const NextBatch& nx) {
   StatsRide sr;
   sr.part = nx.b->part; sr.white = nx.b->white; sr.nparts = nx.B; sr.jobs = 2 * nx.C; sr.C = nx.C;

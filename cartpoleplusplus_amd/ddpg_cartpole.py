@@ -190,11 +190,42 @@ def build_parser():
     a('--sac-log-std-min', type=float, default=argparse.SUPPRESS, help="--soft-actor-critic: lower bound of the policy's log std (default -10)")
     a('--sac-log-std-max', type=float, default=argparse.SUPPRESS, help="--soft-actor-critic: upper bound of the policy's log std (default 2)")
     a('--sac-seed', type=int, default=argparse.SUPPRESS, help="--soft-actor-critic: seed of the policy noise on the device (default 0)")
+    # feature layer norm (an extension beyond the reference, ddpg_cartpole.py:95, :168: the trunk of DrQ-v2, Yarats et al. 2021):
+    # Linear -> LayerNorm -> tanh on the first fully connected layer of actor and critic, between the conv features and the MLP; with
+    # --twin-q, --n-step 3, --target-policy-noise and random shift this is DrQ-v2 (absent unless given; feature_layer_norm() reads them)
+    a('--feature-layer-norm', action='store_true', default=argparse.SUPPRESS,
+      help="pixel networks: layer-normalise the first fully connected layer of actor and critic (Linear -> LayerNorm -> tanh)")
+    a('--feature-norm-activation', type=str, default=argparse.SUPPRESS, choices=list(FEATURE_NORM_ACTIVATIONS),
+      help="--feature-layer-norm: the activation behind the normalisation (default tanh)")
     # n-step returns for this learner (ReplayMemory.enable_n_step; absent unless given): with --prioritized-replay, --data-parallel and
     # --distributional-critic this is D4PG from the command line
     a('--n-step', type=int, default=argparse.SUPPRESS,
       help="train on n-step returns: reward = sum_k discount^k r_k, bootstrap with discount^n (default 1: one-step transitions)")
     return parser
+
+
+FEATURE_NORM_ACTIVATIONS = ("tanh", "relu")
+FEATURE_NORM_EPSILON = 1e-5      # torch.nn.LayerNorm's default, which DrQ-v2 uses (there is no flag for it)
+
+
+def feature_layer_norm(o):
+    """(activation, epsilon) of --feature-layer-norm / --feature-norm-activation, or None (off); refuses what cannot be meant."""
+    on = bool(getattr(o, "feature_layer_norm", False))
+    act = getattr(o, "feature_norm_activation", None)
+    if not on:
+        if act is not None:
+            raise SystemExit("--feature-norm-activation needs --feature-layer-norm")
+        return None
+    act = "tanh" if act is None else act
+    if act not in FEATURE_NORM_ACTIVATIONS:
+        raise SystemExit("--feature-norm-activation %r is not one of %s" % (act, ", ".join(FEATURE_NORM_ACTIVATIONS)))
+    if not bool(getattr(o, "use_raw_pixels", False)):
+        raise SystemExit("--feature-layer-norm needs --use-raw-pixels: a low-dimensional network has no conv features to normalise")
+    if bool(getattr(o, "use_batch_norm", False)):
+        raise SystemExit("--feature-layer-norm cannot be combined with --use-batch-norm")
+    if bool(getattr(o, "use_dropout", False)):
+        raise SystemExit("--feature-layer-norm cannot be combined with --use-dropout")
+    return (act, FEATURE_NORM_EPSILON)
 
 
 DDPG_OPTIMISERS = {"GradientDescent": _lib.CPP_OPT_SGD, "Momentum": _lib.CPP_OPT_MOMENTUM, "Adam": _lib.CPP_OPT_ADAM}
@@ -436,6 +467,7 @@ def default_opts(**overrides):
     o.quantile_critic, o.num_quantiles, o.quantile_huber_kappa, o.drop_top_quantiles = False, None, None, None
     o.n_step = 1
     o.soft_actor_critic = False
+    o.feature_layer_norm, o.feature_norm_activation = False, None
     for k in _SAC_DEFAULTS:
         setattr(o, k, None)
     for k, v in overrides.items():
@@ -479,8 +511,10 @@ class ActorNetwork(base_network.Network):
         self.input_state_network(self.input_state, opts)
         # --soft-actor-critic: output_action emits (m | x), 2A wide; forward returns tanh(m), exploration samples on the host
         self.sac = soft_actor_critic(opts, action_dim)
+        # --feature-layer-norm: h0 is Linear -> LayerNorm -> tanh (the same in every forward: there is no training / inference distinction)
+        self.feature_norm = feature_layer_norm(opts)
         self._build_native(_lib.CPP_ACTOR, action_dim, max(int(opts.batch_size), 1),
-                           gaussian=(self.sac["log_std_min"], self.sac["log_std_max"]) if self.sac else None)
+                           gaussian=(self.sac["log_std_min"], self.sac["log_std_max"]) if self.sac else None, feature_norm=self.feature_norm)
         self._sac_rng = np.random.default_rng(self.sac["seed"]) if self.sac else None
         self.output_action = _OpHandle(namespace + "/output_action")
         self.train_op = None
@@ -730,6 +764,21 @@ class _Trainer(object):
         o.update(alpha=float(alpha.value), g_alpha=float(g.value), n=int(n.value))
         return o
 
+    def last_feature_norm(self, B):
+        """what the last gradient pass of a --feature-layer-norm trainer left of the normalised layer: {"actor": .., "critic": ..}, each a
+        dict of xhat, y, dz (B, n), rstd (B) and dgamma, dbeta (n) before the clip, n the width of that network's first fully connected layer"""
+        B, out = int(B), {}
+        for which, (name, net) in enumerate((("actor", self.nets[0]), ("critic", self.nets[1]))):
+            n = [v for v in net.trainable_model_vars() if v.name.endswith("/LayerNorm/gamma:0")]
+            n = n[0].shape[0] if n else 1
+            o = {k: np.empty((B, n), np.float32) for k in ("xhat", "y", "dz")}
+            o["rstd"] = np.empty(B, np.float32)
+            o.update({k: np.empty(n, np.float32) for k in ("dgamma", "dbeta")})
+            check(lib.cpp_ddpg_last_feature_norm(self.handle, B, which, ptr(o["xhat"]), ptr(o["rstd"]), ptr(o["y"]), ptr(o["dz"]),
+                                                 ptr(o["dgamma"]), ptr(o["dbeta"])))
+            out[name] = o
+        return out
+
     def get_sac_state(self):
         """{log_alpha, m, v, step}: the temperature and its Adam state (checkpoints; the noise count is not part of it)"""
         la, m, v, t = C.c_float(), C.c_float(), C.c_float(), C.c_uint64()
@@ -831,8 +880,10 @@ class CriticNetwork(base_network.Network):
         self.distribution = distributional_critic(opts)
         # --quantile-critic: q_value emits num_quantiles quantile atoms; q_value, forward and dQ/da are their mean
         self.quantiles = quantile_critic(opts)
+        # --feature-layer-norm: hidden1 is Linear -> LayerNorm -> tanh
+        self.feature_norm = feature_layer_norm(opts)
         self._build_native(_lib.CPP_CRITIC, self.action_dim, max(int(opts.batch_size), 1), twin_q=self.twin_q, distribution=self.distribution,
-                           quantiles=self.quantiles[0] if self.quantiles else None)
+                           quantiles=self.quantiles[0] if self.quantiles else None, feature_norm=self.feature_norm)
         self.q_value = _OpHandle(namespace + "/q_value")
         self.target_critic = None
         self._ddpg = None
@@ -921,6 +972,7 @@ class DeepDeterministicPolicyGradientAgent(object):
         distributional_critic(opts)
         quantile_critic(opts)
         soft_actor_critic(opts, action_dim)
+        feature_layer_norm(opts)
         n_step(opts)
         # (--exact-products asks for the exact arithmetic contract; without the flag the context keeps whatever mode its owner chose --
         # an explicit Context.set_precision("exact") is not undone, and a second agent on the shared context does not fight the first)

@@ -247,6 +247,45 @@ int cpp_net_gaussian_info(const cpp_net* net, int* gaussian, float* log_std_min,
 /* The head of a Gaussian actor on a fed state batch (ddpg_cartpole.py:123-125 widened; the exploration noise of :127-134 stays on the
  * host): m and ls, each (B, A); each != 0: every row whitened with its own statistics, as cpp_net_forward_each. */
 int cpp_net_forward_gaussian(cpp_net* net, const void* state, int state_dtype, int B, int each, float* m, float* ls);
+/* Feature layer norm: Linear -> LayerNorm -> tanh on the first fully connected layer, between the conv features and the MLP (the trunk of
+ * DrQ-v2, Yarats et al. 2021; layer normalisation: Ba et al. 2016), an extension of the actor's 'h0' (ddpg_cartpole.py:95, through
+ * base_network.py:64-71) and of the pixel critic's 'hidden1' (ddpg_cartpole.py:168).  Pixel networks only.  Per row b of layer 0, of width
+ * n <= 1024, with z = [x, 1][W; b] from the layer's GEMM, which has no activation of its own.  All arithmetic is float32, every operation
+ * rounded on its own:
+ *   mu = mean_j z_j          var = mean_j (z_j - mu)^2          (biased, two passes)
+ *   rstd = 1 / sqrt(var + epsilon)          xhat_j = (z_j - mu) rstd
+ *   u_j = gamma_j xhat_j + beta_j           y_j = act(u_j),  act = tanh (CPP_NORM_TANH) or relu (CPP_NORM_RELU)
+ * Backward, with g = dL/dy from the layer above (no activation derivative applied yet):
+ *   du = g act'(y)           (1 - y^2, or y > 0)
+ *   dgamma_j = sum_b du_bj xhat_bj          dbeta_j = sum_b du_bj          (one fixed order, a function of B alone: sixteen contiguous
+ *                                                                           parts of the batch, b ascending in each, added in order)
+ *   dxh = du gamma           dz = rstd ((dxh - mean_j dxh) - xhat mean_j(dxh xhat))
+ * and dz feeds layer 0's [dW; db] and the gradient of the conv features unchanged.  There is no training / inference distinction: target
+ * networks, cpp_net_forward*, cpp_ddpg_check_loss and every train op normalise the same way.
+ * Layout: two variables, '<layer0>/LayerNorm/gamma' and '<layer0>/LayerNorm/beta', each (n), behind EVERY other variable of the network
+ * (twin ones included): the first cpp_net_num_params(the same network without the norm) floats keep their names, shapes and offsets.  The
+ * clip's norm, the optimiser slots, the soft update, soft actor-critic's target-actor copy and the collectives cover the longer buffer.
+ * The constructor leaves gamma = 1, beta = 0.  A checkpoint carries both by name: a plain checkpoint fails the layout check, in both directions.
+ * variant (NULL: the plain network): what the network is besides -- at most one of twin_q (cpp_net_create_twin_q), n_atoms with
+ * (v_min, v_max) (cpp_net_create_distributional), n_quantiles (cpp_net_create_quantile), gaussian with the log std bounds
+ * (cpp_net_create_gaussian), each under that constructor's rules.
+ * CPP_ERR_ARG, by name and before anything is allocated: a low-dimensional network, use_batch_norm, use_dropout, a CPP_HEAD network, an
+ * activation other than the two, epsilon not finite and positive.  cpp_naf_create refuses such networks; cpp_ddpg_create takes four of
+ * them with one activation and one epsilon, or none.  The fused heads launch of the gradient pass never owns the normalised layer's
+ * activation derivative: an actor with three or more hidden layers keeps the default route, one with two hidden layers keeps the heads
+ * launch without its leading actor layer, one with a single hidden layer takes the GEMM levels. */
+#define CPP_NORM_TANH 0
+#define CPP_NORM_RELU 1
+typedef struct cpp_net_variant {
+  int32_t twin_q;                        /* != 0: twin Q heads                                  */
+  int32_t n_atoms; float v_min, v_max;   /* n_atoms != 0: a categorical value distribution      */
+  int32_t n_quantiles;                   /* != 0: a quantile critic                             */
+  int32_t gaussian; float log_std_min, log_std_max;   /* gaussian != 0: a Gaussian actor        */
+} cpp_net_variant;
+int cpp_net_create_feature_norm(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, const cpp_net_variant* variant, int activation,
+                                float epsilon, cpp_net** out);
+/* on = 1, the activation and epsilon of a network made by cpp_net_create_feature_norm; on = 0 for any other.  NULL pointers are skipped. */
+int cpp_net_feature_norm_info(const cpp_net* net, int* on, int* activation, float* epsilon);
 int cpp_net_destroy(cpp_net* net);
 /* Network.trainable_model_vars (base_network.py:51-56): variables in creation order. */
 int64_t cpp_net_num_params(const cpp_net* net);
@@ -574,6 +613,10 @@ int cpp_ddpg_last_sac(cpp_ddpg* ddpg, int B, float* eps, float* a, float* logp, 
 /* log_alpha, its Adam slots m, v and its count for checkpoints (util.py:88-90).  set == 0: read into the pointers (NULL: skipped); else
  * written from them (all needed).  The noise count is not checkpointed. */
 int cpp_ddpg_sac_temperature(cpp_ddpg* ddpg, int set, float* log_alpha, float* m, float* v, uint64_t* step);
+/* Trainers on networks with a feature layer norm (cpp_net_create_feature_norm; an extension of ddpg_cartpole.py:95 and :168): what the last
+ * minibatch's gradient pass left for the actor (which = 0) or the critic (which = 1), n the width of its layer 0 -- xhat (B, n), rstd (B),
+ * y (B, n), dz = dL/dz (B, n), and dgamma, dbeta (n) as computed, before the clip.  NULL pointers are skipped; CPP_ERR_STATE on any other trainer. */
+int cpp_ddpg_last_feature_norm(cpp_ddpg* ddpg, int B, int which, float* xhat, float* rstd, float* y, float* dz, float* dgamma, float* dbeta);
 
 /* ---- data-parallel actor-learners (the reference's TODO "switch back to async training with multiple replicas",
  * ddpg_cartpole.py:259, naf_cartpole.py:294; its exps only launch independent processes, exps/run_87.sh:12-36) ------------
