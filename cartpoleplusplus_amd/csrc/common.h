@@ -515,7 +515,14 @@ struct DdpgHeadsArgs {
   const float *W3b, *W3b_t, *wqb, *wqb_t;
   float *h3b_out;                                  // input buffer of head 2's q layer (row stride ld_h3)
   float *q2_out, *tq2_out, *td2, *dzq2, *dz3b;
+  // optional, appended likewise (min_sel != nullptr: the TWIN_MIN instances of heads_twin_min.hip, which alone read them): the actor follows the
+  // smaller online head (rt_ddpg.cpp, cpp_ddpg_set_actor_min_q).  min_q1 / min_q2: Q1 and Q2 at a = mu(s1); min_sel: 1 where Q1 <= Q2, else 2.
+  // dq_da, adz and everything behind them are the chosen head's; the critic's side is the twin instance's.
+  float *min_q1, *min_q2; int* min_sel;
 };
+// the choice where the heads kernel does not run (actor_min.hip, the GEMM levels): from Q1 and Q2 of the second evaluation the two per-row
+// tops -- 1 for the chosen head, 0 for the other -- that stand where `ones` stands under a switch that is off, and the choice
+int launch_actor_min(cpp_ctx* ctx, const float* q1, const float* q2, int B, float* top1, float* top2, int* sel);
 enum { PD_N = 0, PD_HOLD = 1, PD_PHASE = 2, PD_WORDS = 3 };
 // ---- distributional (categorical) critic (dist.hip; include/cartpolepp_abi.h, cpp_net_create_distributional).  logits: (B, N), N in [2, 64].
 // job (a): q_out[b] = Q = sum_i p_i z_i and, dz != nullptr, dz[b][i] = p_i (z_i - Q)

@@ -16,6 +16,7 @@
 #undef HEADS_KERNEL
 
 int launch_ddpg_heads_twin(cpp_ctx* ctx, const DdpgHeadsArgs& h, size_t lds);      // heads_twin.hip
+int launch_ddpg_heads_twin_min(cpp_ctx* ctx, const DdpgHeadsArgs& h, size_t lds);  // heads_twin_min.hip
 
 size_t ddpg_heads_lds_bytes(const DdpgHeadsArgs& h) {
   const size_t k3 = h.n2c + h.A + 1, n3p = HEADS_N3P, n2cp = (h.n2c + 3) & ~3;
@@ -37,6 +38,7 @@ bool ddpg_heads_supported(const DdpgHeadsArgs& h) {
 int launch_ddpg_heads(cpp_ctx* ctx, const DdpgHeadsArgs& h) {
   const size_t lds = ddpg_heads_lds_bytes(h);
   typedef void (*kern_t)(const DdpgHeadsArgs);
+  if (h.min_sel) return launch_ddpg_heads_twin_min(ctx, h, lds);      // (twin Q heads, the actor on the smaller head: heads_twin_min.hip)
   if (h.W3b) return launch_ddpg_heads_twin(ctx, h, lds);      // (twin Q heads: the instances of heads_twin.hip)
 #define HEADS_SIX(W, S) ddpg_heads_kernel<1, true, W, S>, ddpg_heads_kernel<2, true, W, S>, ddpg_heads_kernel<4, true, W, S>, \
                         ddpg_heads_kernel<8, true, W, S>, ddpg_heads_kernel<4, false, W, S>, ddpg_heads_kernel<8, false, W, S>

@@ -1,5 +1,6 @@
-// The DDPG heads kernel's body, shared by its two translation units: heads.hip compiles it as ddpg_heads_kernel, heads_twin.hip -- with
-// HEADS_TWIN defined -- as ddpg_heads_twin_kernel, the instances for twin Q heads (common.h, DdpgHeadsArgs::W3b).  Everything twin sits in
+// The DDPG heads kernel's body, shared by its translation units: heads.hip compiles it as ddpg_heads_kernel, heads_twin.hip -- with
+// HEADS_TWIN defined -- as ddpg_heads_twin_kernel, the instances for twin Q heads (common.h, DdpgHeadsArgs::W3b), heads_twin_min.hip -- with
+// HEADS_TWIN_MIN as well -- as ddpg_heads_twin_min_kernel, whose actor follows the smaller head.  Everything twin sits in
 // #ifdef HEADS_TWIN sections: without the macro the preprocessor leaves the plain kernel's text as it was before twin heads existed, and with
 // it its instructions (a template flag did not: declarations that the plain instances never use still moved their instruction order).
 #include "common.h"
@@ -50,6 +51,10 @@ __device__ __forceinline__ float team_sum(float v) {
 // plain kernel's LDS (whose offsets stay); two more accumulators through the concat loop (head 2 on the fed action, head 2 of the target; none
 // for the a = mu(s1) evaluation: the actor follows head 1); the target is the smaller of the two target team sums.  The plain kernel never reads
 // the appended arguments.
+// HEADS_TWIN_MIN (a macro likewise, with HEADS_TWIN; heads_twin_min.hip): the actor follows the smaller online head (common.h, DdpgHeadsArgs::
+// min_sel).  One more accumulator through the action loop (head 2 at a = mu(s1)), two more team sums (Q1 and Q2 there), a wave-uniform choice
+// per row (a team is one wave; a tie is head 1's), and dz of the concat layer and the A team sums of dQ/da from the chosen head's wq and [W3; b3]
+// action rows.  No LDS and no global load beyond the twin instances'.
 template <int AT, bool EXACT, bool WEIGHTED, bool SMOOTH>
 __global__ __launch_bounds__(HEADS_THREADS) void HEADS_KERNEL(const DdpgHeadsArgs h) {
   extern __shared__ __attribute__((aligned(16))) float hl[];
@@ -255,6 +260,9 @@ __global__ __launch_bounds__(HEADS_THREADS) void HEADS_KERNEL(const DdpgHeadsArg
   p2 += q2_; pt2 += qt2_;
 #endif
   float pm = p, pb = p;
+#ifdef HEADS_TWIN_MIN
+  float pm2 = p2;                                      // (head 2's state sum before the fed action is added)
+#endif
 #pragma unroll
   for (int i = 0; i < AT; ++i)
     if (i < A) {
@@ -263,16 +271,33 @@ __global__ __launch_bounds__(HEADS_THREADS) void HEADS_KERNEL(const DdpgHeadsArg
 #ifdef HEADS_TWIN
       p2 = fmaf(ab[i], W3b[(n2c + i) * WS + t], p2); pt2 = fmaf(at[i], W3bt[(n2c + i) * WS + t], pt2);      // (one a' for both target heads)
 #endif
+#ifdef HEADS_TWIN_MIN
+      pm2 = fmaf(a[i], W3b[(n2c + i) * WS + t], pm2);
+#endif
     }
   const float wqv = wq[t], wqtv = wqt[t];
   const float h3b = fmaxf(pb, 0.f);
+#ifndef HEADS_TWIN_MIN
   const float dzm = pm > 0.f ? wqv : 0.f;               // dz of the concat layer on the 2nd evaluation (dz of q is 1)
+#endif
   if (rv && t < n3) h.h3_out[(long)row * h.ld_h3 + t] = h3b;
   HCK();
   const float qb = team_sum(h3b * wqv) + wq[N3P], qt = team_sum(fmaxf(pt, 0.f) * wqtv) + wqt[N3P];
+#ifdef HEADS_TWIN_MIN
+  // Q1 and Q2 at a = mu(s1); the row follows the smaller (every lane holds both sums: the choice is the wave's)
+  const float qm1 = team_sum(fmaxf(pm, 0.f) * wqv) + wq[N3P], qm2 = team_sum(fmaxf(pm2, 0.f) * wqb[t]) + wqb[N3P];
+  const bool first = qm1 <= qm2;
+  const float* W3s = first ? W3 : W3b;
+  const float dzm = first ? (pm > 0.f ? wqv : 0.f) : (pm2 > 0.f ? wqb[t] : 0.f);
+  if (rv && t == 0) { h.min_q1[row] = qm1; h.min_q2[row] = qm2; h.min_sel[row] = first ? 1 : 2; }
+#pragma unroll
+  for (int i = 0; i < AT; ++i)
+    if (i < A) { dqda[i] = team_sum(dzm * W3s[(n2c + i) * WS + t]); adz[i] = -dqda[i] * (1.f - a[i] * a[i]); }
+#else
 #pragma unroll
   for (int i = 0; i < AT; ++i)
     if (i < A) { dqda[i] = team_sum(dzm * W3[(n2c + i) * WS + t]); adz[i] = -dqda[i] * (1.f - a[i] * a[i]); }
+#endif
 #ifdef HEADS_TWIN
   const float wqbv = wqb[t];
   const float h3b2 = fmaxf(p2, 0.f);

@@ -50,6 +50,10 @@ struct cpp_ddpg {
   // twin Q heads (cpp_net_create_twin_q: both critics are twin critics, or neither): head 2's temporal difference, maxB.  The trainer
   // has no switch of its own -- what the critics are decides every path
   bool twin = false; float* td2 = nullptr;
+  // the actor on the minimum head (cpp_ddpg_set_actor_min_q; twin critics only): dq_da -- and with it the actor's list -- is the gradient of
+  // the smaller online head at a = mu(s1), chosen per row.  amin_sel: the last pass's choices (1 or 2), maxB; Q1 and Q2 at mu(s1) are left in
+  // the critic's second workspace (out, out2) by whoever ran the pass -- the GEMM levels' q layers or the heads kernel's TWIN_MIN instances
+  bool amin = false; int* amin_sel = nullptr;
   // distributional critic (cpp_net_create_distributional: both critics with one (N, v_min, v_max), or neither): what the last gradient
   // pass left for cpp_ddpg_last_distribution -- p of the fed evaluation, p' of the target evaluation, the projected target m, each
   // maxB x N.  Such a trainer always takes the GEMM levels of compute_gradients; dist.hip stands where td_kernel and `ones` stand
@@ -461,6 +465,8 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
       hd.W3b = c->params + L3b.w_off; hd.W3b_t = tc->params + L3b.w_off; hd.wqb = c->params + Lqb.w_off; hd.wqb_t = tc->params + Lqb.w_off;
       hd.h3b_out = c->ws[0].fcin2[nc - 1]; hd.q2_out = c->ws[0].out2; hd.tq2_out = tc->ws[0].out2; hd.td2 = d->td2;
       hd.dzq2 = c->ws[0].dz2[nc - 1]; hd.dz3b = c->ws[0].dz2[cat];
+      // the actor on the minimum head: Q1 and Q2 at mu(s1) land where the GEMM levels leave them
+      if (d->amin) { hd.min_q1 = c->ws[1].out; hd.min_q2 = c->ws[1].out2; hd.min_sel = d->amin_sel; }
     }
     fused = ddpg_heads_supported(hd);
     // the actors are one layer deeper than the critics' prefix (100-100-50 against 200-50): their last hidden layer joins the
@@ -561,9 +567,12 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
     float* col = tc->ws[0].fcin[cat] + (Lcat.n_in - A);
     taS = G.fn([=] { return launch_tps_smooth(ctx, ts, col, (int)ldcat, col, (int)ldcat, B, A); }, {taF});
   }
-  int c1 = -1, c0 = -1, tcH = -1, c0b = -1, tcHb = -1;
+  const bool amin = d->amin;      // (twin critics: cpp_ddpg_set_actor_min_q)
+  int c1 = -1, c0 = -1, tcH = -1, c0b = -1, tcHb = -1, c1b = -1;
   for (int l = cat; l < nc; ++l) {
     if (doA) c1 = G.gemm(fc_fwd_args(c, c->ws[1], l, B), {l == cat ? cP : c1, l == cat ? aF : -1});
+    // the actor on the minimum head: head 2 at a = mu(s1) as well, in head 1's levels (with the actor's half alone too)
+    if (doA && amin) c1b = G.gemm(twin_fwd_args(c, c->ws[1], l, B), {l == cat ? cP : c1b, l == cat ? aF : -1});
     if (!doC) continue;
     c0 = G.gemm(fc_fwd_args(c, c->ws[0], l, B), {l == cat ? cP : c0, l == cat ? cb : -1, l == cat ? tC : -1});
     tcH = G.gemm(fc_fwd_args(tc, tc->ws[0], l, B), {l == cat ? tcP : tcH, l == cat ? taS : -1});
@@ -578,18 +587,27 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
   int g = c1;
   // (a distributional critic: the gradient of the expectation, p (z - Q), stands where the scalar critic's q layer is fed ones)
   if (dist) g = G.fn([=] { return dist_expect(c, c->ws[1], B, c->ws[1].dz[nc - 1]); }, {c1});
-  const float* top = dist ? c->ws[1].dz[nc - 1] : d->ones;
+  // (the minimum head: per row 1 for the chosen head and 0 for the other, in the q layers' dz of the second workspace -- actor_min.hip)
+  if (amin) g = G.fn([=] { return launch_actor_min(ctx, c->ws[1].out, c->ws[1].out2, B, c->ws[1].dz[nc - 1], c->ws[1].dz2[nc - 1], d->amin_sel); }, {c1, c1b});
+  const float* top = (dist || amin) ? c->ws[1].dz[nc - 1] : d->ones;
+  int g2 = g;      // head 2's chain down to the concat layer, beside head 1's
   for (int l = nc - 1; l > cat; --l) {
     const FcL& L = c->fc[l];
     const float* dz = (l == nc - 1) ? top : c->ws[1].dz[l];
     g = G.gemm(fc_dx_args(c, l, B, dz, L.n_out, 0, L.n_in, c->ws[1].dz[l - 1], L.n_in, GE_MUL_RELU_GRAD,
                           c->ws[1].fcin[l], L.n_in + 1), {g});
+    if (amin) g2 = G.gemm(twin_dx_args(c, c->ws[1], l, B), {g2});
   }
   {   // dQ/da (kept for cpp_ddpg_q_gradients_wrt_actions) and, in the same epilogue, the actor's head gradient
     const float* dz = (cat == nc - 1) ? top : c->ws[1].dz[cat];
-    GemmArgs ga = fc_dx_args(c, cat, B, dz, Lcat.n_out, Lcat.n_in - A, A, d->dq_da, A, sac ? GE_NONE : GE_ACTOR_HEAD, sac ? nullptr : a->ws[0].out, sac ? 0 : A);
+    const int epi = sac ? GE_NONE : GE_ACTOR_HEAD;
+    const float* ay = sac ? nullptr : a->ws[0].out; const long lday = sac ? 0 : A;
+    // the minimum head: (head 1's action columns) + (head 2's), then the epilogue -- a row's unselected head adds exact zeros
+    const int h1 = amin ? G.gemm(fc_dx_args(c, cat, B, dz, Lcat.n_out, Lcat.n_in - A, A, d->dq_da, A, GE_NONE, nullptr, 0), {g}) : -1;
+    GemmArgs ga = amin ? twin_da_args(c, c->ws[1], B, d->dq_da, epi, ay, lday)
+                       : fc_dx_args(c, cat, B, dz, Lcat.n_out, Lcat.n_in - A, A, d->dq_da, A, epi, ay, lday);
     if (!sac) { ga.C2 = a->ws[0].dz[na - 1]; ga.ldc2 = A; }
-    adz = G.gemm(ga, {g, aF});
+    adz = amin ? G.gemm(ga, {h1, g2, aF}) : G.gemm(ga, {g, aF});
     if (sac) {      // job 3: the (B, 2A) head gradient and the temperature gradient's partials
       SacGradArgs sg = sac_grad_args(d, B);
       if (!train) { sg.part = nullptr; sg.alpha_out = nullptr; }      // (an evaluation leaves both to the last training pass)
@@ -807,6 +825,29 @@ extern "C" int cpp_ddpg_set_policy_delay(cpp_ddpg* d, int delay) {
   d->pd_d = delay;
   reconfigured(d);      // (the captured launches carry the old delay, or none)
   return CPP_OK;
+}
+
+// The actor on the minimum head (TD3 / DrQ-v2 / SAC's actor objective on twin critics: min(Q1, Q2) at the policy's action; an extension of
+// ddpg_cartpole.py:111-113, :220-222; include/cartpolepp_abi.h).  The switch is captured by the launches: the call drops the cached graphs.
+extern "C" int cpp_ddpg_set_actor_min_q(cpp_ddpg* d, int on) {
+  ARG_CHECK(d, "cpp_ddpg_set_actor_min_q: NULL argument");
+  ARG_CHECK(d->twin, "cpp_ddpg_set_actor_min_q: both critics must carry twin Q heads (cpp_net_create_twin_q)");
+  cpp_ctx* ctx = d->ctx;
+  HIP_CHECK(hipSetDevice(ctx->device));
+  HIP_CHECK(ctx_sync_stream(ctx));
+  if (on && !d->amin_sel) RC(dalloc(d->arena, &d->amin_sel, (size_t)d->maxB));
+  d->amin = on != 0;
+  reconfigured(d);      // (the captured launches carry the other family of heads instances, or the other GEMM levels)
+  return CPP_OK;
+}
+
+extern "C" int cpp_ddpg_last_actor_min(cpp_ddpg* d, int B, float* q1, float* q2, int32_t* sel) {
+  ARG_CHECK(d, "cpp_ddpg_last_actor_min: NULL argument");
+  ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_actor_min: batch %d outside [1,%d]", B, d->maxB);
+  if (!d->amin) { cpp_set_error("cpp_ddpg_last_actor_min: the actor follows Q1 (cpp_ddpg_set_actor_min_q is off)"); return CPP_ERR_STATE; }
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  const size_t n = (size_t)B * sizeof(float);
+  return read_back(d->ctx, {{q1, d->critic->ws[1].out, n}, {q2, d->critic->ws[1].out2, n}, {sel, d->amin_sel, (size_t)B * sizeof(int32_t)}}, true);
 }
 
 extern "C" int cpp_ddpg_policy_delay_status(cpp_ddpg* d, int* delay, uint64_t* n, int* held) {

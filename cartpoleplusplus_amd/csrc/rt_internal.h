@@ -77,7 +77,8 @@ struct Workspace {
   float* bn_stat[3] = {nullptr, nullptr, nullptr};
   std::vector<float*> fcin, dz;
   float* out = nullptr;
-  // twin Q heads (cpp_net_create_twin_q): the second copy of the layers [cat, nfc) on the fed action (ws[0] only).  fcin2[cat] is
+  // twin Q heads (cpp_net_create_twin_q): the second copy of the layers [cat, nfc) on the fed action (ws[0]) and, for an actor on the
+  // minimum head (cpp_ddpg_set_actor_min_q), at a = mu(s1) (a critic's ws[1]).  fcin2[cat] is the workspace's
   // fcin[cat] itself -- both heads read one concat input, and with it one smoothed target action --, the others are its own
   std::vector<float*> fcin2, dz2;
   float* out2 = nullptr;
@@ -326,6 +327,7 @@ GemmArgs fc_dx_args(cpp_net* n, int l, int B, const float* dz, long dz_ld, int c
 GemmArgs twin_fwd_args(cpp_net* n, Workspace& w, int l, int B);
 GemmArgs twin_dw_args(cpp_net* n, Workspace& w, int l, int B);
 GemmArgs twin_dx_args(cpp_net* n, Workspace& w, int l, int B);
+GemmArgs twin_da_args(cpp_net* n, Workspace& w, int B, float* C, int epi, const float* Y, long ldy);      // (the concat layer's action columns)
 // where the last layer's GEMM writes: the logits of a distributional critic, `out` otherwise
 inline float* fc_last_out(const Workspace& w) { return w.logits ? w.logits : w.out; }
 // Q (and, dz != nullptr, p (z - Q); a quantile critic: 1 / N) from the logits the forward left in w: a no-op for every other network

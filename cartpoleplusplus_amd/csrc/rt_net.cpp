@@ -103,7 +103,7 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
     RC(dalloc(n->arena, &w.out, (size_t)mb * n->spec.action_dim));
   } else
   RC(dalloc(n->arena, &w.out, (size_t)mb * n->fc.back().n_out));
-  if (n->twin && trunk) {      // (head 2 runs on the fed action only: the first workspace)
+  if (n->twin) {      // (head 2 on the fed action: the first workspace; at a = mu(s1), for an actor on the minimum head: the second)
     w.fcin2.assign(nfc, nullptr);
     w.dz2.assign(nfc, nullptr);
     for (int l = n->cat_layer; l < nfc; ++l) {
@@ -345,7 +345,6 @@ static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, boo
   if (n->ln && (rc = launch_fill(ctx, n->params + n->ln_g_off, 1, 0, 1, n->fc[0].n_out, 1.0f))) return fail(rc);      // (gamma = 1, beta = 0)
   if (spec->kind == CPP_CRITIC) {
     n->ws[1] = n->ws[0];
-    n->ws[1].fcin2.clear(); n->ws[1].dz2.clear(); n->ws[1].out2 = nullptr;
     if ((rc = ws_alloc(n, n->ws[1], n->cat_layer, false))) return fail(rc);
     for (int l = 0; l < n->cat_layer; ++l) { n->ws[1].fcin[l] = n->ws[0].fcin[l]; n->ws[1].dz[l] = n->ws[0].dz[l]; }
     for (int i = 0; i < 3; ++i) { n->ws[1].pool[i] = n->ws[0].pool[i]; n->ws[1].amax[i] = n->ws[0].amax[i]; n->ws[1].dpool[i] = n->ws[0].dpool[i]; n->ws[1].dpool_imax = n->ws[0].dpool_imax;
@@ -790,6 +789,14 @@ GemmArgs twin_dx_args(cpp_net* n, Workspace& w, int l, int B) {
     return mk_gemm(w.dz2[l], L.n_out, 1, n->params + L.w_off, 1, L.n_out, w.dz2[l - 1], L.n_in, B, L.n_in, L.n_out, GE_MUL_RELU_GRAD, w.fcin2[l], L.n_in + 1);
   const int ncols = L.n_in - n->spec.action_dim;
   GemmArgs g = mk_gemm(w.dz2[l], L.n_out, 1, n->params + L.w_off, 1, L.n_out, w.dz[l - 1], ncols, B, ncols, L.n_out, relu_grad_epi(n, l - 1), w.fcin[l], L.n_in + 1);
+  g.accumulate = 1;
+  return g;
+}
+// the action columns of head 2's concat layer, added to head 1's in C (B x A), then the epilogue: dQ/da of an actor on the minimum head
+GemmArgs twin_da_args(cpp_net* n, Workspace& w, int B, float* C, int epi, const float* Y, long ldy) {
+  const int cat = n->cat_layer, A = n->spec.action_dim;
+  const FcL& L = n->fc2[cat];
+  GemmArgs g = mk_gemm(w.dz2[cat], L.n_out, 1, n->params + L.w_off + (long)(L.n_in - A) * L.n_out, 1, L.n_out, C, A, B, A, L.n_out, epi, Y, ldy);
   g.accumulate = 1;
   return g;
 }

@@ -158,7 +158,12 @@ def build_parser():
     # on a shared representation as in DrQ-v2): the critic's layers from the concat layer upward exist twice, the target takes the smaller
     # of the two target heads (absent from the parsed options unless given, like --ddpg-optimiser; twin_q() reads it with its default)
     a('--twin-q', action='store_true', default=argparse.SUPPRESS,
-      help="critics with two Q heads on one representation; both regress onto r + discount * min(Q1', Q2'), the actor follows Q1")
+      help="critics with two Q heads on one representation; both regress onto r + discount * min(Q1', Q2'), the actor follows Q1 unless --actor-min-q")
+    # the actor on the minimum head (an extension beyond the reference, ddpg_cartpole.py:111-113, :220-222: the actor's objective of TD3's
+    # descendants on twin critics -- DrQ-v2, SAC, DrQ): the actor ascends min(Q1, Q2) at its own action, chosen per row (absent from the
+    # parsed options unless given, like --twin-q; actor_min_q() reads it with its default)
+    a('--actor-min-q', action='store_true', default=argparse.SUPPRESS,
+      help="--twin-q: the actor follows the smaller of Q1 and Q2 at its own action, row by row (default: Q1)")
     # distributional critic (an extension beyond the reference, ddpg_cartpole.py:166-177, :199-214: the categorical value distribution of
     # Bellemare et al. 2017 as D4PG uses it, Barth-Maron et al. 2018): the critic's last layer emits logits over a fixed support, trained
     # with the projected Bellman target and cross-entropy; the actor ascends the distribution's mean (absent from the parsed options
@@ -304,6 +309,14 @@ def policy_delay(o):
 def twin_q(o):
     """--twin-q; off unless given"""
     return bool(getattr(o, "twin_q", False))
+
+
+def actor_min_q(o):
+    """--actor-min-q; off unless given; refused without --twin-q"""
+    on = bool(getattr(o, "actor_min_q", False))
+    if on and not twin_q(o):
+        raise SystemExit("--actor-min-q needs --twin-q (the minimum is over the two heads of twin critics)")
+    return on
 
 
 _NUM_ATOMS_DEFAULT, NUM_ATOMS_MAX = 51, 64
@@ -463,6 +476,7 @@ def default_opts(**overrides):
     o.target_policy_noise, o.target_policy_noise_clip, o.target_policy_noise_seed = _TARGET_SMOOTHING_DEFAULTS
     o.policy_delay = _POLICY_DELAY_DEFAULT
     o.twin_q = False
+    o.actor_min_q = False
     o.distributional_critic, o.num_atoms, o.v_min, o.v_max = False, None, None, None
     o.quantile_critic, o.num_quantiles, o.quantile_huber_kappa, o.drop_top_quantiles = False, None, None, None
     o.n_step = 1
@@ -647,6 +661,11 @@ class _Trainer(object):
         self.sac = getattr(actor, "sac", None)
         if self.sac:
             self.set_sac(self.sac["init_temperature"], self.sac["target_entropy"], self.sac["temperature_learning_rate"], self.sac["seed"])
+        # --actor-min-q, as parsed when the critic's train op was declared (off, the trainer's state as created, needs no call)
+        self.actor_min_q = False
+        amin = getattr(critic, "_actor_min_q", None)
+        if actor_min_q(opts) if amin is None else amin:
+            self.set_actor_min_q(True)
 
     @property
     def handle(self):
@@ -814,6 +833,20 @@ class _Trainer(object):
         check(lib.cpp_ddpg_set_policy_delay(self.handle, int(delay)))
         self.policy_delay = int(delay)
 
+    def set_actor_min_q(self, on):
+        """the actor on the minimum head (include/cartpolepp_abi.h, cpp_ddpg_set_actor_min_q; twin critics only): dq_da and the actor's
+        list follow the smaller of Q1 and Q2 at mu(state_1), row by row; off restores the actor on Q1; drops the captured graphs."""
+        check(lib.cpp_ddpg_set_actor_min_q(self.handle, 1 if on else 0))
+        self.actor_min_q = bool(on)
+
+    def last_actor_min(self, B):
+        """(q1, q2, sel) of the last gradient pass of an --actor-min-q trainer: Q1 and Q2 at mu(state_1), each (B, 1) float32, and the
+        head each row followed, (B,) int32, 1 or 2"""
+        B = int(B)
+        q1, q2, sel = np.empty((B, 1), np.float32), np.empty((B, 1), np.float32), np.empty(B, np.int32)
+        check(lib.cpp_ddpg_last_actor_min(self.handle, B, ptr(q1), ptr(q2), ptr(sel)))
+        return q1, q2, sel
+
     def policy_delay_status(self):
         """(delay, critic updates counted since it was set, whether the last minibatch held the actor)"""
         d, n, held = C.c_int(), C.c_uint64(), C.c_int()
@@ -900,6 +933,7 @@ class CriticNetwork(base_network.Network):
         self._optimiser = ddpg_optimiser(opts)      # (kind, momentum, beta1, beta2, epsilon) of this train op and the actor's
         self._target_smoothing = target_policy_smoothing(opts)      # (sigma, clip, seed) of this train op's target
         self._policy_delay = policy_delay(opts)      # critic updates per actor update (the actor's train op is bound to this one)
+        self._actor_min_q = actor_min_q(opts)      # whether the actor's train op follows min(Q1, Q2)
         self.reward = base_network.Placeholder([None, 1], name="critic_reward")
         self.terminal_mask = base_network.Placeholder([None, 1], name="critic_terminal_mask")
         self.input_state_2 = target_critic.input_state
@@ -974,6 +1008,7 @@ class DeepDeterministicPolicyGradientAgent(object):
         soft_actor_critic(opts, action_dim)
         feature_layer_norm(opts)
         n_step(opts)
+        actor_min_q(opts)
         # (--exact-products asks for the exact arithmetic contract; without the flag the context keeps whatever mode its owner chose --
         # an explicit Context.set_precision("exact") is not undone, and a second agent on the shared context does not fight the first)
         if getattr(opts, "exact_products", False) and _lib.default_context().precision != "exact":

@@ -153,7 +153,7 @@ int cpp_net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, cpp_ne
  * evaluate it and never read head 2.  A trainer built on twin critics (cpp_ddpg_create: both critics, or neither) is a twin trainer:
  *     y = r + mask discount min(Q1'(s2, a'), Q2'(s2, a')),  td_k = Q_k(s1, a) - y,  loss = mean_b(w_b (td_1^2 + td_2^2))
  * with ONE a' for both target heads (target policy smoothing: one noise draw).  The gradient into the shared layer below the concat
- * layer is head 1's term plus head 2's, added in that order, then the ReLU mask.  The actor follows dQ1/da only; priorities,
+ * layer is head 1's term plus head 2's, added in that order, then the ReLU mask.  The actor follows dQ1/da only (unless cpp_ddpg_set_actor_min_q); priorities,
  * cpp_ddpg_last_values, cpp_ddpg_check_loss's td and q and q_gradients_wrt_actions stay head 1's; the loss they report is the twin
  * loss.  The clip's norm, the optimiser slots, the soft update and the collectives cover the longer buffer.  cpp_naf_create refuses
  * twin networks. */
@@ -232,7 +232,7 @@ int cpp_net_quantile_info(const cpp_net* net, int* n_quantiles);
  *   r_soft = r - ((mask discount) alpha) logp' ;   td = Q(s1, a_fed) - (r_soft + mask discount Q'(s2, a'))
  *          (twin heads: min(Q1', Q2'); an n-step memory has folded its powers into mask) -- priorities, cpp_ddpg_last_values and
  *          cpp_ddpg_check_loss read this td; check_loss keeps the entropy term at eps = 0 and draws nothing
- *   actor  minimises sum_b (alpha logp - Q(s1, a)) at a sample a at state_1 (twin heads: head 1).  With dq = dQ/da_k:
+ *   actor  minimises sum_b (alpha logp - Q(s1, a)) at a sample a at state_1 (twin heads: head 1; cpp_ddpg_set_actor_min_q: min(Q1, Q2)(s1, a), row by row).  With dq = dQ/da_k:
  *          g_u = 2 alpha a_k - dq (1 - a_k^2);   d m_k = g_u;   d x_k = ((g_u exp(ls_k)) eps_k - alpha) * ((0.5 (hi - lo)) (1 - tanh(x_k)^2))
  *   temperature  g_alpha = -(1/B) sum_b (logp_b + Hbar), the gradient of -log_alpha (logp + Hbar), from per-workgroup f64 partials (four
  *          rows each, in order) added in order; applied by Adam (TensorFlow's semantics, betas 0.9 / 0.999, epsilon 1e-8) at the
@@ -587,6 +587,25 @@ int cpp_ddpg_last_values(cpp_ddpg* ddpg, int B, float* actions, float* dq_da, fl
  * in the last minibatch's gradient pass -- Q2(state_1, fed action), Q1'(state_2, a'), Q2'(state_2, a') and td_2 = Q2 - y, each (B).
  * NULL pointers are skipped.  CPP_ERR_STATE on a trainer of plain critics. */
 int cpp_ddpg_last_twin_values(cpp_ddpg* ddpg, int B, float* q2, float* target_q1, float* target_q2, float* td2);
+/* The actor on the minimum head (the actor's objective of DrQ-v2, SAC and DrQ on twin critics; an extension of the actor's train op
+ * ddpg_cartpole.py:111-113, :220-222).  Twin trainers only: CPP_ERR_ARG unless both critics are twin critics (so never with a
+ * distributional or quantile critic).  With on != 0 every gradient pass chooses, per row b, at a = mu(state_1) (soft actor-critic: at its
+ * sample),
+ *     q1 = Q1(s1_b, a),  q2 = Q2(s1_b, a),  sel_b = 1 if q1 <= q2 else 2      (a tie is head 1's)
+ *     dq_da_b = d Q_{sel_b}(s1_b, a) / da
+ * with the shared prefix of the critic evaluated once.  The deterministic actor's head gradient is -dq_da (1 - a^2) as before; a soft
+ * actor-critic trainer's actor minimises alpha logp - min(Q1, Q2)(s1, a) through the same dq_da.  A row's unselected head contributes
+ * exact zeros.  Everything else stays head 1's or the twin step's: the critic's target, both temporal differences and the twin loss,
+ * priorities, cpp_ddpg_last_values' q and td, cpp_ddpg_check_loss, cpp_net_forward*, and what a held actor means under a policy delay.
+ * cpp_ddpg_q_gradients_wrt_actions returns the minimum's dq_da, and Q1 as q.  Where the fused heads kernel runs, its instances for
+ * this switch run in its place: no launch is added.  On the GEMM levels head 2's forward and dX GEMMs ride beside head 1's, one kernel
+ * makes the choice and one more GEMM level adds head 2's action columns.  There is no new state: checkpoints are unchanged.  The switch
+ * is captured by the launches: the call drops the captured graphs, as cpp_ddpg_set_policy_delay does.  on == 0 restores the trainer the
+ * call found after cpp_ddpg_create, bit for bit. */
+int cpp_ddpg_set_actor_min_q(cpp_ddpg* ddpg, int on);
+/* Such trainers: Q1 and Q2 at mu(state_1) (B each) and the head each row followed (B, int32: 1 or 2) in the last gradient pass that ran
+ * the actor's half.  NULL pointers are skipped.  CPP_ERR_STATE while the switch is off. */
+int cpp_ddpg_last_actor_min(cpp_ddpg* ddpg, int B, float* q1, float* q2, int32_t* sel);
 /* Distributional trainers (cpp_net_create_distributional): p of the fed evaluation, p' of the target evaluation and the projected target m
  * of the last minibatch's gradient pass, each (B, N).  NULL pointers are skipped.  CPP_ERR_STATE on any other trainer. */
 int cpp_ddpg_last_distribution(cpp_ddpg* ddpg, int B, float* p, float* target_p, float* m);
