@@ -161,6 +161,8 @@ SIGNATURES = {
     "cpp_ddpg_last_twin_values": (_I, [_P, _I, _P, _P, _P, _P]),
     "cpp_ddpg_set_actor_min_q": (_I, [_P, _I]),
     "cpp_ddpg_last_actor_min": (_I, [_P, _I, _P, _P, _P]),
+    "cpp_ddpg_set_behaviour_cloning": (_I, [_P, C.c_float, C.c_float]),
+    "cpp_ddpg_last_behaviour_cloning": (_I, [_P, _I, _P, _P, _P, _P]),
     "cpp_ddpg_last_distribution": (_I, [_P, _I, _P, _P, _P]),
     "cpp_ddpg_set_quantile_target": (_I, [_P, C.c_float, _I]),
     "cpp_ddpg_last_quantiles": (_I, [_P, _I, _P, _P, _P]),

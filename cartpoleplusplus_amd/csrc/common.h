@@ -64,6 +64,7 @@ enum KernelId {
   K_SAC,                  // soft actor-critic: policy sample / mean, soft reward, actor head gradient, temperature (sac.hip)
   K_LN_FWD,               // feature layer norm on fully connected layer 0, forward (ln.hip)
   K_LN_BWD,               // ... its backward: the column sums' launch and the row-local launch
+  K_BC,                   // behaviour-cloning actor term: the batch-wide mean of |Q| and the actor's head gradient (bc.hip)
   K_NUM_KERNELS
 };
 
@@ -523,6 +524,18 @@ struct DdpgHeadsArgs {
 // the choice where the heads kernel does not run (actor_min.hip, the GEMM levels): from Q1 and Q2 of the second evaluation the two per-row
 // tops -- 1 for the chosen head, 0 for the other -- that stand where `ones` stands under a switch that is off, and the choice
 int launch_actor_min(cpp_ctx* ctx, const float* q1, const float* q2, int B, float* top1, float* top2, int* sel);
+// the behaviour-cloning actor term where it runs (bc.hip, the GEMM levels; rt_ddpg.cpp, cpp_ddpg_set_behaviour_cloning): from Q(s1, mu(s1))
+// of the head the actor follows (q1; sel != nullptr: q2 where sel[b] == 2), the unscaled dq_da (B, A), mu (B, A) and the minibatch's stored
+// actions act (B, A): lambda = alpha / max(mean_b |q_b|, q_floor), g = -lambda dq_da + (2 / A) (mu - act), adz = g (1 - mu^2).
+// stat: {lambda, m}; g: (B, A); rows: (B), (1 / A) sum_i (mu - act)^2
+#define BC_THREADS 256
+struct BcArgs {
+  const float *q1, *q2; const int* sel;
+  const float *dq_da, *mu, *act;
+  int B, A; float alpha, q_floor;
+  float *adz, *stat, *g, *rows;
+};
+int launch_bc(cpp_ctx* ctx, const BcArgs& s);
 enum { PD_N = 0, PD_HOLD = 1, PD_PHASE = 2, PD_WORDS = 3 };
 // ---- distributional (categorical) critic (dist.hip; include/cartpolepp_abi.h, cpp_net_create_distributional).  logits: (B, N), N in [2, 64].
 // job (a): q_out[b] = Q = sum_i p_i z_i and, dz != nullptr, dz[b][i] = p_i (z_i - Q)

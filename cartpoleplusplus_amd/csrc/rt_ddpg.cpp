@@ -54,6 +54,11 @@ struct cpp_ddpg {
   // the smaller online head at a = mu(s1), chosen per row.  amin_sel: the last pass's choices (1 or 2), maxB; Q1 and Q2 at mu(s1) are left in
   // the critic's second workspace (out, out2) by whoever ran the pass -- the GEMM levels' q layers or the heads kernel's TWIN_MIN instances
   bool amin = false; int* amin_sel = nullptr;
+  // the behaviour-cloning actor term (cpp_ddpg_set_behaviour_cloning; TD3+BC): bc_alpha > 0 switches it on -- such a trainer always takes
+  // the GEMM levels of compute_gradients, where bc.hip stands behind the action-columns dX GEMM.  bc_stat: {lambda, m} of the last pass that
+  // ran the actor's half, bc_g: its grad_ys at the actor's output (maxB x A), bc_rows: its per-row (1/A) sum (mu - a)^2 (maxB).  Alpha and
+  // the floor are captured by value
+  float bc_alpha = 0.f, bc_floor = 0.f; float *bc_stat = nullptr, *bc_g = nullptr, *bc_rows = nullptr;
   // distributional critic (cpp_net_create_distributional: both critics with one (N, v_min, v_max), or neither): what the last gradient
   // pass left for cpp_ddpg_last_distribution -- p of the fed evaluation, p' of the target evaluation, the projected target m, each
   // maxB x N.  Such a trainer always takes the GEMM levels of compute_gradients; dist.hip stands where td_kernel and `ones` stand
@@ -435,7 +440,8 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
   const bool twin = d->twin;
   const bool sac = d->sac;         // (its actor's head is 2A wide and linear: never the fused heads)
   const int dist = d->dist_n;      // (its q layer has N outputs: never the fused heads)
-  bool fused = both && !dist && !no_heads && na >= 2 && cat >= 1 && nc - cat == 2 && a->fc[na - 1].act == GE_TANH && Lcat.act == GE_RELU &&
+  const bool bc = d->bc_alpha > 0.f;      // (lambda needs every row of the minibatch: never the fused heads, whose rows are spread over workgroups)
+  bool fused = both && !dist && !bc && !no_heads && na >= 2 && cat >= 1 && nc - cat == 2 && a->fc[na - 1].act == GE_TANH && Lcat.act == GE_RELU &&
                c->fc[nc - 1].n_out == 1 && c->fc[nc - 1].act == GE_NONE && a->fc[na - 1].n_out == A;
   // feature layer norm: the heads kernel writes dz[na - 2] through that layer's ReLU mask -- never the normalised layer 0, whose
   // activation derivative is ln.hip's.  (The critic's is dz[cat - 1] = dz[1].)
@@ -600,14 +606,22 @@ static int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phas
   }
   {   // dQ/da (kept for cpp_ddpg_q_gradients_wrt_actions) and, in the same epilogue, the actor's head gradient
     const float* dz = (cat == nc - 1) ? top : c->ws[1].dz[cat];
-    const int epi = sac ? GE_NONE : GE_ACTOR_HEAD;
-    const float* ay = sac ? nullptr : a->ws[0].out; const long lday = sac ? 0 : A;
+    const bool plain_da = sac || bc;      // (the head gradient is a launch of its own behind this GEMM: sac.hip's job 3, bc.hip)
+    const int epi = plain_da ? GE_NONE : GE_ACTOR_HEAD;
+    const float* ay = plain_da ? nullptr : a->ws[0].out; const long lday = plain_da ? 0 : A;
     // the minimum head: (head 1's action columns) + (head 2's), then the epilogue -- a row's unselected head adds exact zeros
     const int h1 = amin ? G.gemm(fc_dx_args(c, cat, B, dz, Lcat.n_out, Lcat.n_in - A, A, d->dq_da, A, GE_NONE, nullptr, 0), {g}) : -1;
     GemmArgs ga = amin ? twin_da_args(c, c->ws[1], B, d->dq_da, epi, ay, lday)
                        : fc_dx_args(c, cat, B, dz, Lcat.n_out, Lcat.n_in - A, A, d->dq_da, A, epi, ay, lday);
-    if (!sac) { ga.C2 = a->ws[0].dz[na - 1]; ga.ldc2 = A; }
+    if (!plain_da) { ga.C2 = a->ws[0].dz[na - 1]; ga.ldc2 = A; }
     adz = amin ? G.gemm(ga, {h1, g2, aF}) : G.gemm(ga, {g, aF});
+    if (bc) {      // behaviour cloning: lambda from Q(s1, mu(s1)) of the followed head (this chain started behind its q layer), then the head gradient
+      BcArgs ba; memset(&ba, 0, sizeof(ba));
+      ba.q1 = c->ws[1].out; ba.q2 = amin ? c->ws[1].out2 : nullptr; ba.sel = amin ? d->amin_sel : nullptr;
+      ba.dq_da = d->dq_da; ba.mu = a->ws[0].out; ba.act = b->a; ba.B = B; ba.A = A; ba.alpha = d->bc_alpha; ba.q_floor = d->bc_floor;
+      ba.adz = a->ws[0].dz[na - 1]; ba.stat = d->bc_stat; ba.g = d->bc_g; ba.rows = d->bc_rows;
+      adz = G.fn([=] { return launch_bc(ctx, ba); }, {adz});
+    }
     if (sac) {      // job 3: the (B, 2A) head gradient and the temperature gradient's partials
       SacGradArgs sg = sac_grad_args(d, B);
       if (!train) { sg.part = nullptr; sg.alpha_out = nullptr; }      // (an evaluation leaves both to the last training pass)
@@ -848,6 +862,40 @@ extern "C" int cpp_ddpg_last_actor_min(cpp_ddpg* d, int B, float* q1, float* q2,
   HIP_CHECK(hipSetDevice(d->ctx->device));
   const size_t n = (size_t)B * sizeof(float);
   return read_back(d->ctx, {{q1, d->critic->ws[1].out, n}, {q2, d->critic->ws[1].out2, n}, {sel, d->amin_sel, (size_t)B * sizeof(int32_t)}}, true);
+}
+
+// The behaviour-cloning actor term (TD3+BC, Fujimoto & Gu 2021: the actor ascends lambda Q and regresses onto the minibatch's stored action;
+// an extension of ddpg_cartpole.py:111-113; include/cartpolepp_abi.h).  Alpha and the floor are captured by value: the call drops the cached
+// graphs.  alpha 0 is off: the trainer cpp_ddpg_create left.
+extern "C" int cpp_ddpg_set_behaviour_cloning(cpp_ddpg* d, float alpha, float q_floor) {
+  ARG_CHECK(d, "cpp_ddpg_set_behaviour_cloning: NULL argument");
+  ARG_CHECK(alpha >= 0.f && alpha < 1e30f && q_floor > 0.f && q_floor < 1e30f,
+            "cpp_ddpg_set_behaviour_cloning: alpha %g (finite, >= 0; 0 is off), q_floor %g (finite, > 0)", (double)alpha, (double)q_floor);
+  ARG_CHECK(!d->dist_n, "cpp_ddpg_set_behaviour_cloning: a distributional or quantile critic");
+  ARG_CHECK(!d->sac, "cpp_ddpg_set_behaviour_cloning: a soft actor-critic trainer (its actor's head is a Gaussian's)");
+  cpp_ctx* ctx = d->ctx;
+  HIP_CHECK(hipSetDevice(ctx->device));
+  HIP_CHECK(ctx_sync_stream(ctx));
+  if (alpha > 0.f && !d->bc_stat) {
+    const size_t n = (size_t)d->maxB * d->actor->spec.action_dim;
+    RC(dalloc(d->arena, &d->bc_stat, (size_t)2));
+    RC(dalloc(d->arena, &d->bc_g, n));
+    RC(dalloc(d->arena, &d->bc_rows, (size_t)d->maxB));
+    HIP_CHECK(ctx_sync_stream(ctx));      // (the arena zeroes what it hands out)
+  }
+  d->bc_alpha = alpha; d->bc_floor = q_floor;
+  reconfigured(d);      // (the captured launches carry the fused heads, or the other alpha)
+  return CPP_OK;
+}
+
+extern "C" int cpp_ddpg_last_behaviour_cloning(cpp_ddpg* d, int B, float* lambda, float* m, float* g, float* bc_rows) {
+  ARG_CHECK(d, "cpp_ddpg_last_behaviour_cloning: NULL argument");
+  ARG_CHECK(B >= 1 && B <= d->maxB, "cpp_ddpg_last_behaviour_cloning: batch %d outside [1,%d]", B, d->maxB);
+  if (!(d->bc_alpha > 0.f)) { cpp_set_error("cpp_ddpg_last_behaviour_cloning: behaviour cloning is off (cpp_ddpg_set_behaviour_cloning)"); return CPP_ERR_STATE; }
+  HIP_CHECK(hipSetDevice(d->ctx->device));
+  const size_t nB = (size_t)B * sizeof(float);
+  return read_back(d->ctx, {{lambda, d->bc_stat, sizeof(float)}, {m, d->bc_stat + 1, sizeof(float)},
+                            {g, d->bc_g, nB * d->actor->spec.action_dim}, {bc_rows, d->bc_rows, nB}}, true);
 }
 
 extern "C" int cpp_ddpg_policy_delay_status(cpp_ddpg* d, int* delay, uint64_t* n, int* held) {

@@ -164,6 +164,14 @@ def build_parser():
     # parsed options unless given, like --twin-q; actor_min_q() reads it with its default)
     a('--actor-min-q', action='store_true', default=argparse.SUPPRESS,
       help="--twin-q: the actor follows the smaller of Q1 and Q2 at its own action, row by row (default: Q1)")
+    # the behaviour-cloning actor term (an extension beyond the reference, ddpg_cartpole.py:111-113: TD3+BC, Fujimoto & Gu 2021, the cure for
+    # extrapolation error when the memory is a fixed data set -- --event-log-in .. --dont-do-rollouts): the actor ascends lambda * Q with
+    # lambda = alpha / mean|Q| of the minibatch and regresses onto the minibatch's stored action (absent from the parsed options unless
+    # given, like --actor-min-q; behaviour_cloning() reads them with their defaults)
+    a('--bc-alpha', type=float, metavar='ALPHA', default=argparse.SUPPRESS,
+      help="TD3+BC: the actor's grad_ys become -(alpha / mean|Q|) dQ/da + (2/A)(mu - a) with a the stored action; the paper's value is 2.5 (default: off)")
+    a('--bc-q-floor', type=float, metavar='F', default=argparse.SUPPRESS,
+      help="--bc-alpha: lambda = alpha / max(mean|Q|, F), so that a critic whose Q is 0 gives a finite step (default 1e-3)")
     # distributional critic (an extension beyond the reference, ddpg_cartpole.py:166-177, :199-214: the categorical value distribution of
     # Bellemare et al. 2017 as D4PG uses it, Barth-Maron et al. 2018): the critic's last layer emits logits over a fixed support, trained
     # with the projected Bellman target and cross-entropy; the actor ascends the distribution's mean (absent from the parsed options
@@ -317,6 +325,29 @@ def actor_min_q(o):
     if on and not twin_q(o):
         raise SystemExit("--actor-min-q needs --twin-q (the minimum is over the two heads of twin critics)")
     return on
+
+
+_BC_Q_FLOOR_DEFAULT = 1e-3
+
+
+def behaviour_cloning(o):
+    """(alpha, q_floor) of --bc-alpha / --bc-q-floor; (0.0, default floor) is off; refuses what cannot be meant"""
+    import math
+    alpha, floor = getattr(o, "bc_alpha", None), getattr(o, "bc_q_floor", None)
+    if alpha is None or alpha == 0:
+        if floor is not None:
+            raise SystemExit("--bc-q-floor %r needs --bc-alpha (the floor is of the behaviour-cloning term's lambda)" % (floor,))
+        return 0.0, _BC_Q_FLOOR_DEFAULT
+    alpha, floor = float(alpha), float(_BC_Q_FLOOR_DEFAULT if floor is None else floor)
+    if not (math.isfinite(alpha) and alpha > 0.0):
+        raise SystemExit("--bc-alpha %r is not a finite weight >= 0" % (alpha,))
+    if not (math.isfinite(floor) and floor > 0.0):
+        raise SystemExit("--bc-q-floor %r is not a finite value > 0" % (floor,))
+    for flag, name in (("soft_actor_critic", "--soft-actor-critic"), ("distributional_critic", "--distributional-critic"),
+                       ("quantile_critic", "--quantile-critic")):
+        if getattr(o, flag, False):
+            raise SystemExit("--bc-alpha with %s (the behaviour-cloning term is of a deterministic actor on a scalar critic)" % name)
+    return alpha, floor
 
 
 _NUM_ATOMS_DEFAULT, NUM_ATOMS_MAX = 51, 64
@@ -477,6 +508,7 @@ def default_opts(**overrides):
     o.policy_delay = _POLICY_DELAY_DEFAULT
     o.twin_q = False
     o.actor_min_q = False
+    o.bc_alpha, o.bc_q_floor = None, None
     o.distributional_critic, o.num_atoms, o.v_min, o.v_max = False, None, None, None
     o.quantile_critic, o.num_quantiles, o.quantile_huber_kappa, o.drop_top_quantiles = False, None, None, None
     o.n_step = 1
@@ -613,7 +645,15 @@ class ActorNetwork(base_network.Network):
                 and self.critic.target_critic is not None):
             trainer.defer_actor(self, state.batch)
             return
-        dev = trainer.device_batch_for(state, state_only=True)
+        if trainer.behaviour_cloning[0] > 0.0:
+            # --bc-alpha: the update regresses onto the minibatch's stored actions, which only a Batch carries (its device copy, or its
+            # columns uploaded whole)
+            b = state.batch if isinstance(state, replay_memory.StateColumn) else state
+            if not hasattr(b, "action"):
+                raise ValueError("actor.train(state) on a host array has no actions to clone: with --bc-alpha pass a Batch or its state_1 column")
+            dev = trainer.device_batch_for(b)
+        else:
+            dev = trainer.device_batch_for(state, state_only=True)
         check(lib.cpp_ddpg_train_actor(trainer.handle, dev.handle))
         if opts.print_gradients:
             print("gradient %s l2_norm %s" % (self.namespace, trainer.last_stats()[1]))
@@ -666,6 +706,11 @@ class _Trainer(object):
         amin = getattr(critic, "_actor_min_q", None)
         if actor_min_q(opts) if amin is None else amin:
             self.set_actor_min_q(True)
+        # --bc-alpha / --bc-q-floor, as parsed when the critic's train op was declared (off, the trainer's state as created, needs no call)
+        self.behaviour_cloning = (0.0, _BC_Q_FLOOR_DEFAULT)
+        bc = getattr(critic, "_behaviour_cloning", None) or behaviour_cloning(opts)
+        if bc[0] > 0.0:
+            self.set_behaviour_cloning(*bc)
 
     @property
     def handle(self):
@@ -847,6 +892,22 @@ class _Trainer(object):
         check(lib.cpp_ddpg_last_actor_min(self.handle, B, ptr(q1), ptr(q2), ptr(sel)))
         return q1, q2, sel
 
+    def set_behaviour_cloning(self, alpha, q_floor=_BC_Q_FLOOR_DEFAULT):
+        """the behaviour-cloning actor term (include/cartpolepp_abi.h, cpp_ddpg_set_behaviour_cloning; TD3+BC): the actor's grad_ys become
+        -lambda dQ/da + (2/A)(mu - a) with lambda = alpha / max(mean|Q|, q_floor) of each minibatch and a its stored action; alpha 0 is off;
+        drops the captured graphs."""
+        check(lib.cpp_ddpg_set_behaviour_cloning(self.handle, float(alpha), float(q_floor)))
+        self.behaviour_cloning = (float(alpha), float(q_floor))
+
+    def last_behaviour_cloning(self, B):
+        """(lambda, m, g, bc_rows) of the last gradient pass of a --bc-alpha trainer that ran the actor's half: two floats, the grad_ys at
+        the actor's output, (B, A) float32, and (1/A) sum_i (mu - a)^2 per row, (B,) float32"""
+        B = int(B)
+        lam, m = np.empty(1, np.float32), np.empty(1, np.float32)
+        g, rows = np.empty((B, self.action_dim), np.float32), np.empty(B, np.float32)
+        check(lib.cpp_ddpg_last_behaviour_cloning(self.handle, B, ptr(lam), ptr(m), ptr(g), ptr(rows)))
+        return float(lam[0]), float(m[0]), g, rows
+
     def policy_delay_status(self):
         """(delay, critic updates counted since it was set, whether the last minibatch held the actor)"""
         d, n, held = C.c_int(), C.c_uint64(), C.c_int()
@@ -934,6 +995,7 @@ class CriticNetwork(base_network.Network):
         self._target_smoothing = target_policy_smoothing(opts)      # (sigma, clip, seed) of this train op's target
         self._policy_delay = policy_delay(opts)      # critic updates per actor update (the actor's train op is bound to this one)
         self._actor_min_q = actor_min_q(opts)      # whether the actor's train op follows min(Q1, Q2)
+        self._behaviour_cloning = behaviour_cloning(opts)      # (alpha, q_floor) of the actor's train op; alpha 0: off
         self.reward = base_network.Placeholder([None, 1], name="critic_reward")
         self.terminal_mask = base_network.Placeholder([None, 1], name="critic_terminal_mask")
         self.input_state_2 = target_critic.input_state
@@ -965,7 +1027,8 @@ class CriticNetwork(base_network.Network):
         if batch is None:
             return _OpHandle(self.namespace + "/q_gradients_wrt_actions")
         trainer = self._trainer()
-        dev = trainer.device_batch_for(batch, state_only=True)
+        # (--bc-alpha: the pass's cloning term reads the stored actions of a batch that carries them; dQ/da itself never does)
+        dev = trainer.device_batch_for(batch, state_only=not (trainer.behaviour_cloning[0] > 0.0 and hasattr(batch, "action")))
         out = np.empty((dev.size, self.action_dim), np.float32)
         check(lib.cpp_ddpg_q_gradients_wrt_actions(trainer.handle, dev.handle, ptr(out), None, None))
         return out
@@ -1009,6 +1072,7 @@ class DeepDeterministicPolicyGradientAgent(object):
         feature_layer_norm(opts)
         n_step(opts)
         actor_min_q(opts)
+        behaviour_cloning(opts)
         # (--exact-products asks for the exact arithmetic contract; without the flag the context keeps whatever mode its owner chose --
         # an explicit Context.set_precision("exact") is not undone, and a second agent on the shared context does not fight the first)
         if getattr(opts, "exact_products", False) and _lib.default_context().precision != "exact":

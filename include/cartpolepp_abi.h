@@ -606,6 +606,28 @@ int cpp_ddpg_set_actor_min_q(cpp_ddpg* ddpg, int on);
 /* Such trainers: Q1 and Q2 at mu(state_1) (B each) and the head each row followed (B, int32: 1 or 2) in the last gradient pass that ran
  * the actor's half.  NULL pointers are skipped.  CPP_ERR_STATE while the switch is off. */
 int cpp_ddpg_last_actor_min(cpp_ddpg* ddpg, int B, float* q1, float* q2, int32_t* sel);
+/* The behaviour-cloning actor term (TD3+BC, Fujimoto & Gu 2021: the cure for extrapolation error when the memory is a fixed data set; an
+ * extension of the actor's train op ddpg_cartpole.py:111-113, whose grad_ys -dQ/da these lines replace).  With alpha > 0 every gradient pass
+ * that runs the actor's half computes, with a_b the minibatch's stored action, mu_b = actor(state_1_b) and B the rows of THIS minibatch,
+ *     q_b    = Q(s1_b, mu_b) of the head the actor follows (Q1; cpp_ddpg_set_actor_min_q: the row's selected head)
+ *     m      = (1 / B) sum_b |q_b|             (every workgroup adds all B values itself in one fixed order, in f64: one lambda to the bit)
+ *     lambda = alpha / max(m, q_floor)         (a constant of the minibatch: no gradient flows through it)
+ *     g_bi   = -lambda dq_da_bi + (2 / A) (mu_bi - a_bi)         (grad_ys at the actor's output)
+ *     adz_bi = g_bi (1 - mu_bi^2)                                (what the actor's backward starts from)
+ * which is B times the paper's loss -lambda mean(Q) + mse(mu, a), as the actor's list without the term is B times the usual mean: the
+ * actor's learning rate keeps its meaning.  q_floor is the one departure from the paper: a critic whose Q is exactly 0 gives a finite step.
+ * dq_da as cpp_ddpg_last_values and cpp_ddpg_q_gradients_wrt_actions report it stays the unscaled dQ/da; the critic's side, priorities,
+ * cpp_ddpg_check_loss and what a held actor means under a policy delay are unchanged; the actor's term takes no importance weights, as
+ * before.  Such a trainer always takes the GEMM levels of the gradient pass (as soft actor-critic does), plus one launch per minibatch.  In
+ * the data-parallel step each rank takes lambda from its own minibatch: the summed list is the sum of the ranks' lists, each under its own
+ * lambda, not the list of the concatenated minibatch.  There is no new state: checkpoints are unchanged.
+ * alpha == 0 switches the term off, the state after cpp_ddpg_create, bit for bit.  CPP_ERR_ARG, with nothing written: alpha < 0, q_floor <= 0,
+ * a value that is not finite, a trainer whose critic is distributional or quantile or whose actor is soft actor-critic's.  Alpha and the floor
+ * are captured by the launches: the call drops the captured graphs, as cpp_ddpg_set_actor_min_q does. */
+int cpp_ddpg_set_behaviour_cloning(cpp_ddpg* ddpg, float alpha, float q_floor);
+/* Such trainers: lambda and m (one float each), g (B, A) and the per-row (1 / A) sum_i (mu_bi - a_bi)^2 (B) of the last gradient pass that ran
+ * the actor's half.  NULL pointers are skipped.  CPP_ERR_STATE while the term is off. */
+int cpp_ddpg_last_behaviour_cloning(cpp_ddpg* ddpg, int B, float* lambda, float* m, float* g, float* bc_rows);
 /* Distributional trainers (cpp_net_create_distributional): p of the fed evaluation, p' of the target evaluation and the projected target m
  * of the last minibatch's gradient pass, each (B, N).  NULL pointers are skipped.  CPP_ERR_STATE on any other trainer. */
 int cpp_ddpg_last_distribution(cpp_ddpg* ddpg, int B, float* p, float* target_p, float* m);
