@@ -12,6 +12,9 @@ nothing -- and on the head, then merge:
     step_digest.py > parent_a.json; step_digest.py > parent_b.json; step_digest.py > head.json        (each in its own tree)
     CARTPOLEPP_ABLATION=1 CPP_FUSED_HEADS=0 step_digest.py > ..._abl.json                             (the GEMM levels of the DDPG step)
     step_digest.py --merge parent_a.json parent_b.json head.json [the three _abl files] > step_digest.json
+While the ABI stands, one tree does: the parent's two libraries copied into cartpoleplusplus_amd/lib/ under build names, the runs
+    CARTPOLEPP_ABLATION=<release name> step_digest.py;  CARTPOLEPP_ABLATION=<ablation name> CPP_FUSED_HEADS=0 step_digest.py
+(CPP_FUSED_HEADS=0 selects the ablation list; the library is whichever CARTPOLEPP_ABLATION names).
 Equality is the bar.  The single_* configurations drive the four single entry points (train_actor, train_critic, check_loss,
 q_gradients_wrt_actions) on host batches, one round of the four per outer step; their digests also cover what check_loss and
 q_gradients_wrt_actions return and both networks' gradient buffers after every call.  Their launch counts are recorded and not compared
@@ -23,7 +26,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 PIXEL, LOWDIM, B, NB, ROWS, OUTER = (64, 64, 3, 1, 2), (2, 2, 7), 8, 4, 64, 3
-ABLATION = os.environ.get("CARTPOLEPP_ABLATION") == "1"
+ABLATION = os.environ.get("CPP_FUSED_HEADS") == "0"      # (on CARTPOLEPP_ABLATION=1, or =<name> of an ablation build of another commit)
 MOMENTUM = dict(optimiser="Momentum", optimiser_args='{"learning_rate": 0.001, "momentum": 0.9}')
 ADAM = dict(optimiser="Adam", optimiser_args='{"learning_rate": 0.001}')
 # the trainers of the single entry points' configurations (single_<trainer>, single_<trainer>_lowdim)
@@ -34,8 +37,14 @@ SINGLE_TRAINERS = {
     "quantile": dict(quantile_critic=True, num_quantiles=25, drop_top_quantiles=2),
     "sac": dict(soft_actor_critic=True),
     "smoothing_adam_delay2": dict(target_policy_noise=0.2, ddpg_optimiser="Adam", policy_delay=2),
+    "twin_min": dict(twin_q=True, actor_min_q=True),
+    "bc": dict(bc_alpha=2.5),
+    "feature_norm": dict(feature_layer_norm=True),
+    "sac_twin_min": dict(soft_actor_critic=True, twin_q=True, actor_min_q=True),
 }
-LAUNCHES_RECORDED_ONLY = set("single_%s%s" % (t, sfx) for t in SINGLE_TRAINERS for sfx in ("", "_lowdim"))
+# (--feature-layer-norm is refused without --use-raw-pixels: a low-dimensional network has no conv features to normalise)
+PIXEL_ONLY = ("feature_norm",)
+LAUNCHES_RECORDED_ONLY = set("single_%s%s" % (t, sfx) for t in SINGLE_TRAINERS for sfx in ("", "_lowdim") if not (sfx and t in PIXEL_ONLY))
 
 
 def merge(paths):
@@ -152,7 +161,7 @@ def single_ops(a, k):      # one round of the four single entry points on host b
     shape = a.env.observation_space.shape
     hb = HostBatch(O.synthetic_batch(np.random.default_rng(700 + k), B, shape, 2, len(shape) == 5))
     a.single = []
-    a.actor.train(hb.state_1)
+    a.actor.train(hb if a.trainer.behaviour_cloning[0] > 0.0 else hb.state_1)      # (--bc-alpha clones the batch's actions: the whole batch)
     a.single += grads()
     a.critic.train(hb)
     a.single += grads()
@@ -227,6 +236,15 @@ CONFIGS = {
     "ddpg_dp": (DDPG, PIXEL, {}, ddpg_dp(1, 0)),
     "ddpg_dp_sync_every_2": (DDPG, PIXEL, {}, ddpg_dp(2, 0)),
     "ddpg_dp_overlap": (DDPG, PIXEL, {}, ddpg_dp(1, 1)),
+    "ddpg_feature_norm": (DDPG, PIXEL, dict(feature_layer_norm=True), ddpg_step),
+    "ddpg_categorical_feature_norm": (DDPG, PIXEL, dict(feature_layer_norm=True, distributional_critic=True, num_atoms=21, v_min=-5.0, v_max=25.0), ddpg_step),
+    "ddpg_twin_min": (DDPG, PIXEL, dict(twin_q=True, actor_min_q=True), ddpg_step),
+    "ddpg_twin_min_adam_delay2_smoothing": (DDPG, PIXEL, dict(twin_q=True, actor_min_q=True, ddpg_optimiser="Adam", policy_delay=2, target_policy_noise=0.2), ddpg_step),
+    "ddpg_bc": (DDPG, PIXEL, dict(bc_alpha=2.5), ddpg_step),
+    "ddpg_twin_min_bc_lowdim": (DDPG, LOWDIM, dict(twin_q=True, actor_min_q=True, bc_alpha=2.5), ddpg_step),
+    "ddpg_sac_twin_min": (DDPG, PIXEL, dict(soft_actor_critic=True, twin_q=True, actor_min_q=True), ddpg_step),
+    "ddpg_dropout": (DDPG, PIXEL, dict(use_dropout=True), ddpg_step),
+    "ddpg_drqv2": (DDPG, PIXEL, dict(twin_q=True, actor_min_q=True, feature_layer_norm=True, n_step=3, target_policy_noise=0.2, shift=4), ddpg_step),
     "naf_shared": (NAF, PIXEL, dict(share_input_state_representation=True), naf_step),
     "naf_unshared": (NAF, PIXEL, {}, naf_step),
     "naf_lowdim": (NAF, LOWDIM, {}, naf_step),
@@ -243,15 +261,21 @@ CONFIGS = {
 }
 for _t, _kw in SINGLE_TRAINERS.items():
     CONFIGS["single_" + _t] = (SINGLE, PIXEL, _kw, single_ops)
-    CONFIGS["single_%s_lowdim" % _t] = (SINGLE, LOWDIM, _kw, single_ops)
+    if _t not in PIXEL_ONLY:
+        CONFIGS["single_%s_lowdim" % _t] = (SINGLE, LOWDIM, _kw, single_ops)
 assert LAUNCHES_RECORDED_ONLY == set(n for n in CONFIGS if n.startswith("single_"))
-# CPP_FUSED_HEADS=0 on the ablation library: the GEMM levels of compute_gradients under the scalar critic
+# CPP_FUSED_HEADS=0 on an ablation library: the GEMM levels of compute_gradients (rt_ddpg_pass.cpp) under the trainers that otherwise
+# take the heads kernel
 ABLATION_CONFIGS = {
     "ddpg_sgd_gemm_levels": (DDPG, PIXEL, {}, ddpg_step),
     "ddpg_adam_clip_gemm_levels": (DDPG, PIXEL, dict(ddpg_optimiser="Adam", gradient_clip=0.05), ddpg_step),
+    "ddpg_twin_gemm_levels": (DDPG, PIXEL, dict(twin_q=True), ddpg_step),
+    "ddpg_twin_min_gemm_levels": (DDPG, PIXEL, dict(twin_q=True, actor_min_q=True), ddpg_step),
+    "ddpg_feature_norm_gemm_levels": (DDPG, PIXEL, dict(feature_layer_norm=True), ddpg_step),
+    "ddpg_dropout_gemm_levels": (DDPG, PIXEL, dict(use_dropout=True), ddpg_step),
 }
 if ABLATION:
-    assert os.environ.get("CPP_FUSED_HEADS") == "0", "the ablation run is CARTPOLEPP_ABLATION=1 CPP_FUSED_HEADS=0"
+    assert os.environ.get("CARTPOLEPP_ABLATION") not in (None, "", "0"), "the switch is compiled into the ablation builds only: CARTPOLEPP_ABLATION=1 (or a named ablation build) CPP_FUSED_HEADS=0"
     CONFIGS = ABLATION_CONFIGS
 
 def run(name):

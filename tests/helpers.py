@@ -234,7 +234,7 @@ F32_GRAD_FACTOR = 1.5
 
 # ---- which kernels ran the heads: one eager, profiled minibatch, its launch counts against the ones the layer lists imply
 def ddpg_gemm_levels(path, actor_hidden, critic_hidden, pixel):
-    """GEMM launches of one DDPG minibatch (rt_ddpg.cpp compute_gradients: the op graph launches every GEMM that is ready at
+    """GEMM launches of one DDPG minibatch (rt_ddpg_pass.cpp compute_gradients: the op graph launches every GEMM that is ready at
     once, so this is the number of levels that hold one).  na = actor layers with the head.  Fused heads (pixel critic: two
     levels in front of its action splice): the forward of the actors' first na - 1 - pre layers and the critics' prefix side by
     side, the heads kernel, then their backward chains side by side -- pre, the actor's last hidden layer in the heads kernel,

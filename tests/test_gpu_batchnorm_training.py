@@ -1,5 +1,5 @@
 """--use-batch-norm training beyond batch size 4: bn.hip's five kernels, the dense-dY instances of the conv dW / dX kernels and the
-batch-norm branches of rt_ddpg.cpp / rt_naf.cpp (nets_forward_trunk_bn, launch_sumsq for the clip norms, dbeta written by the BN
+batch-norm branches of rt_ddpg_pass.cpp / rt_ddpg.cpp / rt_naf.cpp (nets_forward_trunk_bn, launch_sumsq for the clip norms, dbeta written by the BN
 backward kernels) against oracle.DDPG(float64) / oracle.naf_np on the same rows and starting parameters.
 
 Bars (the ones tests/test_gpu_batchnorm.py and the helpers already use for this mode): actions, Q, TD, dQ/da 1e-5; pools 2e-5;

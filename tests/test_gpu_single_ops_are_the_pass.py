@@ -1,4 +1,4 @@
-"""The single train ops are the gradient pass with one half asked for (rt_ddpg.cpp: compute_gradients, PassParts).
+"""The single train ops are the gradient pass with one half asked for (rt_ddpg_pass.cpp: compute_gradients; rt_ddpg.h: PassParts).
 
 Two trainers are built from the same seeds and fed the same host batch.  One runs cpp_ddpg_compute_gradients -- on the GEMM levels of
 the release library: a low-dimensional critic has no prefix in front of its action splice, nine actions are more than the fused heads

@@ -177,7 +177,7 @@ def test_every_new_entry_point_is_bound_and_cites_the_reference_lines_it_extends
     from cartpoleplusplus_amd import _lib
     header = open(os.path.join(ROOT, "include", "cartpolepp_abi.h")).read()
     csrc = os.path.join(ROOT, "cartpoleplusplus_amd", "csrc")
-    source = open(os.path.join(csrc, "rt_net.cpp")).read() + open(os.path.join(csrc, "rt_ddpg.cpp")).read()
+    source = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.startswith("rt_") and f.endswith(".cpp"))
     for name in NEW_ENTRY_POINTS:
         assert name in _lib.SIGNATURES, name
         for text, pattern in ((header, r"/\*((?:(?!\*/).)*)\*/\s*int %s\(" % name), (source, r"((?://[^\n]*\n)+)extern \"C\" int %s\(" % name)):
