@@ -29,6 +29,7 @@ CPP_ACTOR, CPP_CRITIC, CPP_HEAD = 0, 1, 2
 CPP_OPT_SGD, CPP_OPT_MOMENTUM, CPP_OPT_ADAM = 0, 1, 2
 CPP_PRECISION_FAST, CPP_PRECISION_EXACT = 0, 1      # cpp_ctx_set_precision
 CPP_NORM_TANH, CPP_NORM_RELU = 0, 1                  # cpp_net_create_feature_norm
+CPP_NORM_NONE = -1                                   # cpp_net_create_encoderless: no feature layer norm
 
 
 class NetSpec(C.Structure):
@@ -93,6 +94,9 @@ SIGNATURES = {
     "cpp_net_forward_gaussian": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "cpp_net_create_feature_norm": (_I, [_P, C.POINTER(NetSpec), _I, C.POINTER(NetVariant), _I, C.c_float, _PP]),
     "cpp_net_feature_norm_info": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_float)]),
+    "cpp_net_create_encoderless": (_I, [_P, C.POINTER(NetSpec), _I, C.POINTER(NetVariant), _I, C.c_float, _PP]),
+    "cpp_net_set_encoder": (_I, [_P, _P]),
+    "cpp_net_encoder_info": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
     "cpp_net_destroy": (_I, [_P]),
     "cpp_net_num_params": (_L, [_P]),
     "cpp_net_num_vars": (_I, [_P]),

@@ -144,7 +144,7 @@ class Network(object):
 
     # ------------------------------------------------------------------ native instantiation
     def _build_native(self, kind, action_dim, max_batch, ctx=None, head_out=0, head_act=0, twin_q=False, distribution=None, quantiles=None, gaussian=None,
-                      feature_norm=None):
+                      feature_norm=None, encoderless=False):
         self.ctx = ctx or _lib.default_context()
         spec = _lib.NetSpec()
         spec.kind, spec.action_dim = kind, int(action_dim)
@@ -164,7 +164,15 @@ class Network(object):
         handle = C.c_void_p()
         # (twin_q: a critic with twin Q heads, include/cartpolepp_abi.h cpp_net_create_twin_q; without it the call is what it always was)
         create = lib.cpp_net_create_twin_q if twin_q else lib.cpp_net_create
-        if feature_norm is not None:      # (activation, epsilon): Linear -> LayerNorm -> act on layer 0, cpp_net_create_feature_norm
+        if encoderless:      # --shared-encoder: an actor without conv layers (cpp_net_create_encoderless); CriticNetwork binds it
+            v = _lib.NetVariant()
+            if gaussian is not None:
+                v.gaussian, v.log_std_min, v.log_std_max = 1, float(gaussian[0]), float(gaussian[1])
+            norm, epsilon = _lib.CPP_NORM_NONE, 0.0
+            if feature_norm is not None:
+                norm, epsilon = {"tanh": _lib.CPP_NORM_TANH, "relu": _lib.CPP_NORM_RELU}[feature_norm[0]], float(feature_norm[1])
+            check(lib.cpp_net_create_encoderless(self.ctx.handle, C.byref(spec), int(max_batch), C.byref(v), norm, epsilon, C.byref(handle)))
+        elif feature_norm is not None:      # (activation, epsilon): Linear -> LayerNorm -> act on layer 0, cpp_net_create_feature_norm
             activation, epsilon = feature_norm
             v = _lib.NetVariant()
             v.twin_q = int(bool(twin_q))

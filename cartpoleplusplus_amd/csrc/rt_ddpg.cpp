@@ -30,6 +30,9 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   for (cpp_net* n : {critic, tactor, tcritic})
     ARG_CHECK(!actor->ln || (n->ln_act == actor->ln_act && n->ln_eps == actor->ln_eps),
               "cpp_ddpg_create: the four networks' feature layer norms differ in activation or epsilon");
+  ARG_CHECK(actor->enc_less == tactor->enc_less, "cpp_ddpg_create: one encoder-less actor (cpp_net_create_encoderless: the actor and the target actor, or neither)");
+  ARG_CHECK(!actor->enc_less || (actor->encoder == critic && tactor->encoder == tcritic),      // (actor-only training binds the live pair twice)
+            "cpp_ddpg_create: encoder-less actors come as a pair, each bound (cpp_net_set_encoder) to the critic it is created with");
   ARG_CHECK(actor->nparams == tactor->nparams && critic->nparams == tcritic->nparams, "cpp_ddpg_create: target shapes differ");
   ARG_CHECK(actor->state_elems == critic->state_elems && actor->spec.action_dim == critic->spec.action_dim,
             "cpp_ddpg_create: actor/critic input shapes differ");
@@ -39,6 +42,7 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   d->ctx = ctx; d->actor = actor; d->critic = critic; d->tactor = tactor; d->tcritic = tcritic; d->hp = *hp;
   d->maxB = actor->maxB < critic->maxB ? actor->maxB : critic->maxB;
   d->nA = actor->nparams; d->nC = critic->nparams;
+  d->shared = actor->enc_less; d->trunk = d->shared ? critic : actor;
   d->step_batch = nullptr;
   d->epoch = ctx->kernel_epoch;
   d->dp_local = 0;
@@ -178,21 +182,26 @@ static int apply(cpp_ddpg* d, const OptPlan& plan, bool* targets_left = nullptr)
   RC(opt_norms(d->ctx, s, plan, 2, d->norm_part));
   // conv1's operand images of the next minibatch ride along too (conv_rs16.h; opt_apply_kernel's second rider): both updates are in
   // this launch, the next minibatch's statistics are, conv1 of all four networks will run on that kernel
+  // (a shared encoder: the two critics are the networks with a conv1 -- one trained and one target, as NAF's pair)
   cpp_net* inets[4] = {d->actor, d->critic, d->tactor, d->tcritic};
-  const ConvL* L0 = d->actor->spec.pixel ? &d->actor->conv[0] : nullptr;
+  if (d->shared) { inets[0] = d->critic; inets[1] = d->tcritic; }
+  const int n_img = d->shared ? 2 : 4;
+  const ConvL* L0 = has_conv(d->trunk) ? &d->trunk->conv[0] : nullptr;
   // (CPP_RIDE_IMAGE_UPDATE=0, ablation build: no image workgroups at all -- conv1's parameters and slots are advanced by the update's
   // plain workgroups and the forward builds its image by a launch of its own: what the rider's restated update is compared with)
   static const bool no_img = cpp_switch_off("CPP_RIDE_IMAGE_UPDATE");
   const bool img = nx.b && nx.C > 0 && do_actor && do_critic && L0 && !d->actor->spec.use_batch_norm && !d->critic->spec.use_batch_norm &&
                    conv_rs16_ok(d->ctx, L0->Cin, L0->H, L0->W, kConvOut) && nx.B >= 2 && !no_img &&
-                   conv1_opens_params(d->actor) && conv1_opens_params(d->critic);
+                   (d->shared || conv1_opens_params(d->actor)) && conv1_opens_params(d->critic);
   if (img) {
-    s.img_n = 4; s.img_cin = L0->Cin;
-    for (int j = 0; j < 4; ++j) {      // (the trained networks read state_1's tables, the targets state_2's)
-      opt_img_net(s, j, inets[j], j < 2 ? j : -1, j < 2 ? 0 : 1, nx);
+    s.img_n = n_img; s.img_cin = L0->Cin;
+    for (int j = 0; j < n_img; ++j) {      // (the trained networks read state_1's tables, the targets state_2's)
+      const bool trained = j < n_img / 2;
+      const int seg = d->shared ? 1 : j;      // (the segment of a trained network: the shared encoder is in the critic's)
+      opt_img_net(s, j, inets[j], trained ? seg : -1, trained ? 0 : 1, nx);
       const ConvL& L = inets[j]->conv[0];
-      if (j < 2 && s.kind != OPT_SGD) { s.img[j].mw = s.m[j] + L.w_off; s.img[j].mb = s.m[j] + L.b_off; }
-      if (j < 2 && s.kind == OPT_ADAM) { s.img[j].vw = s.v[j] + L.w_off; s.img[j].vb = s.v[j] + L.b_off; }
+      if (trained && s.kind != OPT_SGD) { s.img[j].mw = s.m[seg] + L.w_off; s.img[j].mb = s.m[seg] + L.b_off; }
+      if (trained && s.kind == OPT_ADAM) { s.img[j].vw = s.v[seg] + L.w_off; s.img[j].vb = s.v[seg] + L.b_off; }
     }
   }
   // soft actor-critic: the temperature's update leaves with the actor's list, a launch of its own (rate 0: a fixed temperature, none)
@@ -330,7 +339,7 @@ static int step_body(cpp_ddpg* d, cpp_replay* r, int B, int n_batches, const int
   d->pre_variant = 0;        // (the half steps' presampled minibatch lives in the same step_batch)
   cpp_ctx* ctx = d->ctx;
   MinibatchLoop L;
-  L.ctx = ctx; L.r = r; L.step_batch = d->step_batch; L.trunk = d->actor;
+  L.ctx = ctx; L.r = r; L.step_batch = d->step_batch; L.trunk = d->trunk;
   L.td = d->td; L.stats_switch = true;
   L.gradients = [=](const PerPass& per, PassLeft* left) {
     RC(compute_gradients(d, d->step_batch, left, 0, true, per));      // (the apply() behind it takes both lists)
@@ -400,7 +409,7 @@ static int half_step_body(cpp_ddpg* d, cpp_replay* r, int B, uint64_t seed, int 
   const int C = d->actor->spec.pixel ? d->actor->spec.C : 0;
   cpp_ctx* ctx = d->ctx;
   cpp_batch* b = d->step_batch;
-  const bool direct = direct_replay_ok(d->actor, r, B);
+  const bool direct = direct_replay_ok(d->trunk, r, B);
   static const bool no_ride = cpp_switch_off("CPP_RIDE_DP");
   const int cur = variant == 1 ? 1 : 0;
   for (int k = 0; k < 2; ++k) { b->slot[k] = d->slot_set[cur][k]; b->slot_alt[k] = d->slot_set[1 - cur][k]; }

@@ -73,6 +73,10 @@ struct cpp_ddpg {
   bool sac = false; float sac_hbar = 0.f, sac_lr = 0.f; uint64_t sac_seed = 0;
   float* sac_w = nullptr; uint64_t* sac_step = nullptr; double* sac_part = nullptr;
   float *sac_eps[2] = {nullptr, nullptr}, *sac_logp[2] = {nullptr, nullptr}, *sac_rsoft = nullptr;
+  // shared conv encoder (cpp_net_create_encoderless: both actors without conv layers, each bound to the critic beside it, or neither): the
+  // actors read the critics' conv3 outputs, and only the critic's loss reaches the conv gradients.  trunk: the network whose conv1 decides
+  // the form of a minibatch (direct_replay_ok) -- the critic then, the actor otherwise
+  bool shared = false; cpp_net* trunk = nullptr;
 };
 
 // What a caller wants of the gradient pass: the halves to run -- the actor's (ddpg_cartpole.py:111-113, :220-222: dQ/da at actor(s1),

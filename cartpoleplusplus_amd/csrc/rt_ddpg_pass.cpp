@@ -82,6 +82,7 @@ struct Pass {
   const bool sac = d->sac;                        // (its actor's head is 2A wide and linear: never the fused heads)
   const int dist = d->dist_n;                     // (its q layer has N outputs: never the fused heads)
   const bool bc = d->bc_alpha > 0.f;              // (lambda needs every row of the minibatch: never the fused heads, whose rows are spread over workgroups)
+  const bool shared = d->shared;                  // (the actors read the critics' conv features; only the critic's loss reaches a conv gradient)
   OpGraph G;
   int tA = -1, tC = -1, tTA = -1, tTC = -1;       // the four conv trunks (or the low-dimensional state's conversions)
   int aF = -1, taF = -1, cP = -1, tcP = -1;       // how far the actors' stacks and the critics' prefixes have come
@@ -100,7 +101,18 @@ struct Pass {
 // ---- forward: the four conv trunks.  conv1 saturates the chip per network; the narrow conv2 / conv3 layers
 // of all four networks share one launch each.  (One half: its own networks, one by one -- batch norm follows each network's is_training.)
 void Pass::trunks() {
-  if (both && a->spec.pixel) {
+  if (shared) {      // a shared encoder: the critics' trunks are the actors' -- one trained network and one target, as NAF's pair
+    if (both) {
+      cpp_net* nets[2] = {c, tc};
+      const void* sts[2] = {s1, s2};
+      const float* whs[2] = {w1, w2};
+      tC = tTC = G.fn([=] { return nets_forward_trunk_fused(ctx, nets, 2, sts, whs, 1, dt, B); }, {});
+    } else {      // one half: the critic's trunk on s1 either way, the target critic's on s2 for the critic's half
+      tC = G.fn([=] { return net_forward_trunk(c, c->ws[0], s1, dt, w1, B); }, {});
+      if (doC) tTC = G.fn([=] { return net_forward_trunk(tc, tc->ws[0], s2, dt, w2, B); }, {});
+    }
+    tA = tC; tTA = tTC;
+  } else if (both && a->spec.pixel) {
     cpp_net* nets[4] = {a, c, ta, tc};
     const void* sts[4] = {s1, s1, s2, s2};
     const float* whs[4] = {w1, w1, w2, w2};
@@ -365,7 +377,12 @@ int Pass::close(const SqScope& sq_scope, PassLeft* left) {
     if (doC && train) cdz = ln_deps[nn++];
   }
   int conv_bwd = -1;
-  if (c->spec.pixel && both) {     // both conv backward passes, layer by layer, two networks per launch
+  if (shared) {      // the encoder's backward is the critic's alone (the actor's chain ended at its layer-0 dW): three layers x one network
+    if (doC && train) {
+      cpp_net* bn[1] = {c};
+      conv_bwd = G.fn([=] { return nets_backward_conv(ctx, bn, 1, B, s1, dt, w1); }, {adz, cdz});
+    }
+  } else if (c->spec.pixel && both) {     // both conv backward passes, layer by layer, two networks per launch
     cpp_net* bn[2] = {a, c};
     conv_bwd = G.fn([=] { return nets_backward_conv(ctx, bn, 2, B, s1, dt, w1); }, {adz, cdz});
   } else if (c->spec.pixel && (doA || train)) {      // one half: its trained network's
@@ -379,7 +396,7 @@ int Pass::close(const SqScope& sq_scope, PassLeft* left) {
     RC(G.run(ctx, phase == 1 ? conv_bwd : -1));
   }
   if (phase == 1) pending.keep();
-  else RC(flush_dw_reduce(ctx));      // all six dW reductions (3 layers x 2 networks) in one launch
+  else RC(flush_dw_reduce(ctx));      // all six dW reductions (3 layers x 2 networks; a shared encoder: 3 x 1) in one launch
   left->counted = fused && (hd.step_bump != nullptr || hd.pd != nullptr);
   left->noise_owed = (d->tps_on || sac) && phase != 2 && doC && train;      // (this pass read the count: exactly one increment follows it)
   sq_scope.left(left->sq_cnt);
@@ -403,7 +420,8 @@ int compute_gradients(cpp_ddpg* d, cpp_batch* b, PassLeft* left, int phase, bool
   Pass p{d, b, phase, count_in_heads, per, want};
   // The kernels that write the gradients also leave their share of the two lists' squared norms (cpp_ctx::sq_part): list 0 = actor,
   // list 1 = critic.  Not with batch norm (dbeta comes out of the BN backward kernels) and not for a split pass.
-  SqScope sq_scope(p.ctx, 2, {0, 1}, p.both && phase == 0 && !p.a->spec.use_batch_norm && !p.c->spec.use_batch_norm);
+  // (a shared encoder: the conv backward's only network is the critic's, list 1)
+  SqScope sq_scope(p.ctx, 2, {d->shared ? 1 : 0, d->shared ? -1 : 1}, p.both && phase == 0 && !p.a->spec.use_batch_norm && !p.c->spec.use_batch_norm);
   p.trunks();
   p.plan_heads();
   p.layer0_norm();

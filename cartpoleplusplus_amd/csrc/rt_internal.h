@@ -124,7 +124,13 @@ struct cpp_net {
   // feature layer norm (cpp_net_create_feature_norm): fc[0] is a plain GEMM (GE_NONE) and ln.hip stands behind it -- y = act(gamma xhat
   // + beta) with ln_act GE_TANH or GE_RELU.  '<layer0>/LayerNorm/gamma' and '.../beta' sit behind every other variable of the flat buffer
   bool ln = false; int ln_act = GE_TANH; float ln_eps = 0.f; long ln_g_off = 0, ln_b_off = 0;
+  // shared conv encoder (cpp_net_create_encoderless): a pixel actor without conv layers -- `conv` is empty, `flat` is the width the
+  // critic's conv3 leaves, and ws[0].fcin[0] is nullptr until cpp_net_set_encoder makes it the encoder's very buffer (bias column included)
+  bool enc_less = false; cpp_net* encoder = nullptr;
+  std::vector<cpp_net*> enc_users;      // a critic: the actors bound to it (cpp_net_destroy unbinds them)
 };
+// a network with conv layers of its own (a low-dimensional network and an encoder-less actor have none)
+inline bool has_conv(const cpp_net* n) { return !n->conv.empty(); }
 
 struct cpp_batch {
   cpp_ctx* ctx; int maxB, B; long elems; int A; int dtype;
@@ -402,8 +408,8 @@ double* sq_take(cpp_ctx* ctx, int list, int count);
 struct SlotScope {
   cpp_net* n[4]; int nn = 0;
   SlotScope(const cpp_batch* b, std::initializer_list<cpp_net*> s1, std::initializer_list<cpp_net*> s2) {
-    for (cpp_net* x : s1) { n[nn++] = x; if (b->direct_store) x->img_slot = b->slot[0]; }
-    for (cpp_net* x : s2) { n[nn++] = x; if (b->direct_store) x->img_slot = b->slot[1]; }
+    for (cpp_net* x : s1) { if (x->enc_less) continue; n[nn++] = x; if (b->direct_store) x->img_slot = b->slot[0]; }      // (an encoder-less actor has no conv1)
+    for (cpp_net* x : s2) { if (x->enc_less) continue; n[nn++] = x; if (b->direct_store) x->img_slot = b->slot[1]; }
   }
   ~SlotScope() { for (int k = 0; k < nn; ++k) n[k]->img_slot = nullptr; }
 };

@@ -30,6 +30,7 @@ extern "C" int cpp_naf_create(cpp_ctx* ctx, cpp_net* value, cpp_net* tvalue, cpp
   ARG_CHECK(ctx && value && tvalue && mu && lv && hp && out, "cpp_naf_create: NULL argument");
   for (cpp_net* n : {value, tvalue, mu, lv}) ARG_CHECK(!n->twin, "cpp_naf_create: a twin Q network (cpp_net_create_twin_q) belongs to the DDPG learner");
   for (cpp_net* n : {value, tvalue, mu, lv}) ARG_CHECK(!n->ln, "cpp_naf_create: a network with a feature layer norm (cpp_net_create_feature_norm) belongs to the DDPG learner");
+  for (cpp_net* n : {value, tvalue, mu, lv}) ARG_CHECK(!n->enc_less, "cpp_naf_create: an encoder-less actor (cpp_net_create_encoderless) belongs to the DDPG learner");
   for (cpp_net* n : {value, tvalue, mu, lv}) ARG_CHECK(!n->gauss, "cpp_naf_create: a Gaussian actor (cpp_net_create_gaussian) belongs to the DDPG learner");
   for (cpp_net* n : {value, tvalue, mu, lv}) ARG_CHECK(!n->quant, "cpp_naf_create: a quantile critic (cpp_net_create_quantile) belongs to the DDPG learner");
   for (cpp_net* n : {value, tvalue, mu, lv}) ARG_CHECK(!n->dist_n, "cpp_naf_create: a distributional critic (cpp_net_create_distributional) belongs to the DDPG learner");

@@ -5,7 +5,12 @@ static int net_build(cpp_net* n) {
   const cpp_net_spec& s = n->spec;
   long off = 0;
   int h = s.H, w = s.W, cin = s.C;
-  if (s.pixel) {
+  if (s.pixel && n->enc_less) {      // the features are the bound critic's: no conv variable, the same flat width
+    for (int i = 0; i < 3; ++i) { h /= 2; w /= 2; }
+    if (h < 1 || w < 1) { cpp_set_error("image %dx%d too small for three 2x2 pools", s.H, s.W); return CPP_ERR_ARG; }
+    n->flat = h * w * kConvOut;
+    n->state_elems = (long)s.H * s.W * s.C;
+  } else if (s.pixel) {
     for (int i = 0; i < 3; ++i) {
       ConvL L; L.H = h; L.W = w; L.Cin = cin; L.ks = kConvKs[i]; L.Hp = h / 2; L.Wp = w / 2;
       L.w_off = off; off += (long)L.ks * L.ks * cin * kConvOut; L.b_off = off; off += kConvOut;
@@ -91,8 +96,10 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
   w.dz.assign(nfc, nullptr);
   for (int l = from_layer; l < nfc; ++l) {
     const FcL& L = n->fc[l];
-    RC(dalloc(n->arena, &w.fcin[l], (size_t)mb * (L.n_in + 1)));
-    RC(launch_fill(n->ctx, w.fcin[l], L.n_in + 1, L.n_in, 1, mb, 1.0f));   // the bias "ones" column
+    if (!(l == 0 && n->enc_less)) {      // (an encoder-less actor: cpp_net_set_encoder aliases the critic's buffer, ones column included)
+      RC(dalloc(n->arena, &w.fcin[l], (size_t)mb * (L.n_in + 1)));
+      RC(launch_fill(n->ctx, w.fcin[l], L.n_in + 1, L.n_in, 1, mb, 1.0f));   // the bias "ones" column
+    }
     RC(dalloc(n->arena, &w.dz[l], (size_t)mb * L.n_out));
   }
   if (n->dist_n) {      // distributional critic: the logits beside a Q of width one
@@ -121,7 +128,7 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
     RC(dalloc(n->arena, &w.ln_xhat, (size_t)mb * n->fc[0].n_out));
     RC(dalloc(n->arena, &w.ln_rstd, (size_t)mb));
   }
-  if (trunk && n->spec.pixel) {
+  if (trunk && has_conv(n)) {
     for (int i = 0; i < 3; ++i) {
       const ConvL& L = n->conv[i];
       const size_t pe = (size_t)mb * L.Hp * L.Wp * kConvOut;
@@ -140,7 +147,8 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
 }
 
 static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out, int dist_n = 0, float v_min = 0.f, float v_max = 0.f,
-                      bool quant = false, bool gauss = false, float ls_lo = 0.f, float ls_hi = 0.f, int ln_act = 0, float ln_eps = 0.f);
+                      bool quant = false, bool gauss = false, float ls_lo = 0.f, float ls_hi = 0.f, int ln_act = 0, float ln_eps = 0.f,
+                      bool enc_less = false);
 // the variants' own argument rules, shared by their constructors and cpp_net_create_feature_norm (who: the entry point's name)
 static int check_twin(const char* who, const cpp_net_spec* spec) {
   ARG_CHECK(spec->kind == CPP_CRITIC, "%s: kind %d (twin Q heads belong to a critic)", who, spec->kind);
@@ -261,6 +269,66 @@ extern "C" int cpp_net_feature_norm_info(const cpp_net* n, int* on, int* activat
   if (epsilon) *epsilon = n->ln_eps;
   return CPP_OK;
 }
+// A pixel actor without conv layers, for a shared conv encoder (SAC-AE, DrQ, DrQ-v2; an extension of ddpg_cartpole.py:78-100, whose
+// actor runs base_network.py:73-127 on its own): see include/cartpolepp_abi.h
+extern "C" int cpp_net_create_encoderless(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, const cpp_net_variant* v, int norm, float epsilon,
+                                          cpp_net** out) {
+  const char* who = "cpp_net_create_encoderless";
+  ARG_CHECK(ctx && spec && out, "%s: NULL argument", who);
+  ARG_CHECK(spec->kind == CPP_ACTOR, "%s: kind %d (the encoder is a critic's; only an actor goes without one)", who, spec->kind);
+  ARG_CHECK(spec->pixel, "%s: a low-dimensional network (there is no conv encoder to share)", who);
+  ARG_CHECK(!spec->use_batch_norm, "%s: use_batch_norm (the critic's batch statistics would be the actor's)", who);
+  ARG_CHECK(!spec->use_dropout, "%s: use_dropout", who);
+  ARG_CHECK(norm == CPP_NORM_NONE || norm == CPP_NORM_TANH || norm == CPP_NORM_RELU, "%s: norm %d (CPP_NORM_NONE, CPP_NORM_TANH or CPP_NORM_RELU)", who, norm);
+  int ln_act = 0;
+  if (norm != CPP_NORM_NONE) {
+    ARG_CHECK(std::isfinite(epsilon) && epsilon > 0.f, "%s: epsilon %g (finite, positive)", who, (double)epsilon);
+    const int width = spec->n_hidden >= 1 ? spec->hidden[0] : 0;
+    ARG_CHECK(width >= 1 && width <= LN_MAX_WIDTH, "%s: layer 0 has width %d outside [1, %d]", who, width, LN_MAX_WIDTH);
+    ln_act = norm == CPP_NORM_TANH ? GE_TANH : GE_RELU;
+  }
+  if (v) ARG_CHECK(!v->twin_q && !v->n_atoms && !v->n_quantiles, "%s: a critic's variant (an actor is plain or gaussian)", who);
+  const bool gauss = v && v->gaussian;
+  if (gauss) RC(check_gaussian(who, spec, v->log_std_min, v->log_std_max));
+  return net_create(ctx, spec, max_batch, false, out, 0, 0.f, 0.f, false, gauss, gauss ? v->log_std_min : 0.f, gauss ? v->log_std_max : 0.f, ln_act,
+                    ln_act ? epsilon : 0.f, true);
+}
+// the actor's layer 0 reads the critic's flattened conv3 output: the very buffer, bias column of ones included
+extern "C" int cpp_net_set_encoder(cpp_net* actor, cpp_net* critic) {
+  ARG_CHECK(actor && critic, "cpp_net_set_encoder: NULL argument");
+  ARG_CHECK(actor->enc_less, "cpp_net_set_encoder: the first network has conv layers of its own (cpp_net_create_encoderless makes one without)");
+  ARG_CHECK(critic->spec.kind == CPP_CRITIC && has_conv(critic), "cpp_net_set_encoder: the encoder is a pixel critic's");
+  ARG_CHECK(actor->ctx == critic->ctx, "cpp_net_set_encoder: the two networks live on different contexts");
+  ARG_CHECK(!critic->spec.use_batch_norm, "cpp_net_set_encoder: a critic with batch norm");
+  ARG_CHECK(actor->spec.H == critic->spec.H && actor->spec.W == critic->spec.W && actor->spec.C == critic->spec.C && actor->flat == critic->flat,
+            "cpp_net_set_encoder: geometry differs (actor %dx%dx%d, critic %dx%dx%d)", actor->spec.H, actor->spec.W, actor->spec.C, critic->spec.H,
+            critic->spec.W, critic->spec.C);
+  ARG_CHECK(actor->spec.action_dim == critic->spec.action_dim, "cpp_net_set_encoder: action_dim differs (%d vs %d)", actor->spec.action_dim, critic->spec.action_dim);
+  ARG_CHECK(actor->maxB == critic->maxB, "cpp_net_set_encoder: max_batch differs (%d vs %d)", actor->maxB, critic->maxB);
+  ARG_CHECK(!actor->grads, "cpp_net_set_encoder: the actor belongs to a trainer already");
+  ARG_CHECK(!actor->encoder, "cpp_net_set_encoder: the actor is bound already (an actor keeps the encoder it was given)");
+  actor->encoder = critic;
+  actor->ws[0].fcin[0] = critic->ws[0].fcin[0];
+  critic->enc_users.push_back(actor);
+  return CPP_OK;
+}
+// Either end of a binding going away: a destroyed critic leaves its actors unbound (their next forward answers CPP_ERR_STATE instead of
+// reading freed memory), a destroyed actor leaves its critic's list
+static void encoder_unbind(cpp_net* n) {
+  for (cpp_net* a : n->enc_users) { a->encoder = nullptr; a->ws[0].fcin[0] = nullptr; }
+  n->enc_users.clear();
+  if (n->encoder) {
+    std::vector<cpp_net*>& u = n->encoder->enc_users;
+    u.erase(std::remove(u.begin(), u.end(), n), u.end());
+    n->encoder = nullptr;
+  }
+}
+extern "C" int cpp_net_encoder_info(const cpp_net* n, int* encoderless, int* bound) {
+  ARG_CHECK(n, "cpp_net_encoder_info: NULL argument");
+  if (encoderless) *encoderless = n->enc_less ? 1 : 0;
+  if (bound) *bound = n->encoder ? 1 : 0;
+  return CPP_OK;
+}
 // the ln.hip job of a network's first workspace (backward pointers once a trainer has bound the gradient buffer)
 static LnJob ln_job(cpp_net* n) {
   Workspace& w = n->ws[0];
@@ -289,7 +357,8 @@ void add_ln_backward(OpGraph& G, cpp_ctx* ctx, cpp_net* const* nets, int nn, int
   for (int k = 0; k < nn; ++k) {
     cpp_net* n = nets[k];
     Workspace& w = n->ws[0];
-    G.gemm(sq_gemm(ctx, lists[k], fc_dw_args(n, w, 0, B, w.dz[0])), {rows});
+    const int dw = G.gemm(sq_gemm(ctx, lists[k], fc_dw_args(n, w, 0, B, w.dz[0])), {rows});
+    if (!has_conv(n)) { deps[k] = dw; continue; }      // (an encoder-less actor: the stop gradient -- its backward ends at layer 0's dW)
     deps[k] = G.gemm(fc_dx_args(n, 0, B, w.dz[0], n->fc[0].n_out, 0, n->flat, w.dpool[2], n->flat, GE_NONE, nullptr, 0), {rows});
   }
 }
@@ -308,7 +377,7 @@ int dist_expect(cpp_net* n, Workspace& w, int B, float* dz) {
 }
 
 static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, bool twin, cpp_net** out, int dist_n, float v_min, float v_max, bool quant,
-                      bool gauss, float ls_lo, float ls_hi, int ln_act, float ln_eps) {
+                      bool gauss, float ls_lo, float ls_hi, int ln_act, float ln_eps, bool enc_less) {
   ARG_CHECK(ctx && spec && out, "cpp_net_create: NULL argument");
   ARG_CHECK(max_batch >= 1, "cpp_net_create: max_batch %d", max_batch);
   ARG_CHECK(spec->kind == CPP_ACTOR || spec->kind == CPP_CRITIC || spec->kind == CPP_HEAD, "cpp_net_create: kind %d", spec->kind);
@@ -336,6 +405,7 @@ static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, boo
   n->dist_n = dist_n; n->dist_vmin = v_min; n->dist_vmax = v_max; n->quant = quant;
   n->gauss = gauss; n->ls_lo = ls_lo; n->ls_hi = ls_hi;
   n->ln = ln_act != 0; n->ln_act = ln_act ? ln_act : GE_TANH; n->ln_eps = ln_eps;      // (ln_act: GE_TANH / GE_RELU, 0: no feature layer norm)
+  n->enc_less = enc_less;
   int rc = net_build(n);
   if (rc) { delete n; return rc; }
   auto fail = [&](int r) { n->arena.release(); delete n; return r; };
@@ -350,7 +420,7 @@ static int net_create(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, boo
     for (int i = 0; i < 3; ++i) { n->ws[1].pool[i] = n->ws[0].pool[i]; n->ws[1].amax[i] = n->ws[0].amax[i]; n->ws[1].dpool[i] = n->ws[0].dpool[i]; n->ws[1].dpool_imax = n->ws[0].dpool_imax;
                                   n->ws[1].z[i] = n->ws[0].z[i]; n->ws[1].bn_stat[i] = n->ws[0].bn_stat[i]; }
   }
-  if (spec->pixel) {
+  if (has_conv(n)) {
     for (int i = 0; i < 3; ++i)
       if ((rc = dalloc(n->arena, &n->dw_partial[i], conv_dw_partial_floats(ctx, n->conv[i].Cin, n->conv[i].ks, kConvOut)))) return fail(rc);
     if ((rc = n->arena.alloc(&n->wimg, conv_rs16_image_bytes(), true))) return fail(rc);
@@ -374,6 +444,7 @@ extern "C" int cpp_net_destroy(cpp_net* n) {
   if (!n) return CPP_OK;
   (void)hipSetDevice(n->ctx->device);
   (void)ctx_sync_stream(n->ctx);
+  encoder_unbind(n);
   n->arena.release();
   delete n;
   return CPP_OK;
@@ -509,7 +580,7 @@ BnBatch bn_batch(cpp_net* const* nets, int nn, int i, int B) {
 // conv trunk (pixel) or state conversion (low-dim) into ws.fcin[0]
 // conv1 on the f16 pipes can leave bf16 planes of pool1 for a conv2 forward on the bf16 pipes (same launch sequence only)
 bool trunk_b16(const cpp_net* n, int dtype, int B, long white_bstride) {
-  return n->spec.pixel && !n->spec.use_batch_norm && dtype == CPP_F16 && white_bstride == 0 &&
+  return has_conv(n) && !n->spec.use_batch_norm && dtype == CPP_F16 && white_bstride == 0 &&
          conv12_b16_ok(n->ctx, n->conv[0].Cin, n->conv[0].H, n->conv[0].W, B);
 }
 
@@ -764,7 +835,7 @@ int add_fc_backward(OpGraph& G, cpp_net* n, Workspace& w, int B, int start, int 
       dep = G.gemm(fc_dx_args(n, l, B, w.dz[l], L.n_out, 0, L.n_in, w.dz[0], L.n_in, GE_NONE, nullptr, 0), {dep});
     else if (l > 0)
       dep = G.gemm(fc_dx_args(n, l, B, w.dz[l], L.n_out, 0, L.n_in, w.dz[l - 1], L.n_in, relu_grad_epi(n, l - 1), w.fcin[l], L.n_in + 1), {dep});
-    else if (n->spec.pixel)
+    else if (has_conv(n))      // (an encoder-less actor: the stop gradient -- no dX of layer 0 is formed)
       dep = G.gemm(fc_dx_args(n, 0, B, w.dz[0], L.n_out, 0, n->flat, w.dpool[2], n->flat, GE_NONE, nullptr, 0), {dep});
   }
   return dep;
@@ -819,6 +890,15 @@ int batch_stats(cpp_ctx* ctx, const void* s0, const void* s1, int dtype, long el
   return CPP_OK;
 }
 
+// The network whose conv trunk (or state conversion) feeds n's fully connected stack: n itself, or the critic an encoder-less actor is
+// bound to -- whose staging buffers, statistics and first workspace the inference entry points then use (ws[0].fcin[0] is shared)
+static int trunk_owner(cpp_net* n, const char* who, cpp_net** e) {
+  *e = n;
+  if (!n->enc_less) return CPP_OK;
+  if (!n->encoder) { cpp_set_error("%s: an encoder-less actor that is not bound to a critic yet (cpp_net_set_encoder)", who); return CPP_ERR_STATE; }
+  *e = n->encoder;
+  return CPP_OK;
+}
 // (m_out / ls_out: device buffers a Gaussian actor's mean kernel also fills -- cpp_net_forward_gaussian; out == nullptr: nothing is copied back)
 static int forward_batch(cpp_net* n, const void* state, int state_dtype, int B, const float* action, float* out, float* m_out, float* ls_out) {
   ARG_CHECK(n && state, "cpp_net_forward / cpp_net_forward_gaussian: NULL argument");
@@ -826,23 +906,25 @@ static int forward_batch(cpp_net* n, const void* state, int state_dtype, int B, 
   ARG_CHECK(state_dtype == CPP_F32 || state_dtype == CPP_F16, "cpp_net_forward: dtype %d", state_dtype);
   ARG_CHECK(n->spec.kind != CPP_CRITIC || action, "cpp_net_forward: critic needs an action batch");
   cpp_ctx* ctx = n->ctx;
+  cpp_net* e = nullptr;
+  RC(trunk_owner(n, "cpp_net_forward", &e));
   HIP_CHECK(hipSetDevice(ctx->device));
   const int A = n->spec.action_dim, no = n->dist_n ? 1 : n->gauss ? A : n->fc.back().n_out;      // (a distributional critic returns Q, a Gaussian actor tanh(m))
-  if (!n->stage_state) {
-    RC(n->arena.alloc(&n->stage_state, (size_t)n->maxB * n->state_elems * sizeof(float), false));
-    RC(dalloc(n->arena, &n->stage_action, (size_t)n->maxB * A));
+  if (!e->stage_state) {
+    RC(e->arena.alloc(&e->stage_state, (size_t)n->maxB * e->state_elems * sizeof(float), false));
+    RC(dalloc(e->arena, &e->stage_action, (size_t)n->maxB * A));
   }
   const size_t esz = state_dtype == CPP_F16 ? 2 : 4;
-  HIP_CHECK(hipMemcpyAsync(n->stage_state, state, (size_t)B * n->state_elems * esz, hipMemcpyHostToDevice, ctx->stream));
-  if (action) HIP_CHECK(hipMemcpyAsync(n->stage_action, action, (size_t)B * A * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  if (n->spec.pixel)
-    RC(batch_stats(ctx, n->stage_state, nullptr, state_dtype, n->state_elems, B, n->spec.C, n->stats_part, n->white));
-  n->is_training = false;                              // IS_TRAINING: False (ddpg_cartpole.py:125)
-  int frc = net_forward_trunk(n, n->ws[0], n->stage_state, state_dtype, n->white, B);
-  if (!frc) frc = net_forward_fc(n, n->ws[0], 0, B, action ? n->stage_action : nullptr);
+  HIP_CHECK(hipMemcpyAsync(e->stage_state, state, (size_t)B * e->state_elems * esz, hipMemcpyHostToDevice, ctx->stream));
+  if (action) HIP_CHECK(hipMemcpyAsync(e->stage_action, action, (size_t)B * A * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if (e->spec.pixel)
+    RC(batch_stats(ctx, e->stage_state, nullptr, state_dtype, e->state_elems, B, e->spec.C, e->stats_part, e->white));
+  n->is_training = e->is_training = false;                              // IS_TRAINING: False (ddpg_cartpole.py:125)
+  int frc = net_forward_trunk(e, e->ws[0], e->stage_state, state_dtype, e->white, B);
+  if (!frc) frc = net_forward_fc(n, n->ws[0], 0, B, action ? e->stage_action : nullptr);
   if (!frc) frc = dist_expect(n, n->ws[0], B, nullptr);
   if (!frc) frc = gauss_mean(n, n->ws[0], B, m_out, ls_out);
-  n->is_training = true;
+  n->is_training = e->is_training = true;
   if (frc) return frc;
   if (!out) return CPP_OK;
   HIP_CHECK(hipMemcpyAsync(out, n->ws[0].out, (size_t)B * no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -859,37 +941,39 @@ static int forward_each(cpp_net* n, const void* state, int state_dtype, int B, c
   ARG_CHECK(state_dtype == CPP_F32 || state_dtype == CPP_F16, "cpp_net_forward_each: dtype %d", state_dtype);
   ARG_CHECK(n->spec.kind != CPP_CRITIC || action, "cpp_net_forward_each: critic needs an action batch");
   cpp_ctx* ctx = n->ctx;
+  cpp_net* e = nullptr;
+  RC(trunk_owner(n, "cpp_net_forward_each", &e));
   HIP_CHECK(hipSetDevice(ctx->device));
-  const int A = n->spec.action_dim, no = n->dist_n ? 1 : n->gauss ? A : n->fc.back().n_out, C = n->spec.C;
-  if (!n->stage_state) {
-    RC(n->arena.alloc(&n->stage_state, (size_t)n->maxB * n->state_elems * sizeof(float), false));
-    RC(dalloc(n->arena, &n->stage_action, (size_t)n->maxB * A));
+  const int A = n->spec.action_dim, no = n->dist_n ? 1 : n->gauss ? A : n->fc.back().n_out, C = e->spec.C;
+  if (!e->stage_state) {
+    RC(e->arena.alloc(&e->stage_state, (size_t)n->maxB * e->state_elems * sizeof(float), false));
+    RC(dalloc(e->arena, &e->stage_action, (size_t)n->maxB * A));
   }
   const size_t esz = state_dtype == CPP_F16 ? 2 : 4;
-  HIP_CHECK(hipMemcpyAsync(n->stage_state, state, (size_t)B * n->state_elems * esz, hipMemcpyHostToDevice, ctx->stream));
-  if (action) HIP_CHECK(hipMemcpyAsync(n->stage_action, action, (size_t)B * A * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  HIP_CHECK(hipMemcpyAsync(e->stage_state, state, (size_t)B * e->state_elems * esz, hipMemcpyHostToDevice, ctx->stream));
+  if (action) HIP_CHECK(hipMemcpyAsync(e->stage_action, action, (size_t)B * A * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   long wbs = 0;
-  if (n->spec.pixel) {
+  if (e->spec.pixel) {
     int g = 8, c = C; while (c) { int t = g % c; g = c; c = t; }
-    const long npix = n->state_elems / C;
-    if (n->state_elems % 8 == 0 && C / g <= 16) {       // per-row partial sums, finalised row by row
+    const long npix = e->state_elems / C;
+    if (e->state_elems % 8 == 0 && C / g <= 16) {       // per-row partial sums, finalised row by row
       GatherArgs ga; memset(&ga, 0, sizeof(ga));
-      ga.store[0] = n->stage_state; ga.store[1] = n->stage_state; ga.part = n->stats_part; ga.elems = n->state_elems; ga.B = B; ga.C = C;
+      ga.store[0] = e->stage_state; ga.store[1] = e->stage_state; ga.part = e->stats_part; ga.elems = e->state_elems; ga.B = B; ga.C = C;
       RC(launch_gather_stats(ctx, ga, state_dtype));
-      RC(launch_stats_finalize(ctx, n->stats_part, 1, B, C, (double)npix, n->white_rows));
+      RC(launch_stats_finalize(ctx, e->stats_part, 1, B, C, (double)npix, e->white_rows));
     } else {
       for (int b = 0; b < B; ++b)
-        RC(launch_stats_generic(ctx, (const char*)n->stage_state + (size_t)b * n->state_elems * esz, state_dtype, npix, C,
-                                n->white_rows + (long)b * 2 * C));
+        RC(launch_stats_generic(ctx, (const char*)e->stage_state + (size_t)b * e->state_elems * esz, state_dtype, npix, C,
+                                e->white_rows + (long)b * 2 * C));
     }
     wbs = 2 * C;
   }
-  n->is_training = false;
-  int frc = net_forward_trunk(n, n->ws[0], n->stage_state, state_dtype, n->white_rows, B, wbs);
-  if (!frc) frc = net_forward_fc(n, n->ws[0], 0, B, action ? n->stage_action : nullptr);
+  n->is_training = e->is_training = false;
+  int frc = net_forward_trunk(e, e->ws[0], e->stage_state, state_dtype, e->white_rows, B, wbs);
+  if (!frc) frc = net_forward_fc(n, n->ws[0], 0, B, action ? e->stage_action : nullptr);
   if (!frc) frc = dist_expect(n, n->ws[0], B, nullptr);
   if (!frc) frc = gauss_mean(n, n->ws[0], B, m_out, ls_out);
-  n->is_training = true;
+  n->is_training = e->is_training = true;
   if (frc) return frc;
   if (!out) return CPP_OK;
   HIP_CHECK(hipMemcpyAsync(out, n->ws[0].out, (size_t)B * no * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -926,6 +1010,7 @@ extern "C" int cpp_net_forward_gaussian(cpp_net* n, const void* state, int state
 extern "C" int cpp_net_get_pool(cpp_net* n, int which, int B, float* out) {
   ARG_CHECK(n && out, "cpp_net_get_pool: NULL argument");
   ARG_CHECK(B >= 1 && B <= n->maxB, "cpp_net_get_pool: batch %d", B);
+  ARG_CHECK(!n->enc_less, "cpp_net_get_pool: an encoder-less actor has no conv layers (ask the critic it is bound to)");
   if (n->spec.pixel && which >= 11 && which <= 13) {   // debug: arg-max codes (0..3) of the 2x2 windows, as floats
     const ConvL& L = n->conv[which - 11];
     const size_t cnt = (size_t)B * L.Hp * L.Wp * kConvOut;

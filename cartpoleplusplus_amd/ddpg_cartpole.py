@@ -214,7 +214,46 @@ def build_parser():
     # --distributional-critic this is D4PG from the command line
     a('--n-step', type=int, default=argparse.SUPPRESS,
       help="train on n-step returns: reward = sum_k discount^k r_k, bootstrap with discount^n (default 1: one-step transitions)")
+    # shared conv encoder (an extension beyond the reference, ddpg_cartpole.py:78-100, :148-171, whose four networks each own three conv
+    # layers: SAC-AE, DrQ, DrQ-v2): the actors have no conv layers and read the critics' conv features, which only the critic's loss
+    # trains (absent from the parsed options unless given, like --twin-q; shared_encoder() reads it)
+    a('--shared-encoder', action='store_true', default=argparse.SUPPRESS,
+      help="pixel networks: actor and target actor read the conv features of critic and target critic; only the critic's loss trains the encoder")
+    # DrQ's random shift from the command line (ReplayMemory.enable_random_shift; absent unless given; random_shift() reads them)
+    a('--random-shift', type=int, metavar='PAD', default=argparse.SUPPRESS,
+      help="--use-raw-pixels: pad every gathered image by PAD pixels of its own edge and crop it back at a random offset (default 0: off)")
+    a('--random-shift-seed', type=int, metavar='N', default=argparse.SUPPRESS, help="--random-shift: seed of the shifts (default 0)")
     return parser
+
+
+def shared_encoder(o):
+    """--shared-encoder; off unless given; refuses what cannot be meant"""
+    if not bool(getattr(o, "shared_encoder", False)):
+        return False
+    if not bool(getattr(o, "use_raw_pixels", False)):
+        raise SystemExit("--shared-encoder needs --use-raw-pixels: a low-dimensional network has no conv encoder to share")
+    if bool(getattr(o, "use_batch_norm", False)):
+        raise SystemExit("--shared-encoder cannot be combined with --use-batch-norm")
+    if bool(getattr(o, "use_dropout", False)):
+        raise SystemExit("--shared-encoder cannot be combined with --use-dropout")
+    return True
+
+
+def random_shift(o):
+    """(pad, seed) of --random-shift / --random-shift-seed; (0, 0) is off; refuses what cannot be meant"""
+    pad, seed = getattr(o, "random_shift", None), getattr(o, "random_shift_seed", None)
+    if pad is None or (not isinstance(pad, bool) and pad == 0):
+        if seed is not None:
+            raise SystemExit("--random-shift-seed %r needs --random-shift PAD" % (seed,))
+        return (0, 0)
+    if isinstance(pad, bool) or not isinstance(pad, (int, np.integer)) or int(pad) < 0:
+        raise SystemExit("--random-shift %r is not a whole number of pixels >= 0" % (pad,))
+    seed = 0 if seed is None else seed
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise SystemExit("--random-shift-seed %r is not in [0, 2^64)" % (seed,))
+    if not bool(getattr(o, "use_raw_pixels", False)):
+        raise SystemExit("--random-shift needs --use-raw-pixels: a low-dimensional state has no image to shift")
+    return (int(pad), int(seed))
 
 
 FEATURE_NORM_ACTIVATIONS = ("tanh", "relu")
@@ -514,6 +553,8 @@ def default_opts(**overrides):
     o.n_step = 1
     o.soft_actor_critic = False
     o.feature_layer_norm, o.feature_norm_activation = False, None
+    o.shared_encoder = False
+    o.random_shift, o.random_shift_seed = None, None
     for k in _SAC_DEFAULTS:
         setattr(o, k, None)
     for k, v in overrides.items():
@@ -554,13 +595,23 @@ class ActorNetwork(base_network.Network):
         self.exploration_noise = util.OrnsteinUhlenbeckNoise(action_dim, opts.action_noise_theta,
                                                              opts.action_noise_sigma)
         opts.hidden_layers = opts.actor_hidden_layers                 # ddpg_cartpole.py:91
-        self.input_state_network(self.input_state, opts)
+        # --shared-encoder: no simple_conv_net_on -- the hidden stack starts at the conv features of the critic this actor is given to
+        # (CriticNetwork.__init__ binds it; until then forward refuses)
+        self.shared_encoder = shared_encoder(opts)
+        if self.shared_encoder:
+            shape = self.input_state.get_shape()
+            self._state_elems = int(np.prod([int(d) for d in shape[1:]]))
+            self._conv_input = (int(shape[1]), int(shape[2]), int(np.prod([int(d) for d in shape[3:]])))
+            self.hidden_layers_starting_at(self.input_state, opts.hidden_layers, opts)
+        else:
+            self.input_state_network(self.input_state, opts)
         # --soft-actor-critic: output_action emits (m | x), 2A wide; forward returns tanh(m), exploration samples on the host
         self.sac = soft_actor_critic(opts, action_dim)
         # --feature-layer-norm: h0 is Linear -> LayerNorm -> tanh (the same in every forward: there is no training / inference distinction)
         self.feature_norm = feature_layer_norm(opts)
         self._build_native(_lib.CPP_ACTOR, action_dim, max(int(opts.batch_size), 1),
-                           gaussian=(self.sac["log_std_min"], self.sac["log_std_max"]) if self.sac else None, feature_norm=self.feature_norm)
+                           gaussian=(self.sac["log_std_min"], self.sac["log_std_max"]) if self.sac else None, feature_norm=self.feature_norm,
+                           encoderless=self.shared_encoder)
         self._sac_rng = np.random.default_rng(self.sac["seed"]) if self.sac else None
         self.output_action = _OpHandle(namespace + "/output_action")
         self.train_op = None
@@ -978,6 +1029,9 @@ class CriticNetwork(base_network.Network):
         self.feature_norm = feature_layer_norm(opts)
         self._build_native(_lib.CPP_CRITIC, self.action_dim, max(int(opts.batch_size), 1), twin_q=self.twin_q, distribution=self.distribution,
                            quantiles=self.quantiles[0] if self.quantiles else None, feature_norm=self.feature_norm)
+        # --shared-encoder: this critic's conv trunk is its actor's encoder from here on
+        if getattr(actor, "shared_encoder", False):
+            check(lib.cpp_net_set_encoder(actor.handle, self.handle))
         self.q_value = _OpHandle(namespace + "/q_value")
         self.target_critic = None
         self._ddpg = None
@@ -1073,6 +1127,8 @@ class DeepDeterministicPolicyGradientAgent(object):
         n_step(opts)
         actor_min_q(opts)
         behaviour_cloning(opts)
+        shared_encoder(opts)
+        shift = random_shift(opts)
         # (--exact-products asks for the exact arithmetic contract; without the flag the context keeps whatever mode its owner chose --
         # an explicit Context.set_precision("exact") is not undone, and a second agent on the shared context does not fight the first)
         if getattr(opts, "exact_products", False) and _lib.default_context().precision != "exact":
@@ -1086,6 +1142,11 @@ class DeepDeterministicPolicyGradientAgent(object):
             self.replay_memory.set_priority_beta(priority_beta(opts, 0))
         if n_step(opts) > 1:
             self.replay_memory.enable_n_step(n_step(opts), opts.discount)
+        if shift[0] > 0:
+            try:
+                self.replay_memory.enable_random_shift(*shift)
+            except ValueError as e:
+                raise SystemExit("--random-shift: %s" % e)
         # s1 and s2 placeholders
         batched_state_shape = [None] + list(state_shape)
         s1 = base_network.Placeholder(batched_state_shape)

@@ -286,6 +286,41 @@ int cpp_net_create_feature_norm(cpp_ctx* ctx, const cpp_net_spec* spec, int max_
                                 float epsilon, cpp_net** out);
 /* on = 1, the activation and epsilon of a network made by cpp_net_create_feature_norm; on = 0 for any other.  NULL pointers are skipped. */
 int cpp_net_feature_norm_info(const cpp_net* net, int* on, int* activation, float* epsilon);
+/* Shared conv encoder: the actor reads the critic's features (SAC-AE, Yarats et al. 2019; DrQ, Kostrikov et al. 2020; DrQ-v2, Yarats et
+ * al. 2021), an extension of ddpg_cartpole.py:78-100 and :148-171, where each of the four networks runs base_network.py:73-127 on its own.
+ * Pixel DDPG learners only.  Definition:
+ *   - The actor and the target actor have NO conv variables: cpp_net_create_encoderless makes a pixel actor whose variable list is its
+ *     fully connected layers alone ('h<i>', 'output_action', then the feature layer norm's pair if any), from offset 0.  Flat buffers,
+ *     gradient lists, optimiser slots, the clip's norm, soft updates, soft actor-critic's target-actor copy, checkpoints and the
+ *     collectives cover that shorter buffer.  'h0/weights' is (flat, n) with flat the width of the critic's flattened conv3 output.
+ *   - cpp_net_set_encoder(actor, critic) binds such an actor to a pixel critic of the same image geometry, action_dim, context and
+ *     max_batch (no batch norm): the actor's layer 0 reads the critic's flattened conv3 output of the same state -- the very buffer,
+ *     whose bias column of ones serves both; no copy and no second conv forward.  An actor is bound once (a second call answers CPP_ERR_ARG); cpp_net_destroy of
+ *     the critic leaves its actors unbound again, and their forwards then answer CPP_ERR_STATE.
+ *   - cpp_ddpg_create takes encoder-less actors only as a pair: the actor bound to the critic, the target actor bound to the target
+ *     critic (CPP_ERR_ARG otherwise).  The target actor therefore reads the target critic's conv3 output at state_2: a' = mu'(s2) is
+ *     computed on the soft-updated encoder.  Four networks and the target update as before.
+ *   - Stop gradient: the actor's backward pass ends at its layer-0 [dW; db].  No dX of that layer is formed, nothing of the actor's
+ *     objective reaches a conv gradient: the encoder's gradient is exactly the critic's loss gradient, and the encoder is stepped by
+ *     the critic's optimiser, rate and clip alone.
+ *   - Conv launches of a minibatch: forward {critic @ s1, target critic @ s2} (one trained network, one target), backward {critic};
+ *     the dW-reduction launch carries three layers x one network.  A single half (cpp_ddpg_train_actor alone) runs the critic's trunk
+ *     on s1 and no conv backward.
+ *   - Soft actor-critic: the target actor stays a bit copy of the actor's (fully connected) parameters; (a', logp') are sampled on the
+ *     target critic's features.  No conv1 operand image is rebuilt for it: it has no conv1.
+ *   - Inference: cpp_net_forward, cpp_net_forward_each and cpp_net_forward_gaussian of such an actor run the bound critic's trunk in
+ *     inference mode on the given states (its staging buffers, statistics and first workspace), then the actor's fully connected
+ *     stack; an actor that is not bound yet answers CPP_ERR_STATE.
+ * norm: CPP_NORM_NONE, or the feature layer norm's activation with its epsilon (cpp_net_create_feature_norm's rules).  variant (NULL:
+ * plain): only `gaussian` with its bounds (cpp_net_create_gaussian's rules).
+ * CPP_ERR_ARG, by name and before anything is allocated: a network that is not a CPP_ACTOR, a low-dimensional network, use_batch_norm,
+ * use_dropout, a critic's variant.  cpp_naf_create has no actor and takes none. */
+#define CPP_NORM_NONE (-1)
+int cpp_net_create_encoderless(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, const cpp_net_variant* variant, int norm, float epsilon,
+                               cpp_net** out);
+int cpp_net_set_encoder(cpp_net* actor, cpp_net* critic);
+/* encoderless = 1 for a network made by cpp_net_create_encoderless, bound = 1 once cpp_net_set_encoder has bound it.  NULL pointers are skipped. */
+int cpp_net_encoder_info(const cpp_net* net, int* encoderless, int* bound);
 int cpp_net_destroy(cpp_net* net);
 /* Network.trainable_model_vars (base_network.py:51-56): variables in creation order. */
 int64_t cpp_net_num_params(const cpp_net* net);
