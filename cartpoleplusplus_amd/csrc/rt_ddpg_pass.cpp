@@ -117,7 +117,7 @@ void Pass::trunks() {
     const void* sts[4] = {s1, s1, s2, s2};
     const float* whs[4] = {w1, w1, w2, w2};
     // conv1 / conv2 (+ conv3 as conv2's tail) of the four networks in one launch per layer; the two target networks have no
-    // backward pass (nets_forward_trunk_fused, rt_net.cpp).  Batch norm: training mode for the whole graph (ddpg_cartpole.py:145,237)
+    // backward pass (nets_forward_trunk_fused, rt_net_conv.cpp).  Batch norm: training mode for the whole graph (ddpg_cartpole.py:145,237)
     const bool bn = a->spec.use_batch_norm;
     tA = tC = tTA = tTC = G.fn([=] { return bn ? nets_forward_trunk_bn(ctx, nets, 4, sts, whs, dt, B)
                                                : nets_forward_trunk_fused(ctx, nets, 4, sts, whs, 2, dt, B); }, {});

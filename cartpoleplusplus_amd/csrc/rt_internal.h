@@ -131,6 +131,23 @@ struct cpp_net {
 };
 // a network with conv layers of its own (a low-dimensional network and an encoder-less actor have none)
 inline bool has_conv(const cpp_net* n) { return !n->conv.empty(); }
+// What net_create (rt_net.cpp) needs beyond the spec: which variant of the network the entry point asked for.  The defaults mean "plain";
+// net_create copies the record into the cpp_net fields of the same names (their comments above say what each one is).
+struct NetVariant {
+  bool twin = false;                                       // twin Q heads
+  int dist_n = 0; float v_min = 0.f, v_max = 0.f;          // atoms on the support [v_min, v_max] -- or, quant, that many quantiles and no support
+  bool quant = false;
+  bool gauss = false; float ls_lo = 0.f, ls_hi = 0.f;      // Gaussian actor and its log-std bounds
+  int ln_act = 0; float ln_eps = 0.f;                      // feature layer norm: GE_TANH / GE_RELU and epsilon (0: none)
+  bool enc_less = false;                                   // a pixel actor without conv layers
+};
+// floats from one image's row to the next in layer i's pooled output and in its gradient: conv3's pooled output is fc[0]'s input, whose
+// rows end in the bias column of ones
+struct PoolRows { long pool, dpool; };
+inline PoolRows pool_rows(const cpp_net* n, int i) {
+  const long dense = (long)n->conv[i].Hp * n->conv[i].Wp * kConvOut;
+  return i == 2 ? PoolRows{(long)n->flat + 1, (long)n->flat} : PoolRows{dense, dense};
+}
 
 struct cpp_batch {
   cpp_ctx* ctx; int maxB, B; long elems; int A; int dtype;
@@ -301,30 +318,29 @@ static const int kFwdKid[3] = {K_CONV1_FWD, K_CONV2_FWD, K_CONV3_FWD};
 static const int kDwKid[3] = {K_CONV1_DW, K_CONV2_DW, K_CONV3_DW};
 static const int kDxKid[3] = {-1, K_CONV2_DX, K_CONV3_DX};
 
-// ---- launch-sequence helpers shared by the translation units (definitions: rt_net.cpp, rt_replay.cpp, rt_ddpg.cpp; what the two learners share of a step: the end of this file)
-int gemm(cpp_ctx* ctx, const float* A, long sAm, long sAk, const float* Bm, long sBk, long sBn, float* C, long ldc, int M, int N, int K, int epi, const float* Y = nullptr, long ldy = 0, int accumulate = 0);
+// ---- rt_net_conv.cpp: launch descriptors of conv layer i, the trunk's forward and the conv backward sequences, whitening statistics
 ConvArgs conv_fwd_args(cpp_net* n, Workspace& w, int i, const void* state, int dtype, const float* white, int B, int* mode, long white_bstride = 0);
 void conv_dy_desc(cpp_net* n, Workspace& w, int i, ConvArgs& a, int B);
 ConvArgs conv_dw_args(cpp_net* n, Workspace& w, int i, const void* state, int dtype, const float* white, int B, int* mode);
 ConvArgs conv_dx_args(cpp_net* n, Workspace& w, int i, int B);
 BnNet bn_net_desc(cpp_net* n, Workspace& w, int i);
-BnBatch bn_batch(cpp_net* const* nets, int nn, int i, int B);
+// layer i of nn batch-norm networks for one bn.hip launch: their first workspaces, or (one network) the workspace given
+BnBatch bn_batch(cpp_net* const* nets, int nn, int i, int B, Workspace* w = nullptr);
 bool trunk_b16(const cpp_net* n, int dtype, int B, long white_bstride);
 int net_forward_trunk(cpp_net* n, Workspace& w, const void* state, int dtype, const float* white, int B, long white_bstride = 0);
 int nets_forward_trunk_fused(cpp_ctx* ctx, cpp_net* const* nets, int nn, const void* const* sts, const float* const* whs, int first_target, int dt, int B);
 int nets_forward_trunk_bn(cpp_ctx* ctx, cpp_net* const* nets, int nn, const void* const* states, const float* const* whites, int dtype, int B);
-GemmArgs mk_gemm(const float* A, long sAm, long sAk, const float* Bm, long sBk, long sBn, float* C, long ldc, int M, int N, int K, int epi);
-GemmArgs mk_gemm(const float* A, long sAm, long sAk, const float* Bm, long sBk, long sBn, float* C, long ldc, int M, int N, int K, int epi, const float* Y, long ldy);
+int net_backward_conv(cpp_net* n, Workspace& w, int B, const void* state, int dtype, const float* white);
+int nets_backward_conv(cpp_ctx* ctx, cpp_net* const* nets, int nn, int B, const void* state, int dtype, const float* white);
+int batch_stats(cpp_ctx* ctx, const void* s0, const void* s1, int dtype, long elems, int B, int C, double* part, float* white);
+int batch_stats_each(cpp_ctx* ctx, const void* s, int dtype, long elems, int B, int C, double* part, float* white_rows);
+// ---- rt_net_fc.cpp: GEMM descriptors of the fully connected stacks, dropout, the eager forward, the heads behind the last layer
+// (add_fc_backward, add_ln_backward: the end of this file)
+GemmArgs mk_gemm(const float* A, long sAm, long sAk, const float* Bm, long sBk, long sBn, float* C, long ldc, int M, int N, int K, int epi, const float* Y = nullptr, long ldy = 0);
 void set_dropout(GemmArgs& g, cpp_net* n, int l);
 int relu_grad_epi(const cpp_net* n, int producer_layer);
 int bump_dropout(cpp_net* n);
 int net_forward_fc(cpp_net* n, Workspace& w, int from, int B, const float* action);
-// feature layer norm behind the layer-0 GEMMs of `nn` networks (their first workspaces), one launch: the inference path's call
-int ln_forward(cpp_ctx* ctx, cpp_net* const* nets, int nn, int B);
-// ... and the same launch as a node of a gradient pass, behind the GEMM level that holds those GEMMs (deps; -1: none).  Returns the node.
-int add_ln_forward(struct OpGraph& G, cpp_ctx* ctx, cpp_net* const* nets, int nn, const int* deps, int B);
-int net_backward_conv(cpp_net* n, Workspace& w, int B, const void* state, int dtype, const float* white);
-int nets_backward_conv(cpp_ctx* ctx, cpp_net* const* nets, int nn, int B, const void* state, int dtype, const float* white);
 GemmArgs fc_fwd_args(cpp_net* n, Workspace& w, int l, int B);
 GemmArgs fc_dw_args(cpp_net* n, Workspace& w, int l, int B, const float* dz);
 GemmArgs fc_dx_args(cpp_net* n, int l, int B, const float* dz, long dz_ld, int col0, int ncols, float* C, long ldc, int epi, const float* Y, long ldy);
@@ -334,13 +350,20 @@ GemmArgs twin_fwd_args(cpp_net* n, Workspace& w, int l, int B);
 GemmArgs twin_dw_args(cpp_net* n, Workspace& w, int l, int B);
 GemmArgs twin_dx_args(cpp_net* n, Workspace& w, int l, int B);
 GemmArgs twin_da_args(cpp_net* n, Workspace& w, int B, float* C, int epi, const float* Y, long ldy);      // (the concat layer's action columns)
+// feature layer norm behind the layer-0 GEMMs of `nn` networks (their first workspaces), one launch: the inference path's call
+int ln_forward(cpp_ctx* ctx, cpp_net* const* nets, int nn, int B);
+// ... and the same launch as a node of a gradient pass, behind the GEMM level that holds those GEMMs (deps; -1: none).  Returns the node.
+int add_ln_forward(struct OpGraph& G, cpp_ctx* ctx, cpp_net* const* nets, int nn, const int* deps, int B);
 // where the last layer's GEMM writes: the logits of a distributional critic, `out` otherwise
 inline float* fc_last_out(const Workspace& w) { return w.logits ? w.logits : w.out; }
 // Q (and, dz != nullptr, p (z - Q); a quantile critic: 1 / N) from the logits the forward left in w: a no-op for every other network
 int dist_expect(cpp_net* n, Workspace& w, int B, float* dz);
 // a = tanh(m) (eps = 0) of a Gaussian actor from the head the forward left in w, into w.out: a no-op for every other network
 int gauss_mean(cpp_net* n, Workspace& w, int B, float* m_out = nullptr, float* ls_out = nullptr);
-int batch_stats(cpp_ctx* ctx, const void* s0, const void* s1, int dtype, long elems, int B, int C, double* part, float* white);
+// ---- rt_net_infer.cpp: a host batch through e's trunk and the stacks of nets[0 .. nn) in inference mode (the definition says what the callers vary)
+int infer_host_batch(cpp_net* e, cpp_net* const* nets, int nn, bool each, const void* state, int dtype, int B, const float* action, int A,
+                     float* m_out = nullptr, float* ls_out = nullptr);
+// ---- rt_replay.cpp, rt_ddpg.cpp, rt_ddpg_pass.cpp (what the two learners share of a step: the end of this file)
 int batch_ensure_stats(cpp_batch* b, int C);
 uint64_t replay_next_uid();      // graph keys: a fresh uid per cpp_replay_create and per change of a sampled memory's statistics setting
 int nstep_refuse(const cpp_replay* r, float discount, const char* who);      // CPP_ERR_ARG: an n-step memory folded with another discount
@@ -377,7 +400,7 @@ struct cpp_comm {
   } while (0)
 
 // ---------------------------------------------------------------------------------------------
-// What the DDPG and the NAF learner share of a training call (definitions: rt_step.cpp; add_fc_backward: rt_net.cpp)
+// What the DDPG and the NAF learner share of a training call (definitions: rt_step.cpp; add_fc_backward, add_ln_backward: rt_net_fc.cpp)
 // ---------------------------------------------------------------------------------------------
 // The squared norms of `lists` gradient lists (1 or 2), folded into the kernels that write the gradients (cpp_ctx::sq_part) while the
 // scope lives; groups: the list of each network of the conv backward.  left(cnt), once the pass has run: the partials it left for list

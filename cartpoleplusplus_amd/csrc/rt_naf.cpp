@@ -161,7 +161,7 @@ static int naf_compute_gradients(cpp_naf* f, cpp_batch* b, PassLeft* left, bool 
   int t1;
   if (v->spec.pixel && !v->spec.use_batch_norm) {
     std::vector<cpp_net*> nets(tn, tn + nt); std::vector<const void*> sts(ts, ts + nt); std::vector<const float*> whs(tw, tw + nt);
-    // one launch per conv layer for all trunks, conv3 as conv2's tail, the target network forward-only (rt_net.cpp)
+    // one launch per conv layer for all trunks, conv3 as conv2's tail, the target network forward-only (rt_net_conv.cpp)
     t1 = G.fn([=] { return nets_forward_trunk_fused(ctx, nets.data(), nt, sts.data(), whs.data(), nt - 1, dt, B); }, {});
   } else {
     std::vector<cpp_net*> nets(tn, tn + nt); std::vector<const void*> sts(ts, ts + nt); std::vector<const float*> whs(tw, tw + nt);
@@ -332,20 +332,9 @@ extern "C" int cpp_naf_action(cpp_naf* f, const void* state, int dtype, int B, f
   ARG_CHECK(B >= 1 && B <= f->maxB, "cpp_naf_action: batch %d outside [1,%d]", B, f->maxB);
   ARG_CHECK(dtype == CPP_F32 || dtype == CPP_F16, "cpp_naf_action: dtype %d", dtype);
   cpp_ctx* ctx = f->ctx;
-  cpp_net* n = f->share ? f->value : f->mu;       // the network whose trunk sees the state
-  HIP_CHECK(hipSetDevice(ctx->device));
-  if (!n->stage_state) {
-    RC(n->arena.alloc(&n->stage_state, (size_t)n->maxB * n->state_elems * sizeof(float), false));
-    RC(dalloc(n->arena, &n->stage_action, (size_t)n->maxB * f->A));
-  }
-  HIP_CHECK(hipMemcpyAsync(n->stage_state, state, (size_t)B * n->state_elems * (dtype == CPP_F16 ? 2 : 4), hipMemcpyHostToDevice, ctx->stream));
-  if (n->spec.pixel) RC(batch_stats(ctx, n->stage_state, nullptr, dtype, n->state_elems, B, n->spec.C, n->stats_part, n->white));
-  n->is_training = false; f->mu->is_training = false;  // IS_TRAINING: False (naf_cartpole.py:253)
-  int frc = net_forward_trunk(n, n->ws[0], n->stage_state, dtype, n->white, B);
-  if (!frc) frc = net_forward_fc(n, n->ws[0], 0, B, nullptr);
-  if (!frc && f->share) frc = net_forward_fc(f->mu, f->mu->ws[0], 0, B, nullptr);
-  n->is_training = true; f->mu->is_training = true;
-  if (frc) return frc;
+  // the network whose trunk sees the state; shared: the value network's stack (the representation), then mu's on top of it
+  cpp_net* stacks[2] = {f->share ? f->value : f->mu, f->mu};
+  RC(infer_host_batch(stacks[0], stacks, f->share ? 2 : 1, false, state, dtype, B, nullptr, f->A));
   HIP_CHECK(hipMemcpyAsync(out, f->mu->ws[0].out, (size_t)B * f->A * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(ctx_sync_stream(ctx));
   return CPP_OK;

@@ -18,7 +18,9 @@ While the ABI stands, one tree does: the parent's two libraries copied into cart
 Equality is the bar.  The single_* configurations drive the four single entry points (train_actor, train_critic, check_loss,
 q_gradients_wrt_actions) on host batches, one round of the four per outer step; their digests also cover what check_loss and
 q_gradients_wrt_actions return and both networks' gradient buffers after every call.  Their launch counts are recorded and not compared
-(LAUNCHES_RECORDED_ONLY): a build that batches the GEMMs of a level launches fewer.  The merged file is a record of one comparison, not a fixture: the digests move with every intended kernel change.
+(LAUNCHES_RECORDED_ONLY): a build that batches the GEMMs of a level launches fewer.  The infer_* configurations drive the host-batch
+inference entry points (cpp_net_forward, cpp_net_forward_each, cpp_net_forward_gaussian, cpp_net_get_pool, cpp_naf_action) on fresh states,
+one round per outer step, and digest the bytes they return; no training step runs in them.  The merged file is a record of one comparison, not a fixture: the digests move with every intended kernel change.
 Usage: step_digest.py [config name ...] | --merge parent_a parent_b head [parent_a_abl parent_b_abl head_abl]"""
 import ctypes as C
 import hashlib, json, os, sys
@@ -174,6 +176,42 @@ def single_state(a):
     return ddpg_state(a) + a.single
 
 
+def infer_states(a, k):      # float32 states of round k: pixel values in [0, 1), standard normal low-dimensional ones
+    shape, rng = a.env.observation_space.shape, np.random.default_rng(800 + k)
+    return (rng.random((B,) + tuple(shape)) if len(shape) == 5 else rng.standard_normal((B,) + tuple(shape))).astype(np.float32)
+
+
+def pools_of(net, shape):      # pool1..3 of the network's last forward
+    out = []
+    for i in (1, 2, 3):
+        p = np.empty((B, shape[0] >> i, shape[1] >> i, 10), np.float32)
+        check(lib.cpp_net_get_pool(net.handle, i, B, ptr(p)))
+        out.append(p)
+    return out
+
+
+def infer_ddpg(a, k):      # one round of the inference entry points; what they return rides in a.infer
+    s, shape = infer_states(a, k), a.env.observation_space.shape
+    owner = a.critic if a.actor.shared_encoder else a.actor      # (the network whose trunk sees the actor's states)
+    pools = (lambda n: pools_of(n, shape)) if len(shape) == 5 else (lambda n: [])
+    a.infer = [a.actor.forward(s[:1]), a.actor.forward(s)] + pools(owner)
+    a.infer += [a.actor.actions_given(s), a.actor.actions_given(s.astype(np.float16))] + pools(owner)
+    act = np.random.default_rng(850 + k).uniform(-1, 1, (B, a.actor.action_dim)).astype(np.float32)
+    a.infer += [a.critic.forward(s, act)] + pools(a.critic)
+    if a.actor.sac:
+        for each in (False, True):
+            a.infer += list(a.actor.forward_gaussian(s, each=each)) + pools(owner)
+
+
+def infer_naf(a, k):
+    s = infer_states(a, k)
+    a.infer = [a.naf.forward(s[:1]), a.naf.forward(s)]
+
+
+def infer_state(a):
+    return a.infer
+
+
 def naf_state(a):
     st = a.naf.get_optimiser_state()
     out = [n.get_params() for n in a.networks()] + [np.asarray(st[k]) for k in sorted(st)]
@@ -213,6 +251,8 @@ def naf_dp(a, k): check(lib.cpp_naf_dp_train_step(a.naf.handle, a.replay_memory.
 
 
 DDPG, NAF, SINGLE = (ddpg_agent, ddpg_state), (naf_agent, naf_state), (ddpg_agent, single_state)
+INFER_DDPG, INFER_NAF = (ddpg_agent, infer_state), (naf_agent, infer_state)
+DRQV2 = dict(twin_q=True, actor_min_q=True, feature_layer_norm=True, n_step=3, target_policy_noise=0.2, shift=4)
 # name: (learner, shape, options, one outer step)
 CONFIGS = {
     "ddpg_sgd": (DDPG, PIXEL, {}, ddpg_step),
@@ -244,7 +284,10 @@ CONFIGS = {
     "ddpg_twin_min_bc_lowdim": (DDPG, LOWDIM, dict(twin_q=True, actor_min_q=True, bc_alpha=2.5), ddpg_step),
     "ddpg_sac_twin_min": (DDPG, PIXEL, dict(soft_actor_critic=True, twin_q=True, actor_min_q=True), ddpg_step),
     "ddpg_dropout": (DDPG, PIXEL, dict(use_dropout=True), ddpg_step),
-    "ddpg_drqv2": (DDPG, PIXEL, dict(twin_q=True, actor_min_q=True, feature_layer_norm=True, n_step=3, target_policy_noise=0.2, shift=4), ddpg_step),
+    "ddpg_drqv2": (DDPG, PIXEL, DRQV2, ddpg_step),
+    "ddpg_shared_encoder": (DDPG, PIXEL, dict(shared_encoder=True), ddpg_step),
+    "ddpg_shared_encoder_sac": (DDPG, PIXEL, dict(shared_encoder=True, soft_actor_critic=True), ddpg_step),
+    "ddpg_shared_encoder_drqv2": (DDPG, PIXEL, dict(DRQV2, shared_encoder=True), ddpg_step),
     "naf_shared": (NAF, PIXEL, dict(share_input_state_representation=True), naf_step),
     "naf_unshared": (NAF, PIXEL, {}, naf_step),
     "naf_lowdim": (NAF, LOWDIM, {}, naf_step),
@@ -258,6 +301,18 @@ CONFIGS = {
     "naf_rows_prioritized": (NAF, PIXEL, dict(share_input_state_representation=True, prioritized_replay=True), naf_rows),
     "naf_rows_async": (NAF, PIXEL, dict(share_input_state_representation=True, **MOMENTUM), naf_rows_async),
     "naf_dp": (NAF, PIXEL, dict(share_input_state_representation=True), naf_dp),
+    "infer_ddpg": (INFER_DDPG, PIXEL, {}, infer_ddpg),
+    "infer_ddpg_lowdim": (INFER_DDPG, LOWDIM, {}, infer_ddpg),
+    "infer_ddpg_batch_norm": (INFER_DDPG, PIXEL, dict(use_batch_norm=True), infer_ddpg),
+    "infer_ddpg_categorical": (INFER_DDPG, PIXEL, dict(distributional_critic=True, num_atoms=21, v_min=-5.0, v_max=25.0), infer_ddpg),
+    "infer_ddpg_quantile": (INFER_DDPG, PIXEL, dict(quantile_critic=True, num_quantiles=9, drop_top_quantiles=2), infer_ddpg),
+    "infer_ddpg_twin": (INFER_DDPG, PIXEL, dict(twin_q=True), infer_ddpg),
+    "infer_ddpg_feature_norm": (INFER_DDPG, PIXEL, dict(feature_layer_norm=True), infer_ddpg),
+    "infer_ddpg_sac": (INFER_DDPG, PIXEL, dict(soft_actor_critic=True), infer_ddpg),
+    "infer_ddpg_shared_encoder": (INFER_DDPG, PIXEL, dict(shared_encoder=True), infer_ddpg),
+    "infer_naf_shared": (INFER_NAF, PIXEL, dict(share_input_state_representation=True), infer_naf),
+    "infer_naf_unshared": (INFER_NAF, PIXEL, {}, infer_naf),
+    "infer_naf_lowdim": (INFER_NAF, LOWDIM, {}, infer_naf),
 }
 for _t, _kw in SINGLE_TRAINERS.items():
     CONFIGS["single_" + _t] = (SINGLE, PIXEL, _kw, single_ops)
@@ -273,6 +328,7 @@ ABLATION_CONFIGS = {
     "ddpg_twin_min_gemm_levels": (DDPG, PIXEL, dict(twin_q=True, actor_min_q=True), ddpg_step),
     "ddpg_feature_norm_gemm_levels": (DDPG, PIXEL, dict(feature_layer_norm=True), ddpg_step),
     "ddpg_dropout_gemm_levels": (DDPG, PIXEL, dict(use_dropout=True), ddpg_step),
+    "ddpg_shared_encoder_gemm_levels": (DDPG, PIXEL, dict(shared_encoder=True), ddpg_step),
 }
 if ABLATION:
     assert os.environ.get("CARTPOLEPP_ABLATION") not in (None, "", "0"), "the switch is compiled into the ablation builds only: CARTPOLEPP_ABLATION=1 (or a named ablation build) CPP_FUSED_HEADS=0"
