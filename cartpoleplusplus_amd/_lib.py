@@ -174,6 +174,11 @@ SIGNATURES = {
     "cpp_ddpg_last_sac": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_U64), _P]),
     "cpp_ddpg_sac_temperature": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_U64)]),
     "cpp_ddpg_last_feature_norm": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "cpp_ddpg_set_param_noise": (_I, [_P, _P, C.c_float, C.c_float, C.c_float, _U64]),
+    "cpp_ddpg_param_noise_resample": (_I, [_P, _P]),
+    "cpp_ddpg_param_noise_status": (_I, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_U64), C.POINTER(_I)]),
+    "cpp_ddpg_param_noise_state": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(_U64)]),
+    "cpp_ddpg_last_param_noise": (_I, [_P, _I, _P, _P]),
     "cpp_comm_unique_id": (_I, [_P, _I]),
     "cpp_comm_create": (_I, [_P, _P, _I, _I, _PP]),
     "cpp_comm_destroy": (_I, [_P]),

@@ -65,6 +65,7 @@ enum KernelId {
   K_LN_FWD,               // feature layer norm on fully connected layer 0, forward (ln.hip)
   K_LN_BWD,               // ... its backward: the column sums' launch and the row-local launch
   K_BC,                   // behaviour-cloning actor term: the batch-wide mean of |Q| and the actor's head gradient (bc.hip)
+  K_PARAM_NOISE,          // parameter-space exploration noise: the perturbed copy of the actor, and its distance / adapt / count launch (param_noise.hip)
   K_NUM_KERNELS
 };
 
@@ -536,6 +537,28 @@ struct BcArgs {
   float *adz, *stat, *g, *rows;
 };
 int launch_bc(cpp_ctx* ctx, const BcArgs& s);
+// Parameter-space exploration noise (Plappert et al. 2018; param_noise.hip; rt_ddpg_noise.cpp, cpp_ddpg_set_param_noise; an extension of the
+// exploration of ddpg_cartpole.py:127-134).  The trainer's device words: the launches read sigma and n from here, so that a resample needs no
+// host wait; the second launch alone writes them.
+struct PnWords { unsigned long long n; float sigma, d; unsigned adapted, reserved; };
+// the standard normal of draw n for element i of the flat parameter buffer: tps_noise's Box-Muller on the same two 24-bit uniforms, unclipped, of
+// philox4x32_10({i, 0x200, n_lo, n_hi}, seed) -- word 1 = 0x200 is no other stream's (the sampler's 0..3, smoothing's 0x100 + component;
+// soft actor-critic's 0x200 / 0x300 sit in another trainer: such a trainer is refused)
+__device__ __forceinline__ float pn_normal(unsigned seed_lo, unsigned seed_hi, unsigned long long n, unsigned i) {
+  const u32x4 r = philox4x32_10(u32x4{i, 0x200u, (uint32_t)n, (uint32_t)(n >> 32)}, seed_lo, seed_hi);
+  const float u1 = (float)((r.x >> 8) + 1u) * 0x1p-24f;      // (0, 1]: exact
+  const float u2 = (float)(r.y >> 8) * 0x1p-24f;             // [0, 1): exact
+  return sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
+}
+// dst[i] = fmaf(sigma, z(seed, n, i), src[i]) for i < n_noise, dst[i] = src[i] for n_noise <= i < count (the feature layer norm's gamma and
+// beta, which close the flat buffer)
+#define PN_THREADS 256
+int launch_pn_perturb(cpp_ctx* ctx, const PnWords* words, uint64_t seed, const float* src, float* dst, long count, long n_noise);
+// One workgroup.  B > 0: d = sqrt(sum_{b,k} (a[b][k] - at[b][k])^2 / (B A)) -- the differences and their squares in f64 (both exact up to the
+// square's one rounding), thread t adds elements t, t + 256, .. in order, then one tree over the 256 partials, one rounding to f32 -- kept in
+// words->d; sigma <- d < delta ? sigma * alpha : sigma / alpha; adapted = 1; a and at are kept in a_keep / at_keep.  B == 0: sigma and d stay,
+// adapted = 0.  Either way n += 1.
+int launch_pn_measure(cpp_ctx* ctx, PnWords* words, const float* a, const float* at, int B, int A, float delta, float alpha, float* a_keep, float* at_keep);
 enum { PD_N = 0, PD_HOLD = 1, PD_PHASE = 2, PD_WORDS = 3 };
 // ---- distributional (categorical) critic (dist.hip; include/cartpolepp_abi.h, cpp_net_create_distributional).  logits: (B, N), N in [2, 64].
 // job (a): q_out[b] = Q = sum_i p_i z_i and, dz != nullptr, dz[b][i] = p_i (z_i - Q)

@@ -77,6 +77,12 @@ struct cpp_ddpg {
   // actors read the critics' conv3 outputs, and only the critic's loss reaches the conv gradients.  trunk: the network whose conv1 decides
   // the form of a minibatch (direct_replay_ok) -- the critic then, the actor otherwise
   bool shared = false; cpp_net* trunk = nullptr;
+  // parameter-space exploration noise (cpp_ddpg_set_param_noise; rt_ddpg_noise.cpp; common.h: PnWords).  pn_net: the perturbed copy of the
+  // actor, the caller's network (nullptr: off); pn_words: sigma, the draw count, the last distance and whether the last resample adapted, on the
+  // device; pn_a / pn_at: the two action batches of the last measured resample (maxB x A), pn_B its rows (0: none yet).  Target distance,
+  // factor and seed travel by value in launches that are never captured: no graph knows of any of this
+  cpp_net* pn_net = nullptr; PnWords* pn_words = nullptr; float pn_delta = 0.f, pn_alpha = 1.f; uint64_t pn_seed = 0;
+  float *pn_a = nullptr, *pn_at = nullptr; int pn_B = 0;
 };
 
 // What a caller wants of the gradient pass: the halves to run -- the actor's (ddpg_cartpole.py:111-113, :220-222: dQ/da at actor(s1),

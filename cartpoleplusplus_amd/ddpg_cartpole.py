@@ -223,6 +223,23 @@ def build_parser():
     a('--random-shift', type=int, metavar='PAD', default=argparse.SUPPRESS,
       help="--use-raw-pixels: pad every gathered image by PAD pixels of its own edge and crop it back at a random offset (default 0: off)")
     a('--random-shift-seed', type=int, metavar='N', default=argparse.SUPPRESS, help="--random-shift: seed of the shifts (default 0)")
+    # parameter-space exploration noise (an extension beyond the reference, ddpg_cartpole.py:127-134, whose exploration is one
+    # Ornstein-Uhlenbeck process added to the action: Plappert et al. 2018): the actor's weights are perturbed once per episode on the
+    # device, the episode is played with the perturbed copy, and the perturbation's scale adapts until it moves the actions by DELTA
+    # (absent from the parsed options unless given, like --random-shift; param_noise() reads them)
+    a('--param-noise-stddev', type=float, metavar='S', default=argparse.SUPPRESS,
+      help="explore with a copy of the actor whose weights carry N(0, S^2) noise, redrawn at every episode boundary, instead of the "
+           "Ornstein-Uhlenbeck action noise; S is the initial standard deviation (default: off)")
+    a('--param-noise-target', type=float, metavar='DELTA', default=argparse.SUPPRESS,
+      help="--param-noise-stddev: the root-mean-square distance between the actor's and the perturbed actor's actions that the standard "
+           "deviation is adapted towards (default 0.1)")
+    a('--param-noise-adapt', type=float, metavar='ALPHA', default=argparse.SUPPRESS,
+      help="--param-noise-stddev: the standard deviation is multiplied (distance below DELTA) or divided by ALPHA at every measured resample "
+           "(default 1.01; 1 keeps it fixed)")
+    a('--param-noise-adapt-rounds', type=int, metavar='R', default=argparse.SUPPRESS,
+      help="--param-noise-stddev: resamples per episode boundary, each adapting; the last is the exploring copy (default 1)")
+    a('--param-noise-seed', type=int, metavar='N', default=argparse.SUPPRESS,
+      help="--param-noise-stddev: seed of the device's noise stream (default 0; --data-parallel: rank r draws with N + r)")
     return parser
 
 
@@ -254,6 +271,54 @@ def random_shift(o):
     if not bool(getattr(o, "use_raw_pixels", False)):
         raise SystemExit("--random-shift needs --use-raw-pixels: a low-dimensional state has no image to shift")
     return (int(pad), int(seed))
+
+
+_PARAM_NOISE_DEFAULTS = {"param_noise_target": 0.1, "param_noise_adapt": 1.01, "param_noise_adapt_rounds": 1, "param_noise_seed": 0}
+PARAM_NOISE_ROUNDS_MAX = 64
+
+
+def param_noise(o):
+    """{stddev, target, adapt, rounds, seed} of --param-noise-stddev and its --param-noise-* flags, or None (off); refuses what cannot be
+    meant"""
+    import math
+    s = getattr(o, "param_noise_stddev", None)
+    given = [k for k in _PARAM_NOISE_DEFAULTS if getattr(o, k, None) is not None]
+    if s is None:
+        if given:
+            raise SystemExit("--%s needs --param-noise-stddev" % given[0].replace("_", "-"))
+        return None
+    v = {}
+    for k, name in (("param_noise_stddev", "stddev"), ("param_noise_target", "target"), ("param_noise_adapt", "adapt")):
+        x = getattr(o, k, None)
+        x = _PARAM_NOISE_DEFAULTS.get(k) if x is None else x
+        try:
+            x = float(np.float32(x))
+        except (TypeError, ValueError) as e:
+            raise SystemExit("--%s: %s" % (k.replace("_", "-"), e))
+        if isinstance(getattr(o, k, None), bool) or not math.isfinite(x):
+            raise SystemExit("--%s %r is not a finite number" % (k.replace("_", "-"), getattr(o, k, None)))
+        v[name] = x
+    if v["stddev"] < 0.0:
+        raise SystemExit("--param-noise-stddev %r is not a standard deviation >= 0" % (s,))
+    if not v["target"] > 0.0:
+        raise SystemExit("--param-noise-target %r is not a distance > 0" % (getattr(o, "param_noise_target"),))
+    if v["adapt"] < 1.0:
+        raise SystemExit("--param-noise-adapt %r is not a factor >= 1 (1 keeps the standard deviation fixed)" % (getattr(o, "param_noise_adapt"),))
+    r = getattr(o, "param_noise_adapt_rounds", None)
+    r = _PARAM_NOISE_DEFAULTS["param_noise_adapt_rounds"] if r is None else r
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= int(r) <= PARAM_NOISE_ROUNDS_MAX:
+        raise SystemExit("--param-noise-adapt-rounds %r is not a whole number in [1, %d]" % (r, PARAM_NOISE_ROUNDS_MAX))
+    seed = getattr(o, "param_noise_seed", None)
+    seed = _PARAM_NOISE_DEFAULTS["param_noise_seed"] if seed is None else seed
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise SystemExit("--param-noise-seed %r is not in [0, 2^64)" % (seed,))
+    v["rounds"], v["seed"] = int(r), int(seed)
+    if bool(getattr(o, "soft_actor_critic", False)):
+        raise SystemExit("--param-noise-stddev cannot be combined with --soft-actor-critic (its policy explores by itself)")
+    if bool(getattr(o, "use_batch_norm", False)):
+        raise SystemExit("--param-noise-stddev cannot be combined with --use-batch-norm (the perturbed copy would be measured in inference "
+                         "mode against statistics its weights never shaped; the paper's normalisation is --feature-layer-norm)")
+    return v
 
 
 FEATURE_NORM_ACTIVATIONS = ("tanh", "relu")
@@ -555,6 +620,9 @@ def default_opts(**overrides):
     o.feature_layer_norm, o.feature_norm_activation = False, None
     o.shared_encoder = False
     o.random_shift, o.random_shift_seed = None, None
+    o.param_noise_stddev = None
+    for k in _PARAM_NOISE_DEFAULTS:
+        setattr(o, k, None)
     for k in _SAC_DEFAULTS:
         setattr(o, k, None)
     for k, v in overrides.items():
@@ -616,6 +684,9 @@ class ActorNetwork(base_network.Network):
         self.output_action = _OpHandle(namespace + "/output_action")
         self.train_op = None
         self.critic = None
+        # --param-noise-stddev: the copy of this actor that explores in its place (the agent's 'perturbed_actor'); None: this actor itself,
+        # with the Ornstein-Uhlenbeck process
+        self.perturbed = None
 
     def init_ops_for_training(self, critic):
         # gradients of output_action w.r.t. the actor's variables with grad_ys = -dQ/da from the critic
@@ -640,6 +711,8 @@ class ActorNetwork(base_network.Network):
         B = s.shape[0]
         if self.sac and add_noise:
             return self._sample_gaussian(s, dt, B, each=True)
+        if add_noise and self.perturbed is not None:      # --param-noise-stddev: the perturbed copy's own actions; tanh bounds them
+            return self.perturbed.actions_given(s)
         actions = np.empty((B, self.action_dim), np.float32)
         check(lib.cpp_net_forward_each(self.handle, ptr(s), dt, B, None, ptr(actions)))
         if add_noise:
@@ -671,6 +744,13 @@ class ActorNetwork(base_network.Network):
         if self.sac and add_noise:
             s, dt = _lib.as_state_array(np.asarray(state)[None])
             return self._sample_gaussian(s, dt, 1, each=False)
+        if add_noise and self.perturbed is not None:
+            # --param-noise-stddev: the exploration is in the weights of the perturbed copy (redrawn by agent.begin_episode, consistent
+            # within the episode); no Ornstein-Uhlenbeck sample, and no clip: tanh bounds the action
+            actions = self.perturbed.forward(np.asarray(state)[None])
+            if VERBOSE_DEBUG:
+                print("TRAIN action_given pre_noise %s post_noise %s" % (self.forward(np.asarray(state)[None]), actions))
+            return actions
         actions = self.forward(np.asarray(state)[None])
         # NOTE: noise is added outside the device graph, as in the reference (:127-134)
         if add_noise:
@@ -762,6 +842,8 @@ class _Trainer(object):
         bc = getattr(critic, "_behaviour_cloning", None) or behaviour_cloning(opts)
         if bc[0] > 0.0:
             self.set_behaviour_cloning(*bc)
+        # --param-noise-stddev: off until the agent hands over its perturbed copy (set_param_noise); the trainer's state as created
+        self.param_noise = None
 
     @property
     def handle(self):
@@ -959,6 +1041,45 @@ class _Trainer(object):
         check(lib.cpp_ddpg_last_behaviour_cloning(self.handle, B, ptr(lam), ptr(m), ptr(g), ptr(rows)))
         return float(lam[0]), float(m[0]), g, rows
 
+    def set_param_noise(self, perturbed_actor, stddev=0.0, target=0.1, adapt=1.0, seed=0):
+        """parameter-space exploration noise (include/cartpolepp_abi.h, cpp_ddpg_set_param_noise): `perturbed_actor`, an ActorNetwork with
+        the actor's layout, becomes the actor plus N(0, stddev^2) noise on every weight, is redrawn by param_noise_resample and answers
+        the actor's action_given(.., add_noise=True); set_param_noise(None) switches it off.  Ends with one resample without a batch;
+        drops no captured graph."""
+        h = perturbed_actor.handle if perturbed_actor is not None else None
+        check(lib.cpp_ddpg_set_param_noise(self.handle, h, float(stddev), float(target), float(adapt), int(seed)))
+        self.param_noise = None if perturbed_actor is None else (float(stddev), float(target), float(adapt), int(seed))
+        self.nets[0].perturbed = perturbed_actor
+
+    def param_noise_resample(self, device_batch=None):
+        """one resample (cpp_ddpg_param_noise_resample): perturb; with a DeviceBatch also measure the action distance on its state_1 and
+        adapt the standard deviation of the next resample; count.  Nothing waits for the device."""
+        check(lib.cpp_ddpg_param_noise_resample(self.handle, device_batch.handle if device_batch is not None else None))
+
+    def param_noise_status(self):
+        """(sigma the next resample reads, distance of the last measured resample, draw count n, whether the last resample adapted)"""
+        s, d, n, ad = C.c_float(), C.c_float(), C.c_uint64(), C.c_int()
+        check(lib.cpp_ddpg_param_noise_status(self.handle, C.byref(s), C.byref(d), C.byref(n), C.byref(ad)))
+        return np.float32(s.value), np.float32(d.value), int(n.value), bool(ad.value)
+
+    def get_param_noise_state(self):
+        """{sigma, n}: what a checkpoint carries of the noise (the perturbed copy itself is redrawn)"""
+        s, n = C.c_float(), C.c_uint64()
+        check(lib.cpp_ddpg_param_noise_state(self.handle, 0, C.byref(s), C.byref(n)))
+        return {"sigma": np.float32(s.value), "n": np.uint64(n.value)}
+
+    def set_param_noise_state(self, state):
+        s = C.c_float(float(np.asarray(state["sigma"]).reshape(())))
+        n = C.c_uint64(int(np.asarray(state["n"]).reshape(())))
+        check(lib.cpp_ddpg_param_noise_state(self.handle, 1, C.byref(s), C.byref(n)))
+
+    def last_param_noise(self, B):
+        """(a, at), each (B, action_dim): the actor's and the perturbed actor's actions on the rows of the last measured resample"""
+        B = int(B)
+        a, at = np.empty((B, self.action_dim), np.float32), np.empty((B, self.action_dim), np.float32)
+        check(lib.cpp_ddpg_last_param_noise(self.handle, B, ptr(a), ptr(at)))
+        return a, at
+
     def policy_delay_status(self):
         """(delay, critic updates counted since it was set, whether the last minibatch held the actor)"""
         d, n, held = C.c_int(), C.c_uint64(), C.c_int()
@@ -1129,6 +1250,7 @@ class DeepDeterministicPolicyGradientAgent(object):
         behaviour_cloning(opts)
         shared_encoder(opts)
         shift = random_shift(opts)
+        self.param_noise = param_noise(opts)
         # (--exact-products asks for the exact arithmetic contract; without the flag the context keeps whatever mode its owner chose --
         # an explicit Context.set_precision("exact") is not undone, and a second agent on the shared context does not fight the first)
         if getattr(opts, "exact_products", False) and _lib.default_context().precision != "exact":
@@ -1161,6 +1283,13 @@ class DeepDeterministicPolicyGradientAgent(object):
         self.critic.init_ops_for_training(self.target_critic)
         self.ddpg_optimiser_kind = self.critic._optimiser[0]      # (util.optimiser_slot_owner: who holds slots is a fact about this agent)
         self.train_steps = 0
+        # --param-noise-stddev: one more actor, the copy that explores.  Not one of networks(): it is a function of the actor, sigma and the
+        # draw count, so it is neither checkpointed nor broadcast; under --shared-encoder it reads the critic's conv features as the actor does
+        self.perturbed_actor = None
+        if self.param_noise is not None:
+            self.perturbed_actor = ActorNetwork("perturbed_actor", s1, action_dim)
+            if self.perturbed_actor.shared_encoder:
+                check(lib.cpp_net_set_encoder(self.perturbed_actor.handle, self.critic.handle))
 
     def initialise_variables(self, seed=None):
         """tf.initialize_all_variables() (ddpg_cartpole.py:424)."""
@@ -1173,10 +1302,46 @@ class DeepDeterministicPolicyGradientAgent(object):
 
     def checkpoint_extras(self):
         """(prefix, get, set) of state a checkpoint carries by name besides the networks and the optimiser slots: the temperature of a
-        --soft-actor-critic agent ('sac::log_alpha', 'sac::m', 'sac::v', 'sac::step'); nothing for any other agent"""
+        --soft-actor-critic agent ('sac::log_alpha', 'sac::m', 'sac::v', 'sac::step'), the standard deviation and the draw count of a
+        --param-noise-stddev agent ('param_noise::sigma', 'param_noise::n'); nothing for any other agent"""
+        if getattr(self, "param_noise", None) is not None:
+            return [("param_noise::", lambda: self._param_noise_trainer().get_param_noise_state(),
+                     lambda st: self._param_noise_trainer().set_param_noise_state(st))]
         if not self.actor.sac:
             return []
         return [("sac::", lambda: self.trainer.get_sac_state(), lambda st: self.trainer.set_sac_state(st))]
+
+    def _param_noise_trainer(self):
+        """the trainer with the perturbed copy handed over (once: cpp_ddpg_set_param_noise zeroes the draw count).  Under --data-parallel
+        rank r draws with seed + r, so that the replicas explore differently."""
+        t = self.trainer
+        if t.param_noise is None:
+            pn = self.param_noise
+            rank = int(os.environ.get("RANK", "0")) if getattr(opts, "data_parallel", False) else 0
+            t.set_param_noise(self.perturbed_actor, pn["stddev"], pn["target"], pn["adapt"], (pn["seed"] + rank) % 2 ** 64)
+        return t
+
+    def begin_episode(self):
+        """--param-noise-stddev: redraw the perturbed copy for the episode about to start (Plappert et al. 2018: the perturbation is held
+        for a whole episode) -- --param-noise-adapt-rounds resamples, each on its own device minibatch of opts.batch_size rows (the
+        inspection sampler: the training sampler's counter stays where it is; the stored pixels, no random shift) once the memory holds
+        that many, without a batch before that.  A no-op for every other agent.  Under --async-rollouts the rollout thread calls it: it
+        takes the device lock, as _action does."""
+        if getattr(self, "param_noise", None) is None:
+            return
+        lock = getattr(self, "device_lock", None)
+        if lock is None:
+            return self._begin_episode()
+        with lock:
+            return self._begin_episode()
+
+    def _begin_episode(self):
+        t, B = self._param_noise_trainer(), int(opts.batch_size)
+        for _ in range(self.param_noise["rounds"]):
+            dev = None
+            if self.replay_memory.size() >= B:
+                dev = self.replay_memory.sample_on_device(B, seed=self.param_noise["seed"]).device
+            t.param_noise_resample(dev)
 
     def post_var_init_setup(self):
         if opts.event_log_in:
@@ -1184,6 +1349,8 @@ class DeepDeterministicPolicyGradientAgent(object):
         # hook networks up to their targets ( one off clobber of all vars in target network )
         self.target_actor.set_as_target_network_for(self.actor, opts.target_update_rate)
         self.target_critic.set_as_target_network_for(self.critic, opts.target_update_rate)
+        if getattr(self, "param_noise", None) is not None:      # the actor's variables exist: the perturbed copy can be drawn, and acts from here on
+            self._param_noise_trainer()
 
     @property
     def trainer(self):
@@ -1262,7 +1429,8 @@ class DeepDeterministicPolicyGradientAgent(object):
             return False
         loop = training_loop.TrainingLoop(self, opts, act=lambda s: self._action(s, True), train=self._train_once,
                                           agreement=agreement, verbose=lambda: VERBOSE_DEBUG,
-                                          after_train=self._verbose_after_train, dump_weights_requested=dump_requested)
+                                          after_train=self._verbose_after_train, dump_weights_requested=dump_requested,
+                                          begin_episode=self.begin_episode if getattr(self, "param_noise", None) is not None else None)
         loop.run(max_num_actions, max_run_time, batch_size, batches_per_step, saver_util)
         return loop
 
@@ -1299,6 +1467,8 @@ class DeepDeterministicPolicyGradientAgent(object):
             self._learner = None
         if self.critic._ddpg is not None:
             self.critic._ddpg.close()
+        if getattr(self, "perturbed_actor", None) is not None:
+            self.perturbed_actor.close()
         for net in (self.actor, self.critic, self.target_actor, self.target_critic):
             net.close()
         self.replay_memory.close()

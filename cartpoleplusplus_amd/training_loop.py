@@ -71,9 +71,12 @@ class FairLock(object):
 Episode = collections.namedtuple("Episode", "initial_state sequence rewards seconds")
 
 
-def play_episode(env, act):
-    """one episode with `act(state) -> action` (ddpg_cartpole.py:313-326)."""
+def play_episode(env, act, begin_episode=None):
+    """one episode with `act(state) -> action` (ddpg_cartpole.py:313-326).  begin_episode: called first, before the environment is
+    reset (an agent whose exploration is drawn once per episode: --param-noise-stddev)."""
     t0 = time.time()
+    if begin_episode is not None:
+        begin_episode()
     state_1 = env.reset()
     initial_state = np.copy(state_1)
     sequence, rewards = [], []
@@ -91,8 +94,9 @@ class AsyncRollouts(object):
     """the rollout thread of --async-rollouts: plays episodes with `act` and, after every `eval_every`-th, one evaluation episode
     through `evaluate()` (the environment belongs to this thread, so the learner thread must not run its own)."""
 
-    def __init__(self, env, act, evaluate=None, eval_every=10, max_queued=8):
+    def __init__(self, env, act, evaluate=None, eval_every=10, max_queued=8, begin_episode=None):
         self.env, self.act, self.evaluate, self.eval_every = env, act, evaluate, int(eval_every)
+        self.begin_episode = begin_episode           # (runs on this thread: it takes the device lock itself, as `act` does)
         self.queue = queue.Queue(maxsize=max_queued)
         self._stop = threading.Event()
         self.error = None
@@ -106,7 +110,7 @@ class AsyncRollouts(object):
     def _run(self):
         try:
             while not self._stop.is_set():
-                ep = play_episode(self.env, self.act)
+                ep = play_episode(self.env, self.act, self.begin_episode)
                 self.episodes_played += 1
                 while not self._stop.is_set():
                     try:
@@ -158,11 +162,13 @@ class AsyncRollouts(object):
 class TrainingLoop(object):
     """agent: replay_memory, env, run_eval(n); act(state) -> action with exploration noise; train(batch_size, batches_per_step)
     -> list of losses (the inner step ddpg_cartpole.py:331-337 / naf_cartpole.py:367-373, whichever way the agent runs it).
-    `agreement` (distributed.LoopAgreement or None), `device_lock` (FairLock, --async-rollouts) and `verbose()` are optional."""
+    `agreement` (distributed.LoopAgreement or None), `device_lock` (FairLock, --async-rollouts), `verbose()` and `begin_episode()`
+    (called before every training episode's env.reset()) are optional."""
 
     def __init__(self, agent, opts, act, train, agreement=None, verbose=None, after_train=None, timing_prints=False,
-                 dump_weights_requested=None, out=None):
+                 dump_weights_requested=None, out=None, begin_episode=None):
         self.agent, self.opts, self.act, self.train = agent, opts, act, train
+        self.begin_episode = begin_episode
         self.agreement, self.verbose, self.after_train = agreement, verbose or (lambda: False), after_train
         self.timing_prints, self.dump_weights_requested = timing_prints, dump_weights_requested
         self.out = out or sys.stdout
@@ -176,7 +182,7 @@ class TrainingLoop(object):
         lock = getattr(agent, "device_lock", None) or contextlib.nullcontext()
         rollouts = None
         if getattr(opts, "async_rollouts", False) and not opts.dont_do_rollouts:
-            rollouts = AsyncRollouts(agent.env, self.act, evaluate=lambda: agent.run_eval(1)).start()
+            rollouts = AsyncRollouts(agent.env, self.act, evaluate=lambda: agent.run_eval(1), begin_episode=self.begin_episode).start()
         start_time = time.time()
         num_actions_taken = 0
         n = 0
@@ -188,7 +194,7 @@ class TrainingLoop(object):
                     below = agent.replay_memory.size() <= opts.replay_memory_burn_in
                     episodes = rollouts.drain(wait_for_one=below, timeout=1.0)
                 elif not opts.dont_do_rollouts:
-                    episodes = [play_episode(agent.env, self.act)]          # physics + rendering stay on the host
+                    episodes = [play_episode(agent.env, self.act, self.begin_episode)]          # physics + rendering stay on the host
                 with lock:
                     for ep in episodes:
                         if self.timing_prints:

@@ -693,6 +693,42 @@ int cpp_ddpg_sac_temperature(cpp_ddpg* ddpg, int set, float* log_alpha, float* m
  * minibatch's gradient pass left for the actor (which = 0) or the critic (which = 1), n the width of its layer 0 -- xhat (B, n), rstd (B),
  * y (B, n), dz = dL/dz (B, n), and dgamma, dbeta (n) as computed, before the clip.  NULL pointers are skipped; CPP_ERR_STATE on any other trainer. */
 int cpp_ddpg_last_feature_norm(cpp_ddpg* ddpg, int B, int which, float* xhat, float* rstd, float* y, float* dz, float* dgamma, float* dbeta);
+/* Parameter-space exploration noise (Plappert et al. 2018; an extension of ddpg_cartpole.py:127-134, where the reference adds one
+ * Ornstein-Uhlenbeck sample to the action on the host).  perturbed_actor is a network of the caller's with the actor's layout (an
+ * encoder-less one bound to the trainer's critic); the trainer keeps sigma (f32), the draw count n (u64), the last distance d (f32) and
+ * whether the last resample adapted on the device.  A RESAMPLE (cpp_ddpg_param_noise_resample) does, in this order, on the context's
+ * stream and with no host wait:
+ *   1. perturb: for every element i of the actor's flat parameter buffer p, pt[i] = fmaf(sigma, z(seed, n, i), p[i]), where z is the
+ *      Box-Muller normal of target policy smoothing -- u1 = ((x >> 8) + 1) 2^-24, u2 = (y >> 8) 2^-24, z = sqrt(-2 log u1) cos(2 pi u2),
+ *      the accurate logf / cospif, no clip -- on (x, y, _, _) = philox4x32_10({i, 0x200, n_lo, n_hi}, key = seed).  The elements of
+ *      '<layer 0>/LayerNorm/gamma' and '.../beta' (cpp_net_create_feature_norm), which close the flat buffer, are copied unperturbed.
+ *   2. measure (batch != NULL): the actor and the perturbed actor on the batch's state_1 in inference mode with the batch's whitening
+ *      statistics, a and at, (B, A); d = sqrt(sum_{b,k} (a[b][k] - at[b][k])^2 / (B A)), the differences and squares in f64, added by one
+ *      workgroup in one fixed order, rounded to f32 once.
+ *   3. adapt (batch != NULL): sigma <- d < delta ? sigma * alpha : sigma / alpha, one f32 operation, read by the NEXT resample.
+ *   4. count: n <- n + 1.
+ * The copy that was measured is the copy the caller acts with until the next resample.  No launch of a training call reads or writes any
+ * of this and no captured graph is dropped: the actor, the critic, the targets, the optimisers' slots and every count stay what a trainer
+ * without the noise holds, bit for bit.
+ * cpp_ddpg_set_param_noise: sigma0 the initial sigma (>= 0), delta the target distance (> 0), alpha the factor (>= 1; 1 keeps sigma
+ * fixed), all finite; zeroes n and d and ends with a resample without a batch (n = 1 behind it).  perturbed_actor == NULL with sigma0 == 0
+ * switches the noise off, the trainer cpp_ddpg_create left.  CPP_ERR_ARG, with nothing changed: a value out of range, a network whose
+ * layout is not the actor's or that a trainer owns, an encoder-less copy not bound to the trainer's critic, a soft actor-critic trainer
+ * (its policy explores by itself).  The network must outlive the setting. */
+int cpp_ddpg_set_param_noise(cpp_ddpg* ddpg, cpp_net* perturbed_actor, float sigma0, float delta, float alpha, uint64_t seed);
+/* One resample (ddpg_cartpole.py:127-134 extended: the episode boundary, where the reference's noise process would be reset).  batch: a
+ * device minibatch with a gathered copy of its states (cpp_replay_sample, cpp_batch_upload), or NULL for steps 1 and 4 alone.
+ * CPP_ERR_STATE while the noise is off. */
+int cpp_ddpg_param_noise_resample(cpp_ddpg* ddpg, cpp_batch* batch_or_null);
+/* The device's words (the state of the exploration ddpg_cartpole.py:127-134 kept on the host): sigma as the next resample will read it,
+ * d of the last measured resample, n, and whether the last resample adapted.  NULL pointers are skipped.  Waits for the stream. */
+int cpp_ddpg_param_noise_status(cpp_ddpg* ddpg, float* sigma, float* distance, uint64_t* n, int* adapted);
+/* sigma and n for checkpoints (util.py:88-90) and tests.  set == 0: read into the pointers (NULL: skipped); else written from them (both
+ * needed); the perturbed copy stays what it is until the next resample, which then draws at (seed, n). */
+int cpp_ddpg_param_noise_state(cpp_ddpg* ddpg, int set, float* sigma, uint64_t* n);
+/* a and at of the last measured resample (step 2 above; the policy of ddpg_cartpole.py:95-100 beside its perturbed copy), each (B, A) with
+ * B at most that resample's rows.  NULL pointers are skipped.  CPP_ERR_STATE before the first measured resample. */
+int cpp_ddpg_last_param_noise(cpp_ddpg* ddpg, int B, float* a, float* at);
 
 /* ---- data-parallel actor-learners (the reference's TODO "switch back to async training with multiple replicas",
  * ddpg_cartpole.py:259, naf_cartpole.py:294; its exps only launch independent processes, exps/run_87.sh:12-36) ------------
