@@ -31,10 +31,11 @@ class FakeEnv(object):
 
 
 def make_pair(shape, B, pixel, seed=0, replay_size=64, perturb=True, dt=np.float64, actor_hidden=None, critic_hidden=None,
-              action_dim=2, **optkw):
+              action_dim=2, capacity=None, **optkw):
     """returns (agent, oracle DDPG, specs).  Parameters are perturbed away from the near-zero actor
     head / zero biases so every path carries signal.  actor_hidden / critic_hidden: lists of widths
-    (--actor-hidden-layers / --critic-hidden-layers; None: the defaults), action_dim: the env's action size."""
+    (--actor-hidden-layers / --critic-hidden-layers; None: the defaults), action_dim: the env's action size.
+    capacity: the batch size the agent is built with (--batch-size; None: B), the largest batch it takes."""
     import os
     from cartpoleplusplus_amd import ddpg_cartpole as D
     if os.environ.get("TEST_EXACT_PRODUCTS") == "1":      # (test snippets run in subprocesses: the TEST's switch for --exact-products)
@@ -42,7 +43,7 @@ def make_pair(shape, B, pixel, seed=0, replay_size=64, perturb=True, dt=np.float
     for key, widths in (("actor_hidden_layers", actor_hidden), ("critic_hidden_layers", critic_hidden)):
         if widths is not None:
             optkw[key] = ",".join(str(int(w)) for w in widths)
-    make_opts(D, shape, B, pixel, replay_memory_size=replay_size, **optkw)
+    make_opts(D, shape, B if capacity is None else int(capacity), pixel, replay_memory_size=replay_size, **optkw)
     agent = D.DeepDeterministicPolicyGradientAgent(FakeEnv(shape, action_dim))
     agent.initialise_variables(seed=seed)
     rng = np.random.default_rng(seed + 100)
@@ -334,7 +335,7 @@ def conv_routes(agent, B):
 def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_size=None, seed=0, graph=True,
                                   atol=1e-5, grad_rel=2e-5, param_rel=2e-6, warm="philox", report_only=False,
                                   fill="noise", f32_twin=False, flip_tol=1e-5, probe=False, before_step=None, pixel=True, hyper=None,
-                                  prepare=None, host_seed=None, probe_conv=False, **pair_kw):
+                                  prepare=None, host_seed=None, probe_conv=False, capacity=None, **pair_kw):
     """ONE minibatch of the fused inner step (cpp_ddpg_train_step, default kernels: f16-pipe conv1 reading the replay store
     through the sampled slots, bf16-pipe conv2, fused heads, paired launches) -- with graph=True the hipGraph REPLAY of it,
     on rows drawn by the device's Philox sampler -- against oracle.DDPG(float64) on the same rows and the same starting
@@ -347,7 +348,11 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
     anything runs (edge-case parameters).  host_seed: parameters, episodes and (graph=False) rows are host_case(shape, B, 1, host_seed,
     rows)'s, so that a CPU-only test can compute from the same numbers (tests/test_batchnorm_sensitivity.py).  use_batch_norm=True
     (pair_kw): the pool codes and ReLU decisions read back are bn_relu_pool_kernel's, the oracle normalises with the batch moments in
-    all four networks.  report["grads"]: the device's two pre-clip lists."""
+    all four networks.  report["grads"]: the device's two pre-clip lists.
+    capacity=C > B: the agent is built for batches of C rows and the checked minibatch of B rows comes behind a C-row one (eager, and
+    with graph=True its capture and a replay) that leaves real data in every workspace row, partial slot and noise buffer, and behind
+    one B-row step (eager, with graph=True the capture); one more C-row step follows and is held to the oracle at the same bars
+    (report["back"]: its report).  probe / probe_conv then profile the B-row minibatch on the capacity-C agent."""
     import ctypes
     from cartpoleplusplus_amd import _lib
     if hyper is not None:
@@ -357,7 +362,7 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
         case = host_case(shape, B, 1, host_seed, rows=rows, batch_norm=bool(pair_kw.get("use_batch_norm", False)))
         pair_kw = dict(pair_kw, perturb=False)
     agent, _ref, (aspec, cspec) = make_pair(shape, B, pixel, seed=seed, replay_size=replay_size or rows + 50,
-                                           replay_store=replay_store, **pair_kw)
+                                           replay_store=replay_store, capacity=capacity, **pair_kw)
     report = {}
     steps = 0                                             # training-mode forwards before the one checked (dropout masks)
     try:
@@ -378,6 +383,17 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
             assert fill in ("render", "render-blind", "render-glint"), fill
             fill_with_rendered_episodes(agent, shape, rows, seed=seed, blind_camera=(fill != "render"),
                                         glint=0.02 if fill == "render-glint" else 0.0)
+        C = B if capacity is None else int(capacity)
+        assert C >= B
+        rows_of = lambda n, salt: np.random.default_rng(seed + salt).integers(0, rows, n).astype(np.int32)
+        if C > B:                                         # a full-capacity minibatch first: every row and slot holds real data
+            if graph:
+                agent.train_step(C, 1)                    # eager pass + capture
+                agent.train_step(C, 1)                    # replay
+                steps += 2
+            else:
+                agent.train_step(C, 1, idxs=rows_of(C, 6))
+                steps += 1
         if probe:
             report["path"] = ddpg_path(agent, B, aspec.hidden, cspec.hidden, pixel)
             steps += 1
@@ -387,40 +403,64 @@ def fused_step_against_f64_oracle(shape, B, rows, replay_store="f16", replay_siz
         if graph or warm == "philox-eager":
             agent.train_step(B, 1)                        # eager pass + capture
             steps += 1
-        elif warm == "rows":
-            agent.train_step(B, 1, idxs=np.random.default_rng(seed + 77).integers(0, rows, B).astype(np.int32))
+        elif warm == "rows" or C > B:
+            agent.train_step(B, 1, idxs=rows_of(B, 77))
             steps += 1
         nets = (agent.actor, agent.critic, agent.target_actor, agent.target_critic)
-        P = [n.get_params() for n in nets]
-        if before_step is not None:
-            before_step()
-        if graph:
-            agent.train_step(B, 1)                        # hipGraph replay, device-drawn rows
-            idxs = np.empty(B, np.int32)
-            _lib.check(_lib.lib.cpp_replay_last_indexes(rm.handle, B, idxs.ctypes.data_as(ctypes.c_void_p)))
-        else:
-            idxs = np.random.default_rng(seed + 5).integers(0, rows, B).astype(np.int32) if case is None else case[3]
-            agent.train_step(B, 1, idxs=idxs)             # same launch sequence, eager, caller's rows
-        assert idxs.min() >= 0 and idxs.max() < rows and len(np.unique(idxs)) > B // 2
-        actions, dq_da, q, td = agent.trainer.last_values(B)
-        g_a, g_c = agent.actor.get_grads(), agent.critic.get_grads()
-        report["grads"] = (g_a, g_c)
-        stats = agent.trainer.last_stats()
-        report["norms"] = (float(stats[1]), float(stats[2]))  # (pre-clip, actor's and critic's lists: which side of a clip they fall on)
-        Pn = [n.get_params() for n in nets]
-        if pixel:
-            codes_a, codes_c = device_pool_codes(agent.actor, B), device_pool_codes(agent.critic, B)
-            relu_a, relu_c = device_relu_active(agent.actor, B), device_relu_active(agent.critic, B)
-            pools_c = [getattr(agent.critic, "pool%d" % i).eval(B) for i in (1, 2, 3)]
-        else:
-            codes_a = codes_c = relu_a = relu_c = None
-        # the minibatch, read back through paths that do not involve the gather kernel's state copy
-        s1, s2 = rm.state[rm.state_1_idx[idxs]], rm.state[rm.state_2_idx[idxs]]
-        hb = rm.batch(idxs=idxs)
-        a, r, m = hb.action, hb.reward, hb.terminal_mask
-        assert np.array_equal(m[:, 0], rm.terminal_mask[idxs, 0]) and np.array_equal(r[:, 0], rm.reward[idxs, 0])
+
+        def step_and_read(Bx, idxs, before=None):
+            """one minibatch of Bx rows (idxs None: the device's draw, a replay where this key's graph is held) and what it left"""
+            d = {"B": Bx, "steps": steps, "P": [n.get_params() for n in nets]}
+            if before is not None:
+                before()
+            if idxs is None:
+                agent.train_step(Bx, 1)
+                idxs = np.empty(Bx, np.int32)
+                _lib.check(_lib.lib.cpp_replay_last_indexes(rm.handle, Bx, idxs.ctypes.data_as(ctypes.c_void_p)))
+            else:
+                agent.train_step(Bx, 1, idxs=idxs)        # same launch sequence, eager, caller's rows
+            assert idxs.min() >= 0 and idxs.max() < rows and len(np.unique(idxs)) > Bx // 2
+            d["values"] = agent.trainer.last_values(Bx)
+            d["grads"] = (agent.actor.get_grads(), agent.critic.get_grads())
+            d["stats"] = agent.trainer.last_stats()
+            d["Pn"] = [n.get_params() for n in nets]
+            if pixel:
+                d["codes"] = (device_pool_codes(agent.actor, Bx), device_pool_codes(agent.critic, Bx))
+                d["relu"] = (device_relu_active(agent.actor, Bx), device_relu_active(agent.critic, Bx))
+                d["pools_c"] = [getattr(agent.critic, "pool%d" % i).eval(Bx) for i in (1, 2, 3)]
+            else:
+                d["codes"] = d["relu"] = (None, None)
+            # the minibatch, read back through paths that do not involve the gather kernel's state copy
+            s1, s2 = rm.state[rm.state_1_idx[idxs]], rm.state[rm.state_2_idx[idxs]]
+            hb = rm.batch(idxs=idxs)
+            a, r, m = hb.action, hb.reward, hb.terminal_mask
+            assert np.array_equal(m[:, 0], rm.terminal_mask[idxs, 0]) and np.array_equal(r[:, 0], rm.reward[idxs, 0])
+            d["batch"] = (s1, a, r, m, s2)
+            return d
+
+        checked = step_and_read(B, None if graph else rows_of(B, 5) if case is None else case[3], before_step)
+        steps += 1
+        back = step_and_read(C, None if graph else rows_of(C, 8)) if C > B else None      # the way back: no count of the small batch survives
     finally:
         agent.close()
+    check_kw = dict(pixel=pixel, hyper=hyper, atol=atol, grad_rel=grad_rel, param_rel=param_rel, report_only=report_only,
+                    f32_twin=f32_twin, flip_tol=flip_tol)
+    report = _check_fused_step(checked, aspec, cspec, report, **check_kw)
+    if back is not None:
+        report["back"] = _check_fused_step(back, aspec, cspec, {}, **check_kw)
+    return report
+
+
+def _check_fused_step(d, aspec, cspec, report, pixel, hyper, atol, grad_rel, param_rel, report_only, f32_twin, flip_tol):
+    """what fused_step_against_f64_oracle's step_and_read() brought back from one minibatch against oracle.DDPG(float64) started from
+    the parameters read just before it"""
+    B, steps, P, Pn, stats = d["B"], d["steps"], d["P"], d["Pn"], d["stats"]
+    actions, dq_da, q, td = d["values"]
+    g_a, g_c = d["grads"]
+    (codes_a, codes_c), (relu_a, relu_c), pools_c = d["codes"], d["relu"], d.get("pools_c")
+    s1, a, r, m, s2 = d["batch"]
+    report["grads"] = (g_a, g_c)
+    report["norms"] = (float(stats[1]), float(stats[2]))  # (pre-clip, actor's and critic's lists: which side of a clip they fall on)
     ref = O.DDPG(aspec, cspec, P[0], P[1], np.float64, **({} if hyper is None else {"hyper": hyper}))
     ref.set_targets(P[2], P[3])
     if aspec.dropout:
@@ -675,14 +715,15 @@ NAF_OPTIMISERS = {"momentum-0.5": ("Momentum", {"learning_rate": 0.01, "momentum
 NAF_RIDER_CASE = ((64, 64, 3, 2, 3), 8, 3, 30, 5)         # shape, B, minibatches, rows, seed: the shared trunk, conv1 on the operand image
 
 
-def naf_host_case(shape, B, nb, rows, seed, hidden=(100, 50), action_dim=2, share=True, dropout=False):
+def naf_host_case(shape, B, nb, rows, seed, hidden=(100, 50), action_dim=2, share=True, dropout=False, batch_norm=False):
     """host_case for the shared-trunk NAF agent: (value, mu, l) specs, the three parameter vectors + the target value network's,
     episodes, rows and the minibatches they select.  share=False: mu and l_values on trunks and hidden stacks of their own; dropout:
-    --use-dropout; a low-dimensional `shape` gives networks without a trunk."""
+    --use-dropout; batch_norm: --use-batch-norm (the same numbers: the conv bias slots then hold BatchNorm/beta); a low-dimensional
+    `shape` gives networks without a trunk."""
     from oracle import naf_np as N
     from oracle.replay_np import OracleReplayMemory
     if len(shape) == 5:
-        kw = dict(pixel=True, H=shape[0], W=shape[1], C=int(np.prod(shape[2:])), dropout=dropout)
+        kw = dict(pixel=True, H=shape[0], W=shape[1], C=int(np.prod(shape[2:])), dropout=dropout, batch_norm=batch_norm)
     else:
         kw = dict(pixel=False, state_elems=int(np.prod(shape)), dropout=dropout)
     if share:
@@ -823,3 +864,52 @@ def twin_rs(want, twin, start):
         d = float(np.linalg.norm(w - p))
         rs.append(max(5e-5, F32_GRAD_FACTOR * float(np.linalg.norm(t - w)) / d) if d > 0 else 5e-5)
     return rs
+
+
+# ---- batches below the capacity the agent was built with (tests/test_gpu_partial_batch.py, tests/test_partial_batch_host.py): four
+# ---- minibatches of C, B, B and C rows on one agent of capacity C.  The C-row one leaves real data in every workspace row and partial
+# ---- slot; the B-row ones must not see it; the last one must not see a count cached from the small ones.
+PARTIAL_PIX, PARTIAL_LOWDIM = (16, 16, 3, 1, 2), (2, 2, 7)
+PARTIAL_C, PARTIAL_B, PARTIAL_SEED = 8, 5, 11
+
+
+def partial_sizes(C, B):
+    return (C, B, B, C)
+
+
+def _cut(idxs, batches, C, B):
+    sizes = partial_sizes(C, B)
+    return ([np.ascontiguousarray(idxs[i * C:i * C + n], dtype=np.int32) for i, n in enumerate(sizes)],
+            [tuple(np.asarray(x)[:n] for x in batches[i]) for i, n in enumerate(sizes)])
+
+
+def partial_case(shape, C=PARTIAL_C, B=PARTIAL_B, seed=PARTIAL_SEED, rows=24, **kw):
+    """host_case drawn for four minibatches of C rows, the second and third cut to their first B rows: (specs, P, episodes, the four
+    row lists, the four minibatches)"""
+    specs, P, episodes, idxs, batches = host_case(shape, C, 4, seed, rows=rows, **kw)
+    return (specs, P, episodes) + _cut(idxs, batches, C, B)
+
+
+def naf_partial_case(shape, C=PARTIAL_C, B=PARTIAL_B, seed=PARTIAL_SEED, rows=24, **kw):
+    """the same of naf_host_case"""
+    specs, flats, episodes, idxs, batches = naf_host_case(shape, C, 4, rows, seed, **kw)
+    return (specs, flats, episodes) + _cut(idxs, batches, C, B)
+
+
+def minibatch_of_rows(rows, shape, action_dim, episodes, idxs):
+    """the one-step minibatch rows `idxs` select from a memory of `rows` rows holding `episodes` (the oracle memory's own gather)"""
+    from oracle.replay_np import OracleReplayMemory
+    orm = OracleReplayMemory(rows, shape, action_dim)
+    for ep in episodes:
+        orm.add_episode(*ep)
+    ob = orm.batch(idxs=np.asarray(idxs))
+    return (ob.state_1, ob.action, ob.reward, ob.terminal_mask, ob.state_2)
+
+
+def capacity_plan(rows, shape, action_dim, episodes, idxs, batches, B, capacity):
+    """the minibatches of a variant case's run below the capacity: [(row list, minibatch)] of capacity, B, B and capacity rows -- the last
+    `capacity` of the case's rows in front and behind, the case's first two minibatches between them"""
+    assert capacity > B and len(idxs) >= max(capacity, 2 * B)
+    big = np.ascontiguousarray(idxs[-capacity:], dtype=np.int32)
+    wide = minibatch_of_rows(rows, shape, action_dim, episodes, big)
+    return [(big, wide), (idxs[:B], batches[0]), (idxs[B:2 * B], batches[1]), (big, wide)]

@@ -588,8 +588,27 @@ C_SEEDS = {"twin-sgd-clip0.5-A2-B8": 1, "twin-adam-unclipped-A1-B5": 230, "twin-
 C_SINGLE_OPS = (("single-ops-lowdim-twin-momentum", "lowdim", 3, 16, "momentum-0.5", 0.5, 0.25, True, False, 1, 0), 3, 3)      # case, seed, minibatches
 
 
+# the case of the run below the capacity (tests/test_gpu_sac_composed.py: an agent built for C_PARTIAL_CAPACITY rows walking C, B, B, C
+# rows): the scalar Adam case at five rows.  Not one of C_CASES -- its minibatches are tests.helpers.capacity_plan's, and
+# tests/test_partial_batch_host.py holds THOSE to the side of the clip registered here (a twin case at five rows does not keep both
+# heads in play through a C-row minibatch: see C_SEEDS' note on twin-adam-unclipped-A1-B5)
+C_PARTIAL_CASE = ("scalar-adam-clip0.5-A2-B5", "16x16x6", 2, 5, "adam", 0.5, 0.25, False, False, 1, 0)
+C_PARTIAL_CAPACITY = 8
+C_SIDES[C_PARTIAL_CASE[0]] = ("above", "above")
+C_SEEDS[C_PARTIAL_CASE[0]] = 1
+
+
 def composed_case(cid):
-    return [c for c in C_CASES if c[0] == cid][0]
+    return [c for c in C_CASES + (C_PARTIAL_CASE,) if c[0] == cid][0]
+
+
+def partial_rows(case, inputs, capacity=C_PARTIAL_CAPACITY):
+    """the four row lists of the run below the capacity: the last `capacity` of the case's rows, its first two minibatches, the
+    last `capacity` again"""
+    B, idxs = case[3], inputs[3]
+    assert capacity > B and len(idxs) >= max(capacity, 2 * B)
+    big = idxs[-capacity:]
+    return [big, idxs[:B], idxs[B:2 * B], big]
 
 
 def composed_hyper(case):

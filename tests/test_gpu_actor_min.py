@@ -152,24 +152,34 @@ def ref_backward(case, specs, P, batch, got, ww):
     return W.flatten_grads(specs[1], grads, np.float64), da
 
 
-def _run_case(cid, **kw):
+def partial_plan(case, inputs, capacity):
+    """tests.helpers.capacity_plan of a case"""
+    from tests.helpers import capacity_plan
+    _cid, shape_name, A, B = case[:4]
+    return capacity_plan(M.ROWS, M.SHAPES[shape_name], A, inputs[2], inputs[3], inputs[4], B, capacity)
+
+
+def _run_case(cid, capacity=None, **kw):
+    """capacity=C > B: the agent is built for C rows and walks partial_plan's minibatches -- C rows, B, B, C -- each held to the
+    restatement from the device's own state in front of it, at the same bars"""
     case = M.case_of(cid)
     B, weighted = case[3], bool(case[9].get("weighted"))
     inputs = M.case_inputs(case)
     specs, _P, _ep, idxs, batches = inputs
-    agent = _agent(case, inputs, **kw)
+    plan = [(idxs[k * B:(k + 1) * B], batches[k]) for k in range(M.NB)] if capacity is None else partial_plan(case, inputs, capacity)
+    agent = _agent(case, inputs, capacity=capacity, **kw)
     shares, sels = [], []
     try:
         assert agent.trainer.actor_min_q
         if weighted:
             _set_priorities(agent)
-        for k in range(M.NB):
+        for k, (rows, batch) in enumerate(plan):
             sl, counts = _slots(agent)
             start = (_params(agent), sl, counts)
-            agent.train_step(B, 1, idxs=idxs[k * B:(k + 1) * B])
-            got = _read(agent, B, weighted)
+            agent.train_step(len(rows), 1, idxs=rows)
+            got = _read(agent, len(rows), weighted)
             sl2, counts2 = _slots(agent)
-            shares.append(_compare_minibatch(case, specs, start, got, (_params(agent), sl2, counts2), k, batches[k]))
+            shares.append(_compare_minibatch(case, specs, start, got, (_params(agent), sl2, counts2), k, batch))
             sels.append(int(got["sel"][0]))
     finally:
         agent.close()
@@ -183,6 +193,12 @@ def _run_case(cid, **kw):
 @pytest.mark.parametrize("cid", [c[0] for c in M.CASES])
 def test_minibatches_against_the_float64_restatement(cid):
     _run_case(cid)
+
+
+def test_minibatches_below_the_capacity_against_the_float64_restatement():
+    """(C, B) = (8, 5), twin heads with the actor on the minimum: the rows of both heads, actor_min's selection and the gradient lists at B
+    behind a C-row minibatch, and at C again behind the B-row ones"""
+    _run_case("A1-B5-sgd", capacity=8)
 
 
 def test_the_eight_bit_store_changes_nothing():

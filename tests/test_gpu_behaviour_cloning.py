@@ -148,8 +148,8 @@ def _take_over(ref, P, slots, counts, k):
     return ref
 
 
-def _read(agent, case):
-    B, kind, t = case[3], _kind(case), agent.trainer
+def _read(agent, case, B=None):
+    B, kind, t = case[3] if B is None else B, _kind(case), agent.trainer
     actions, dq_da, q, td = t.last_values(B)
     lam, m, g, rows = t.last_behaviour_cloning(B)
     stats = t.last_stats()
@@ -238,29 +238,45 @@ def _compare_minibatch(case, specs, start, got, after, k, batch):
     return out
 
 
-def _run_case(cid, nb=Bc.NB, **kw):
+def partial_plan(case, inputs, capacity):
+    """tests.helpers.capacity_plan of a case"""
+    from tests.helpers import capacity_plan
+    _cid, shape_name, A, B = case[:4]
+    return capacity_plan(Bc.rows_of(case), Bc.SHAPES[shape_name], A, inputs[2], inputs[3], inputs[4], B, capacity)
+
+
+def _run_case(cid, nb=Bc.NB, capacity=None, **kw):
+    """capacity=C > B: the agent is built for C rows and walks partial_plan's minibatches -- C rows, B, B, C -- each held to the
+    restatement from the device's own state in front of it, at the same bars"""
     case = Bc.case_of(cid)
     B = case[3]
     inputs = Bc.case_inputs(case, nb=nb)
     specs, _P, _ep, idxs, batches = inputs
-    agent = _agent(case, inputs, **kw)
+    plan = [(idxs[k * B:(k + 1) * B], batches[k]) for k in range(nb)] if capacity is None else partial_plan(case, inputs, capacity)
+    agent = _agent(case, inputs, capacity=capacity, **kw)
     outs = []
     try:
         assert agent.trainer.behaviour_cloning == (Bc.ALPHA, Bc.floor_of(case))
         if case[9].get("weighted"):
             agent.replay_memory.update_priorities(np.arange(Bc.rows_of(case)),
                                                   np.random.default_rng(9).lognormal(0.0, 1.0, Bc.rows_of(case)).astype(np.float32))
-        for k in range(nb):
+        for k, (rows, batch) in enumerate(plan):
             sl, counts = _slots(agent)
             start = (_params(agent), sl, counts)
-            census = _profiled_calls(agent.actor.ctx, lambda: agent.train_step(B, 1, idxs=idxs[k * B:(k + 1) * B]))
+            census = _profiled_calls(agent.actor.ctx, lambda: agent.train_step(len(rows), 1, idxs=rows))
             assert census.get("bc", 0) == 1 and census.get("heads", 0) == 0, census
-            got = _read(agent, case)
+            got = _read(agent, case, len(rows))
             sl2, counts2 = _slots(agent)
-            outs.append(_compare_minibatch(case, specs, start, got, (_params(agent), sl2, counts2), k, batches[k]))
+            outs.append(_compare_minibatch(case, specs, start, got, (_params(agent), sl2, counts2), k, batch))
     finally:
         agent.close()
     return case, outs
+
+
+def test_minibatches_below_the_capacity_against_the_float64_restatement():
+    """(C, B) = (8, 5): the batch mean m of |Q| behind lambda, the term's rows and both gradient lists at B behind a C-row minibatch, and at C
+    again behind the B-row ones"""
+    _run_case("A1-B5-sgd", capacity=8)
 
 
 @pytest.mark.parametrize("cid", [c[0] for c in Bc.CASES if c[0] not in Bc.BIG])

@@ -30,8 +30,9 @@ def _abi():
     return lib, check, ptr
 
 
-def _agent(B, hidden, act, hp, P=None, episodes=None, rows=24, norm=True, opt=None, seed=0, **kw):
-    """a device agent through the public Python surface, holding P and the episodes (None: its own initialisation, an empty memory)"""
+def _agent(B, hidden, act, hp, P=None, episodes=None, rows=24, norm=True, opt=None, seed=0, capacity=None, **kw):
+    """a device agent through the public Python surface, holding P and the episodes (None: its own initialisation, an empty memory);
+    capacity: the batch size it is built with (None: B)"""
     from cartpoleplusplus_amd import ddpg_cartpole as D
     from tests import ddpg_opt_np as R
     if opt is not None:
@@ -40,7 +41,8 @@ def _agent(B, hidden, act, hp, P=None, episodes=None, rows=24, norm=True, opt=No
     if norm:
         kw.update(feature_layer_norm=True, feature_norm_activation=act)
     kw.update(hyper_options(hp))
-    make_opts(D, SHAPE, B, True, replay_memory_size=rows, actor_hidden_layers=",".join(str(h) for h in hidden), **kw)
+    make_opts(D, SHAPE, B if capacity is None else int(capacity), True, replay_memory_size=rows,
+              actor_hidden_layers=",".join(str(h) for h in hidden), **kw)
     agent = D.DeepDeterministicPolicyGradientAgent(FakeEnv(SHAPE, 2))
     try:
         agent.initialise_variables(seed=seed)
@@ -79,16 +81,47 @@ def _flips(ag, cg, routes):
 
 
 # ---- 1. kernel edges, through last_feature_norm: widths 5 .. 1024 (the critic's: 200), B = 1 .. 33, both activations
-def _edge(case, act, B, hidden):
+def wide_edge_case(case, capacity):
+    """an edge case with its minibatch replaced by rows 0 .. capacity-1 of its memory: (the case, the rows)"""
+    from tests.helpers import minibatch_of_rows
+    rows = np.arange(capacity, dtype=np.int32)
+    return case[:3] + (rows, [minibatch_of_rows(L.EDGE_ROWS, SHAPE, 2, case[2], rows)]) + case[5:], rows
+
+
+def _edge(case, act, B, hidden, capacity=None):
+    """capacity=C > B: the agent is built for C rows; a C-row minibatch (rows 0 .. C-1) and one at B run first and the parameters are put
+    back, the checked minibatch follows, the parameters are put back once more and the C-row minibatch is held to its own bars"""
     specs, P, episodes, idxs, batches = case[:5]
     hp = O.DEFAULT_HYPER
-    agent = _agent(B, hidden, act, hp, P, episodes, rows=L.EDGE_ROWS)
+    agent = _agent(B, hidden, act, hp, P, episodes, rows=L.EDGE_ROWS, capacity=capacity)
+    wide = back = None
     try:
+        if capacity is not None:
+            assert capacity > B
+            wide, rows = wide_edge_case(case, capacity)
+            agent.train_step(capacity, 1, idxs=rows)
+            agent.train_step(B, 1, idxs=idxs)
+            for net, p in zip(agent.networks(), P):
+                net.set_params(p)
         agent.train_step(B, 1, idxs=idxs)
         got = agent.trainer.last_feature_norm(B)
         routes = _routes(agent, B)
+        if capacity is not None:
+            for net, p in zip(agent.networks(), P):
+                net.set_params(p)
+            agent.train_step(capacity, 1, idxs=rows)
+            back = (agent.trainer.last_feature_norm(capacity), _routes(agent, capacity))
     finally:
         agent.close()
+    q = _check_edge(case, got, routes)
+    if back is not None:
+        _check_edge(wide, back[0], back[1])
+    return got, q
+
+
+def _check_edge(case, got, routes):
+    specs, P, _episodes, _idxs, batches = case[:5]
+    hp = O.DEFAULT_HYPER
     q, ag, cg = L.ln_quantities(_pinned_oracle(specs, P, hp, routes), batches[0])
     flips = _flips(ag, cg, routes)
     bars, _q = L.edge_bars(case)
@@ -102,7 +135,14 @@ def _edge(case, act, B, hidden):
                 bad.append((net, k, e, bar))
     print("  (%d route flips at ties)" % flips)
     assert not bad, bad
-    return got, q
+    return q
+
+
+def test_a_kernel_edge_below_the_capacity_against_float64():
+    """(C, B) = (8, 5), width 65, ReLU: the per-row statistics, xhat, y and the dgamma / dbeta partials of both feature layers at B behind
+    a C-row minibatch, and at C again behind the B-row ones (tests.layer_norm_np.conditions hold on the C-row minibatch too:
+    tests/test_partial_batch_host.py)"""
+    _edge(L.edge_case("w65-b5-relu"), "relu", 5, (65,) + L.EDGE_TAIL, capacity=8)
 
 
 @pytest.mark.parametrize("cid", [c[0] for c in L.EDGE_CASES])

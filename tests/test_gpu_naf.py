@@ -20,14 +20,15 @@ class HB(object):
 
 
 def make_naf(shape, B, share, optimiser="GradientDescent", optimiser_args=None, seed=0, replay_size=64, clip=5.0,
-             use_batch_norm=False, use_dropout=False, hidden=None, action_dim=2, discount=0.99, target_update_rate=1e-4):
+             use_batch_norm=False, use_dropout=False, hidden=None, action_dim=2, discount=0.99, target_update_rate=1e-4, capacity=None):
     """hidden: list of widths (--hidden-layers; None: the default 100,50), action_dim: the env's action size; clip (None: no clipping),
-    discount, target_update_rate: --gradient-clip, --discount, --target-update-rate for the agent and the oracle alike"""
+    discount, target_update_rate: --gradient-clip, --discount, --target-update-rate for the agent and the oracle alike; capacity: the
+    batch size the agent is built with (--batch-size; None: B), the largest batch it takes"""
     from cartpoleplusplus_amd import naf_cartpole as F
     pixel = len(shape) == 5
     hidden = [100, 50] if hidden is None else [int(h) for h in hidden]
     A = int(action_dim)
-    kw = dict(batch_size=B, replay_memory_size=replay_size, share_input_state_representation=share,
+    kw = dict(batch_size=B if capacity is None else int(capacity), replay_memory_size=replay_size, share_input_state_representation=share,
               optimiser=optimiser, optimiser_args=json.dumps(optimiser_args or {"learning_rate": 0.01}),
               gradient_clip=clip, use_batch_norm=use_batch_norm, use_dropout=use_dropout,
               hidden_layers=",".join(str(h) for h in hidden), discount=discount, target_update_rate=target_update_rate)
@@ -275,7 +276,8 @@ def test_cfg4_B256_graph_replayed_naf_step_against_f64_oracle(shape, B, share):
 
 
 def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, probe=False, optimiser="Momentum", optimiser_args=None,
-                                      warm_steps=1, clip=5.0, discount=0.99, target_update_rate=1e-4, report=None, grad_rel=2e-5, **naf_kw):
+                                      warm_steps=1, clip=5.0, discount=0.99, target_update_rate=1e-4, report=None, grad_rel=2e-5, capacity=None,
+                                      **naf_kw):
     """cfg4 at the size the metric is quoted on (64x64x18, B = 256, shared trunk, Momentum as in exps/run_93.sh): the hipGraph REPLAY
     of the fused NAF step (naf_cartpole.py:365-373) on rows drawn by the device's sampler against oracle.NAF(float64) started from the
     same parameters and Momentum slots: loss at 1e-5, the pre-clip gradient list per variable at 2e-5 (the trunk's two
@@ -284,14 +286,17 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, p
     naf_cartpole.py's three networks on trunks of their own).  naf_kw: make_naf's widths and action size; probe: one profiled
     minibatch first, its head path (tests.helpers.naf_path) returned.  grad_rel: the bar of the gradient list (batch-norm networks:
     tests/test_gpu_batchnorm.py's 5e-5).  use_dropout=True (naf_kw): the checked replay is training-mode forward number
-    (probe ? 1 : 0) + warm_steps of every network with a hidden stack, and the oracle is handed the masks of that count."""
+    (probe ? 1 : 0) + warm_steps of every network with a hidden stack, and the oracle is handed the masks of that count.
+    capacity=C > B: the agent is built for batches of C rows; a C-row step and its replay come first (every workspace row and partial
+    slot then holds real data), the probe, the warm steps and the checked replay run at B, and one more C-row step is held to the
+    oracle at the same bars."""
     import ctypes
     from cartpoleplusplus_amd import _lib
     from tests.helpers import (device_pool_codes, device_relu_active, dropout_masks, naf_path, pool_flips_are_near_ties,
                                relu_flips_are_at_the_boundary)
     oargs = {"learning_rate": 0.01, "momentum": 0.9} if optimiser_args is None else optimiser_args
     agent, _ref, specs = make_naf(shape, B, share, optimiser, oargs, seed=4, replay_size=rows + 50, clip=clip, discount=discount,
-                                  target_update_rate=target_update_rate, **naf_kw)
+                                  target_update_rate=target_update_rate, capacity=capacity, **naf_kw)
     path = None
     dropout = bool(naf_kw.get("use_dropout", False))
     forwards = 0                                                  # training-mode forwards before the one checked (dropout masks)
@@ -303,6 +308,11 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, p
             from cartpoleplusplus_amd import naf_cartpole as F
             from tests.helpers import fill_with_rendered_episodes
             fill_with_rendered_episodes(agent, shape, rows, seed=33, blind_camera=(fill == "render-blind"), opts=F.opts)
+        C = B if capacity is None else int(capacity)
+        assert C >= B
+        for _ in range(2 if C > B else 0):
+            agent.train_step(C, 1)                                # eager pass + capture, then its replay
+            forwards += 1
         if probe:
             path = naf_path(agent, B, specs[0].hidden, share, dropout=dropout)
             forwards += 1
@@ -310,21 +320,40 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, p
             agent.train_step(B, 1)                                # eager pass + capture (also fills the Momentum slots)
             forwards += 1
         nets = (agent.value_net, agent.naf.mu_net, agent.naf.l_net, agent.target_value_net)
-        P = [n.get_params() for n in nets]
-        opt = agent.naf.get_optimiser_state()
-        agent.train_step(B, 1)                                    # hipGraph replay, device-drawn rows
-        idxs = np.empty(B, np.int32)
-        _lib.check(_lib.lib.cpp_replay_last_indexes(rm.handle, B, idxs.ctypes.data_as(ctypes.c_void_p)))
-        assert idxs.min() >= 0 and idxs.max() < rows and len(np.unique(idxs)) > B // 2
-        grads, stats = agent.naf.get_grads(), agent.naf.last_stats()
-        Pn = [n.get_params() for n in nets]
         trunks = [agent.value_net] if share else [agent.value_net, agent.naf.mu_net, agent.naf.l_net]
-        codes, relu = [device_pool_codes(n, B) for n in trunks], [device_relu_active(n, B) for n in trunks]
-        s1, s2 = rm.state[rm.state_1_idx[idxs]], rm.state[rm.state_2_idx[idxs]]
-        hb = rm.batch(idxs=idxs)
-        batch = (s1, hb.action, hb.reward, hb.terminal_mask, s2)
+
+        def step_and_read(Bx):
+            d = {"B": Bx, "forwards": forwards, "P": [n.get_params() for n in nets], "opt": agent.naf.get_optimiser_state()}
+            agent.train_step(Bx, 1)                               # hipGraph replay where this key's graph is held, device-drawn rows
+            idxs = np.empty(Bx, np.int32)
+            _lib.check(_lib.lib.cpp_replay_last_indexes(rm.handle, Bx, idxs.ctypes.data_as(ctypes.c_void_p)))
+            assert idxs.min() >= 0 and idxs.max() < rows and len(np.unique(idxs)) > Bx // 2
+            d["grads"], d["stats"] = agent.naf.get_grads(), agent.naf.last_stats()
+            d["Pn"] = [n.get_params() for n in nets]
+            d["codes"], d["relu"] = [device_pool_codes(n, Bx) for n in trunks], [device_relu_active(n, Bx) for n in trunks]
+            s1, s2 = rm.state[rm.state_1_idx[idxs]], rm.state[rm.state_2_idx[idxs]]
+            hb = rm.batch(idxs=idxs)
+            d["batch"] = (s1, hb.action, hb.reward, hb.terminal_mask, s2)
+            return d
+
+        checked = step_and_read(B)
+        forwards += 1
+        back = step_and_read(C) if C > B else None
     finally:
         agent.close()
+    for d, rep in ((checked, report), (back, None)):
+        if d is not None:
+            _check_naf_step(d, specs, share, optimiser, oargs, clip, discount, target_update_rate, dropout, grad_rel, rep)
+    return path
+
+
+def _check_naf_step(d, specs, share, optimiser, oargs, clip, discount, target_update_rate, dropout, grad_rel, report):
+    """what naf_fused_step_against_f64_oracle's step_and_read() brought back from one minibatch against oracle.NAF(float64) started
+    from the parameters and optimiser slots read just before it"""
+    from tests.helpers import dropout_masks, pool_flips_are_near_ties, relu_flips_are_at_the_boundary
+    B, forwards, P, Pn, opt, grads, stats, codes, relu = (d[k] for k in ("B", "forwards", "P", "Pn", "opt", "grads", "stats", "codes", "relu"))
+    batch = d["batch"]
+    s1 = batch[0]
     vspec, mspec, lspec = specs
     ref = N.NAF(vspec, mspec, lspec, P[0], P[1], P[2], share, mspec.head_out, np.float64, gradient_clip=clip, discount=discount,
                 target_update_rate=target_update_rate, optimiser=N.make_optimiser(optimiser, oargs))
@@ -332,7 +361,7 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, p
     ref.m = opt["m"].astype(np.float64)
     if optimiser == "Adam":
         ref.v, ref.t = opt["v"].astype(np.float64), int(opt["step"])
-        assert ref.t == warm_steps + (1 if probe else 0), (ref.t, warm_steps)
+        assert ref.t == forwards, (ref.t, forwards)
     rnets = [ref.value] if share else [ref.value, ref.mu, ref.l]
     if dropout:
         hidden = specs[0].hidden
@@ -370,7 +399,6 @@ def naf_fused_step_against_f64_oracle(shape, B, share, fill="noise", rows=700, p
     if report is not None:
         report["rel_delta_target"] = float(np.linalg.norm(t_got - t_want) / np.linalg.norm(t_want))
     assert np.linalg.norm(t_got - t_want) < 2.0 ** -23 * np.linalg.norm(target_before) + 5e-5 * np.linalg.norm(t_want)
-    return path
 
 
 @pytest.mark.parametrize("switch", ["CPP_NAF_MLP", "CPP_NAF_HEADS"])

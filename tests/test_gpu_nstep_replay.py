@@ -122,51 +122,74 @@ def test_explicit_n1_is_the_one_step_memory():
         b.close()
 
 
-def _ddpg_nstep_against_f64_oracle(shape, B, rows, pixel=True, seed=0, per=False, atol=1e-5, grad_rel=2e-5, flip_tol=1e-5, hyper=None, **pair_kw):
+def _ddpg_nstep_against_f64_oracle(shape, B, rows, pixel=True, seed=0, per=False, atol=1e-5, grad_rel=2e-5, flip_tol=1e-5, hyper=None,
+                                   capacity=None, **pair_kw):
     """ONE graph-replayed minibatch of the fused DDPG step on an n = 3 memory against oracle.DDPG(float64), unmodified, on the n-step
     columns (reward, terminal_mask, state_2 of the last row walked): actions / Q / TD at `atol`, the pre-clip gradients at `grad_rel`.
     per: a prioritized memory as well -- the critic's gradient against the oracle's backward pass of w * td_dev, and the priorities
     written from the n-step TD.  hyper: an O.Hyper for the agent and the oracle (None: the defaults).  pair_kw: make_pair's options
-    (use_batch_norm)."""
+    (use_batch_norm).  capacity=C > B: the agent is built for C rows; a C-row step and its replay run first, and behind the checked
+    B-row replay one more C-row step is held to the same bars."""
     kw = dict(prioritized_replay=True, priority_alpha=0.6, priority_beta=0.4, priority_eps=1e-6) if per else {}
     if hyper is not None:
         from tests.helpers import hyper_options
         kw.update(hyper_options(hyper))
     kw.update(pair_kw)
-    agent, _ref, (aspec, cspec) = make_pair(shape, B, pixel, seed=seed, replay_size=rows + 50, **kw)
+    agent, _ref, (aspec, cspec) = make_pair(shape, B, pixel, seed=seed, replay_size=rows + 50, capacity=capacity, **kw)
     from cartpoleplusplus_amd import ddpg_cartpole as D
     try:
         rm = agent.replay_memory
         rm.fill_synthetic(rows, seed=21 + seed)
         rm.enable_n_step(3, D.opts.discount)
+        C = B if capacity is None else int(capacity)
+        for _ in range(2 if C > B else 0):
+            agent.train_step(C, 1)                            # eager pass + capture, its replay
         agent.train_step(B, 1)                                # eager pass + capture
         if per:
             rm.update_priorities(np.arange(rows), np.random.default_rng(seed + 9).lognormal(0.0, 2.0, rows).astype(np.float32))
         nets = (agent.actor, agent.critic, agent.target_actor, agent.target_critic)
-        Pm = [n.get_params() for n in nets]
-        agent.train_step(B, 1)                                # hipGraph replay
         lib, check, ptr = _lib()
-        idxs = np.empty(B, np.int32)
-        check(lib.cpp_replay_last_indexes(rm.handle, B, ptr(idxs)))
-        w = rm.last_weights(B) if per else None
-        actions, _dq, q, td = agent.trainer.last_values(B)
-        g_a, g_c = agent.actor.get_grads(), agent.critic.get_grads()
-        if per:
-            last = {int(r): i for i, r in enumerate(idxs)}
-            keys = np.array(sorted(last), np.int32)
-            written = rm.priorities(keys)
-        if pixel:
-            codes_a, codes_c = device_pool_codes(agent.actor, B), device_pool_codes(agent.critic, B)
-            relu_a, relu_c = device_relu_active(agent.actor, B), device_relu_active(agent.critic, B)
-        hb = rm.batch(idxs=idxs)
-        s1, s2 = rm.state[hb.state_1_idx], rm.state[hb.state_2_idx]
-        a, r, m = hb.action, hb.reward, hb.terminal_mask
-        assert (hb.state_2_idx != rm.state_2_idx[idxs]).any() and (m != rm.terminal_mask[idxs]).any()
+
+        def step_and_read(Bx):
+            d = {"Pm": [n.get_params() for n in nets]}
+            agent.train_step(Bx, 1)                           # hipGraph replay where this key's graph is held
+            idxs = np.empty(Bx, np.int32)
+            check(lib.cpp_replay_last_indexes(rm.handle, Bx, ptr(idxs)))
+            d["w"] = rm.last_weights(Bx) if per else None
+            d["values"] = agent.trainer.last_values(Bx)
+            d["grads"] = (agent.actor.get_grads(), agent.critic.get_grads())
+            if per:
+                last = {int(r): i for i, r in enumerate(idxs)}
+                keys = np.array(sorted(last), np.int32)
+                d["last"], d["keys"], d["written"] = last, keys, rm.priorities(keys)
+            if pixel:
+                d["codes"] = (device_pool_codes(agent.actor, Bx), device_pool_codes(agent.critic, Bx))
+                d["relu"] = (device_relu_active(agent.actor, Bx), device_relu_active(agent.critic, Bx))
+            hb = rm.batch(idxs=idxs)
+            s1, s2 = rm.state[hb.state_1_idx], rm.state[hb.state_2_idx]
+            a, r, m = hb.action, hb.reward, hb.terminal_mask
+            assert (hb.state_2_idx != rm.state_2_idx[idxs]).any() and (m != rm.terminal_mask[idxs]).any()
+            d["batch"] = (s1, a, r, m, s2)
+            return d
+        checked = step_and_read(B)
+        back = step_and_read(C) if C > B else None
     finally:
         agent.close()
+    for d in (checked, back):
+        if d is not None:
+            _check_nstep(d, aspec, cspec, pixel, per, atol, grad_rel, flip_tol, hyper)
+
+
+def _check_nstep(d, aspec, cspec, pixel, per, atol, grad_rel, flip_tol, hyper):
+    """what _ddpg_nstep_against_f64_oracle's step_and_read() brought back from one minibatch"""
+    Pm, w = d["Pm"], d["w"]
+    actions, _dq, q, td = d["values"]
+    g_a, g_c = d["grads"]
+    s1, a, r, m, s2 = d["batch"]
     ref = O.DDPG(aspec, cspec, Pm[0], Pm[1], np.float64, **({} if hyper is None else {"hyper": hyper}))
     ref.set_targets(Pm[2], Pm[3])
     if pixel:
+        (codes_a, codes_c), (relu_a, relu_c) = d["codes"], d["relu"]
         ref.actor.amax_override, ref.critic.amax_override = codes_a, codes_c
         ref.actor.relu_override, ref.critic.relu_override = relu_a, relu_c
     t = (s1, a, r, m, s2)
@@ -181,6 +204,7 @@ def _ddpg_nstep_against_f64_oracle(shape, B, rows, pixel=True, seed=0, per=False
     assert np.abs(q - cg["q"]).max() < atol and np.abs(td - cg["td"]).max() < atol
     assert_flat_close(aspec, g_a, ag["grads"], rel=grad_rel, what="actor pre-clip grads vs f64 oracle")
     if per:
+        last, keys, written = d["last"], d["keys"], d["written"]
         w64 = w.astype(np.float64).reshape(-1, 1)
         cw = ref.critic_gradients(t, td_override=w64 * td.astype(np.float64))
         assert_flat_close(cspec, g_c, cw["grads"], rel=grad_rel, what="weighted critic pre-clip grads vs f64 oracle (n-step)")
@@ -188,6 +212,11 @@ def _ddpg_nstep_against_f64_oracle(shape, B, rows, pixel=True, seed=0, per=False
         assert np.abs(written / want - 1).max() < 2e-6
     else:
         assert_flat_close(cspec, g_c, cg["grads"], rel=grad_rel, what="critic pre-clip grads vs f64 oracle (n-step)")
+
+
+def test_nstep_step_below_the_capacity_against_f64_oracle():
+    """(C, B) = (8, 5), n = 3: the gather's n-step walk for B rows behind C-row steps, and back"""
+    _ddpg_nstep_against_f64_oracle((16, 16, 3, 1, 2), 5, 300, capacity=8)
 
 
 def test_nstep_fused_step_against_f64_oracle_cfg3():

@@ -17,6 +17,8 @@ pytestmark = pytest.mark.gpu
 
 LOWDIM = (2, 2, 7)
 PIX = (32, 32, 3, 2, 3)
+PARTIAL_PER_SEED = 3          # (test_prioritized_step_below_the_capacity_against_f64_oracle: of seeds 0 .. 11 one whose priorities give the five-row
+#                               and the eight-row draw a weight below 0.5 at every sampler counter 0 .. 7 -- tests/per_np.py's draw over the known tree)
 
 
 def _memory(n, alpha=0.6, eps=1e-6):
@@ -210,46 +212,76 @@ def test_reference_loop_is_the_fused_step(shape, B, pixel, per_step):
 
 
 def _per_step_against_f64_oracle(shape, B, rows, pixel=True, replay_store="f16", seed=0, alpha=0.6, beta=0.4, eps=1e-6,
-                                 atol=1e-5, grad_rel=2e-5, flip_tol=1e-5, probe=False, **pair_kw):
+                                 atol=1e-5, grad_rel=2e-5, flip_tol=1e-5, probe=False, capacity=None, **pair_kw):
     """ONE graph-replayed minibatch of the fused step on a prioritized memory (rows drawn by priority, importance weights w) against
     oracle.DDPG(float64) on the same rows and parameters: actions / Q / TD at `atol`, the actor's pre-clip gradients at `grad_rel`
     (unweighted), the critic's at `grad_rel` against the oracle's backward pass of w * td_dev -- the weighted gradient, the critic's
-    gradient being linear in TD --, the weighted loss mean(w td^2), and the priorities written: (|td_dev| + eps)^alpha."""
-    agent, _ref, (aspec, cspec) = make_pair(shape, B, pixel, seed=seed, replay_size=rows + 50, replay_store=replay_store,
+    gradient being linear in TD --, the weighted loss mean(w td^2), and the priorities written: (|td_dev| + eps)^alpha.
+    capacity=C > B: the agent is built for C rows; a C-row step and its replay run first, the checked B-row replay behind them and one
+    more C-row step behind it are both held to the same bars, and besides to tests/per_np.py: the weights of the rows drawn from the
+    tree as it stood (1e-6, tests' bar for last_weights) and the tree behind the step, every inner node left + right bit for bit."""
+    agent, _ref, (aspec, cspec) = make_pair(shape, B, pixel, seed=seed, replay_size=rows + 50, replay_store=replay_store, capacity=capacity,
                                            prioritized_replay=True, priority_alpha=alpha, priority_beta=beta, priority_eps=eps, **pair_kw)
     path = None
     try:
         rm = agent.replay_memory
         rm.fill_synthetic(rows, seed=21 + seed)
+        C = B if capacity is None else int(capacity)
+        for _ in range(2 if C > B else 0):
+            agent.train_step(C, 1)                        # eager pass + capture, its replay
         if probe:
             from tests.helpers import ddpg_path
             path = ddpg_path(agent, B, aspec.hidden, cspec.hidden, pixel)
         agent.train_step(B, 1)                            # eager pass + capture
-        # priorities spread over three decades: the next draw's importance weights are far from 1
-        rm.update_priorities(np.arange(rows), np.random.default_rng(seed + 9).lognormal(0.0, 2.0, rows).astype(np.float32))
         nets = (agent.actor, agent.critic, agent.target_actor, agent.target_critic)
-        Pm = [n.get_params() for n in nets]
-        agent.train_step(B, 1)                            # hipGraph replay, rows drawn by priority
-        idxs = _rows_of_last_minibatch(agent, B)
-        w = rm.last_weights(B)
-        assert w.max() == 1.0 and w.min() < 0.5, (w.min(), w.max())
-        actions, _dq_da, q, td = agent.trainer.last_values(B)
-        g_a, g_c = agent.actor.get_grads(), agent.critic.get_grads()
-        stats = agent.trainer.last_stats()
-        last = {int(r): i for i, r in enumerate(idxs)}
-        keys = np.array(sorted(last), np.int32)
-        written = rm.priorities(keys)
-        if pixel:
-            codes_a, codes_c = device_pool_codes(agent.actor, B), device_pool_codes(agent.critic, B)
-            relu_a, relu_c = device_relu_active(agent.actor, B), device_relu_active(agent.critic, B)
-        s1, s2 = rm.state[rm.state_1_idx[idxs]], rm.state[rm.state_2_idx[idxs]]
-        hb = rm.batch(idxs=idxs)
-        a, r, m = hb.action, hb.reward, hb.terminal_mask
+
+        def step_and_read(Bx, salt):
+            # priorities spread over three decades: the next draw's importance weights are far from 1
+            rm.update_priorities(np.arange(rows), np.random.default_rng(seed + salt).lognormal(0.0, 2.0, rows).astype(np.float32))
+            d = {"B": Bx, "Pm": [n.get_params() for n in nets], "tree": rm.priority_tree()}
+            agent.train_step(Bx, 1)                       # hipGraph replay where this key's graph is held, rows drawn by priority
+            idxs = _rows_of_last_minibatch(agent, Bx)
+            d["idxs"], d["w"] = idxs, rm.last_weights(Bx)
+            d["values"] = agent.trainer.last_values(Bx)
+            d["grads"] = (agent.actor.get_grads(), agent.critic.get_grads())
+            d["stats"] = agent.trainer.last_stats()
+            last = {int(r): i for i, r in enumerate(idxs)}
+            keys = np.array(sorted(last), np.int32)
+            d["last"], d["keys"], d["written"], d["tree_after"] = last, keys, rm.priorities(keys), rm.priority_tree()
+            if pixel:
+                d["codes"] = (device_pool_codes(agent.actor, Bx), device_pool_codes(agent.critic, Bx))
+                d["relu"] = (device_relu_active(agent.actor, Bx), device_relu_active(agent.critic, Bx))
+            s1, s2 = rm.state[rm.state_1_idx[idxs]], rm.state[rm.state_2_idx[idxs]]
+            hb = rm.batch(idxs=idxs)
+            d["batch"] = (s1, hb.action, hb.reward, hb.terminal_mask, s2)
+            return d
+        checked = step_and_read(B, 9)
+        back = step_and_read(C, 10) if C > B else None
+        L, size = P.levels(rm.buffer_size), rm.size()
     finally:
         agent.close()
+    for d in (checked, back):
+        if d is not None:
+            _check_per_step(d, aspec, cspec, pixel, alpha, beta, eps, atol, grad_rel, flip_tol, (L, size) if C > B else None)
+    return path
+
+
+def _check_per_step(d, aspec, cspec, pixel, alpha, beta, eps, atol, grad_rel, flip_tol, tree_shape):
+    """what _per_step_against_f64_oracle's step_and_read() brought back from one minibatch"""
+    Pm, w, idxs, stats, last, keys, written = d["Pm"], d["w"], d["idxs"], d["stats"], d["last"], d["keys"], d["written"]
+    actions, _dq_da, q, td = d["values"]
+    g_a, g_c = d["grads"]
+    s1, a, r, m, s2 = d["batch"]
+    assert w.max() == 1.0 and w.min() < 0.5, (w.min(), w.max())
+    if tree_shape is not None:
+        L, size = tree_shape
+        want_w = P.weights(d["tree"], L, size, idxs, beta)
+        assert np.abs(w / want_w - 1).max() < 1e-6, (w, want_w)
+        assert np.array_equal(d["tree_after"], P.build(d["tree_after"][1 << L:], L))
     ref = O.DDPG(aspec, cspec, Pm[0], Pm[1], np.float64)
     ref.set_targets(Pm[2], Pm[3])
     if pixel:
+        (codes_a, codes_c), (relu_a, relu_c) = d["codes"], d["relu"]
         ref.actor.amax_override, ref.critic.amax_override = codes_a, codes_c
         ref.actor.relu_override, ref.critic.relu_override = relu_a, relu_c
     t = (s1, a, r, m, s2)
@@ -272,7 +304,24 @@ def _per_step_against_f64_oracle(shape, B, rows, pixel=True, replay_store="f16",
     assert float(np.linalg.norm(g_c - cg["grads"]) / np.linalg.norm(cg["grads"])) > 100 * grad_rel
     want = P.priority(td.reshape(-1)[[last[k] for k in keys]], alpha, eps)
     assert np.abs(written / want - 1).max() < 2e-6
-    return path
+    if tree_shape is not None:
+        # which leaves the step wrote: the rows of THIS minibatch hold the priorities of its TD (a repeated row its last occurrence's),
+        # every other leaf the bits it held in front of the step.  An update that walked the entries of an earlier, larger minibatch
+        # (n_up following the capacity) would rewrite rows this minibatch never drew -- and leave the tree as self-consistent as before
+        L, _size = tree_shape
+        before, after = d["tree"][1 << L:], d["tree_after"][1 << L:]
+        others = np.ones(len(after), bool)
+        others[keys] = False
+        changed = np.nonzero(others & (after != before))[0]
+        assert changed.size == 0, "leaves of rows %s changed, the minibatch drew %s" % (changed[:16], keys)
+        assert np.abs(after[keys] / want - 1).max() < 2e-6 and np.array_equal(after[keys].astype(np.float32), written)
+        assert (after[keys] != before[keys]).any()
+
+
+def test_prioritized_step_below_the_capacity_against_f64_oracle():
+    """(C, B) = (8, 5): n_up (the leaves a step writes are its own rows' and no others), the weights and the weighted loss partials at B
+    behind C-row steps, and back"""
+    _per_step_against_f64_oracle((16, 16, 3, 1, 2), 5, 300, seed=PARTIAL_PER_SEED, capacity=8)
 
 
 @pytest.mark.parametrize("shape,store,seed", [((64, 64, 3, 2, 3), "f16", 0), ((64, 64, 3, 2, 3), "u8", 2), ((64, 64, 3, 1, 3), "f16", 1)],

@@ -37,13 +37,14 @@ def _abi():
     return lib, check, ptr
 
 
-def _build(shape, B, A, hp, quant, P=None, episodes=None, rows=W.ROWS, seed=1, **kw):
-    """a device agent (quantile critics unless quant is None; quant: (N, kappa, drop_top)) holding the case's parameters and episodes"""
+def _build(shape, B, A, hp, quant, P=None, episodes=None, rows=W.ROWS, seed=1, capacity=None, **kw):
+    """a device agent (quantile critics unless quant is None; quant: (N, kappa, drop_top)) holding the case's parameters and episodes;
+    capacity: the batch size it is built with (None: B)"""
     from cartpoleplusplus_amd import ddpg_cartpole as D
     pixel = len(shape) == 5
     if quant is not None:
         kw = dict(kw, quantile_critic=True, num_quantiles=quant[0], quantile_huber_kappa=quant[1], drop_top_quantiles=quant[2])
-    make_opts(D, shape, B, pixel, replay_memory_size=rows, **dict(hyper_options(hp), **kw))
+    make_opts(D, shape, B if capacity is None else int(capacity), pixel, replay_memory_size=rows, **dict(hyper_options(hp), **kw))
     agent = D.DeepDeterministicPolicyGradientAgent(FakeEnv(shape, A))
     try:
         agent.initialise_variables(seed=seed)
@@ -150,34 +151,57 @@ def test_a_minibatch_with_dropout_against_the_float64_restatement():
     _one_minibatch("A2-B8-N25-d0-sgd", use_dropout=True, warm=1, launches={"quant": 2, "heads": 0, "td": 0})
 
 
-def _one_minibatch(cid, use_dropout=False, warm=0, launches=None):
+def _one_minibatch(cid, use_dropout=False, warm=0, launches=None, capacity=None):
     """use_dropout: --use-dropout, the restatement's actor and target actor drawing the masks of forward count `warm` -- `warm` training
     calls on the same rows run first and the parameters are put back behind them (plain gradient descent only: no slots, no noise count).
-    launches: {kernel family: count} the checked minibatch, profiled, must show."""
+    launches: {kernel family: count} the checked minibatch, profiled, must show.  capacity=C > B: the agent is built for C rows and a
+    C-row minibatch (the last C of the case's rows) runs first, then one warm call at B; behind the checked minibatch the parameters
+    are put back once more and the C-row minibatch is held to the restatement at the same bars."""
     case = W.case_of(cid)
-    B, N, drop, opt, d, sm = case[3], case[4], case[5], case[8], case[9], case[10]
+    A, B, N, drop, opt, d, sm = case[2], case[3], case[4], case[5], case[8], case[9], case[10]
     inputs = W.case_inputs(case, **(dict(dropout=True) if use_dropout else {}))
-    specs, P, _ep, idxs, batches = inputs
+    specs, P, episodes, idxs, batches = inputs
     weighted = "weighted" in cid
+    big = None
+    if capacity is not None:
+        assert capacity > B and len(idxs) >= capacity
+        big, warm = np.ascontiguousarray(idxs[-capacity:], dtype=np.int32), max(warm, 1)
     assert warm == 0 or (opt == "gradient-descent" and sm is None and d == 1 and not weighted and case[13] == 1)
-    agent = _case_agent(case, inputs, **(dict(use_dropout=True) if use_dropout else {}))
+    agent = _case_agent(case, inputs, capacity=capacity, **(dict(use_dropout=True) if use_dropout else {}))
+    forwards = 0
+
+    def put_back():
+        for net, p in zip(agent.networks(), P):
+            net.set_params(p)
+
+    def read(Bx, weighted):
+        return {"rows": tuple(agent.trainer.last_values(Bx)) + tuple(agent.trainer.last_quantiles(Bx)), "stats": agent.trainer.last_stats(),
+                "grads": (agent.actor.get_grads(), agent.critic.get_grads()), "forwards": forwards - 1,
+                "w": agent.replay_memory.last_weights(Bx).astype(np.float64).reshape(Bx, 1) if weighted else None,
+                "noise": _device_noise(agent, case, Bx, 0)}
     try:
         if weighted:
             _set_priorities(agent)
+        if big is not None:
+            agent.train_step(capacity, 1, idxs=big)
+            forwards += 1
         for _ in range(warm):
             agent.train_step(B, 1, idxs=idxs[:B])
+            forwards += 1
         if warm:
-            for net, p in zip(agent.networks(), P):
-                net.set_params(p)
+            put_back()
         seen = _profiled_calls(agent.actor.ctx, lambda: agent.train_step(B, 1, idxs=idxs[:B])) if launches is not None else \
             agent.train_step(B, 1, idxs=idxs[:B])
+        forwards += 1
         if launches is not None:
             assert {k: seen.get(k, 0) for k in launches} == launches, seen
-        dev = tuple(agent.trainer.last_values(B)) + tuple(agent.trainer.last_quantiles(B))
-        stats = agent.trainer.last_stats()
-        g_a, g_c = agent.actor.get_grads(), agent.critic.get_grads()
-        w = agent.replay_memory.last_weights(B).astype(np.float64).reshape(B, 1) if weighted else None
-        noise = _device_noise(agent, case, B, 0)
+        dev = read(B, weighted)
+        back = None
+        if big is not None:
+            put_back()
+            agent.train_step(capacity, 1, idxs=big)
+            forwards += 1
+            back = read(capacity, False)
         n_q, n_atoms = ctypes.c_int(-1), ctypes.c_int(-1)
         lib, check, _ptr = _abi()
         check(lib.cpp_net_quantile_info(agent.critic.handle, ctypes.byref(n_q)))
@@ -187,10 +211,22 @@ def _one_minibatch(cid, use_dropout=False, warm=0, launches=None):
         assert n_q.value == 0 and agent.trainer.quantile_target == (float(np.float32(case[6])), drop)
     finally:
         agent.close()
+    _check_minibatch(cid, case, specs, P, dev, batches[0], weighted)
+    if back is not None:
+        from tests.helpers import minibatch_of_rows
+        _check_minibatch(cid + " back at capacity %d" % capacity, case, specs, P, back,
+                         minibatch_of_rows(W.ROWS, W.SHAPES[case[1]], A, episodes, big), False)
+
+
+def _check_minibatch(cid, case, specs, P, got, batch, weighted):
+    """what _one_minibatch read back from one minibatch against the float64 restatement on `batch` from the parameters P"""
+    N, drop, opt, d, sm = case[4], case[5], case[8], case[9], case[10]
+    B = int(np.asarray(batch[1]).shape[0])
+    dev, stats, (g_a, g_c), w, noise = got["rows"], got["stats"], got["grads"], got["w"], got["noise"]
     ref = W.restatement(specs, P, W.quant_of(case), np.float64, W.hyper_of(case), opt, d, sm)
-    set_actor_masks(ref, B, warm)
-    ag = ref.actor_gradients(batches[0][0])
-    cg = ref.critic_gradients(batches[0], noise=noise, w=w)
+    set_actor_masks(ref, B, got["forwards"])
+    ag = ref.actor_gradients(batch[0])
+    cg = ref.critic_gradients(batch, noise=noise, w=w)
     if weighted:
         assert w.min() < 0.9 and abs(w.max() - 1.0) < 1e-6, w.ravel()
     err = _row_errors(dev, cg, ag)
@@ -205,6 +241,12 @@ def _one_minibatch(cid, use_dropout=False, warm=0, launches=None):
     assert_flat_close(specs[0], g_a, ag["grads"], rel=W.GRAD_REL, what="actor pre-clip grads vs f64 restatement")
     assert len(g_c) == specs[1].num_params()
     assert_flat_close(specs[1], g_c, cg["grads"], rel=W.GRAD_REL, what="critic pre-clip grads vs f64 restatement")
+
+
+def test_a_minibatch_below_the_capacity_against_the_float64_restatement():
+    """(C, B) = (8, 5), two top quantiles dropped: the atoms, the sorted and truncated targets and the loss partials at B behind a C-row
+    minibatch, and back"""
+    _one_minibatch("A2-B5-N33-d2", capacity=8)
 
 
 # ---- 2. the cases' outer steps: parameters, targets, slots, counts

@@ -144,41 +144,66 @@ def test_counter_moves_once_per_augmented_minibatch_and_never_otherwise():
 
 
 # ---- 3. one fused minibatch against the float64 oracles ---------------------------------------------------------------------------
-def _ddpg_shift_against_f64_oracle(shape, B, rows, seed=0, per=False, nstep=1, store="f16", pad=4, grad_rel=None, **pair_kw):
+def _ddpg_shift_against_f64_oracle(shape, B, rows, seed=0, per=False, nstep=1, store="f16", pad=4, grad_rel=None, capacity=None, **pair_kw):
     """ONE graph-replayed minibatch of the fused DDPG step on a memory with random shift on against oracle.DDPG(float64), unmodified,
     fed the shifted minibatch rebuilt on the host: actions / Q / TD at ATOL, the pre-clip gradients at GRAD_REL; the same oracle fed
     the stored (unshifted) pixels must miss the device's Q by more than 100 x ATOL.  grad_rel (None: GRAD_REL), pair_kw: the bar of the
-    gradient lists and make_pair's options for other networks (use_batch_norm)."""
+    gradient lists and make_pair's options for other networks (use_batch_norm).  capacity=C > B: the agent is built for C rows; a C-row
+    step and its replay run first (two draws of C shifts), and behind the checked B-row replay one more C-row step is held to the same
+    bars."""
     grad_rel = GRAD_REL if grad_rel is None else grad_rel
     from cartpoleplusplus_amd import ddpg_cartpole as D
     from tests import per_np as P
     kw = dict(prioritized_replay=True, priority_alpha=0.6, priority_beta=0.4, priority_eps=1e-6) if per else {}
     kw.update(pair_kw)
-    agent, _ref, (aspec, cspec) = make_pair(shape, B, True, seed=seed, replay_size=rows + 50, replay_store=store, **kw)
+    agent, _ref, (aspec, cspec) = make_pair(shape, B, True, seed=seed, replay_size=rows + 50, replay_store=store, capacity=capacity, **kw)
     try:
         rm = agent.replay_memory
         rm.fill_synthetic(rows, seed=21 + seed)
         if nstep > 1:
             rm.enable_n_step(nstep, D.opts.discount)
         rm.enable_random_shift(pad, seed=SEED + seed)
+        C = B if capacity is None else int(capacity)
+        draws = 0
+        for _ in range(2 if C > B else 0):
+            agent.train_step(C, 1)                            # eager pass + capture, its replay
+            draws += 1
         agent.train_step(B, 1)                                # eager pass + capture
+        draws += 1
         if per:
             rm.update_priorities(np.arange(rows), np.random.default_rng(seed + 9).lognormal(0.0, 2.0, rows).astype(np.float32))
         nets = (agent.actor, agent.critic, agent.target_actor, agent.target_critic)
-        Pm = [n.get_params() for n in nets]
-        assert rm.shift_counter() == 1
-        agent.train_step(B, 1)                                # hipGraph replay
-        assert rm.shift_counter() == 2
-        idxs = _rows(agent, B)
-        w = rm.last_weights(B) if per else None
-        actions, _dq, q, td = agent.trainer.last_values(B)
-        g_a, g_c = agent.actor.get_grads(), agent.critic.get_grads()
-        codes_a, codes_c = device_pool_codes(agent.actor, B), device_pool_codes(agent.critic, B)
-        relu_a, relu_c = device_relu_active(agent.actor, B), device_relu_active(agent.critic, B)
-        t, t_unshifted, sh = _shifted_minibatch(rm, idxs)
-        assert np.array_equal(sh, S.shifts(SEED + seed, 1, B, pad))
+
+        def step_and_read(Bx):
+            d = {"Pm": [n.get_params() for n in nets]}
+            assert rm.shift_counter() == draws
+            agent.train_step(Bx, 1)                           # hipGraph replay where this key's graph is held
+            assert rm.shift_counter() == draws + 1
+            idxs = _rows(agent, Bx)
+            d["w"] = rm.last_weights(Bx) if per else None
+            d["values"] = agent.trainer.last_values(Bx)
+            d["grads"] = (agent.actor.get_grads(), agent.critic.get_grads())
+            d["codes"] = (device_pool_codes(agent.actor, Bx), device_pool_codes(agent.critic, Bx))
+            d["relu"] = (device_relu_active(agent.actor, Bx), device_relu_active(agent.critic, Bx))
+            d["t"], d["t_unshifted"], sh = _shifted_minibatch(rm, idxs)
+            assert np.array_equal(sh, S.shifts(SEED + seed, draws, Bx, pad))
+            return d
+        checked = step_and_read(B)
+        draws += 1
+        back = step_and_read(C) if C > B else None
     finally:
         agent.close()
+    for d in (checked, back):
+        if d is not None:
+            _check_shifted(d, aspec, cspec, per, grad_rel)
+
+
+def _check_shifted(d, aspec, cspec, per, grad_rel):
+    """what _ddpg_shift_against_f64_oracle's step_and_read() brought back from one minibatch"""
+    Pm, w, t, t_unshifted = d["Pm"], d["w"], d["t"], d["t_unshifted"]
+    actions, _dq, q, td = d["values"]
+    g_a, g_c = d["grads"]
+    (codes_a, codes_c), (relu_a, relu_c) = d["codes"], d["relu"]
     ref = O.DDPG(aspec, cspec, Pm[0], Pm[1], np.float64)
     ref.set_targets(Pm[2], Pm[3])
     ref.actor.amax_override, ref.critic.amax_override = codes_a, codes_c
@@ -200,6 +225,11 @@ def _ddpg_shift_against_f64_oracle(shape, B, rows, seed=0, per=False, nstep=1, s
         assert_flat_close(cspec, g_c, cw["grads"], rel=grad_rel, what="weighted critic pre-clip grads vs f64 oracle (random shift)")
     else:
         assert_flat_close(cspec, g_c, cg["grads"], rel=grad_rel, what="critic pre-clip grads vs f64 oracle (random shift)")
+
+
+def test_shifted_step_below_the_capacity_against_f64_oracle():
+    """(C, B) = (8, 5): B shifts per image set drawn and applied behind C-row steps, and back"""
+    _ddpg_shift_against_f64_oracle((16, 16, 3, 1, 2), 5, 300, capacity=8)
 
 
 def test_shifted_fused_step_against_f64_oracle_cfg3():

@@ -27,7 +27,8 @@ def _abi():
     return lib, check, ptr
 
 
-def _agent(case, inputs, **kw):
+def _agent(case, inputs, capacity=None, **kw):
+    """capacity: the batch size the agent is built with (None: the case's)"""
     from cartpoleplusplus_amd import ddpg_cartpole as D
     _cid, shape_name, A, B, opt, _clip, _tau, twin, weighted, n_step, pad = case
     shape = S.C_SHAPES[shape_name]
@@ -42,7 +43,7 @@ def _agent(case, inputs, **kw):
     if pad:
         opts["replay_store"] = "u8"
     opts.update(kw)
-    make_opts(D, shape, B, len(shape) == 5, **opts)
+    make_opts(D, shape, B if capacity is None else int(capacity), len(shape) == 5, **opts)
     agent = D.DeepDeterministicPolicyGradientAgent(FakeEnv(shape, A))
     try:
         agent.initialise_variables(seed=1)
@@ -88,10 +89,11 @@ def _last_rows(agent, B):
     return rows
 
 
-def _read_minibatch(agent, case, k, fused=True):
+def _read_minibatch(agent, case, k, fused=True, rows=None):
     """what the last minibatch left on the device, in the shape tests.sac_np.ratios takes.  fused=False: behind critic.train of the single
-    ops (the actor's half was read behind actor.train)"""
+    ops (the actor's half was read behind actor.train).  rows: the minibatch's row count (None: the case's)"""
     _cid, shape_name, A, B, _opt, _clip, _tau, twin, _w, _n, _pad = case
+    B = B if rows is None else int(rows)
     t = agent.trainer
     sac = t.last_sac(B)
     assert sac["n"] == k, (sac["n"], k)
@@ -149,11 +151,17 @@ def _compare(case, inputs, refs, start, k, got, sac, routes, got_vec, batch, wei
     return want, refs[0]
 
 
-def _run(case, inputs, device_rows):
+def _run(case, inputs, device_rows, capacity=None):
     """C_MINIBATCHES calls of one minibatch each (the weights, the shifts and eps can be read for the last minibatch of a call only).
-    device_rows: the device draws (the first call is the eager pass and the capture, the others replay the graph)"""
+    device_rows: the device draws (the first call is the eager pass and the capture, the others replay the graph).  capacity=C > B (the
+    caller's rows, no shift): the agent is built for C rows and the four minibatches have C, B, B and C rows -- the last C of the case's
+    rows in front and behind, its first two minibatches between them -- each from the device's own state, at the same bars."""
     cid, shape_name, A, B, _opt, clip, _tau, twin, weighted, n_step, pad = case
-    agent = _agent(case, inputs, **({} if weighted or not device_rows else {"sample_seed": GRAPH_SAMPLE_SEED}))
+    sizes = None
+    if capacity is not None:
+        assert not device_rows and not pad
+        sizes = S.partial_rows(case, inputs, capacity)
+    agent = _agent(case, inputs, capacity=capacity, **({} if weighted or not device_rows else {"sample_seed": GRAPH_SAMPLE_SEED}))
     refs = (S.composed_restatement(case, inputs), S.composed_restatement(case, inputs, np.float32))
     restated_per = S.RestatedPer() if weighted else None
     try:
@@ -181,10 +189,13 @@ def _run(case, inputs, device_rows):
                     assert rel <= 8 * 2.0 ** -23 + 2.0 ** -24, (cid, k, rel)
                 else:
                     assert np.array_equal(rows, T3.device_rows(GRAPH_SAMPLE_SEED, k, B, S.C_ROWS)), "the rows are not the restated draw"
+            elif sizes is not None:
+                rows = np.ascontiguousarray(sizes[k], dtype=np.int32)
+                agent.train_step(len(rows), 1, idxs=rows)
             else:
                 rows = np.ascontiguousarray(inputs[3][k * B:(k + 1) * B], dtype=np.int32)
                 agent.train_step(B, 1, idxs=rows)
-            got, sac, routes = _read_minibatch(agent, case, k)
+            got, sac, routes = _read_minibatch(agent, case, k, rows=len(rows))
             got_vec = _state(agent)
             np.testing.assert_array_equal(agent.target_actor.get_params(), agent.actor.get_params())
             if pad:
@@ -193,7 +204,7 @@ def _run(case, inputs, device_rows):
                 batch, _unshifted, sh = _shifted_minibatch(rm, rows)
                 assert np.array_equal(sh, shift_np.shifts(S.C_SHIFT_SEED, k, B, pad))
             else:
-                batch = S.composed_batches(case, inputs[2], rows)[0]
+                batch = S.composed_batches(case[:3] + (len(rows),) + case[4:], inputs[2], rows)[0]
                 hb = rm.batch(idxs=rows)      # (the memory's own columns: the n-step fold is the restated one)
                 np.testing.assert_array_equal(np.asarray(hb.reward), batch[2])
                 np.testing.assert_array_equal(np.asarray(hb.terminal_mask), batch[3])
@@ -224,6 +235,14 @@ GRAPH_SAMPLE_SEED = 0
 def test_outer_steps_of_every_composed_case_against_the_float64_restatement(cid):
     case = S.composed_case(cid)
     _run(case, S.composed_inputs(case), device_rows=bool(case[8]))
+
+
+def test_minibatches_below_the_capacity_against_the_float64_restatement():
+    """(C, B) = (8, 5), scalar critic, Adam, both lists clipped (tests.sac_np.C_PARTIAL_CASE; its side of the clip over the four
+    minibatches: tests/test_partial_batch_host.py): the policy's noise by row, log pi, the soft reward and the temperature's gradient at
+    B behind a C-row minibatch, and at C again behind the B-row ones"""
+    case = S.C_PARTIAL_CASE
+    _run(case, S.composed_inputs(case), device_rows=False, capacity=S.C_PARTIAL_CAPACITY)
 
 
 # ---- 2. graph replays on the rows the device draws

@@ -45,8 +45,9 @@ def _opt_kw(opt):
     return {} if name == "GradientDescent" else dict(ddpg_optimiser=name, ddpg_optimiser_args=json.dumps(args))
 
 
-def _agent(case, inputs, shared=True, **kw):
-    """a device agent holding the case's parameters and episodes (a separate-trunk agent: the episodes, its own initial parameters)"""
+def _agent(case, inputs, shared=True, capacity=None, **kw):
+    """a device agent holding the case's parameters and episodes (a separate-trunk agent: the episodes, its own initial parameters);
+    capacity: the batch size it is built with (None: the case's)"""
     from cartpoleplusplus_amd import ddpg_cartpole as D
     _cid, shape_name, A, B, opt, _clip, hidden = case
     shape = S.SHAPES[shape_name]
@@ -55,7 +56,7 @@ def _agent(case, inputs, shared=True, **kw):
     if shared:
         opts["shared_encoder"] = True
     opts.update(kw)
-    make_opts(D, shape, B, True, **opts)
+    make_opts(D, shape, B if capacity is None else int(capacity), True, **opts)
     agent = D.DeepDeterministicPolicyGradientAgent(FakeEnv(shape, A))
     try:
         agent.initialise_variables(seed=1)
@@ -93,13 +94,23 @@ def _digest(agent):
     return np.concatenate([st[k] for k in S.VECTORS])
 
 
-def _minibatches(cid, batches_of=None, prepare=None, **kw):
-    """S.NB calls of one minibatch each against the restatement and its float32 twin"""
+def partial_plan(case, inputs, capacity):
+    """tests.helpers.capacity_plan of a case"""
+    from tests.helpers import capacity_plan
+    _c, shape_name, A, B, _opt, _clip, _h = case
+    return capacity_plan(S.ROWS, S.SHAPES[shape_name], A, inputs[2], inputs[3], inputs[4], B, capacity)
+
+
+def _minibatches(cid, batches_of=None, prepare=None, capacity=None, **kw):
+    """S.NB calls of one minibatch each against the restatement and its float32 twin.  capacity=C > B: the agent is built for C rows
+    and walks partial_plan's minibatches -- C rows, B, B, C -- each from the device's own state in front of it, at the same bars."""
     case = S.case_of(cid)
     _c, _sn, A, B, opt, clip, _h = case
     inputs = S.case_inputs(case)
     specs, P, _episodes, idxs, batches = inputs
-    agent = _agent(case, inputs, **kw)
+    plan = [(idxs[k * B:(k + 1) * B], batches[k]) for k in range(S.NB)] if capacity is None else partial_plan(case, inputs, capacity)
+    assert capacity is None or batches_of is None
+    agent = _agent(case, inputs, capacity=capacity, **kw)
     if prepare is not None:
         prepare(agent)
     refs = [S.restatement(specs, P, dt, S.hyper_of(case), opt) for dt in (np.float64, np.float32)]
@@ -109,11 +120,11 @@ def _minibatches(cid, batches_of=None, prepare=None, **kw):
         want0 = S.initial_state(P)
         for key in S.VECTORS[:4]:
             np.testing.assert_array_equal(start[key], want0[key])
-        for k in range(S.NB):
+        for k in range(len(plan)):
             weights = None
             if batches_of is None:
-                rows = np.ascontiguousarray(idxs[k * B:(k + 1) * B], dtype=np.int32)
-                batch = batches[k]
+                rows, batch = np.ascontiguousarray(plan[k][0], dtype=np.int32), plan[k][1]
+                B = len(rows)
                 # a' of the common start: the target actor's inference forward on state_2 (the target critic's trunk, then its stack)
                 a2_forward = agent.target_actor.forward(np.asarray(batch[4]))
                 agent.train_step(B, 1, idxs=rows)
@@ -175,6 +186,11 @@ def _minibatches(cid, batches_of=None, prepare=None, **kw):
 @pytest.mark.parametrize("cid", [c[0] for c in S.CASES])
 def test_minibatches_against_the_float64_restatement(cid):
     _minibatches(cid)
+
+
+def test_minibatches_below_the_capacity_against_the_float64_restatement():
+    """(C, B) = (8, 5): the critic's trunk feeding both networks at B behind a C-row minibatch, and at C again behind the B-row ones"""
+    _minibatches("8x8x6-A2-B5-sgd", capacity=8)
 
 
 PER = dict(alpha=0.6, eps=1e-3, beta=0.5, sample_seed=5)

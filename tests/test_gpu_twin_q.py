@@ -35,11 +35,12 @@ def _abi():
     return lib, check, ptr
 
 
-def _build(shape, B, A, hp, P=None, episodes=None, rows=W.ROWS, twin=True, seed=1, **kw):
-    """a device agent (twin critics unless told otherwise) holding the case's parameters and episodes"""
+def _build(shape, B, A, hp, P=None, episodes=None, rows=W.ROWS, twin=True, seed=1, capacity=None, **kw):
+    """a device agent (twin critics unless told otherwise) holding the case's parameters and episodes; capacity: the batch size it is
+    built with (None: B)"""
     from cartpoleplusplus_amd import ddpg_cartpole as D
     pixel = len(shape) == 5
-    make_opts(D, shape, B, pixel, replay_memory_size=rows, twin_q=twin, **dict(hyper_options(hp), **kw))
+    make_opts(D, shape, B if capacity is None else int(capacity), pixel, replay_memory_size=rows, twin_q=twin, **dict(hyper_options(hp), **kw))
     agent = D.DeepDeterministicPolicyGradientAgent(FakeEnv(shape, A))
     try:
         agent.initialise_variables(seed=seed)
