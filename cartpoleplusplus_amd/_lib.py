@@ -89,6 +89,9 @@ SIGNATURES = {
     "cpp_net_distribution_info": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "cpp_net_create_quantile": (_I, [_P, C.POINTER(NetSpec), _I, _I, _PP]),
     "cpp_net_quantile_info": (_I, [_P, C.POINTER(_I)]),
+    "cpp_net_create_pooled_quantile": (_I, [_P, C.POINTER(NetSpec), _I, _I, _PP]),
+    "cpp_net_create_pooled_quantile_norm": (_I, [_P, C.POINTER(NetSpec), _I, _I, _I, C.c_float, _PP]),
+    "cpp_net_pooled_quantile_info": (_I, [_P, C.POINTER(_I)]),
     "cpp_net_create_gaussian": (_I, [_P, C.POINTER(NetSpec), _I, C.c_float, C.c_float, _PP]),
     "cpp_net_gaussian_info": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "cpp_net_forward_gaussian": (_I, [_P, _P, _I, _I, _I, _P, _P]),
@@ -170,6 +173,7 @@ SIGNATURES = {
     "cpp_ddpg_last_distribution": (_I, [_P, _I, _P, _P, _P]),
     "cpp_ddpg_set_quantile_target": (_I, [_P, C.c_float, _I]),
     "cpp_ddpg_last_quantiles": (_I, [_P, _I, _P, _P, _P]),
+    "cpp_ddpg_last_pooled_quantiles": (_I, [_P, _I, _P, _P, _P, _P]),
     "cpp_ddpg_set_sac": (_I, [_P, C.c_float, C.c_float, C.c_float, _U64]),
     "cpp_ddpg_last_sac": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_U64), _P]),
     "cpp_ddpg_sac_temperature": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_U64)]),

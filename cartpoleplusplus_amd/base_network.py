@@ -144,7 +144,7 @@ class Network(object):
 
     # ------------------------------------------------------------------ native instantiation
     def _build_native(self, kind, action_dim, max_batch, ctx=None, head_out=0, head_act=0, twin_q=False, distribution=None, quantiles=None, gaussian=None,
-                      feature_norm=None, encoderless=False):
+                      feature_norm=None, encoderless=False, pooled=None):
         self.ctx = ctx or _lib.default_context()
         spec = _lib.NetSpec()
         spec.kind, spec.action_dim = kind, int(action_dim)
@@ -172,6 +172,13 @@ class Network(object):
             if feature_norm is not None:
                 norm, epsilon = {"tanh": _lib.CPP_NORM_TANH, "relu": _lib.CPP_NORM_RELU}[feature_norm[0]], float(feature_norm[1])
             check(lib.cpp_net_create_encoderless(self.ctx.handle, C.byref(spec), int(max_batch), C.byref(v), norm, epsilon, C.byref(handle)))
+        elif pooled is not None:          # N per head: pooled twin quantile critics, cpp_net_create_pooled_quantile (_norm: behind a feature layer norm)
+            if feature_norm is not None:
+                act = {"tanh": _lib.CPP_NORM_TANH, "relu": _lib.CPP_NORM_RELU}[feature_norm[0]]
+                check(lib.cpp_net_create_pooled_quantile_norm(self.ctx.handle, C.byref(spec), int(max_batch), int(pooled), act, float(feature_norm[1]),
+                                                              C.byref(handle)))
+            else:
+                check(lib.cpp_net_create_pooled_quantile(self.ctx.handle, C.byref(spec), int(max_batch), int(pooled), C.byref(handle)))
         elif feature_norm is not None:      # (activation, epsilon): Linear -> LayerNorm -> act on layer 0, cpp_net_create_feature_norm
             activation, epsilon = feature_norm
             v = _lib.NetVariant()

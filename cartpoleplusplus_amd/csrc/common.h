@@ -60,7 +60,7 @@ enum KernelId {
   K_CONV1_IMAGE,          // conv1's operand images as a launch of their own (conv_rs16.h; in the fused step they ride in the optimiser's launch)
   K_PER,                  // prioritized replay: sum-tree updates, draws and importance weights (per.hip)
   K_DIST,                 // distributional critic: softmax / expectation, projected target and cross-entropy (dist.hip)
-  K_QUANT,                // quantile critic: expectation, sorted and truncated targets, quantile Huber loss (quant.hip)
+  K_QUANT,                // quantile critic: expectation, sorted and truncated targets, quantile Huber loss (quant.hip; a pooled trainer's: quant_pool.hip)
   K_SAC,                  // soft actor-critic: policy sample / mean, soft reward, actor head gradient, temperature (sac.hip)
   K_LN_FWD,               // feature layer norm on fully connected layer 0, forward (ln.hip)
   K_LN_BWD,               // ... its backward: the column sums' launch and the row-local launch
@@ -579,6 +579,21 @@ int quant_td_grid(int B);
 int launch_quant_td(cpp_ctx* ctx, const float* theta, const float* ttheta, const float* r, const float* mask, float discount, int B, int N,
                     float kappa, int drop_top, float* q_out, float* tq_out, float* theta_out, float* sorted_out, float* y_out, float* td,
                     float* dz, double* loss_part, const float* w = nullptr);
+// ---- pooled twin quantile critics (quant_pool.hip; include/cartpolepp_abi.h, cpp_net_create_pooled_quantile).  theta of each head: (B, N), N in
+// [2, 32]: the pool of 2N atoms fits the 64 lanes of a wave.
+// the expect job: q1_out[b] = Q_1, q2_out[b] = Q_2 and dz1[b][i] = dz2[b][i] = 1 / (2N), the tops of Qbar = (Q_1 + Q_2) / 2
+int launch_qpool_expect(cpp_ctx* ctx, const float* theta1, const float* theta2, int B, int N, float* q1_out, float* q2_out, float* dz1, float* dz2);
+// the td job's buffers: both fed heads and both target heads in; Q_1, Q_2, Q_1', Q_2' (B each), theta^1, theta^2 ((B, N) each), the pool
+// sorted ascending and y_j = r + g s_j for j < 2N - 2 drop_per_head (0 beyond; (B, 2N) each), td_k = Q_k - mean_j y_j, dz_k = head k's
+// quantile Huber gradient (both nullptr: none, check_loss) out
+struct QpoolTdIo {
+  const float *theta1, *theta2, *ttheta1, *ttheta2;
+  float *q1_out, *q2_out, *tq1_out, *tq2_out, *theta1_out, *theta2_out, *sorted_out, *y_out, *td, *td2, *dz1, *dz2;
+};
+// ... and the per-workgroup sums of w_b (L^1_b + L^2_b) in loss_part[qpool_td_grid(B)] (f64, quant.hip's region and finalisation).  w == nullptr: uniform.
+int qpool_td_grid(int B);
+int launch_qpool_td(cpp_ctx* ctx, const QpoolTdIo& io, const float* r, const float* mask, float discount, int B, int N, float kappa, int drop_per_head,
+                    double* loss_part, const float* w = nullptr);
 // ---- feature layer norm (ln.hip; include/cartpolepp_abi.h, cpp_net_create_feature_norm): the rows of fully connected layer 0 of up to
 // LN_JOBS_MAX networks in one launch.  io: (B, n) at row stride ld -- z in, y = act(gamma xhat + beta) out, in place (the next layer's
 // input buffer; its ones column is left alone).  act: GE_TANH or GE_RELU.

@@ -18,11 +18,12 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
   ARG_CHECK(!actor->dist_n && !tactor->dist_n, "cpp_ddpg_create: a distributional actor");
   ARG_CHECK(critic->dist_n == tcritic->dist_n && critic->dist_vmin == tcritic->dist_vmin && critic->dist_vmax == tcritic->dist_vmax,
             "cpp_ddpg_create: critic and target critic must carry one value distribution (N, v_min, v_max), or none");
-  ARG_CHECK(!(critic->dist_n && critic->twin), "cpp_ddpg_create: a distributional critic with twin Q heads");
+  ARG_CHECK(critic->pooled() == tcritic->pooled(), "cpp_ddpg_create: pooled quantile critics come as a pair with one N (cpp_net_create_pooled_quantile: both critics, or neither)");
+  ARG_CHECK(!(critic->dist_n && critic->twin) || critic->pooled(), "cpp_ddpg_create: a distributional critic with twin Q heads");
   ARG_CHECK(critic->quant == tcritic->quant, "cpp_ddpg_create: a quantile critic needs a quantile target critic with the same N (never a categorical or a plain one)");
   ARG_CHECK(actor->gauss == tactor->gauss && actor->ls_lo == tactor->ls_lo && actor->ls_hi == tactor->ls_hi,
             "cpp_ddpg_create: a Gaussian actor needs a Gaussian target actor with the same log std bounds (and a plain one a plain one)");
-  ARG_CHECK(!(actor->gauss && critic->dist_n), "cpp_ddpg_create: a Gaussian actor with a distributional or quantile critic");
+  ARG_CHECK(!(actor->gauss && critic->dist_n) || critic->pooled(), "cpp_ddpg_create: a Gaussian actor with a distributional or quantile critic");
   for (cpp_net* n : {actor, critic, tactor, tcritic})
     ARG_CHECK(!(actor->gauss && (n->spec.use_batch_norm || n->spec.use_dropout)), "cpp_ddpg_create: a Gaussian actor with batch norm or dropout");
   ARG_CHECK(actor->ln == critic->ln && actor->ln == tactor->ln && actor->ln == tcritic->ln,
@@ -68,8 +69,11 @@ extern "C" int cpp_ddpg_create(cpp_ctx* ctx, cpp_net* actor, cpp_net* critic, cp
     cpp_set_error("cpp_ddpg_create: a distributional trainer takes batches up to %d (got %d)", 4 * DDPG_HEADS_MAX_WGS, d->maxB);
     rc = CPP_ERR_ARG;
   }
-  for (float** p : {&d->dist_p, &d->dist_tp, &d->dist_m})
-    if (!rc && d->dist_n) rc = dalloc(d->arena, p, (size_t)d->maxB * d->dist_n);
+  d->pool = critic->pooled();      // (the pool's two buffers are 2N wide, and theta^2 has one of its own)
+  if (!rc && d->dist_n) rc = dalloc(d->arena, &d->dist_p, (size_t)d->maxB * d->dist_n);
+  for (float** p : {&d->dist_tp, &d->dist_m})
+    if (!rc && d->dist_n) rc = dalloc(d->arena, p, (size_t)d->maxB * d->dist_n * (d->pool ? 2 : 1));
+  if (!rc && d->pool) rc = dalloc(d->arena, &d->pool_p2, (size_t)d->maxB * d->dist_n);
   d->sac = actor->gauss;
   if (d->sac && sac_grid(d->maxB) > DDPG_HEADS_MAX_WGS) {
     cpp_set_error("cpp_ddpg_create: a soft actor-critic trainer takes batches up to %d (got %d)", 4 * DDPG_HEADS_MAX_WGS, d->maxB);

@@ -65,6 +65,10 @@ struct cpp_ddpg {
   // target atoms and y for cpp_ddpg_last_quantiles, quant.hip stands where dist.hip stands.  kappa and the dropped top atoms
   // (cpp_ddpg_set_quantile_target) are captured by value
   bool quant = false; float quant_kappa = 1.f; int quant_drop = 0;
+  // pooled twin quantile critics (cpp_net_create_pooled_quantile: both critics with one N, or neither): twin, quant and dist_n = N at once.
+  // quant_pool.hip stands where quant.hip stands and, for the actor, where actor_min.hip stands; quant_drop is d PER HEAD.  dist_p holds
+  // theta^1 and pool_p2 theta^2 (maxB x N each), dist_tp the sorted pool and dist_m y (maxB x 2N each) for cpp_ddpg_last_pooled_quantiles
+  bool pool = false; float* pool_p2 = nullptr;
   // soft actor-critic (cpp_net_create_gaussian: both actors Gaussian with one (lo, hi), or neither; cpp_ddpg_set_sac).  sac_w: the
   // temperature words (common.h: SAC_W_*), sac_step: Adam's count, sac_part: the partials of g_alpha the last actor pass left for a batch
   // of last.sac_rows rows (0: none yet); [0] / [1]: the draw at state_1 / state_2 -- eps (maxB x A), logp (maxB); sac_rsoft: the soft reward the

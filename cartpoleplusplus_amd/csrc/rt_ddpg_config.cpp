@@ -132,6 +132,7 @@ extern "C" int cpp_ddpg_policy_delay_status(cpp_ddpg* d, int* delay, uint64_t* n
 extern "C" int cpp_ddpg_set_actor_min_q(cpp_ddpg* d, int on) {
   ARG_CHECK(d, "cpp_ddpg_set_actor_min_q: NULL argument");
   ARG_CHECK(d->twin, "cpp_ddpg_set_actor_min_q: both critics must carry twin Q heads (cpp_net_create_twin_q)");
+  ARG_CHECK(!d->pool, "cpp_ddpg_set_actor_min_q: pooled quantile critics (their actor ascends the mean over all atoms of both heads)");
   RC(reconfigure(d, [&]() -> int { return (on && !d->amin_sel) ? dalloc(d->arena, &d->amin_sel, (size_t)d->maxB) : (int)CPP_OK; }));
   d->amin = on != 0;      // (the other family of heads instances, or the other GEMM levels)
   return CPP_OK;
@@ -233,9 +234,18 @@ extern "C" int cpp_ddpg_set_quantile_target(cpp_ddpg* d, float kappa, int drop_t
 // :199-214) -- theta of the fed evaluation, the target critic's atoms at the (smoothed) target action sorted ascending, and
 // y_j = r + g s_j (columns j >= M zero), each (B, N).  NULL pointers are skipped.
 extern "C" int cpp_ddpg_last_quantiles(cpp_ddpg* d, int B, float* theta, float* sorted_target_theta, float* y) {
-  RC(last_entry(d, B, "cpp_ddpg_last_quantiles", !(d && d->quant), "the trainer's critics are not quantile critics"));
+  RC(last_entry(d, B, "cpp_ddpg_last_quantiles", !(d && d->quant && !d->pool), "the trainer's critics are not quantile critics"));
   const size_t n = (size_t)B * d->dist_n * sizeof(float);
   return read_back(d->ctx, {{theta, d->dist_p, n}, {sorted_target_theta, d->dist_tp, n}, {y, d->dist_m, n}});
+}
+
+// Pooled quantile trainers (cpp_net_create_pooled_quantile; an extension of the target ddpg_cartpole.py:199-214): what the last minibatch's
+// gradient pass left -- theta^1 and theta^2 of the fed evaluation ((B, N) each), both target heads' atoms at the ONE target action pooled and
+// sorted ascending, and y_j = r* + g s_j (columns j >= M = 2N - 2d zero), (B, 2N) each.  NULL pointers are skipped.
+extern "C" int cpp_ddpg_last_pooled_quantiles(cpp_ddpg* d, int B, float* theta1, float* theta2, float* sorted_pool, float* y) {
+  RC(last_entry(d, B, "cpp_ddpg_last_pooled_quantiles", !(d && d->pool), "the trainer's critics are not pooled quantile critics"));
+  const size_t n = (size_t)B * d->dist_n * sizeof(float);
+  return read_back(d->ctx, {{theta1, d->dist_p, n}, {theta2, d->pool_p2, n}, {sorted_pool, d->dist_tp, 2 * n}, {y, d->dist_m, 2 * n}});
 }
 
 // Distributional trainers: what the last minibatch's gradient pass left -- p of the fed evaluation, p' of the target evaluation at the

@@ -27,6 +27,15 @@ static SacGradArgs sac_grad_args(const cpp_ddpg* d, int B) {
 // job (b) of dist.hip on the fed and the target evaluation the forward passes left in the first workspaces
 static int dist_td(cpp_ddpg* d, const cpp_batch* b, int B, bool backward, const float* w) {
   cpp_net *c = d->critic, *tc = d->tcritic;
+  if (d->pool) {      // both heads of both critics, one launch; the soft reward where critic_td reads it
+    const int last = (int)c->fc.size() - 1;
+    QpoolTdIo io;
+    io.theta1 = c->ws[0].logits; io.theta2 = c->ws[0].logits2; io.ttheta1 = tc->ws[0].logits; io.ttheta2 = tc->ws[0].logits2;
+    io.q1_out = c->ws[0].out; io.q2_out = c->ws[0].out2; io.tq1_out = tc->ws[0].out; io.tq2_out = tc->ws[0].out2;
+    io.theta1_out = d->dist_p; io.theta2_out = d->pool_p2; io.sorted_out = d->dist_tp; io.y_out = d->dist_m; io.td = d->td; io.td2 = d->td2;
+    io.dz1 = backward ? c->ws[0].dz[last] : nullptr; io.dz2 = backward ? c->ws[0].dz2[last] : nullptr;
+    return launch_qpool_td(d->ctx, io, d->sac ? d->sac_rsoft : b->r, b->m, d->hp.discount, B, d->dist_n, d->quant_kappa, d->quant_drop, d->heads_part, w);
+  }
   if (d->quant)
     return launch_quant_td(d->ctx, c->ws[0].logits, tc->ws[0].logits, b->r, b->m, d->hp.discount, B, d->dist_n, d->quant_kappa, d->quant_drop,
                            c->ws[0].out, tc->ws[0].out, d->dist_p, d->dist_tp, d->dist_m, d->td, backward ? c->ws[0].dz[c->fc.size() - 1] : nullptr,
@@ -79,6 +88,8 @@ struct Pass {
   const int na = (int)a->fc.size(), nc = (int)c->fc.size(), cat = c->cat_layer;
   const FcL& Lcat = c->fc[cat]; const long ldcat = Lcat.n_in + 1;
   const bool twin = d->twin, amin = d->amin;      // (amin: twin critics only, cpp_ddpg_set_actor_min_q)
+  const bool pool = d->pool;                      // (pooled quantile critics: twin and dist at once; the actor ascends the mean of both heads)
+  const bool two = amin || pool;                  // (both heads at mu(s1), two dX chains, head 2's action columns added to head 1's)
   const bool sac = d->sac;                        // (its actor's head is 2A wide and linear: never the fused heads)
   const int dist = d->dist_n;                     // (its q layer has N outputs: never the fused heads)
   const bool bc = d->bc_alpha > 0.f;              // (lambda needs every row of the minibatch: never the fused heads, whose rows are spread over workgroups)
@@ -284,7 +295,7 @@ void Pass::levels_forward() {
   for (int l = cat; l < nc; ++l) {
     if (doA) c1 = head_level(fc_fwd_args(c, c->ws[1], l, B), l, c1, cP, aF);
     // the actor on the minimum head: head 2 at a = mu(s1) as well, in head 1's levels (with the actor's half alone too)
-    if (doA && amin) c1b = head_level(twin_fwd_args(c, c->ws[1], l, B), l, c1b, cP, aF);
+    if (doA && two) c1b = head_level(twin_fwd_args(c, c->ws[1], l, B), l, c1b, cP, aF);
     if (!doC) continue;
     c0 = head_level(fc_fwd_args(c, c->ws[0], l, B), l, c0, cP, cb, tC);
     tcH = head_level(fc_fwd_args(tc, tc->ws[0], l, B), l, tcH, tcP, taS);
@@ -300,7 +311,9 @@ void Pass::levels_forward() {
 void Pass::actor_objective() {
   int g = c1;
   // (a distributional critic: the gradient of the expectation, p (z - Q), stands where the scalar critic's q layer is fed ones)
-  if (dist) g = G.fn([=] { return dist_expect(c, c->ws[1], B, c->ws[1].dz[nc - 1]); }, {c1});
+  if (dist && !pool) g = G.fn([=] { return dist_expect(c, c->ws[1], B, c->ws[1].dz[nc - 1]); }, {c1});
+  // (pooled quantile critics: Q_1, Q_2 and the tops of Qbar, 1 / (2N) in both q layers' dz of the second workspace -- quant_pool.hip)
+  if (pool) g = G.fn([=] { return launch_qpool_expect(ctx, c->ws[1].logits, c->ws[1].logits2, B, dist, c->ws[1].out, c->ws[1].out2, c->ws[1].dz[nc - 1], c->ws[1].dz2[nc - 1]); }, {c1, c1b});
   // (the minimum head: per row 1 for the chosen head and 0 for the other, in the q layers' dz of the second workspace -- actor_min.hip)
   if (amin) g = G.fn([=] { return launch_actor_min(ctx, c->ws[1].out, c->ws[1].out2, B, c->ws[1].dz[nc - 1], c->ws[1].dz2[nc - 1], d->amin_sel); }, {c1, c1b});
   const float* top = (dist || amin) ? c->ws[1].dz[nc - 1] : d->ones;
@@ -310,7 +323,7 @@ void Pass::actor_objective() {
     const float* dz = (l == nc - 1) ? top : c->ws[1].dz[l];
     g = G.gemm(fc_dx_args(c, l, B, dz, L.n_out, 0, L.n_in, c->ws[1].dz[l - 1], L.n_in, GE_MUL_RELU_GRAD,
                           c->ws[1].fcin[l], L.n_in + 1), {g});
-    if (amin) g2 = G.gemm(twin_dx_args(c, c->ws[1], l, B), {g2});
+    if (two) g2 = G.gemm(twin_dx_args(c, c->ws[1], l, B), {g2});
   }
   // dQ/da (kept for cpp_ddpg_q_gradients_wrt_actions) and, in the same epilogue, the actor's head gradient
   const float* dz = (cat == nc - 1) ? top : c->ws[1].dz[cat];
@@ -318,11 +331,11 @@ void Pass::actor_objective() {
   const int epi = plain_da ? GE_NONE : GE_ACTOR_HEAD;
   const float* ay = plain_da ? nullptr : a->ws[0].out; const long lday = plain_da ? 0 : A;
   // the minimum head: (head 1's action columns) + (head 2's), then the epilogue -- a row's unselected head adds exact zeros
-  const int h1 = amin ? G.gemm(fc_dx_args(c, cat, B, dz, Lcat.n_out, Lcat.n_in - A, A, d->dq_da, A, GE_NONE, nullptr, 0), {g}) : -1;
-  GemmArgs ga = amin ? twin_da_args(c, c->ws[1], B, d->dq_da, epi, ay, lday)
+  const int h1 = two ? G.gemm(fc_dx_args(c, cat, B, dz, Lcat.n_out, Lcat.n_in - A, A, d->dq_da, A, GE_NONE, nullptr, 0), {g}) : -1;
+  GemmArgs ga = two ? twin_da_args(c, c->ws[1], B, d->dq_da, epi, ay, lday)
                      : fc_dx_args(c, cat, B, dz, Lcat.n_out, Lcat.n_in - A, A, d->dq_da, A, epi, ay, lday);
   if (!plain_da) { ga.C2 = a->ws[0].dz[na - 1]; ga.ldc2 = A; }
-  adz = amin ? G.gemm(ga, {h1, g2, aF}) : G.gemm(ga, {g, aF});
+  adz = two ? G.gemm(ga, {h1, g2, aF}) : G.gemm(ga, {g, aF});
   if (bc) {      // behaviour cloning: lambda from Q(s1, mu(s1)) of the followed head (this chain started behind its q layer), then the head gradient
     BcArgs ba; memset(&ba, 0, sizeof(ba));
     ba.q1 = c->ws[1].out; ba.q2 = amin ? c->ws[1].out2 : nullptr; ba.sel = amin ? d->amin_sel : nullptr;

@@ -85,6 +85,9 @@ struct Workspace {
   // distributional critic (cpp_net_create_distributional): the last layer's N logits land here, (maxB, N), and `out` holds Q = sum_i p_i z_i,
   // (maxB), which dist.hip writes -- every reader of `out` keeps its width of one.  nullptr for every other network.
   float* logits = nullptr;
+  // pooled twin quantile critics (cpp_net_create_pooled_quantile): head 2's N atoms land here, (maxB, N), and `out2` holds Q_2, (maxB), which
+  // quant_pool.hip writes.  nullptr for every other network.
+  float* logits2 = nullptr;
   // feature layer norm (cpp_net_create_feature_norm): xhat, (maxB, fc[0].n_out), and rstd, (maxB), of the last forward of layer 0 -- the
   // first workspace's; a critic's second evaluation shares them with the prefix.  nullptr for every other network.
   float *ln_xhat = nullptr, *ln_rstd = nullptr;
@@ -118,6 +121,8 @@ struct cpp_net {
   // quantile critic (cpp_net_create_quantile): the same N-wide q_value and `logits` workspace, dist_n = N, read as N quantile atoms
   // theta_i at tau_i = (2 i + 1) / (2 N) -- there is no support, and cpp_net_distribution_info keeps answering 0 atoms
   bool quant = false;
+  // pooled twin quantile critics (cpp_net_create_pooled_quantile): twin, quant and dist_n = N <= 32 at once -- head 2's q_valueb is N wide too
+  bool pooled() const { return twin && quant; }
   // Gaussian actor (cpp_net_create_gaussian): output_action is 2A wide, (m | x), and lands in `logits`; `out` stays (maxB, A) and holds
   // the action sac.hip forms from it.  ls = lo + 0.5 (hi - lo) (tanh(x) + 1).  gauss_stage: (2, maxB, A) for cpp_net_forward_gaussian
   bool gauss = false; float ls_lo = 0.f, ls_hi = 0.f; float* gauss_stage = nullptr;
@@ -356,6 +361,7 @@ int ln_forward(cpp_ctx* ctx, cpp_net* const* nets, int nn, int B);
 int add_ln_forward(struct OpGraph& G, cpp_ctx* ctx, cpp_net* const* nets, int nn, const int* deps, int B);
 // where the last layer's GEMM writes: the logits of a distributional critic, `out` otherwise
 inline float* fc_last_out(const Workspace& w) { return w.logits ? w.logits : w.out; }
+inline float* twin_last_out(const Workspace& w) { return w.logits2 ? w.logits2 : w.out2; }      // (head 2's)
 // Q (and, dz != nullptr, p (z - Q); a quantile critic: 1 / N) from the logits the forward left in w: a no-op for every other network
 int dist_expect(cpp_net* n, Workspace& w, int B, float* dz);
 // a = tanh(m) (eps = 0) of a Gaussian actor from the head the forward left in w, into w.out: a no-op for every other network

@@ -124,6 +124,10 @@ static int ws_alloc(cpp_net* n, Workspace& w, int from_layer, bool trunk) {
       }
       RC(dalloc(n->arena, &w.dz2[l], (size_t)mb * L.n_out));
     }
+    if (n->dist_n) {      // pooled twin quantile critics: head 2's atoms beside a Q_2 of width one
+      RC(dalloc(n->arena, &w.logits2, (size_t)mb * n->dist_n));
+      RC(dalloc(n->arena, &w.out2, (size_t)mb));
+    } else
     RC(dalloc(n->arena, &w.out2, (size_t)mb * n->fc2.back().n_out));
   }
   if (trunk && n->ln) {
@@ -162,6 +166,11 @@ static int check_distributional(const char* who, const cpp_net_spec* spec, int n
 static int check_quantile(const char* who, const cpp_net_spec* spec, int n_quantiles) {
   ARG_CHECK(spec->kind == CPP_CRITIC, "%s: kind %d (quantiles belong to a critic)", who, spec->kind);
   ARG_CHECK(n_quantiles >= 2 && n_quantiles <= 64, "%s: %d quantiles outside [2, 64]", who, n_quantiles);
+  return CPP_OK;
+}
+static int check_pooled_quantile(const char* who, const cpp_net_spec* spec, int n_quantiles) {
+  ARG_CHECK(spec->kind == CPP_CRITIC, "%s: kind %d (quantiles belong to a critic)", who, spec->kind);
+  ARG_CHECK(n_quantiles >= 2 && n_quantiles <= 32, "%s: %d quantiles per head outside [2, 32] (the pool of both heads fills one wave's 64 lanes)", who, n_quantiles);
   return CPP_OK;
 }
 static int check_gaussian(const char* who, const cpp_net_spec* spec, float log_std_min, float log_std_max) {
@@ -275,7 +284,37 @@ extern "C" int cpp_net_create_quantile(cpp_ctx* ctx, const cpp_net_spec* spec, i
 // the critic of ddpg_cartpole.py:166-177 widened: N of a network made by cpp_net_create_quantile, 0 for any other
 extern "C" int cpp_net_quantile_info(const cpp_net* n, int* n_quantiles) {
   ARG_CHECK(n, "cpp_net_quantile_info: NULL argument");
-  if (n_quantiles) *n_quantiles = n->quant ? n->dist_n : 0;
+  if (n_quantiles) *n_quantiles = (n->quant && !n->twin) ? n->dist_n : 0;      // (a pooled critic: cpp_net_pooled_quantile_info)
+  return CPP_OK;
+}
+// A critic with two heads of N quantile atoms each on one representation, for the pooled truncated target of TQC (Kuznetsov et al. 2020;
+// an extension of ddpg_cartpole.py:166-177 and :199-214): see include/cartpolepp_abi.h.  The layout is the twin critic's with q_value and
+// q_valueb N wide; head 2's atoms land in a second `logits` workspace (quant_pool.hip reads both)
+extern "C" int cpp_net_create_pooled_quantile(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, int n_quantiles, cpp_net** out) {
+  ARG_CHECK(ctx && spec && out, "cpp_net_create_pooled_quantile: NULL argument");
+  RC(check_pooled_quantile("cpp_net_create_pooled_quantile", spec, n_quantiles));
+  NetVariant nv; nv.twin = true; nv.quant = true; nv.dist_n = n_quantiles;
+  return net_create(ctx, spec, max_batch, nv, out);
+}
+// ... and the same critic behind a feature layer norm (an extension of ddpg_cartpole.py:168 'hidden1'; cpp_net_create_feature_norm's rules for
+// a critic; its variant record names one variant at a time, and this kind is two of its fields at once)
+extern "C" int cpp_net_create_pooled_quantile_norm(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, int n_quantiles, int activation, float epsilon,
+                                                   cpp_net** out) {
+  const char* who = "cpp_net_create_pooled_quantile_norm";
+  ARG_CHECK(ctx && spec && out, "%s: NULL argument", who);
+  RC(check_pooled_quantile(who, spec, n_quantiles));
+  ARG_CHECK(spec->pixel, "%s: a low-dimensional network (there are no conv features to normalise)", who);
+  ARG_CHECK(!spec->use_batch_norm && !spec->use_dropout, "%s: use_batch_norm or use_dropout (cpp_net_create_feature_norm's rules)", who);
+  ARG_CHECK(activation == CPP_NORM_TANH || activation == CPP_NORM_RELU, "%s: activation %d (CPP_NORM_TANH or CPP_NORM_RELU)", who, activation);
+  ARG_CHECK(std::isfinite(epsilon) && epsilon > 0.f, "%s: epsilon %g (finite, positive)", who, (double)epsilon);
+  NetVariant nv; nv.twin = true; nv.quant = true; nv.dist_n = n_quantiles;
+  nv.ln_act = activation == CPP_NORM_TANH ? GE_TANH : GE_RELU; nv.ln_eps = epsilon;
+  return net_create(ctx, spec, max_batch, nv, out);
+}
+// the critic of ddpg_cartpole.py:166-177 widened: N per head of a network made by cpp_net_create_pooled_quantile(_norm), 0 for any other
+extern "C" int cpp_net_pooled_quantile_info(const cpp_net* n, int* n_quantiles) {
+  ARG_CHECK(n, "cpp_net_pooled_quantile_info: NULL argument");
+  if (n_quantiles) *n_quantiles = n->pooled() ? n->dist_n : 0;
   return CPP_OK;
 }
 // An actor whose last layer emits the mean and the bounded log standard deviation of a Gaussian under a tanh (Haarnoja et al. 2018; an

@@ -81,7 +81,7 @@ int add_fc_backward(OpGraph& G, cpp_net* n, Workspace& w, int B, int start, int 
 GemmArgs twin_fwd_args(cpp_net* n, Workspace& w, int l, int B) {
   const FcL& L = n->fc2[l];
   const int nfc = (int)n->fc2.size();
-  float* C = (l + 1 < nfc) ? w.fcin2[l + 1] : w.out2;
+  float* C = (l + 1 < nfc) ? w.fcin2[l + 1] : twin_last_out(w);
   const long ldc = (l + 1 < nfc) ? n->fc2[l + 1].n_in + 1 : L.n_out;
   return mk_gemm(w.fcin2[l], L.n_in + 1, 1, n->params + L.w_off, L.n_out, 1, C, ldc, B, L.n_out, L.n_in + 1, L.act);
 }

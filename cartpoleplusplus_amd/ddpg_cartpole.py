@@ -191,6 +191,16 @@ def build_parser():
     a('--quantile-huber-kappa', type=float, default=argparse.SUPPRESS, help="--quantile-critic: the Huber threshold of the quantile loss (default 1.0)")
     a('--drop-top-quantiles', type=int, default=argparse.SUPPRESS,
       help="--quantile-critic: drop the D largest target quantiles before the regression (overestimation control; default 0; 0 .. N - 1)")
+    # pooled twin quantile critics (an extension beyond the reference, ddpg_cartpole.py:166-177, :199-214: Truncated Quantile Critics, Kuznetsov
+    # et al. 2020, with two heads on one representation): each critic has two heads of N quantile atoms; the atoms of both target heads are
+    # pooled and sorted and the 2d largest dropped, both heads regress onto the kept ones and the actor ascends the mean over all atoms of both
+    # heads.  With --soft-actor-critic this is TQC (absent from the parsed options unless given, like --twin-q; pooled_quantile_critics() reads them)
+    a('--pooled-quantile-critics', action='store_true', default=argparse.SUPPRESS,
+      help="critics with two heads of --pooled-num-quantiles quantiles each; the target pools both target heads' atoms and drops the largest")
+    a('--pooled-num-quantiles', type=int, default=argparse.SUPPRESS, help="--pooled-quantile-critics: quantiles per head (default 25; 2 .. 32)")
+    a('--pooled-drop-per-head', type=int, default=argparse.SUPPRESS,
+      help="--pooled-quantile-critics: drop the 2 d largest atoms of the pool of 2 N before the regression (default 2; 0 .. N - 1)")
+    a('--pooled-huber-kappa', type=float, default=argparse.SUPPRESS, help="--pooled-quantile-critics: the Huber threshold of the quantile loss (default 1.0)")
     # soft actor-critic (an extension beyond the reference, ddpg_cartpole.py:95-119, :199-214: Haarnoja et al. 2018): a stochastic
     # tanh-Gaussian actor, an entropy term in the critic's target and a learned temperature; with --twin-q and random shift this is DrQ
     # (absent from the parsed options unless given, like --twin-q; soft_actor_critic() reads them)
@@ -518,6 +528,46 @@ def quantile_critic(o):
     return (int(n), k, int(d))
 
 
+_POOLED_NUM_QUANTILES_DEFAULT, POOLED_NUM_QUANTILES_MAX, _POOLED_DROP_DEFAULT, _POOLED_KAPPA_DEFAULT = 25, 32, 2, 1.0
+
+
+def pooled_quantile_critics(o):
+    """(n_quantiles per head, kappa, drop per head) of --pooled-quantile-critics / --pooled-num-quantiles / --pooled-huber-kappa /
+    --pooled-drop-per-head, or None (off); refuses what cannot be meant."""
+    import math
+    on = bool(getattr(o, "pooled_quantile_critics", False))
+    given = [k for k in ("pooled_num_quantiles", "pooled_drop_per_head", "pooled_huber_kappa") if getattr(o, k, None) is not None]
+    if not on:
+        if given:
+            raise SystemExit("--%s needs --pooled-quantile-critics" % given[0].replace("_", "-"))
+        return None
+    for flag, name, why in (("quantile_critic", "--quantile-critic", "it makes its own two quantile heads"),
+                            ("distributional_critic", "--distributional-critic", "one value distribution per head"),
+                            ("twin_q", "--twin-q", "it makes its own two heads"),
+                            ("actor_min_q", "--actor-min-q", "its actor ascends the mean over all atoms of both heads")):
+        if bool(getattr(o, flag, False)):
+            raise SystemExit("--pooled-quantile-critics cannot be combined with %s (%s)" % (name, why))
+    alpha = getattr(o, "bc_alpha", None)
+    if alpha is not None and alpha != 0:
+        raise SystemExit("--pooled-quantile-critics cannot be combined with --bc-alpha (the behaviour-cloning term is of a scalar critic)")
+    n = getattr(o, "pooled_num_quantiles", None)
+    n = _POOLED_NUM_QUANTILES_DEFAULT if n is None else n
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= int(n) <= POOLED_NUM_QUANTILES_MAX:
+        raise SystemExit("--pooled-num-quantiles %r is not a whole number in [2, %d] (the pool of both heads fills one wave)" % (n, POOLED_NUM_QUANTILES_MAX))
+    d = getattr(o, "pooled_drop_per_head", None)
+    d = min(_POOLED_DROP_DEFAULT, int(n) - 1) if d is None else d
+    if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or not 0 <= int(d) <= int(n) - 1:
+        raise SystemExit("--pooled-drop-per-head %r is not a whole number in [0, %d] (at least two atoms of the pool stay)" % (d, int(n) - 1))
+    k = getattr(o, "pooled_huber_kappa", None)
+    try:
+        k = _POOLED_KAPPA_DEFAULT if k is None else float(np.float32(k))
+    except (TypeError, ValueError) as e:
+        raise SystemExit("--pooled-huber-kappa: %s" % e)
+    if isinstance(getattr(o, "pooled_huber_kappa", None), bool) or not (math.isfinite(k) and k > 0.0):
+        raise SystemExit("--pooled-huber-kappa %r is not finite and positive" % (getattr(o, "pooled_huber_kappa", None),))
+    return (int(n), k, int(d))
+
+
 _SAC_DEFAULTS = {"sac_init_temperature": 0.1, "sac_target_entropy": None, "sac_temperature_learning_rate": 1e-4,
                  "sac_log_std_min": -10.0, "sac_log_std_max": 2.0, "sac_seed": 0}
 SAC_ACTION_DIM_MAX = 64
@@ -615,6 +665,7 @@ def default_opts(**overrides):
     o.bc_alpha, o.bc_q_floor = None, None
     o.distributional_critic, o.num_atoms, o.v_min, o.v_max = False, None, None, None
     o.quantile_critic, o.num_quantiles, o.quantile_huber_kappa, o.drop_top_quantiles = False, None, None, None
+    o.pooled_quantile_critics, o.pooled_num_quantiles, o.pooled_drop_per_head, o.pooled_huber_kappa = False, None, None, None
     o.n_step = 1
     o.soft_actor_critic = False
     o.feature_layer_norm, o.feature_norm_activation = False, None
@@ -828,6 +879,10 @@ class _Trainer(object):
         quantiles = getattr(critic, "quantiles", None)
         if quantiles:
             self.set_quantile_target(quantiles[1], quantiles[2])
+        # --pooled-quantile-critics: the Huber threshold and the atoms dropped per head, as parsed when the critic was built
+        pooled = getattr(critic, "pooled", None)
+        if pooled:
+            self.set_quantile_target(pooled[1], pooled[2])
         # --soft-actor-critic: temperature, target entropy, rate and seed, as parsed when the actor was built
         self.sac = getattr(actor, "sac", None)
         if self.sac:
@@ -941,6 +996,17 @@ class _Trainer(object):
         n = q[0] if q else 1
         out = [np.empty((B, n), np.float32) for _ in range(3)]
         check(lib.cpp_ddpg_last_quantiles(self.handle, B, *[ptr(x) for x in out]))
+        return tuple(out)
+
+    def last_pooled_quantiles(self, B):
+        """(theta1, theta2, sorted_pool, y) of the last minibatch's gradient pass of a --pooled-quantile-critics trainer: both heads' quantiles
+        of the fed evaluation, each (B, N); both target heads' atoms at the one target action pooled and sorted ascending, and
+        y_j = r* + g s_j with the columns j >= 2N - 2d zero, each (B, 2N)"""
+        B = int(B)
+        p = getattr(self.nets[1], "pooled", None)
+        n = p[0] if p else 1
+        out = [np.empty((B, n), np.float32), np.empty((B, n), np.float32), np.empty((B, 2 * n), np.float32), np.empty((B, 2 * n), np.float32)]
+        check(lib.cpp_ddpg_last_pooled_quantiles(self.handle, B, *[ptr(x) for x in out]))
         return tuple(out)
 
     def set_sac(self, init_temperature, target_entropy, temperature_lr, seed):
@@ -1146,10 +1212,15 @@ class CriticNetwork(base_network.Network):
         self.distribution = distributional_critic(opts)
         # --quantile-critic: q_value emits num_quantiles quantile atoms; q_value, forward and dQ/da are their mean
         self.quantiles = quantile_critic(opts)
+        # --pooled-quantile-critics: two heads of N quantile atoms each; q_value and forward are head 1's mean, dQ/da the mean over both heads'
+        self.pooled = pooled_quantile_critics(opts)
         # --feature-layer-norm: hidden1 is Linear -> LayerNorm -> tanh
         self.feature_norm = feature_layer_norm(opts)
-        self._build_native(_lib.CPP_CRITIC, self.action_dim, max(int(opts.batch_size), 1), twin_q=self.twin_q, distribution=self.distribution,
-                           quantiles=self.quantiles[0] if self.quantiles else None, feature_norm=self.feature_norm)
+        if self.pooled:
+            self._build_native(_lib.CPP_CRITIC, self.action_dim, max(int(opts.batch_size), 1), pooled=self.pooled[0], feature_norm=self.feature_norm)
+        else:
+            self._build_native(_lib.CPP_CRITIC, self.action_dim, max(int(opts.batch_size), 1), twin_q=self.twin_q, distribution=self.distribution,
+                               quantiles=self.quantiles[0] if self.quantiles else None, feature_norm=self.feature_norm)
         # --shared-encoder: this critic's conv trunk is its actor's encoder from here on
         if getattr(actor, "shared_encoder", False):
             check(lib.cpp_net_set_encoder(actor.handle, self.handle))
@@ -1241,6 +1312,7 @@ class DeepDeterministicPolicyGradientAgent(object):
         state_shape = self.env.observation_space.shape
         action_dim = self.env.action_space.shape[1]
         # (the refusals of --distributional-critic and --n-step come before anything exists on the device, as check_prioritized_opts')
+        pooled_quantile_critics(opts)
         distributional_critic(opts)
         quantile_critic(opts)
         soft_actor_critic(opts, action_dim)

@@ -209,6 +209,42 @@ int cpp_net_distribution_info(const cpp_net* net, int* n_atoms, float* v_min, fl
 int cpp_net_create_quantile(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, int n_quantiles, cpp_net** out);
 /* N of a network made by cpp_net_create_quantile (the critic of ddpg_cartpole.py:166-177 widened); 0 for any other.  NULL is skipped. */
 int cpp_net_quantile_info(const cpp_net* net, int* n_quantiles);
+/* Pooled twin quantile critics: Truncated Quantile Critics (Kuznetsov et al. 2020, TQC) with two heads on one representation, an extension
+ * of the critic ddpg_cartpole.py:166-171 (pixel) / :172-177 (low-dimensional) and of its target :199-214.  The layout is
+ * cpp_net_create_twin_q's with both q layers N wide: the plain critic's variables first ('q_value/weights' (n_in, N), 'q_value/biases' (N)),
+ * then head 2's copy of the layers from the concat layer upward ('hidden3b/*', 'q_valueb/*'; low-dimensional: 'h<i>b/*', 'q_valueb/*').
+ * spec->kind must be CPP_CRITIC, 2 <= N <= 32: the pool of both heads' atoms fills the 64 lanes of one wave (CPP_ERR_ARG otherwise).  All
+ * arithmetic below is float32 except the loss, whose terms are formed and added in float64.  Per row b, with kappa and d (PER HEAD) of
+ * cpp_ddpg_set_quantile_target:
+ *   theta^k_i  = atom i of online head k at (s1, a_fed), k = 1, 2, i < N;   tau_i = (2 i + 1) / (2 N)
+ *   z          = (theta'^1_0 .. theta'^1_{N-1}, theta'^2_0 .. theta'^2_{N-1}): both target heads at (s2, a'), ONE a' (smoothed, or soft
+ *                actor-critic's sample)
+ *   s          = z sorted ascending (2N values, always sorted, also at d = 0);   M = 2N - 2d;   g = mask_b * discount
+ *   y_j        = r* + g s_j, j < M;   r* = r_b, or r_soft under soft actor-critic (cpp_ddpg_set_sac)
+ *   u^k_ij     = y_j - theta^k_i;   H and rho as in cpp_net_create_quantile's text
+ *   L^k_b      = (1 / (N M)) sum_i sum_j rho^k_ij   (j ascending inside i);   L_b = L^1_b + L^2_b;   loss = mean_b(w_b L_b)
+ *   d theta^k_i = -(w_b / B) (1 / (N M)) sum_j |tau_i - [u^k_ij < 0]| clip(u^k_ij, -kappa, kappa) / kappa
+ *   Q_k = (sum_i theta^k_i) / N;   Qbar = (Q_1 + Q_2) / 2
+ *   td_b = Q_1 - (sum_{j<M} y_j) / M;   td2_b = Q_2 - the same mean
+ * td (head 1's, as for every twin critic) is what priorities, cpp_ddpg_last_values and cpp_ddpg_check_loss read; cpp_ddpg_last_twin_values
+ * reads Q_2, Q_1', Q_2' (the target heads' own means, before pooling) and td2.  The actor ascends Qbar(s1, mu(s1)): the gradient entering
+ * BOTH q layers on that evaluation is the constant 1 / (2N), and dq_da = dQbar/da; a soft actor-critic trainer's actor minimises
+ * alpha logp - Qbar.  cpp_net_forward* return Q_1 (width 1) and cpp_ddpg_q_gradients_wrt_actions returns Q_1 beside dQbar/da, as
+ * cpp_ddpg_set_actor_min_q returns Q_1 beside the minimum's gradient.  Truncation works on values: ties cannot change any result.
+ * cpp_ddpg_create accepts such critics only as a pair with one N, under plain or Gaussian actors; cpp_ddpg_set_actor_min_q and
+ * cpp_ddpg_set_behaviour_cloning refuse such a trainer, which always takes the GEMM levels of the gradient pass; batches up to 1024.
+ * cpp_naf_create refuses such networks.  A checkpoint carries every variable by name: it fails the layout check against a twin, a quantile
+ * or a plain critic, and against another N.  cpp_net_quantile_info and cpp_net_distribution_info answer 0 for such a network,
+ * cpp_net_is_twin_q answers 1. */
+int cpp_net_create_pooled_quantile(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, int n_quantiles, cpp_net** out);
+/* The same critic behind cpp_net_create_feature_norm's layer norm on fully connected layer 0 (an extension of ddpg_cartpole.py:168 'hidden1';
+ * that entry's variant record names one variant at a time).  Its rules for a critic hold: pixel, no batch norm, no dropout, activation
+ * CPP_NORM_TANH or CPP_NORM_RELU, a finite positive epsilon; gamma and beta sit behind head 2's variables. */
+int cpp_net_create_pooled_quantile_norm(cpp_ctx* ctx, const cpp_net_spec* spec, int max_batch, int n_quantiles, int activation, float epsilon,
+                                        cpp_net** out);
+/* N per head of a network made by cpp_net_create_pooled_quantile(_norm) (the critic of ddpg_cartpole.py:166-177 widened); 0 for any other.
+ * NULL is skipped. */
+int cpp_net_pooled_quantile_info(const cpp_net* net, int* n_quantiles);
 /* Gaussian actor: the stochastic tanh-Gaussian policy of soft actor-critic (Haarnoja et al. 2018), an extension of the actor
  * ddpg_cartpole.py:95-100.  The layout is cpp_net_create's actor except that 'output_action/weights' is (n_in, 2A) and
  * 'output_action/biases' is (2A): the last layer is linear and emits (m_k, x_k), k < A -- m in columns [0, A), x in [A, 2A).  spec->kind
@@ -669,12 +705,18 @@ int cpp_ddpg_last_distribution(cpp_ddpg* ddpg, int B, float* p, float* target_p,
 /* Quantile trainers (cpp_net_create_quantile; an extension of the target ddpg_cartpole.py:199-214): the Huber threshold kappa and the
  * number d of largest target atoms dropped before the regression.  After cpp_ddpg_create: kappa 1, d 0 (plain quantile regression).
  * CPP_ERR_ARG for a kappa that is not finite and positive or a d outside [0, N - 1]; CPP_ERR_STATE on any other trainer.  Both values are
- * captured by value: the call drops the captured graphs, as cpp_ddpg_set_policy_delay does. */
+ * captured by value: the call drops the captured graphs, as cpp_ddpg_set_policy_delay does.  A pooled quantile trainer
+ * (cpp_net_create_pooled_quantile) takes d PER HEAD: the 2d largest atoms of the pool of 2N are dropped. */
 int cpp_ddpg_set_quantile_target(cpp_ddpg* ddpg, float kappa, int drop_top);
 /* Quantile trainers (an extension of ddpg_cartpole.py:166-177, :199-214): theta of the fed evaluation, the target evaluation's atoms
  * sorted ascending and y_j = r + g s_j of the last minibatch's gradient pass, each (B, N); columns j >= M of y are zero.  NULL pointers are
  * skipped.  CPP_ERR_STATE on any other trainer. */
 int cpp_ddpg_last_quantiles(cpp_ddpg* ddpg, int B, float* theta, float* sorted_target_theta, float* y);
+/* Pooled quantile trainers (cpp_net_create_pooled_quantile; an extension of ddpg_cartpole.py:166-177, :199-214): theta^1 and theta^2 of the
+ * fed evaluation ((B, N) each), the pool of both target heads' atoms sorted ascending and y_j = r* + g s_j of the last minibatch's gradient
+ * pass ((B, 2N) each); columns j >= M = 2N - 2d of y are zero.  NULL pointers are skipped.  CPP_ERR_STATE on any other trainer, as
+ * cpp_ddpg_last_quantiles answers on this one. */
+int cpp_ddpg_last_pooled_quantiles(cpp_ddpg* ddpg, int B, float* theta1, float* theta2, float* sorted_pool, float* y);
 /* Soft actor-critic trainers (cpp_net_create_gaussian; an extension of the actor's train op ddpg_cartpole.py:102-119 and of the target
  * :199-214): the initial temperature alpha (> 0), the target entropy Hbar, the temperature's Adam rate (0: fixed) and the noise seed, all
  * captured by value.  Zeroes the noise count, Adam's slots and count, copies the actor into the target actor, drops the cached graphs.  A
