@@ -279,7 +279,14 @@ extern "C" int cpp_ddpg_q_gradients_wrt_actions(cpp_ddpg* d, cpp_batch* b, float
   HIP_CHECK(hipSetDevice(d->ctx->device));
   RC(prep_batch(d, b));
   PassLeft left;      // (an evaluation: nothing drawn, nothing left; the actor's backward runs all the same -- cpp_ddpg_grad_buffer shows it)
-  RC(actor_half(d, b, false, &left));
+  // --use-dropout: nothing drawn means no mask and no count either.  The actor's layers look for its counter while the pass is built:
+  // without one they are the inference layers (no unit dropped, no factor 2) and the forward is not counted, so the masks of the
+  // training calls around this one are the ones they would have drawn without it
+  uint64_t* const drop_counter = d->actor->drop_counter;
+  d->actor->drop_counter = nullptr;
+  const int rc = actor_half(d, b, false, &left);
+  d->actor->drop_counter = drop_counter;
+  RC(rc);
   const size_t nB = (size_t)b->B * sizeof(float), nA = nB * d->actor->spec.action_dim;
   return read_back(d->ctx, {{dq_da, d->dq_da, nA}, {actions, d->actor->ws[0].out, nA}, {q, d->critic->ws[1].out, nB}});
 }

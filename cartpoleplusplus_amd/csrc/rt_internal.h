@@ -377,9 +377,12 @@ int train_entry_checks(const char* who, const cpp_replay* r, int B, int maxB, lo
                        bool nstep = true);      // batch range, replay shape, n-step discount, empty memory, prioritized batch limit
 GatherArgs replay_gather_args(cpp_replay* r, int B, const int32_t* rows_dev, uint64_t seed, const uint64_t* counter_dev, int channels, cpp_batch* out, bool direct, int* C_out,
                               bool augment = true);      // augment: a memory with random shift on gathers shifted (false: cpp_replay_sample, the stored pixels)
-int replay_sample_finish(cpp_replay* r, int B, int C, int channels, cpp_batch* out, uint64_t* bump = nullptr, bool* bumped = nullptr);
+// feeds_route: the minibatch is a training call's -- its largest whitening scale goes into the context's white_max_dev, which that call
+// publishes to the conv1 route.  false: an inspection gather (cpp_replay_sample, cpp_replay_gather_shifted), which a later training
+// call must not publish in its own name
+int replay_sample_finish(cpp_replay* r, int B, int C, int channels, cpp_batch* out, uint64_t* bump = nullptr, bool* bumped = nullptr, bool feeds_route = true);
 int replay_sample_device(cpp_replay* r, int B, const int32_t* rows_dev, uint64_t seed, const uint64_t* counter_dev, int channels, cpp_batch* out, bool direct = false,
-                         uint64_t* bump = nullptr, bool* bumped = nullptr, bool augment = true);
+                         uint64_t* bump = nullptr, bool* bumped = nullptr, bool augment = true, bool feeds_route = true);
 int replay_stage_rows(cpp_replay* r, const int32_t* idxs, int n, const char* who);
 PerArgs per_args(const cpp_replay* r);            // the memory's tree, size word, maximum and beta; nothing to write, nothing to draw
 int per_refuse(const cpp_replay* r, const char* who);   // CPP_ERR_ARG (with the message) on a prioritized memory

@@ -416,11 +416,11 @@ GatherArgs replay_gather_args(cpp_replay* r, int B, const int32_t* rows_dev, uin
 // what follows the gather kernel: the batch's bookkeeping and the whitening tables
 // bump (optional): the sampler's counter, to be advanced by one behind this minibatch's draw -- done by the statistics kernel
 // when there is one (*bumped = true), left to the caller otherwise
-int replay_sample_finish(cpp_replay* r, int B, int C, int channels, cpp_batch* out, uint64_t* bump, bool* bumped) {
+int replay_sample_finish(cpp_replay* r, int B, int C, int channels, cpp_batch* out, uint64_t* bump, bool* bumped, bool feeds_route) {
   out->B = B; out->dtype = CPP_F16; out->stats_C = 0;
   if (bumped) *bumped = false;
   if (C > 0) {
-    RC(launch_stats_finalize(r->ctx, out->part, B, 2, C, (double)B * (double)(r->elems / C), out->white, 1e-6, bump, r->ctx->white_max_dev));
+    RC(launch_stats_finalize(r->ctx, out->part, B, 2, C, (double)B * (double)(r->elems / C), out->white, 1e-6, bump, feeds_route ? r->ctx->white_max_dev : nullptr));
     if (bumped && bump) *bumped = true;
     out->stats_C = C;
   } else if (channels > 0) {
@@ -429,11 +429,11 @@ int replay_sample_finish(cpp_replay* r, int B, int C, int channels, cpp_batch* o
   return CPP_OK;
 }
 int replay_sample_device(cpp_replay* r, int B, const int32_t* rows_dev, uint64_t seed, const uint64_t* counter_dev,
-                                int channels, cpp_batch* out, bool direct, uint64_t* bump, bool* bumped, bool augment) {
+                                int channels, cpp_batch* out, bool direct, uint64_t* bump, bool* bumped, bool augment, bool feeds_route) {
   int C = 0;
   const GatherArgs a = replay_gather_args(r, B, rows_dev, seed, counter_dev, channels, out, direct, &C, augment);
   RC(launch_gather_stats(r->ctx, a, r->store_dtype));      // a CPP_U8 store gathers to f16 as well
-  return replay_sample_finish(r, B, C, channels, out, bump, bumped);
+  return replay_sample_finish(r, B, C, channels, out, bump, bumped, feeds_route);
 }
 
 extern "C" int cpp_replay_sample(cpp_replay* r, int B, const int32_t* idxs, uint64_t seed, uint64_t counter,
@@ -461,8 +461,9 @@ extern "C" int cpp_replay_sample(cpp_replay* r, int B, const int32_t* idxs, uint
       rows_dev = r->per_rows;
     }
   }
-  // (the stored pixels, also on a memory with random shift on: the augmentation belongs to the trainers' gathers and cpp_replay_gather_shifted)
-  RC(replay_sample_device(r, B, rows_dev, seed, rows_dev ? nullptr : r->counter_adhoc, channels, out, false, nullptr, nullptr, false));
+  // (the stored pixels, also on a memory with random shift on: the augmentation belongs to the trainers' gathers and cpp_replay_gather_shifted;
+  // an inspection draw: its whitening scale is no training call's and stays out of the conv1 route)
+  RC(replay_sample_device(r, B, rows_dev, seed, rows_dev ? nullptr : r->counter_adhoc, channels, out, false, nullptr, nullptr, false, false));
   if (idxs) HIP_CHECK(hipStreamSynchronize(st));     // the caller's index array may go away after return
   return CPP_OK;
 }
@@ -750,7 +751,7 @@ extern "C" int cpp_replay_gather_shifted(cpp_replay* r, int B, const int32_t* id
   if (r->size <= 0) { cpp_set_error("cpp_replay_gather_shifted: replay memory is empty"); return CPP_ERR_STATE; }
   HIP_CHECK(hipSetDevice(r->ctx->device));
   RC(replay_stage_rows(r, idxs, B, "cpp_replay_gather_shifted"));
-  RC(replay_sample_device(r, B, r->rows_in, 0, nullptr, channels, out));
+  RC(replay_sample_device(r, B, r->rows_in, 0, nullptr, channels, out, false, nullptr, nullptr, true, false));
   HIP_CHECK(ctx_sync_stream(r->ctx));
   return CPP_OK;
 }

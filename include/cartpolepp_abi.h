@@ -97,7 +97,9 @@ int cpp_ctx_get_precision(cpp_ctx* ctx, int* mode);
  * GPU timing: call k reads call k - 2's (behind an event that guarantees it has landed; no wait in a loop that runs ahead of the
  * GPU), or call k - 1's if the stream has been synchronised since (cpp_sync, a parameter read, the eager pass in front of a graph
  * capture).  The first one or two affected calls therefore still run on the f16 pipes -- the same ones in every run.
- * cpp_ctx_get_route reports the current choice and the scale of the newest call known to have finished. */
+ * cpp_ctx_get_route reports the current choice and the scale of the newest call known to have finished.  Only training calls feed the
+ * scale: the gathers of cpp_replay_sample and cpp_replay_gather_shifted are inspections, and what they whiten never reaches a later
+ * call's choice. */
 int cpp_ctx_set_route_threshold(cpp_ctx* ctx, float threshold);
 int cpp_ctx_get_route(cpp_ctx* ctx, int* conv1_f32, float* last_max_scale);
 
@@ -561,7 +563,8 @@ int cpp_ddpg_train_critic(cpp_ddpg* ddpg, cpp_batch* batch);
 /* CriticNetwork.check_loss(batch) (:239-248): loss scalar, td (B), q (B). */
 int cpp_ddpg_check_loss(cpp_ddpg* ddpg, cpp_batch* batch, float* loss, float* td, float* q);
 /* CriticNetwork.q_gradients_wrt_actions() evaluated at a = actor(state_1) (:220-222): (B, A);
- * also returns the actions and q-values of that evaluation when the pointers are non-NULL. */
+ * also returns the actions and q-values of that evaluation when the pointers are non-NULL.  An evaluation: under use_dropout it drops no
+ * unit and is not counted, as cpp_ddpg_check_loss. */
 int cpp_ddpg_q_gradients_wrt_actions(cpp_ddpg* ddpg, cpp_batch* batch, float* dq_da, float* actions,
                                      float* q);
 /* Fused form of one loop body of :331-334.  Both gradient sets are taken from the same parameter
